@@ -302,6 +302,40 @@ def trajectory_rmse(poses, scales, gt_of_frame, first_scored, lag=0):
     return (float(np.sqrt(np.mean(err))) if err else None), k
 
 
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, loop, ring, state, steps, h, w, ring_slots, torch):
+    """--dump-outputs: what a caller of the timed loop receives after its last step, as out_dir/<name>.npy —
+      poses               (steps, 7) float64: every timed frame's frame->keyframe pose (quaternion w x y z, translation), in order
+      keyframes           (n, 2, h, w) float32: the (idepth, idepthVar) planes of the keyframes the last batch finished, oldest first
+      keyframe_idepth     (h, w) float32: the current keyframe's inverse depth after the last step
+      keyframe_idepth_var (h, w) float32: ... and its variance
+    At most DUMP_BYTES in all: an array too large for its share is replaced by a fixed, seeded sample of its elements (flattened, in
+    index order), so that two builds run with the same arguments can be compared element for element."""
+    poses = np.concatenate(state["poses"])[-steps:] if state["poses"] else np.zeros((0, 7))
+    new = state["last_new"]
+    slots = [i % ring_slots for i in range(max(0, new - ring_slots), new)]
+    kf_idepth = torch.empty((h, w), dtype=torch.float32, device=ring.device)
+    kf_var = torch.empty_like(kf_idepth)
+    loop.copy_keyframe_planes(kf_idepth.data_ptr(), kf_var.data_ptr())
+    from lsd_slam_amd import capi
+    capi.check(capi.lib().lsdhip_ctx_synchronize(loop.ctx_handle()))
+    torch.cuda.synchronize()
+    arrays = {"poses": np.ascontiguousarray(poses, dtype=np.float64),
+              "keyframes": ring[slots].cpu().numpy() if slots else np.zeros((0, 2, h, w), np.float32),
+              "keyframe_idepth": kf_idepth.cpu().numpy(), "keyframe_idepth_var": kf_var.cpu().numpy()}
+    total = sum(a.nbytes for a in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if total > DUMP_BYTES:
+            keep = min(a.size, int(a.size * (DUMP_BYTES - 4096 * len(arrays)) / total))
+            if keep < a.size:
+                idx = np.unique(np.random.default_rng(20241015).integers(0, a.size, keep))
+                a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def other_execution_model(DriverLoop, capi, w, h, K, ptr, depth0, device, pipelined, steps, warmup, trials, trial_cap, regions=3):
     """the same loop in the OTHER execution model (one stream / pipelined), a short leg after the timed region: median of `regions`
     regions of `steps` frames; reported beside `value`"""
@@ -696,11 +730,14 @@ def main():
                          "mapping stream, the mapper one frame behind (the reference's two threads; lsd_slam_hip::SlamLoop)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / process-group plumbing only (no GPU work, gloo when there is no GPU): prints the JSON skeleton")
-    ap.add_argument("--repeats", type=int, default=0,
-                    help="the timed region of exactly --steps steps is run this many times back to back (each between barriers); `value` and "
-                         "`ms_per_step` are those of the MEDIAN region, so one 5 ms window does not decide the line.  0 = automatic: at least 5 "
-                         "regions and at least ~1000 frames in total (the loop shows ~15 %% slower phases lasting tens of milliseconds on some "
-                         "boxes: profiles/r03_notes.md)")
+    ap.add_argument("--repeats", type=int, default=1,
+                    help="split the --steps timed steps into this many back-to-back regions (each between barriers; at most --steps); "
+                         "`value` and `ms_per_step` are those of the MEDIAN region's rate (the loop shows ~15 %% slower phases lasting tens "
+                         "of milliseconds on some boxes: profiles/r03_notes.md).  The number of timed steps is --steps whatever this is")
+    ap.add_argument("--dump-outputs", type=str, default=None, metavar="DIR",
+                    help="after the timed steps, write what the timed loop returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all): the poses of the timed steps, the keyframes finished in the last batch, the current "
+                         "keyframe's inverse-depth planes.  Rank 0 only")
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the two short extra legs (BASELINE.json configs[2] and configs[4])")
     ap.add_argument("--seq-frames", type=int, default=50,
                     help="synthetic frames to render (one camera revolution = 50); fewer are played back and forth")
@@ -804,8 +841,10 @@ def main():
     ctx_h = loop.ctx_handle()
     # frame-memory pool: the validation keeps every keyframe of the run alive, i.e. the loop takes a fresh arena per keyframe — allocated
     # ahead (lsdhip_ctx_reserve_frames), not with one hipMalloc (0.5 ms) per keyframe inside the timed region
-    repeats = args.repeats if args.repeats > 0 else max(5, -(-1000 // max(1, args.steps)))
-    capi.check(L.lsdhip_ctx_reserve_frames(ctx_h, (args.warmup + args.steps * repeats) // KF_EVERY + 24))
+    # the --steps timed steps, split into `repeats` back-to-back regions of (nearly) equal length
+    repeats = max(1, min(args.repeats, args.steps))
+    region_steps = [args.steps // repeats + (1 if i < args.steps % repeats else 0) for i in range(repeats)]
+    capi.check(L.lsdhip_ctx_reserve_frames(ctx_h, (args.warmup + args.steps) // KF_EVERY + 24))
 
     # Finished keyframes leave the loop through a device ring (smoothed idepth + variance planes, copied on the loop's
     # stream); after every batch of frames the ring's new entries are collected on rank 0 with ONE gather (RCCL over xGMI) —
@@ -839,7 +878,7 @@ def main():
             recv_all = torch.empty((world,) + tuple(ring.shape), dtype=torch.float32, device=ring.device) if rank == 0 else None
         else:
             recv = [torch.empty_like(ring) for _ in range(world)] if rank == 0 else None
-    state = {"fi": 0, "exported": 0, "gathered_bytes": 0, "poses": []}
+    state = {"fi": 0, "exported": 0, "gathered_bytes": 0, "poses": [], "last_new": 0}
 
     def run_frames(n):
         """n frames through the C++ loop in batches that produce at most RING keyframes; one gather per batch"""
@@ -854,6 +893,7 @@ def main():
             left -= done
             new = loop.keyframes_exported()
             state["exported"] += new
+            state["last_new"] = new
             if distributed and gather_impl.startswith("rccl"):
                 loop.gather_keyframes(new, 0, recv_all.data_ptr() if rank == 0 else None, ring.numel())
                 state["gathered_bytes"] += new * ring[0].numel() * 4
@@ -875,11 +915,11 @@ def main():
     elapsed_all = []
     own_all = []
     region_wall = []
-    for rep_i in range(repeats):
+    for n_region in region_steps:
         region_wall.append(time.time())
-        # every region: barrier + synchronize, exactly K steps, synchronize + barrier; max over ranks
+        # every region: barrier + synchronize, its share of the K steps, synchronize + barrier; max over ranks
         t0 = clock()
-        run_frames(args.steps)
+        run_frames(n_region)
         capi.check(L.lsdhip_ctx_synchronize(ctx_h))
         torch.cuda.synchronize()
         if distributed:
@@ -895,12 +935,14 @@ def main():
     else:
         elapsed_all = list(own_all)
     capi.check(L.lsdhip_prof_enable(ctx_h, 0))
-    elapsed = float(np.median(elapsed_all))
+    rate = float(np.median([n / e for n, e in zip(region_steps, elapsed_all)]))     # steps per second of the median region
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loop, ring, state, args.steps, h, w, RING, torch)
     # configs[3]: every rank's own rate (its own median region, not the max over ranks that `value` is made of)
     per_rank = None
     bands_rec = None
     if distributed:
-        mine = torch.tensor([args.steps / float(np.median(own_all))], dtype=torch.float64, device="cuda")
+        mine = torch.tensor([float(np.median([n / e for n, e in zip(region_steps, own_all)]))], dtype=torch.float64, device="cuda")
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [float(x.item()) for x in allr]
@@ -922,7 +964,7 @@ def main():
     res_ms, res_launches, res_bytes = ms_.value, n_.value, b_.value
     out = None
     if rank == 0:
-        value = world * args.steps / elapsed
+        value = world * rate
         roofline = None
         if res_launches > 0 and res_ms > 0:
             achieved = (res_bytes / res_launches) / (res_ms / res_launches * 1e-3) / 1e9
@@ -936,8 +978,8 @@ def main():
         out = {
             "metric": "tracked frames/sec (full track+map loop) at %dx%d, frames resident in HBM (8-bit upload excluded: value_pcie_inclusive has it)" % (w, h),
             "value": value, "unit": "frames/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3,
-            "repeats": repeats, "ms_per_step_all_regions": [e / args.steps * 1e3 for e in elapsed_all],
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 / rate,
+            "repeats": repeats, "ms_per_step_all_regions": [e / n * 1e3 for n, e in zip(region_steps, elapsed_all)],
             "region_start_unix_s": region_wall,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
             "config": {"workload": "%dx%d 5-level-pyramid SE3 tracking + semi-dense depth update, single sequence per GPU "
