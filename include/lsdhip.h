@@ -341,6 +341,16 @@ int lsdhip_host_se3f_step(const float increment[6], const float referenceToFrame
 int lsdhip_host_ldlt6(const float A[36], const float b[6], float x[6]);
 int lsdhip_host_sim3_step(const double increment[7], const double referenceToFrame[8], double out[8]);
 int lsdhip_host_ldlt7(const float A[49], const float b[7], float x[7]);
+/* test hooks for the device-side arithmetic of the LM steps: the inline routines the tracking kernels run, in one 64-lane workgroup per
+ * case, on n given systems (arrays of n cases, back to back).  They read no image.
+ * SE3 (lm_wave): inc = solution of (A with its diagonal * damp) inc = -b, (A, b) as LGS6::finish leaves them (SE3Tracker.cpp:356-359),
+ *   Tn = exp(inc) * T; poses as (qw, qx, qy, qz, tx, ty, tz).  A: n x 36, b: n x 6, damp: n, T / Tn: n x 7, inc: n x 6.
+ * Sim3 (k_sim3_fused): inc = solution of (A / nc with its diagonal * (1 + lambda)) inc = -b / nc, (A, b) the LGS7 before the division by
+ *   its constraint count nc (Sim3Tracker.cpp:221-224), Tn = exp(inc) * T in double; poses as (qw, qx, qy, qz, tx, ty, tz, s).
+ *   A: n x 49, b: n x 7, nconstraints / lambda: n, T / Tn: n x 8, inc: n x 7. */
+int lsdhip_devtest_se3f_lm_step(lsdhip_ctx* ctx, int n, const float* A, const float* b, const float* damp, const float* T, float* inc, float* Tn);
+int lsdhip_devtest_sim3_lm_step(lsdhip_ctx* ctx, int n, const float* A, const float* b, const double* nconstraints, const float* lambda,
+                                const double* T, float* inc, double* Tn);
 /* test hook: one evaluation at referenceToFrame on `level` with affine (a, b) */
 int lsdhip_sim3tracker_evaluate(lsdhip_sim3tracker* t, lsdhip_frame* keyframe, lsdhip_frame* frame, const double referenceToFrame[8],
                                 int level, float aff_a, float aff_b, lsdhip_sim3_eval_record* out);

@@ -503,6 +503,11 @@ long long lsd_m_record(lsdhip_ctx* c);             // record point on mstream ->
 int lsd_t_wait_m(lsdhip_ctx* c, long long seq);    // order `stream` behind M-sequence `seq`
 bool lsd_m_done(lsdhip_ctx* c, long long seq);     // has mstream passed M-sequence `seq`?  (never blocks)
 int lsd_sync_all(lsdhip_ctx* c);                   // both streams drained
+// The device test hooks (lsdhip_devtest_*): one device buffer for all inputs and outputs of a call, freed on every return path
+struct LsdDevBuf {
+  void* p = nullptr;
+  ~LsdDevBuf() { if (p) (void)hipFree(p); }
+};
 // Developer instrumentation of the pipeline bug hunt of round 4 (profiles/r04_notes.md §1a) — compiled only into the LSD_DEVTOOLS build
 // (lsd_slam_amd/build.py build_variant("devtools", ["LSD_DEVTOOLS"]), loaded through LSDHIP_LIB); the default library carries none of it:
 //   LSDHIP_PIPE_GATE=1      mapping stream holds until the next tracking job starts (lsd_gate_wait / lsd_gate_open)

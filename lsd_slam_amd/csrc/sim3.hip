@@ -949,6 +949,53 @@ __device__ __forceinline__ void gj7_solve_wave(const Sim3Track& J, Sim3Scratch& 
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
+// the exponential's transcendental values of the increment W.inc side by side: sin / cos of theta and of theta / 2 in two lanes,
+// exp(sigma) in a third
+__device__ __forceinline__ void sim3_trig_lanes(Sim3Scratch& W, const int tid) {
+  if (tid < 3) {
+    const double incd[7] = {0, 0, 0, (double)W.inc[3], (double)W.inc[4], (double)W.inc[5], (double)W.inc[6]};
+    const double theta = sim3_theta(incd);
+    if (tid < 2) {
+      double sn, cs;
+      sincos(tid == 0 ? theta : 0.5 * theta, &sn, &cs);
+      if (tid == 0) { W.trig.sin_theta = sn; W.trig.cos_theta = cs; }
+      else { W.trig.sin_half = sn; W.trig.cos_half = cs; }
+    } else {
+      W.trig.exp_sigma = exp(incd[6]);
+    }
+  }
+}
+// Test hook (lsdhip_devtest_sim3_lm_step): the proposal of k_sim3_fused on given normal equations, one 64-lane workgroup per case: the job
+// state holds (A, b, num_constraints, LM_lambda) where sim3_damped_entry reads them, then gj7_solve_wave, the trigonometric lanes and
+// sim3_propose_finish's product (without its divergence test)
+__global__ __launch_bounds__(64) void k_devtest_sim3_lm_step(const float* __restrict__ A, const float* __restrict__ b, const double* __restrict__ nc,
+                                                             const float* __restrict__ lambda, const double* __restrict__ T8, float* __restrict__ inc7,
+                                                             double* __restrict__ Tn8) {
+  __shared__ Sim3Track s_J;
+  __shared__ Sim3Scratch s_W;
+  const int tid = threadIdx.x, c = blockIdx.x;
+  if (tid < 49) s_J.cur.A[tid] = A[c * 49 + tid];
+  if (tid < 7) s_J.cur.b[tid] = b[c * 7 + tid];
+  if (tid == 0) {
+    s_J.cur.num_constraints = (size_t)nc[c];
+    s_J.LM_lambda = lambda[c];
+    const double* p = T8 + c * 8;
+    s_J.referenceToFrame.q = {p[0], p[1], p[2], p[3]};
+    s_J.referenceToFrame.t[0] = p[4]; s_J.referenceToFrame.t[1] = p[5]; s_J.referenceToFrame.t[2] = p[6];
+    s_J.referenceToFrame.s = p[7];
+  }
+  __syncthreads();
+  gj7_solve_wave(s_J, s_W, tid);
+  sim3_trig_lanes(s_W, tid);
+  __syncthreads();
+  if (tid == 0) {
+    const double incd[7] = {(double)s_W.inc[0], (double)s_W.inc[1], (double)s_W.inc[2], (double)s_W.inc[3], (double)s_W.inc[4], (double)s_W.inc[5], (double)s_W.inc[6]};
+    const Sim3H Tn = sim3_mul(sim3_exp(incd, s_W.trig), s_J.referenceToFrame);
+    for (int i = 0; i < 7; i++) inc7[c * 7 + i] = s_W.inc[i];
+    double* o = Tn8 + c * 8;
+    o[0] = Tn.q.w; o[1] = Tn.q.x; o[2] = Tn.q.y; o[3] = Tn.q.z; o[4] = Tn.t[0]; o[5] = Tn.t[1]; o[6] = Tn.t[2]; o[7] = Tn.s;
+  }
+}
 // One launch per evaluation, as k_track_step does it for the SE3 tracker: every workgroup of a job first brings the job's state up to
 // date — the totals of the evaluation the previous launch left in the rows of this launch's parity, the Levenberg-Marquardt decision
 // and the next request, computed redundantly (same inputs, same instructions, same result in every workgroup; workgroup 0 writes it
@@ -999,19 +1046,7 @@ __global__ __launch_bounds__(S3_BLOCK) void k_sim3_fused(const Sim3Set* __restri
     if (s_W.solve) {
       if (tid < 64) {
         gj7_solve_wave(s_J, s_W, tid);
-        // the exponential's transcendental values side by side: sin / cos of theta and of theta / 2 in two lanes, exp(sigma) in a third
-        if (tid < 3) {
-          const double incd[7] = {0, 0, 0, (double)s_W.inc[3], (double)s_W.inc[4], (double)s_W.inc[5], (double)s_W.inc[6]};
-          const double theta = sim3_theta(incd);
-          if (tid < 2) {
-            double sn, cs;
-            sincos(tid == 0 ? theta : 0.5 * theta, &sn, &cs);
-            if (tid == 0) { s_W.trig.sin_theta = sn; s_W.trig.cos_theta = cs; }
-            else { s_W.trig.sin_half = sn; s_W.trig.cos_half = cs; }
-          } else {
-            s_W.trig.exp_sigma = exp(incd[6]);
-          }
-        }
+        sim3_trig_lanes(s_W, tid);
       }
       __syncthreads();
       S3_MARK(4);
@@ -1264,4 +1299,32 @@ extern "C" int lsdhip_sim3tracker_track_batch(lsdhip_sim3tracker* t, int n, lsdh
   int rcAll = LSDHIP_OK;
   for (int j = 0; j < n; j++) if (jobs[j].rc == LSDHIP_DIVERGED) rcAll = LSDHIP_DIVERGED;
   return rcAll;
+}
+
+// Test hook: k_sim3_fused's proposal (gj7_solve_wave, the trigonometric lanes, exp(inc) * T in double) for n given systems, case k: inc
+// solves (A / nc with its diagonal * (1 + lambda)) inc = -b / nc for the LGS7 (A, b) before the division by num_constraints.  Reads no image.
+extern "C" int lsdhip_devtest_sim3_lm_step(lsdhip_ctx* c, int n, const float* A, const float* b, const double* nconstraints, const float* lambda,
+                                           const double* T, float* inc, double* Tn) {
+  if (!c || n <= 0 || !A || !b || !nconstraints || !lambda || !T || !inc || !Tn) return LSDHIP_E_ARG;
+  LSD_CTX_LOCK(c);
+  HIPCHK(hipSetDevice(c->device));
+  if (c->pipeline) { if (int rc = lsd_sync_all(c)) return rc; }
+  const size_t nd = (size_t)n * (1 + 8 + 8), nf = (size_t)n * (49 + 7 + 1 + 7);
+  LsdDevBuf buf;
+  HIPCHK(hipMalloc(&buf.p, nd * sizeof(double) + nf * sizeof(float)));
+  double* dd = (double*)buf.p;
+  double *dnc = dd, *dT = dnc + n, *dTn = dT + (size_t)n * 8;
+  float* df = (float*)(dd + nd);
+  float *dA = df, *db = dA + (size_t)n * 49, *dl = db + (size_t)n * 7, *dinc = dl + n;
+  HIPCHK(hipMemcpyAsync(dA, A, (size_t)n * 49 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(db, b, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dnc, nconstraints, (size_t)n * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dl, lambda, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dT, T, (size_t)n * 8 * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_devtest_sim3_lm_step, dim3(n), dim3(64), 0, c->stream, dA, db, dnc, dl, dT, dinc, dTn);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(inc, dinc, (size_t)n * 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(Tn, dTn, (size_t)n * 8 * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  return LSDHIP_OK;
 }

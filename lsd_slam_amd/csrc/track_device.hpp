@@ -274,9 +274,13 @@ __device__ __forceinline__ int rli(int v, int l) { return __builtin_amdgcn_readl
 // j < 7 columns) and the pivot row / pivot column read back through LDS: six steps of (write own element, read pivot, pivot-row
 // and pivot-column entries, divide, multiply-subtract) instead of the ~460 dependent lane-exchange instructions of the
 // row-per-lane LDL^T above (3800 -> ~1300 cycles of the single wave the whole launch waits for).  No pivoting: the matrix
-// is J^T W J with its diagonal scaled by (1 + lambda), symmetric positive definite.  Same solution as A.ldlt().solve(b) up
-// to rounding (tolerance-level, like every reduction feeding it); the pivoted LDL^T stays in pose_math.hpp for the host
-// paths and as the CPU-checked reference of this routine (tests/test_host_math_cpu.py).
+// is J^T W J with its diagonal scaled by (1 + lambda), symmetric positive SEMI-definite, and elimination without pivoting is
+// backward stable on it.  It is singular when a degree of freedom gets no constraint at all (a frame with gx = 0 everywhere
+// has a zero tx column in J): its row and column of A are exactly zero, elimination keeps them zero, and a pivot that is
+// exactly zero eliminates nothing and leaves its unknown at 0 — what Eigen's A.ldlt().solve(b) returns there (the pseudo-
+// inverse of D), where the unguarded division made all six increments NaN.  Same solution as the reference up to rounding
+// (tolerance-level, like every reduction feeding it).  The pivoted LDL^T in pose_math.hpp serves the host LM path; this
+// routine is checked on the device against float64 and against that host form (tests/test_lm_step_gpu.py).
 __device__ __forceinline__ void gj6_solve_wave(const float* A /*LDS, 6x6*/, const float* bvec /*LDS*/, const float damp, float* s_m /*LDS [6][8]*/,
                                                const int lane, float (&x)[6]) {
   const int i = lane >> 3, j = lane & 7;
@@ -293,16 +297,19 @@ __device__ __forceinline__ void gj6_solve_wave(const float* A /*LDS, 6x6*/, cons
     const float d = s_m[k * 8 + k], rk = s_m[k * 8 + (act ? j : 0)], ck = s_m[ii * 8 + k];
     const float f = ck * frcp(d);                  // 1-ulp reciprocal: the solve is tolerance-level by construction (see above)
     const float upd = m - f * rk;
-    m = (i == k) ? m : upd;
+    m = (i == k || d == 0.0f) ? m : upd;
     __builtin_amdgcn_wave_barrier();
   }
-  // now diagonal: x_i = rhs_i / m_ii
+  // now diagonal: x_i = rhs_i / m_ii (0 for a zero pivot)
   if (act) s_m[i * 8 + j] = m;
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 #pragma unroll
-  for (int r = 0; r < 6; r++) x[r] = s_m[r * 8 + 6] * frcp(s_m[r * 8 + r]);
+  for (int r = 0; r < 6; r++) {
+    const float d = s_m[r * 8 + r];
+    x[r] = d != 0.0f ? s_m[r * 8 + 6] * frcp(d) : 0.0f;
+  }
 }
 
 // sin / cos for the small angles of an LM increment: Taylor polynomials (|x| < 0.5: truncation error < 2e-10 relative),

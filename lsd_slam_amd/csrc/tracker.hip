@@ -1293,6 +1293,31 @@ __global__ __launch_bounds__(256) void k_overlap(const float* __restrict__ pos, 
   if (threadIdx.x == 0) out[0] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
 }
 
+// Test hook (lsdhip_devtest_se3f_lm_step): the proposal of lm_wave on given normal equations, one 64-lane workgroup per case.  A / b
+// sit in LDS where lm_wave finds them (TrackState::A / b, LGS6 after finish()), and the step is the same three calls.
+__global__ __launch_bounds__(64) void k_devtest_se3f_lm_step(const float* __restrict__ A, const float* __restrict__ b, const float* __restrict__ damp,
+                                                              const float* __restrict__ T7, float* __restrict__ inc6, float* __restrict__ Tn7) {
+  __shared__ TrackState S;
+  __shared__ LmShared sh;
+  const int lane = threadIdx.x, c = blockIdx.x;
+  if (lane < 36) S.A[lane] = A[c * 36 + lane];
+  if (lane < 6) S.b[lane] = b[c * 6 + lane];
+  __syncthreads();
+  const float* p = T7 + c * 7;
+  lsdm::SE3fH T;
+  T.q = {p[0], p[1], p[2], p[3]};
+  T.t[0] = p[4]; T.t[1] = p[5]; T.t[2] = p[6];
+  float inc[6];
+  gj6_solve_wave(S.A, S.b, damp[c], sh.gj, lane, inc);
+  const lsdm::SE3fH Tn = se3f_mul_wave(se3f_exp_wave(inc, lane), T, lane);
+  if (lane == 0) {
+#pragma unroll
+    for (int i = 0; i < 6; i++) inc6[c * 6 + i] = inc[i];
+    float* o = Tn7 + c * 7;
+    o[0] = Tn.q.w; o[1] = Tn.q.x; o[2] = Tn.q.y; o[3] = Tn.q.z; o[4] = Tn.t[0]; o[5] = Tn.t[1]; o[6] = Tn.t[2];
+  }
+}
+
 // ---------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------
@@ -2707,5 +2732,30 @@ extern "C" int lsdhip_tracker_check_overlap(lsdhip_tracker* t, const float* pos,
   HIPCHK(hipStreamSynchronize(c->stream));
   t->pointUsage = t->h_summary->sums[0] / (float)n;
   *usage_out = t->pointUsage;
+  return LSDHIP_OK;
+}
+
+// Test hook: lm_wave's proposal (gj6_solve_wave, se3f_exp_wave, se3f_mul_wave) for n given systems, case k: inc solves
+// (A with its diagonal * damp) inc = -b for the LGS6 (A, b) after finish(), Tn = exp(inc) * T.  Reads no image.
+extern "C" int lsdhip_devtest_se3f_lm_step(lsdhip_ctx* c, int n, const float* A, const float* b, const float* damp, const float* T,
+                                           float* inc, float* Tn) {
+  if (!c || n <= 0 || !A || !b || !damp || !T || !inc || !Tn) return LSDHIP_E_ARG;
+  LSD_CTX_LOCK(c);
+  HIPCHK(hipSetDevice(c->device));
+  if (c->pipeline) { if (int rc = lsd_sync_all(c)) return rc; }
+  const size_t nin = (size_t)n * (36 + 6 + 1 + 7), nout = (size_t)n * (6 + 7);
+  LsdDevBuf buf;
+  HIPCHK(hipMalloc(&buf.p, (nin + nout) * sizeof(float)));
+  float* d = (float*)buf.p;
+  float *dA = d, *db = dA + (size_t)n * 36, *ddamp = db + (size_t)n * 6, *dT = ddamp + n, *dinc = dT + (size_t)n * 7, *dTn = dinc + (size_t)n * 6;
+  HIPCHK(hipMemcpyAsync(dA, A, (size_t)n * 36 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(db, b, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(ddamp, damp, (size_t)n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  HIPCHK(hipMemcpyAsync(dT, T, (size_t)n * 7 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  hipLaunchKernelGGL(k_devtest_se3f_lm_step, dim3(n), dim3(64), 0, c->stream, dA, db, ddamp, dT, dinc, dTn);
+  HIPCHK(hipGetLastError());
+  HIPCHK(hipMemcpyAsync(inc, dinc, (size_t)n * 6 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipMemcpyAsync(Tn, dTn, (size_t)n * 7 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(hipStreamSynchronize(c->stream));
   return LSDHIP_OK;
 }

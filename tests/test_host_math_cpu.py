@@ -69,8 +69,9 @@ def test_ldlt7_solves_damped_normal_equations(L):
 
 
 def test_se3f_exp_and_ldlt6_match_the_oracle_bit_for_bit(L, oracle):
-    """pose_math.hpp (what the device LM runs) compiled for the host, against the oracle's Sophus SE3f restatement: same
-    operation order, contraction off on both sides"""
+    """pose_math.hpp (the host LM path's arithmetic; the device runs gj6_solve_wave / se3f_exp_wave instead, checked against float64
+    in tests/test_lm_step_gpu.py) compiled for the host, against the oracle's Sophus SE3f restatement: same operation order,
+    contraction off on both sides"""
     OL = oracle.lib()
     rng = np.random.default_rng(6)
     ident = np.array([1, 0, 0, 0, 0, 0, 0], np.float32)
@@ -90,3 +91,16 @@ def test_se3f_exp_and_ldlt6_match_the_oracle_bit_for_bit(L, oracle):
         assert L.lsdhip_host_ldlt6(A.ctypes.data, b.ctypes.data, x.ctypes.data) == 0
         OL.orc_ldlt6_solve(A.ravel(), b, xo)
         assert np.array_equal(x, xo), k                                     # pure +,-,*,/ in a fixed order: identical bits
+    # singular direction: a zero row / column leaves its unknown at 0 (Eigen's LDLT on a zero pivot), bit-equal to the oracle
+    for z in ((2,), (0, 5)):
+        J = rng.normal(size=(50, 6)) * rng.uniform(0.01, 50.0, 6)
+        A = (J.T @ J).astype(np.float32)
+        A[list(z), :] = 0
+        A[:, list(z)] = 0
+        A = np.ascontiguousarray(A)
+        b = rng.normal(size=6).astype(np.float32)
+        x, xo = np.zeros(6, np.float32), np.zeros(6, np.float32)
+        assert L.lsdhip_host_ldlt6(A.ctypes.data, b.ctypes.data, x.ctypes.data) == 0
+        OL.orc_ldlt6_solve(A.ravel(), b, xo)
+        assert np.all(np.isfinite(x)) and np.all(x[list(z)] == 0), (z, x)
+        assert np.array_equal(x, xo), z
