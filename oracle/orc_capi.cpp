@@ -306,6 +306,21 @@ void orc_sim3tracker_track(void* t, void* ref, void* frame, const double init_fr
 void orc_sim3tracker_evaluate(void* t, void* ref, void* frame, const double refToFrame[8], int level, float a, float b, Sim3EvalRecord* out) {
   ((Sim3Tracker*)t)->evaluate((TrackingReference*)ref, F(frame), sim3_in(refToFrame), level, a, b, out);
 }
+// which: 0 x 1 y 2 z 3 dx 4 dy 5 residual_p 6 residual_d 7 d 8 idepthVar 9 warped_idepthVar 10 weight_p 11 weight_d: the buffers of
+// the last calcSim3Buffers / calcSim3WeightsAndResidual; returns buf_warped_size
+int orc_sim3tracker_buffer(void* t, int which, float* out) {
+  Sim3Tracker* tr = (Sim3Tracker*)t;
+  float* bufs[12] = {tr->buf_warped_x, tr->buf_warped_y, tr->buf_warped_z, tr->buf_warped_dx, tr->buf_warped_dy, tr->buf_warped_residual,
+                     tr->buf_residual_d, tr->buf_d, tr->buf_idepthVar, tr->buf_warped_idepthVar, tr->buf_weight_p, tr->buf_weight_d};
+  if (which < 0 || which >= 12) return -1;
+  if (out) memcpy(out, bufs[which], sizeof(float) * tr->buf_warped_size);
+  return tr->buf_warped_size;
+}
+// the affine (a, b) the buffers behind the last system were computed with (the last calcSim3LGS of trackFrameSim3 / evaluate)
+void orc_sim3tracker_system_affine(void* t, float out[2]) {
+  Sim3Tracker* tr = (Sim3Tracker*)t;
+  out[0] = tr->lgs_affine_a; out[1] = tr->lgs_affine_b;
+}
 void orc_sim3_exp(const double a[7], double out[8]) {
   Sim3d T = sim3_exp(a);
   out[0] = T.q.w; out[1] = T.q.x; out[2] = T.q.y; out[3] = T.q.z; out[4] = T.t[0]; out[5] = T.t[1]; out[6] = T.t[2]; out[7] = T.s;

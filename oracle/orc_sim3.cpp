@@ -199,6 +199,7 @@ void Sim3Tracker::calcSim3Buffers(TrackingReference* reference, Frame* frame, co
   float xRoll0, xRoll1, yRoll0, yRoll1;
   roll_matrix(rotMatUnscaled, xRoll0, xRoll1, yRoll0, yRoll1);
 
+  buf_affine_a = affineEstimation_a; buf_affine_b = affineEstimation_b;
   const int refNum = reference->numData[level];
   const float* refPoint = reference->posData[level].data();
   const float* refColVar = reference->colorAndVarData[level].data();
@@ -410,6 +411,7 @@ Sim3ResidualStruct Sim3Tracker::callWeights(const Sim3d& T) {
   return calcSim3WeightsAndResidualSSE(T, mode == TRACKER_SSE_EXACT_RCP);
 }
 void Sim3Tracker::callLGS(LGS7s& ls7) {
+  lgs_affine_a = buf_affine_a; lgs_affine_b = buf_affine_b;
   if (mode == TRACKER_SCALAR) calcSim3LGS(ls7);
   else calcSim3LGSSSE(ls7, mode == TRACKER_SSE_EXACT_RCP);
 }

@@ -44,6 +44,9 @@ class Sim3Tracker {
   float *buf_warped_residual, *buf_warped_dx, *buf_warped_dy, *buf_warped_x, *buf_warped_y, *buf_warped_z, *buf_d, *buf_residual_d,
       *buf_idepthVar, *buf_warped_idepthVar, *buf_weight_p, *buf_weight_d;
   int buf_warped_size = 0;
+  // test instrumentation (no arithmetic): the affine pair the current buffers were computed with, and the pair behind the buffers of the
+  // last system (callLGS) — the one lastSim3Hessian comes from
+  float buf_affine_a = 1, buf_affine_b = 0, lgs_affine_a = 1, lgs_affine_b = 0;
 
  private:
   void calcSim3Buffers(TrackingReference* reference, Frame* frame, const Sim3d& referenceToFrame, int level);

@@ -184,6 +184,8 @@ def lib(fast=False, ref=None, native=False):
         "orc_sim3tracker_set_max_its": (None, [vp, ip]),
         "orc_sim3tracker_track": (None, [vp, vp, vp, dp, i, i, C.POINTER(Sim3Result)]),
         "orc_sim3tracker_evaluate": (None, [vp, vp, vp, dp, i, f, f, C.POINTER(Sim3EvalRecord)]),
+        "orc_sim3tracker_buffer": (i, [vp, i, vp]),
+        "orc_sim3tracker_system_affine": (None, [vp, fp]),
         "orc_sim3_exp": (None, [dp, dp]),
         "orc_now_seconds": (d, []),
     }
@@ -389,6 +391,22 @@ class Sim3Tracker:
         self.L.orc_sim3tracker_evaluate(self.h_, ref.h_, frame.h_, np.ascontiguousarray(refToFrame8, dtype=np.float64), level, a, b,
                                         C.byref(r))
         return r
+
+    BUFFERS = ["x", "y", "z", "dx", "dy", "residual_p", "residual_d", "d", "idepthVar", "warped_idepthVar", "weight_p", "weight_d"]
+
+    def buffer(self, name):
+        """a per-point buffer of the last evaluation (buf_warped_size entries, x-outer / y-inner order of the in-image points)"""
+        k = self.BUFFERS.index(name)
+        n = self.L.orc_sim3tracker_buffer(self.h_, k, None)
+        out = np.zeros(n, np.float32)
+        self.L.orc_sim3tracker_buffer(self.h_, k, out.ctypes.data)
+        return out
+
+    def system_affine(self):
+        """(a, b) the buffers behind the last 7x7 system were computed with: lastSim3Hessian's pair after track()"""
+        out = np.zeros(2, np.float32)
+        self.L.orc_sim3tracker_system_affine(self.h_, out)
+        return float(out[0]), float(out[1])
 
 
 def sim3_exp(a7):

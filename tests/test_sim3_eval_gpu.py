@@ -1,0 +1,219 @@
+"""The device's Sim3 evaluation (sim3.hip: sim3_eval_pixel, sim3_eval_strip, sim3_totals) entry by entry against float64 sums of the
+oracle's per-point float32 terms (tests/sim3_terms.py, checked against float64 formulas in test_sim3_terms_cpu.py).
+
+test_sim3_gpu.py compares A, b and lastSim3Hessian relative to their largest entry.  The depth block the Sim3 system adds on rows /
+columns 2, 3, 4, 6 is orders of magnitude smaller than the photometric block, so an error in it, or in b[5], can hide under that
+tolerance.  Here every entry of A (49) and b (7), sumResP and sumResD must satisfy
+
+    |device - sum64| <= gamma * EPS * sum|terms| + 1e-30
+
+with sum64 / sum|terms| the float64 sums of the terms of the first (M // 4) * 4 points (the SSE tail drop), and sum|terms| also taking
+the three points the device adds and then takes out again (the tail) at the size of the largest term.  gamma follows the device's
+summation tree, depth of one term on its way into the total:
+    ppl - 1 sequential additions in a lane (ppl = ceil(pixels / 32768) pixels per lane), a 64-long LDS run (63), 4 slices (3),
+    ceil(R / 2) + 1 in the two interleaved accumulators of a slice of R = ceil(nblocks / 16) strip rows, 16 slices (15), the subtraction
+    of up to 3 tail points (3), the 6x6 + 4x4 sum of LGS7::initializeFrom (1), and 4 roundings per term (the device forms its own
+    terms; they follow the same operation order).  sumResP / sumResD add wh * (|r| sqrt(w))^2, the terms here are (r w) r: 6 more.
+Integers are exact: warped_size, numTermsD / numTermsP, num_constraints.
+
+The fused path (k_sim3_fused, which trackFrameSim3 and the batches run): lastSim3Hessian against the float64 sums of the oracle's terms
+at the returned transformation (inverted in double) on the final level, with the affine pair of the reference's last calcSim3LGS."""
+import numpy as np
+import pytest
+
+from sim3_terms import EPS, scene_pair, sim3_mul, sse_terms, sums64
+
+pytestmark = pytest.mark.gpu
+
+ROLL = np.array([np.cos(0.15), 0.03 * np.sin(0.15), -0.02 * np.sin(0.15), np.sin(0.15), 0, 0, 0, 1.0])   # ~0.3 rad about z, tilted
+ROLL[:4] /= np.linalg.norm(ROLL[:4])
+
+
+@pytest.fixture(scope="module")
+def hip():
+    import lsd_slam_amd as la
+    return la
+
+
+def strips(npix):
+    """sim3_strips: (pixels per lane, strips)"""
+    ppl = -(-npix // (256 * 128))
+    return ppl, -(-npix // (256 * ppl))
+
+
+def gamma(npix):
+    ppl, nblocks = strips(npix)
+    R = -(-nblocks // 16)
+    return (ppl - 1) + 63 + 3 + (-(-R // 2) + 1) + 15 + 3 + 1 + 4
+
+
+class Case:
+    def __init__(self, oracle, hip, w, h, k, scale, holes=False, no_depth=False):
+        P = scene_pair(oracle, w, h, k, scale, holes)
+        if no_depth:                    # the frame has depth, but no warped point lands on it
+            d = np.zeros_like(P["depthB"]); d[0, 0] = P["depthB"][0, 0]; P["depthB"] = d
+        self.P, self.w, self.h = P, w, h
+        self.fa, self.fb = oracle.Frame(0, P["imgA"], P["K"]), oracle.Frame(k, P["imgB"], P["K"])
+        self.fa.set_depth_gt(P["depthA"]); self.fb.set_depth_gt(P["depthB"])
+        self.ra = oracle.TrackingReference(); self.ra.import_frame(self.fa)
+        self.tro = oracle.Sim3Tracker(w, h, P["K"], mode=oracle.SSE_EXACT_RCP)
+        self.ctx = hip.Context(w, h, P["K"])
+        self.ga, self.gb = hip.Frame(self.ctx, 0, P["imgA"]), hip.Frame(self.ctx, k, P["imgB"])
+        self.ga.setDepthFromGroundTruth(P["depthA"]); self.gb.setDepthFromGroundTruth(P["depthB"])
+        self.trg = hip.Sim3Tracker(self.ctx)
+
+
+def hold(tag, A, b, sumResP, sumResD, ro_size, T, gam, worst):
+    """per-entry check of a device system against the float64 sums of the terms T (b, sumResP, sumResD: None to leave out);
+    worst[tag] = max |device - sum64| / (EPS sum|terms|)"""
+    A64, Aa, b64, ba, rP, rPa, rD, rDa = sums64(T)
+    n = T["n"]
+    tail = 0 if ro_size == n else 3
+    big = {k: (np.abs(v.astype(np.float64)).max() if len(v) else 0.0) for k, v in T.items() if isinstance(k, tuple) or k in ("resP", "resD")}
+    Amag, bmag = Aa.copy(), ba.copy()
+    for key, m in big.items():
+        if isinstance(key, tuple) and len(key) == 3:
+            Amag[key[1], key[2]] += tail * m
+            if key[1] != key[2]:
+                Amag[key[2], key[1]] += tail * m
+        elif isinstance(key, tuple):
+            bmag[key[1]] += tail * m
+    Ag, bg = np.array(A, np.float64).reshape(7, 7), np.array(b if b is not None else np.zeros(7), np.float64)
+    rows = [("A", Ag.ravel(), A64.ravel(), Amag.ravel(), gam)]
+    if b is not None:
+        rows += [("b", bg, b64, bmag, gam),
+                 ("sumResP", np.array([sumResP]), np.array([rP]), np.array([rPa + tail * big["resP"]]), gam + 6),
+                 ("sumResD", np.array([sumResD]), np.array([rD]), np.array([rDa + tail * big["resD"]]), gam + 6)]
+    for name, got, want, mag, g in rows:
+        err = np.abs(got - want)
+        bound = g * EPS * mag + 1e-30
+        bad = ~(err <= bound)
+        assert not bad.any(), "%s %s: entries %s outside gamma %d: device %r float64 %r sum|terms| %r" % (
+            tag, name, np.flatnonzero(bad).tolist(), g, got[bad], want[bad], mag[bad])
+        r = float((err / (EPS * np.maximum(mag, 1e-300))).max())
+        worst[tag] = max(worst.get(tag, 0.0), r if np.isfinite(r) else 0.0)
+
+
+def evaluate_and_hold(C, T, level, a, b, tag, worst, seen=None):
+    ro = C.tro.evaluate(C.ra, C.fb, T, level, a, b)
+    rg = C.trg.evaluate(C.ga, C.gb, T, level, a, b)
+    assert rg.warped_size == ro.warped_size, tag
+    if ro.warped_size < 8:
+        return None
+    assert rg.numTermsD == ro.numTermsD and rg.numTermsP == ro.numTermsP == (ro.warped_size // 4) * 4, tag
+    assert rg.num_constraints == ro.num_constraints == 10 * (ro.warped_size // 4), tag
+    Tm = sse_terms(C.tro)
+    assert Tm["n"] == ro.numTermsP
+    wl, hl = C.w >> level, C.h >> level
+    g = gamma(wl * hl)
+    hold(tag, rg.A, rg.b, rg.sumResP, rg.sumResD, ro.warped_size, Tm, g, worst)
+    assert np.isnan(rg.meanD) == np.isnan(ro.meanD), tag
+    if seen is not None:
+        seen.add(ro.warped_size % 4)
+    return ro, rg, g
+
+
+CASES = [  # w, h, holes, affine, scale, pose
+    (160, 128, True, (1.0, 0.0), 1.1, "near"),
+    (176, 144, False, (0.97, 1.5), 0.8, "roll"),
+    (320, 240, False, (0.97, 1.5), 1.25, "huber"),
+    (320, 240, True, (1.0, 0.0), 1.1, "roll"),
+    (640, 480, True, (0.97, 1.5), 1.1, "near"),
+    (1280, 1024, False, (1.0, 0.0), 1.25, "roll"),
+]
+
+
+def pose_of(exp, name):
+    T0 = np.array(exp, float)
+    from oracle.pyoracle import sim3_inv
+    T = sim3_inv(T0)
+    if name == "huber":
+        T[4:7] += [0.03, -0.025, 0.02]; T[7] *= 0.97
+        return T
+    T[4:7] += [0.004, -0.003, 0.002]; T[7] *= 1.03
+    return sim3_mul(ROLL, T) if name == "roll" else T
+
+
+@pytest.mark.parametrize("w,h,holes,aff,scale,pose", CASES)
+def test_sim3_evaluation_per_entry(oracle, hip, w, h, holes, aff, scale, pose):
+    """every level with at least 8 in-image points (level 4 included), per entry against float64 sums of the terms"""
+    C = Case(oracle, hip, w, h, 2, scale, holes)
+    T = pose_of(C.P["exp"], pose)
+    worst, out, levels = {}, [], []
+    for level in range(5):
+        tag = "%dx%d L%d" % (w, h, level)
+        r = evaluate_and_hold(C, T, level, aff[0], aff[1], tag, worst)
+        if r is not None:
+            levels.append(level)
+            out.append("L%d M=%d ppl=%d gamma=%d worst %.1f" % (level, r[0].warped_size, strips((w >> level) * (h >> level))[0], r[2], worst[tag]))
+    assert 4 in levels, "level 4 not evaluated"
+    print("%dx%d %s %s: %s" % (w, h, pose, "holes" if holes else "dense", "; ".join(out)))
+
+
+def test_sim3_evaluation_tails(oracle, hip):
+    """M % 4 in {1, 2, 3}: the tail the device adds and subtracts again, at strip boundaries of partial strips (176 x 144)"""
+    seen, worst = set(), {}
+    C = None
+    for k in (1, 2, 3, 4, 5):
+        C = Case(oracle, hip, 176, 144, k, 1.0, holes=True)
+        T = pose_of(C.P["exp"], "near")
+        for level in (0, 1, 2, 3):
+            evaluate_and_hold(C, T, level, 1.0, 0.0, "176x144 k%d L%d" % (k, level), worst, seen)
+    assert {1, 2, 3} <= seen, seen
+    print("tails %s, worst ratio %.1f" % (sorted(seen), max(worst.values())))
+
+
+def test_sim3_evaluation_without_depth_where_points_land(oracle, hip):
+    """no depth term at all: row / column 6 and b[6] exactly 0, numTermsD 0, sumResD 0, meanD NaN exactly when the oracle's is"""
+    C = Case(oracle, hip, 320, 240, 2, 1.1, no_depth=True)
+    T = pose_of(C.P["exp"], "near")
+    worst = {}
+    for level in (1, 2, 3):
+        ro, rg, _ = evaluate_and_hold(C, T, level, 0.97, 1.5, "no depth L%d" % level, worst)
+        A = np.array(rg.A).reshape(7, 7)
+        assert rg.numTermsD == ro.numTermsD == 0
+        assert np.all(A[6] == 0) and np.all(A[:, 6] == 0) and rg.b[6] == 0 and rg.sumResD == 0
+        assert np.isnan(ro.meanD) and np.isnan(rg.meanD)
+    print("no depth: worst ratio %.1f" % max(worst.values()))
+
+
+def cast_moves(T):
+    """does a round trip through the inverse move the float32 cast of s R or t?"""
+    from oracle.pyoracle import quat_to_rot, sim3_inv
+    T2 = sim3_inv(sim3_inv(T))
+
+    def casts(X):
+        return np.concatenate([(X[7] * quat_to_rot(X[:4])).astype(np.float32).ravel(), np.asarray(X[4:7]).astype(np.float32)])
+    return not np.array_equal(casts(T), casts(T2))
+
+
+@pytest.mark.parametrize("w,h,first,last", [(320, 240, 3, 1), (1280, 1024, 3, 1)])
+def test_sim3_fused_hessian_per_entry(oracle, hip, w, h, first, last):
+    """trackFrameSim3 (k_sim3_fused): lastSim3Hessian per entry.  The system is the one of the last calcSim3LGS: the evaluation at the
+    accepted transformation, recomputed on the final level when the last evaluation was accepted (Sim3Tracker.cpp:354-360).  Its buffers
+    were computed with the affine pair in effect at that calcSim3Buffers call: after the final re-evaluation, the pair the call returns;
+    when the last step was rejected, the pair before the last acceptance's update.  The oracle run of the same call records which
+    (Sim3Tracker::lgs_affine_a / _b); both runs take the same steps (same number of evaluations)."""
+    C = Case(oracle, hip, w, h, 3, 1.25)
+    init = C.P["exp"].copy()
+    init[7] = 1.0
+    ro = C.tro.track(C.ra, C.fb, init, first, last)
+    a, b = C.tro.system_affine()
+    got, rg = C.trg.trackFrameSim3(C.ga, C.gb, init, first, last)
+    assert not ro.diverged and not C.trg.diverged
+    assert rg.numEvaluations == ro.numEvaluations
+    from oracle.pyoracle import sim3_inv
+    T = sim3_inv(np.array(got))
+    # a cast that moves under the round trip changes the warp of every point by up to an ulp of its coordinates: the interpolated
+    # gradients move with it by (image curvature) x (pixel shift), not a rounding of the term; such a case is held to 4x the bound
+    widen = 4 if cast_moves(T) else 1
+    ro2 = C.tro.evaluate(C.ra, C.fb, T, last, a, b)
+    Tm = sse_terms(C.tro)
+    g = widen * gamma((w >> last) * (h >> last))
+    worst = {}
+    H = np.array(rg.lastSim3Hessian)
+    assert np.allclose(H, H.T, rtol=0, atol=0)
+    hold("fused %dx%d L%d" % (w, h, last), H, None, None, None, ro2.warped_size, Tm, g, worst)
+    print("fused %dx%d levels %d..%d: %d evaluations, affine (%.4f, %.3f), ppl %d, gamma %d%s, worst ratio %.1f" % (
+        w, h, first, last, rg.numEvaluations, a, b, strips((w >> last) * (h >> last))[0], g, " (widened)" if widen > 1 else "",
+        max(worst.values())))
