@@ -233,7 +233,7 @@ int lsdhip_tracker_exec_stats(const lsdhip_tracker* t, int out[8]);
  * other values are rounded down to a multiple of 8 (one band of tiles per XCD), values below 8 up to 8.  The per-level overrides of
  * the environment (LSDHIP_SPEC_LEVELS) are cleared by this call. */
 int lsdhip_tracker_set_speculation(lsdhip_tracker* t, int trials, int finestLevelWorkgroups);
-/* Throughput-mode batches (lsdhip_tracker_track_batch): from `minJobs` jobs on, the levels of at most 4800 pixels and 4608 valid
+/* Throughput-mode batches (lsdhip_tracker_track_batch): from `minJobs` jobs on, the levels of at most 4800 pixels and 4544 valid
  * reference points that do not write refPixelWasGood (levels 4 and 3 of a 640x480 job) are walked by ONE workgroup per job — the tracked
  * frame's texel plane of the level staged in LDS (the tile of the bilinear taps), the level's reference points in registers, the whole LM
  * loop of the level in that workgroup — ahead of the lock-step rounds for the larger levels: same per-point arithmetic and LM decisions,
@@ -284,6 +284,16 @@ int lsdhip_tracker_track_batch(lsdhip_tracker* t, int n, lsdhip_frame** keyframe
 int lsdhip_tracker_evaluate(lsdhip_tracker* t, lsdhip_frame* keyframe, lsdhip_frame* frame,
                             const float referenceToFrame[7], int level, float affine_a, float affine_b,
                             lsdhip_residual_record* out);
+/* test hook for the batched evaluation forms: K1+K2+K3 once per job, at fixed poses, through the launches
+ * lsdhip_tracker_track_batch runs for n jobs (fewer than 8: the small-batch form; from 8: throughput-mode strips; from the tracker's
+ * coarse-level job count on, k_track_solo on the levels it takes).  Job j evaluates keyframes[j] against frames[j] at
+ * referenceToFrame[7 j ..] (float (qw,qx,qy,qz,tx,ty,tz)) on `level` (1..4) with affine (affine[2 j], affine[2 j + 1]); at level 1 the
+ * job writes frames[j]'s refPixelWasGood.  out: n records as lsdhip_tracker_evaluate fills them.  form (n x 2, may be NULL):
+ * form[2 j] = 1 if job j's evaluation ran in k_track_solo, form[2 j + 1] = the level's strip size in pixels (0 outside throughput mode).
+ * No tracker state that trackFrame reads is changed. */
+int lsdhip_tracker_evaluate_batch(lsdhip_tracker* t, int n, lsdhip_frame** keyframes, lsdhip_frame** frames,
+                                  const float* referenceToFrame, const float* affine, int level, lsdhip_residual_record* out,
+                                  int* form);
 /* SE3Tracker::trackFrameOnPermaref (SE3Tracker.cpp:162-272) / checkPermaRefOverlap (:121-157) on an explicit
  * level-4 point cloud (Frame::setPermaRef data, Frame.cpp:149-174). */
 int lsdhip_tracker_track_permaref(lsdhip_tracker* t, const float* pos3_host, const float* colorAndVar2_host, int n,

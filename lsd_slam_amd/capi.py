@@ -143,6 +143,7 @@ def _signatures():
         "lsdhip_tracker_track_batch": (i, [vp, i, pvp, pvp, vp, C.POINTER(TrackResult)]),
         "lsdhip_tracker_eval_throughput": (i, [vp, i, pvp, pvp, vp, i, i, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
         "lsdhip_tracker_evaluate": (i, [vp, vp, vp, vp, i, f, f, C.POINTER(ResidualRecord)]),
+        "lsdhip_tracker_evaluate_batch": (i, [vp, i, pvp, pvp, vp, vp, i, C.POINTER(ResidualRecord), vp]),
         "lsdhip_tracker_track_permaref": (i, [vp, vp, vp, i, vp, vp, C.POINTER(TrackResult)]),
         "lsdhip_tracker_track_permaref_batch": (i, [vp, i, vp, vp, vp, pvp, vp, C.POINTER(TrackResult)]),
         "lsdhip_tracker_check_overlap": (i, [vp, vp, i, vp, C.POINTER(C.c_float)]),

@@ -985,6 +985,17 @@ __global__ __launch_bounds__(BLOCK) void k_track_step(TrackJob jobv, const Track
 #define LSD_SOLO_TRIPS 9          // x 512 lanes = 4608 points >= the (w - 2)(h - 2) interior of any level of at most 4800 pixels
 #define LSD_SOLO_MAX_PTS (LSD_SOLO_TRIPS * 512)
 #define LSD_SOLO_LDS_PTS 4544     // (w - 2)(h - 2) <= w h - 4 sqrt(w h) + 4 <= 4527 interior pixels of a level of at most 4800
+static_assert(LSD_SOLO_LDS_PTS <= LSD_SOLO_MAX_PTS, "every point of the LDS lists has a register slot");
+// the largest interior (w - 2)(h - 2) of a level of at most LSD_SOLO_MAX_PX pixels (w, h >= 3)
+constexpr int lsd_solo_max_interior() {
+  int best = 0;
+  for (int w = 3; w <= LSD_SOLO_MAX_PX / 3; w++) {
+    const int h = LSD_SOLO_MAX_PX / w;
+    if ((w - 2) * (h - 2) > best) best = (w - 2) * (h - 2);
+  }
+  return best;
+}
+static_assert(lsd_solo_max_interior() <= LSD_SOLO_LDS_PTS, "the dense interior of any level k_track_solo takes fits its LDS lists");
 // Worth it from this many jobs per batch: one workgroup per job walks its coarse levels in about the time the lock-step rounds take, on
 // n CUs instead of the chip — a gain where other work (the mapping stream of the S-sequence loop) wants the other CUs, a small loss for
 // a few jobs that have the chip to themselves (profiles/r06_notes.md section 21).
@@ -1665,6 +1676,27 @@ struct EvalOut {       // what one evaluation leaves behind, in the reference's 
   double num_constraints;
 };
 
+// an evaluation's summary in the reference's terms (the normalisation of LGS6::finish, LGSX.h:319-325)
+static void eval_out_of(const TrackSummary* S, EvalOut* eo) {
+  const float* r = S->sums;
+  int M = (int)r[RS_M];
+  eo->warped_size = M;
+  eo->retval = r[RS_SUMRES2] / r[RS_GOOD];
+  eo->weightedError = r[RS_WERR] / ((M >> 2) << 2);
+  size_t num_constraints = (size_t)6 * (size_t)(M >> 2);
+  float n = (float)num_constraints;
+  int k = RS_A0;
+  for (int i = 0; i < 6; i++)
+    for (int j = i; j < 6; j++, k++) {
+      float v = (0.0f + r[k]) / n;
+      eo->A[i * 6 + j] = v;
+      eo->A[j * 6 + i] = v;
+    }
+  for (int i = 0; i < 6; i++) eo->b[i] = (0.0f - r[RS_B0 + i]) / n;
+  eo->lsError = (0.0f + r[RS_ERR]) / n;
+  eo->num_constraints = (double)num_constraints;
+}
+
 // one evaluation with a host round trip (evalOnly job): kernel-level parity hook and host-LM debugging path
 static int evaluate_pose(lsdhip_tracker* t, TrackJob& job, const lsdm::SE3fH& T, int level, EvalOut* eo) {
   lsdhip_ctx* c = t->ctx;
@@ -1686,7 +1718,6 @@ static int evaluate_pose(lsdhip_tracker* t, TrackJob& job, const lsdm::SE3fH& T,
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   const TrackSummary* S = t->h_summary;
-  const float* r = S->sums;
   if (c->prof_on) {
     float ms = 0;
     HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
@@ -1697,23 +1728,21 @@ static int evaluate_pose(lsdhip_tracker* t, TrackJob& job, const lsdm::SE3fH& T,
   t->numEvaluations++;
   t->pointUsage = S->pointUsage; t->lastGoodCount = S->goodCount; t->lastBadCount = S->badCount; t->lastMeanRes = S->meanRes;
   t->affineEstimation_a_lastIt = S->aff_a_lastIt; t->affineEstimation_b_lastIt = S->aff_b_lastIt;
-  int M = (int)r[RS_M];
-  eo->warped_size = M;
-  eo->retval = r[RS_SUMRES2] / r[RS_GOOD];
-  eo->weightedError = r[RS_WERR] / ((M >> 2) << 2);
-  size_t num_constraints = (size_t)6 * (size_t)(M >> 2);
-  float n = (float)num_constraints;
-  int k = RS_A0;
-  for (int i = 0; i < 6; i++)
-    for (int j = i; j < 6; j++, k++) {
-      float v = (0.0f + r[k]) / n;
-      eo->A[i * 6 + j] = v;
-      eo->A[j * 6 + i] = v;
-    }
-  for (int i = 0; i < 6; i++) eo->b[i] = (0.0f - r[RS_B0 + i]) / n;
-  eo->lsError = (0.0f + r[RS_ERR]) / n;
-  eo->num_constraints = (double)num_constraints;
+  eval_out_of(S, eo);
   return LSDHIP_OK;
+}
+
+// the record of one evaluation (lsdhip_tracker_evaluate, lsdhip_tracker_evaluate_batch)
+static void record_of(const TrackSummary* S, lsdhip_residual_record* out) {
+  EvalOut ev;
+  eval_out_of(S, &ev);
+  out->warped_size = ev.warped_size;
+  out->goodCount = S->goodCount; out->badCount = S->badCount; out->pointUsage = S->pointUsage;
+  out->meanRes = S->meanRes; out->retval = ev.retval;
+  out->affine_a_lastIt = S->aff_a_lastIt; out->affine_b_lastIt = S->aff_b_lastIt;
+  out->weightedError = ev.weightedError;
+  memcpy(out->A, ev.A, sizeof(ev.A)); memcpy(out->b, ev.b, sizeof(ev.b));
+  out->lsError = ev.lsError; out->num_constraints = ev.num_constraints;
 }
 
 // host-driven LM for one level (debugging path): SE3Tracker.cpp:323-449
@@ -2430,7 +2459,7 @@ extern "C" void lsdhip_build_defaults(lsdhip_build_defaults_t* out) {
   out->spec_workgroups = LSD_SPEC_CAP_WORKGROUPS; out->spec_workgroups_above_pixels = LSD_SPEC_CAP_ABOVE_PX;
   out->spec_trials_max = LSD_SPEC_MAX;
   out->batch_throughput_min_jobs = LSD_BATCH_THROUGHPUT_MIN_JOBS; out->batch_strip_workgroups = LSD_BATCH_STRIP_WORKGROUPS;
-  out->batch_coarse_min_jobs = LSD_SOLO_MIN_JOBS; out->batch_coarse_max_pixels = LSD_SOLO_MAX_PX; out->batch_coarse_max_points = LSD_SOLO_MAX_PTS;
+  out->batch_coarse_min_jobs = LSD_SOLO_MIN_JOBS; out->batch_coarse_max_pixels = LSD_SOLO_MAX_PX; out->batch_coarse_max_points = LSD_SOLO_LDS_PTS;
 }
 
 extern "C" int lsdhip_tracker_track_batch(lsdhip_tracker* t, int n, lsdhip_frame** keyframes, lsdhip_frame** frames,
@@ -2587,13 +2616,69 @@ extern "C" int lsdhip_tracker_evaluate(lsdhip_tracker* t, lsdhip_frame* kf, lsdh
   EvalOut ev;
   int rc = evaluate_pose(t, job, T, level, &ev);
   if (rc) return rc;
-  out->warped_size = ev.warped_size;
-  out->goodCount = t->lastGoodCount; out->badCount = t->lastBadCount; out->pointUsage = t->pointUsage;
-  out->meanRes = t->lastMeanRes; out->retval = ev.retval;
-  out->affine_a_lastIt = t->affineEstimation_a_lastIt; out->affine_b_lastIt = t->affineEstimation_b_lastIt;
-  out->weightedError = ev.weightedError;
-  memcpy(out->A, ev.A, sizeof(ev.A)); memcpy(out->b, ev.b, sizeof(ev.b));
-  out->lsError = ev.lsError; out->num_constraints = ev.num_constraints;
+  record_of(t->h_summary, out);
+  return LSDHIP_OK;
+}
+
+// Test hook: one evaluation per job through the launches of a batch (batch_run: the small-batch form, throughput-mode strips, k_track_solo
+// on the levels it takes), each job an evalOnly job at its own pose and affine pair.  The tracker's LM state, its counters and the
+// round budget of later batches are left as they were.
+extern "C" int lsdhip_tracker_evaluate_batch(lsdhip_tracker* t, int n, lsdhip_frame** keyframes, lsdhip_frame** frames, const float* refToFrame,
+                                             const float* affine, int level, lsdhip_residual_record* out, int* form) {
+  if (!t || n <= 0 || !keyframes || !frames || !refToFrame || !affine || !out) return LSDHIP_E_ARG;
+  if (level < LSD_TRACK_MIN_LEVEL || level >= LSD_TRACK_MAX_LEVEL) {
+    lsd_set_error("lsdhip_tracker_evaluate_batch: level %d is not a tracking level (%d..%d)", level, LSD_TRACK_MIN_LEVEL, LSD_TRACK_MAX_LEVEL - 1);
+    return LSDHIP_E_ARG;
+  }
+  lsdhip_ctx* c = t->ctx;
+  LSD_CTX_LOCK(c);
+  LsdTrackJobScope tjob_(c, true);
+  if (tjob_.rc) return tjob_.rc;
+  HIPCHK(hipSetDevice(c->device));
+  for (int j = 0; j < n; j++) {
+    if (!keyframes[j] || !frames[j]) return LSDHIP_E_ARG;
+    if (!keyframes[j]->hasIDepth) { lsd_set_error("lsdhip_tracker_evaluate_batch: keyframe of job %d has no depth", j); return LSDHIP_E_STATE; }
+  }
+  if (n >= LSD_BATCH_THROUGHPUT_MIN_JOBS) { if (int rcb = lsd_frames_require_ref_blocks(keyframes, n, c->stream)) return rcb; }   // the strips read them
+  int rc = batch_reserve(t, n);
+  if (rc) return rc;
+  batch_begin(t, n);
+  for (int j = 0; j < n; j++) {
+    TrackJob& job = t->h_bjobs[j];
+    fill_job_common(t, job);
+    fill_level(t, job, level, keyframes[j], frames[j], nullptr, nullptr, -1);
+    if (level == LSD_TRACK_MIN_LEVEL) {
+      rc = lsd_frame_ensure_wasgood(frames[j]);
+      if (rc) { t->cap_override = 0; t->batch_jobs = 0; return rc; }
+      job.wasGood = frames[j]->d_wasGood;
+      job.lv[level].writeMask = 1;
+    }
+    job.trackFrameSemantics = 1;
+    job.evalOnly = 1;
+    job.lastLevel = level;
+    job.topLevel = level;
+    const float* T7 = refToFrame + 7 * (size_t)j;
+    job.T0.q = {T7[0], T7[1], T7[2], T7[3]};
+    job.T0.t[0] = T7[4]; job.T0.t[1] = T7[5]; job.T0.t[2] = T7[6];
+    job.aff_a0 = affine[2 * (size_t)j]; job.aff_b0 = affine[2 * (size_t)j + 1];
+  }
+  // what batch_run leaves in the tracker besides the summaries: the rounds of recent batches (the next batch's budget) and launch_stats
+  int recent[4];
+  memcpy(recent, t->batchRecent, sizeof(recent));
+  const int numLaunches = t->numLaunches;
+  rc = batch_run(t, n);
+  memcpy(t->batchRecent, recent, sizeof(recent));
+  t->numLaunches = numLaunches;
+  if (rc) return rc;
+  for (int j = 0; j < n; j++) {
+    const TrackSummary* S = &t->h_bsummary[j];
+    if (!S->done) { lsd_set_error("lsdhip_tracker_evaluate_batch: job %d did not finish", j); return LSDHIP_E_STATE; }
+    record_of(S, &out[j]);
+    if (form) {
+      form[2 * j] = S->numLaunches == 0 ? 1 : 0;   // k_track_solo evaluates without a k_track_step launch (which counts S.numLaunches)
+      form[2 * j + 1] = t->h_bjobs[j].lv[level].tilePx;
+    }
+  }
   return LSDHIP_OK;
 }
 

@@ -396,6 +396,19 @@ class SE3Tracker:
         check(self.L.lsdhip_tracker_evaluate(self.h_, reference.keyframe.h_, frame.h_, T.ctypes.data, level, a, b, C.byref(r)), False)
         return r
 
+    def evaluateBatch(self, references, frames, referenceToFrames, level, affine=None):
+        """test hook: `evaluate` for n jobs through the launches of a batch (lsdhip_tracker_evaluate_batch); affine: n x 2 (a, b),
+        default (1, 0).  Returns (list of n records, form n x 2: [ran in k_track_solo, strip size in pixels or 0])."""
+        n = len(frames)
+        kfs = (C.c_void_p * n)(*[r.keyframe.h_ for r in references])
+        frs = (C.c_void_p * n)(*[f.h_ for f in frames])
+        T = np.ascontiguousarray(referenceToFrames, dtype=np.float32).reshape(n, 7)
+        ab = np.ascontiguousarray(np.tile([1.0, 0.0], (n, 1)) if affine is None else affine, dtype=np.float32).reshape(n, 2)
+        res = (capi.ResidualRecord * n)()
+        form = np.zeros((n, 2), np.int32)
+        check(self.L.lsdhip_tracker_evaluate_batch(self.h_, n, kfs, frs, T.ctypes.data, ab.ctypes.data, int(level), res, form.ctypes.data), False)
+        return list(res), form
+
     def trackFrameOnPermaref(self, permaRef_pos, permaRef_colVar, frame, referenceToFrame):
         pos = np.ascontiguousarray(permaRef_pos, np.float32)
         cv = np.ascontiguousarray(permaRef_colVar, np.float32)

@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from common import ODOMETRY_ITS, assert_bit_equal, pose_distance, sequence
+from se3_terms import oracle_terms64 as _oracle_terms64
 
 pytestmark = pytest.mark.gpu
 
@@ -175,36 +176,6 @@ def test_pointcloud_order_and_bits(oracle, hip):
 # ---------------------------------------------------------------------------------------------------------------
 # residual kernel (K1+K2+K3) at fixed poses
 # ---------------------------------------------------------------------------------------------------------------
-def _oracle_terms64(oracle, tr):
-    """float64 accumulation of the oracle's per-point float32 terms in SSE operation order (exact reciprocal)."""
-    f32 = np.float32
-    x, y, z = tr.buffer("x"), tr.buffer("y"), tr.buffer("z")
-    gx, gy, r, wgt = tr.buffer("dx"), tr.buffer("dy"), tr.buffer("residual"), tr.buffer("weight_p")
-    n = (len(x) // 4) * 4
-    x, y, z, gx, gy, r, wgt = [a[:n] for a in (x, y, z, gx, gy, r, wgt)]
-    pz = f32(1.0) / z
-    J = [pz * gx, pz * gy, None, None, None, (x * gy) * pz - (y * gx) * pz]
-    pz2 = pz * pz
-    v1 = (x * gx) * pz2
-    v2 = (y * gy) * pz2
-    J[2] = f32(0) - (v1 + v2)
-    J[3] = f32(0) - ((v2 * y) + (gy + v1 * y))
-    J[4] = (gx + v1 * x) + v2 * x
-    A = np.zeros((6, 6))
-    Aabs = np.zeros((6, 6))
-    for i in range(6):
-        Jw = J[i] * wgt
-        for j in range(i, 6):
-            t = (Jw * J[j]).astype(np.float64)
-            A[i, j] = A[j, i] = t.sum()
-            Aabs[i, j] = Aabs[j, i] = np.abs(t).sum()
-    resw = r * wgt
-    b = np.array([-(resw * J[i]).astype(np.float64).sum() for i in range(6)])
-    babs = np.array([np.abs((resw * J[i]).astype(np.float64)).sum() for i in range(6)])
-    err = (resw * r).astype(np.float64).sum()
-    return A, Aabs, b, babs, err, n
-
-
 @pytest.mark.parametrize("params", AFFINE)
 @pytest.mark.parametrize("w,h", [(176, 144), (320, 240), (640, 480)])
 def test_residual_kernel_fixed_pose(oracle, hip, w, h, params):
