@@ -17,6 +17,12 @@ N > 1: one process per GPU (torch.distributed, backend nccl = RCCL), every rank 
 (weak scaling; BASELINE.json configs[3]).  Finished keyframes' inverse-depth planes leave the C++ loop through a device
 ring and are collected on rank 0 with one RCCL gather over xGMI per batch of frames — the only exchange step of the path.
 
+A plain run does only what the headline figure needs: set up, warm up, time the --steps steps, write --dump-outputs if given, print
+the line (`value`, `ms_per_step`, the timed loop's own statistics, validation and roofline).  Everything that takes runs of its own —
+the other execution model, the PCIe-inclusive leg, the throughput-mode and per-level evaluation launches, the extra configurations
+(configs[2], configs[4], the S-sequence loop), the CPU baselines and, for N > 1, the row-band regulariser across the ranks — runs
+after the timed region only with --full.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -262,6 +268,22 @@ def cpu_baseline(frames, depth0, K, n_frames, w, h):
         refb["scalar_path"] = {"error": str(e)}
     port["scalar_path"] = refb["scalar_path"]        # (reported with whichever candidate ends up as cpu_baseline)
     return (refb, port) if refb["value"] >= port["value"] else (port, refb)
+
+
+def render_sequence(w, h, n_frames, seq_index=0, kind="S1", workers=16):
+    """synth.make_sequence with the frames rendered on `workers` threads (numpy releases the GIL inside its array loops).  Every frame
+    depends on its index alone and is rendered by the same code, so the arrays are bit-identical to make_sequence's."""
+    from concurrent.futures import ThreadPoolExecutor
+    from lsd_slam_amd import synth
+    sc = synth.Scene(seq_index, kind, n_frames)
+    with ThreadPoolExecutor(max(1, min(workers, n_frames, len(os.sched_getaffinity(0))))) as ex:
+        rendered = list(ex.map(lambda i: sc.render(i, w, h), range(n_frames)))
+    frames = np.zeros((n_frames, h, w), dtype=np.uint8)
+    poses = np.zeros((n_frames, 7), dtype=np.float64)
+    for i, (img, _) in enumerate(rendered):
+        frames[i] = img
+        poses[i] = synth.pose7(*sc.frame_to_ref(i, 0))
+    return frames, rendered[0][1], synth.intrinsics(w, h), poses
 
 
 def quat_to_rot(q):
@@ -729,7 +751,8 @@ def main():
                          "(SlamSystem's blockUntilMapped, C/SlamSystem.cpp:1026-1040).  Default: pipelined — tracking stream beside "
                          "mapping stream, the mapper one frame behind (the reference's two threads; lsd_slam_hip::SlamLoop)")
     ap.add_argument("--dry-run", action="store_true",
-                    help="launcher / process-group plumbing only (no GPU work, gloo when there is no GPU): prints the JSON skeleton")
+                    help="launcher / process-group plumbing only (no GPU work, gloo when there is no GPU): prints the JSON skeleton of a "
+                         "--full line, the keys a run can carry")
     ap.add_argument("--repeats", type=int, default=1,
                     help="split the --steps timed steps into this many back-to-back regions (each between barriers; at most --steps); "
                          "`value` and `ms_per_step` are those of the MEDIAN region's rate (the loop shows ~15 %% slower phases lasting tens "
@@ -741,6 +764,10 @@ def main():
     ap.add_argument("--no-extra-configs", action="store_true", help="skip the two short extra legs (BASELINE.json configs[2] and configs[4])")
     ap.add_argument("--seq-frames", type=int, default=50,
                     help="synthetic frames to render (one camera revolution = 50); fewer are played back and forth")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region, also run every leg beside the headline figure: the other execution model, the "
+                         "PCIe-inclusive leg, throughput mode, the extra configurations, the CPU baselines and, for N > 1, the row-band "
+                         "regulariser across the ranks (each still subject to its --no-... switch).  Default: the headline figure only")
     args = ap.parse_args()
 
     # --gpus N without a launcher: start the N ranks ourselves (one process per GPU, torch.distributed.run on this node)
@@ -815,7 +842,9 @@ def main():
 
     w, h = args.width, args.height
     n_seq = args.seq_frames
-    frames, depth0, K, gt = synth.make_sequence(w, h, n_seq, seq_index=rank, kind=args.scene)
+    # the input frames, rendered on 16 threads per node shared by the node's ranks (outside every timed region)
+    frames, depth0, K, gt = render_sequence(w, h, n_seq, seq_index=rank, kind=args.scene,
+                                            workers=max(1, 16 // int(os.environ.get("LOCAL_WORLD_SIZE", "1"))))
     d_frames = torch.from_numpy(frames).cuda(local_rank)           # inputs resident in HBM
     torch.cuda.synchronize()
     if n_seq >= 50:
@@ -946,6 +975,7 @@ def main():
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
         per_rank = [float(x.item()) for x in allr]
+    if distributed and args.full:
         try:
             bands_rec = bands_distributed(torch, dist, rank, world, local_rank)
         except Exception as e:   # an extra: never let it take the bench line down
@@ -981,7 +1011,7 @@ def main():
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 / rate,
             "repeats": repeats, "ms_per_step_all_regions": [e / n * 1e3 for n, e in zip(region_steps, elapsed_all)],
             "region_start_unix_s": region_wall,
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": "%dx%d 5-level-pyramid SE3 tracking + semi-dense depth update, single sequence per GPU "
                                    "(BASELINE.json configs[%d]); synthetic scene %s, GT-depth init, new keyframe every %d frames"
                                    % (w, h, 1 if (w, h) == (640, 480) else 2, args.scene, KF_EVERY),
@@ -1013,7 +1043,7 @@ def main():
             out["per_rank_frames_s"] = per_rank
         if bands_rec is not None:
             out.setdefault("extra_configs", {})["reg_3840x2160_bands"] = bands_rec
-        if world == 1 and (w, h) == (640, 480):
+        if args.full and world == 1 and (w, h) == (640, 480):
             try:
                 key = "value_block_until_mapped" if pipelined else "value_pipelined"
                 out[key] = other_execution_model(DriverLoop, capi, w, h, K, ptr, depth0, local_rank, not pipelined, min(args.steps, 200), args.warmup,
@@ -1051,12 +1081,12 @@ def main():
                 rd.update({"achieved": ach_a, "frac": ach_a / HBM_PEAK_GBS, "algorithmic_bytes_per_launch": act_bytes, "traffic": obs_traffic,
                            "traffic_source": obs_traffic_src, "traffic_vs_algorithmic": (obs_traffic / act_bytes) if obs_traffic else None,
                            "note": "algorithmic bytes of the pixels that were actually searched (counted in-kernel on the sampled launches); HIP events around every 7th launch"})
-        if world == 1 and (w, h) == (640, 480) and not args.no_throughput_mode:
+        if args.full and world == 1 and (w, h) == (640, 480) and not args.no_throughput_mode:
             try:
                 out["roofline_throughput_mode"] = throughput_mode(la, w, h, K, d_frames, depth0, local_rank)
             except Exception as e:   # an extra: never let it take the bench line down
                 out["roofline_throughput_mode"] = {"error": str(e)}
-        if world == 1 and (w, h) == (640, 480) and not args.no_extra_configs:
+        if args.full and world == 1 and (w, h) == (640, 480) and not args.no_extra_configs:
             # (before the dense 4K leg: a burst like that leaves a box in its slow state for seconds, profiles/r03_notes.md section 1)
             try:
                 # the 8 seeds of configs[3]: this rank's sequence + 7 more, rendered here (outside every timed region)
@@ -1072,7 +1102,7 @@ def main():
                 out.setdefault("extra_configs", {}).update(extra_configs(la, torch, local_rank))
             except Exception as e:   # extras: never let them take the bench line down
                 out.setdefault("extra_configs", {})["error"] = str(e)
-        if world == 1 and not args.no_pcie_leg:
+        if args.full and world == 1 and not args.no_pcie_leg:
             # SURVEY.md §8(d) counts the 8-bit upload inside tracked frames/s: the same loop fed from (pinned) host memory, every frame
             # crossing PCIe inside lsdhip_frame_create.  Reported beside `value`, never as `value`.
             try:
@@ -1101,7 +1131,7 @@ def main():
                 loop2.close()
             except Exception as e:
                 out["value_pcie_inclusive"] = {"error": str(e)}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], other = cpu_baseline(frames, depth0, K, args.cpu_frames, w, h)
             if other is not None:
                 out["cpu_baseline_other"] = other

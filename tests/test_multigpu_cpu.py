@@ -116,6 +116,19 @@ def test_bench_line_skeleton_of_a_one_gpu_run():
     assert set(d["extra_configs"]["multi_seq"]["S32"]["roofline"]) >= {"track_batch", "frame_pyramids", "observe", "regularise", "idepth_pyramids", "keyframe_change"}
 
 
+def test_render_sequence_matches_make_sequence():
+    """bench.py renders its input frames on several threads: the arrays must be bit-identical to synth.make_sequence's."""
+    import sys
+    sys.path.insert(0, ROOT)
+    import bench
+    from lsd_slam_amd import synth
+    for kind, seq_index in (("S1", 0), ("S1", 3), ("S2", 1)):
+        a = bench.render_sequence(96, 64, 7, seq_index=seq_index, kind=kind, workers=4)
+        b = synth.make_sequence(96, 64, 7, seq_index=seq_index, kind=kind)
+        for x, y in zip(a, b):
+            assert x.dtype == y.dtype and x.shape == y.shape and x.tobytes() == y.tobytes(), kind
+
+
 def test_cpu_baseline_two_thread_model():
     """bench.py's cpu_baseline.pipelined: the reference's two-thread model on the CPU library with the mapper one frame behind — every frame
     tracked well, the frame after a keyframe change dropped unmapped, the rest mapped (the GPU loop's pipelined mode, frame for frame)."""

@@ -37,8 +37,8 @@ case $step in
     timeout 1500 "$@" 2>&1 | tail -n 200 | cut -c1-700 | tee $out/$name.txt
     ;;
   bench)
-    # the driver's own command line (+ extra args); the JSON line goes to $out/bench.json
-    timeout 1500 python bench.py --gpus 1 --steps 20 --warmup 5 "$@" > $out/bench.json 2> $out/bench.err
+    # the bench line with every leg (--full, + extra args); the JSON line goes to $out/bench.json
+    timeout 1500 python bench.py --full --gpus 1 --steps 20 --warmup 5 "$@" > $out/bench.json 2> $out/bench.err
     tail -n 5 $out/bench.err | cut -c1-300
     python - <<PY
 import json
