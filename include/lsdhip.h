@@ -392,8 +392,19 @@ int lsdhip_depth_finalize(lsdhip_depthmap* dm);
  * map): [finalize pass + Frame::setDepth + takeReActivationData + propagation candidates] -> [propagation merge] -> regularizeDepthMap(true)
  * -> [fill holes + regularizeDepthMap(false) + rescale sums] -> [rescale + Frame::setDepth] -> both keyframes' idepth pyramids.  Planes,
  * re-activation data, pyramids and deferred results as lsdhip_depth_finalize + lsdhip_depth_create_keyframe leave them.
- * rescale_out: NULL or n floats (asking for them waits for the device). */
+ * rescale_out: NULL or n floats (asking for them waits for the device).  More than 85 maps are processed in consecutive parts of at most
+ * 85 (three deferred-result slots per map, 256 slots per context); a failing part leaves the parts before it changed. */
 int lsdhip_depth_change_keyframe_batch(int n, lsdhip_depthmap** maps, lsdhip_frame** new_keyframes, float* rescale_out);
+/* Which form the last lsdhip_depth_update_batch (which = 0) or lsdhip_depth_change_keyframe_batch (which = 1) on this context took: a
+ * read-only record the calls keep on the host (a call that nobody asks about does no extra device work).  out[0] = maps of the call
+ * (0: no such call yet), out[1] = 1 if observe ran as select + walk launches (0: one launch), out[2] = 1 if the select pass walked the
+ * gradient candidates, out[3] = tile height factor PY of the regulariser launches (1: 32x8, 2: 32x16), out[4] = keyframes that were due
+ * for Frame::setDepth, out[5] = workgroups of the walk launch (0 if not split), out[6] = entries queued by the select pass over all
+ * maps, out[7] = chunks of 64 entries the walk launch dealt out; out[6] / out[7] are -1 unless the call was split, ran on a synchronous
+ * context and its argument record has not been reused since (ask right after the call).  queueCounts: NULL, or maxCounts ints that
+ * receive the queued entries per map (the first min(n, maxCounts); filled whenever out[6] >= 0).  For which = 1 only out[0] and out[3]
+ * are meaningful (out[3]: of the last part when the call went in parts). */
+int lsdhip_ctx_batch_form(lsdhip_ctx* ctx, int which, int out[8], int* queueCounts, int maxCounts);
 /* currentDepthMap <-> host in the reference's 32-byte AoS layout (debug / parity / drop-in users that read it) */
 int lsdhip_depth_download(lsdhip_depthmap* dm, lsdhip_hypothesis* out_host);
 int lsdhip_depth_upload(lsdhip_depthmap* dm, lsdhip_frame* kf, const lsdhip_hypothesis* in_host, int reactivated);

@@ -2331,6 +2331,7 @@ extern "C" int lsdhip_depth_update_batch(int n, lsdhip_depthmap** maps, lsdhip_f
   RegBatchItem* ra = (RegBatchItem*)((uint8_t*)hostBlob + obsBytes);
   int* qcountHost = (int*)((uint8_t*)hostBlob + obsBytes + regBytes);       // the queues' fill counts start from the zeros copied here
   int* qcountDev = (int*)((uint8_t*)dev + obsBytes + regBytes);
+  const unsigned long long argsSerial = c->args.serial, argsGen = c->args.gen;   // (the record's place in the ring: lsdhip_ctx_batch_form)
   int nSet = 0;
   static const bool candOff = getenv("LSDHIP_OBS_CAND") && getenv("LSDHIP_OBS_CAND")[0] == '0';   // developer A/B (round 6)
   bool candidates = !candOff;     // the select pass walks the keyframes' gradient candidates: every map of the call must qualify
@@ -2376,6 +2377,7 @@ extern "C" int lsdhip_depth_update_batch(int n, lsdhip_depthmap** maps, lsdhip_f
     if (candidates) hipLaunchKernelGGL(k_observe_select_cand_batch, dim3((lsd_gradcand_groups(c->w * c->h) + 3) / 4, 1, n), dim3(256), 0, ms, (const ObserveArgs*)dev);
     else hipLaunchKernelGGL(k_observe_select_batch, dim3((c->w + 63) / 64, (c->h + 15) / 16, n), dim3(256), 0, ms, (const ObserveArgs*)dev);
     hipLaunchKernelGGL(k_observe_walk_batch, dim3(walkWaves), dim3(64), 0, ms, (const ObserveArgs*)dev, (const int*)qcountDev, n, acc);
+    c->batchForm[0].walkWorkgroups = walkWaves;
   } else {
     hipLaunchKernelGGL((k_observe_batch<2>), dim3((c->w + 31) / 32, (c->h + 1) / 2, n), dim3(64), 0, ms, (const ObserveArgs*)dev);
   }
@@ -2384,6 +2386,12 @@ extern "C" int lsdhip_depth_update_batch(int n, lsdhip_depthmap** maps, lsdhip_f
   const RegBatchItem* dra = (const RegBatchItem*)((const uint8_t*)dev + obsBytes);
   const int rpy = lsd_reg_py((long long)((c->w + 31) / 32) * ((c->h + 7) / 8) * n);
   const dim3 rgrid((c->w + 31) / 32, lsd_reg_grid_rows((c->h + 7) / 8, rpy), n);
+  {
+    lsdhip_ctx::BatchForm& bf = c->batchForm[0];
+    bf.n = n; bf.py = rpy; bf.nSet = nSet; bf.split = split; bf.candidates = split && candidates; bf.synced = false;
+    if (!split) bf.walkWorkgroups = 0;
+    bf.qcountDev = qcountDev; bf.argsSerial = argsSerial; bf.argsGen = argsGen;
+  }
   bp = lsd_bprof_begin(c, 2, ms);
   if (bp < -1) return bp;
   LSD_REG_DISPATCH(rpy,
@@ -2397,32 +2405,40 @@ extern "C" int lsdhip_depth_update_batch(int n, lsdhip_depthmap** maps, lsdhip_f
   for (int j = 0; j < n; j++) { swap_valid(maps[j]); maps[j]->lowGradHypPossible = false; }   // (every form of the observe pass drops a hypothesis below the threshold)
   // ---- Frame::setDepth's second half for the keyframes that were due -------------------------------------------------------------------
   if (nSet > 0) {
-    std::vector<lsdhip_frame*> kfs;
-    std::vector<const double*> parts;
-    std::vector<double*> outs;
-    for (int j = 0; j < n; j++) {
-      lsdhip_frame* kf = maps[j]->activeKeyFrame;
-      if (kf->depthHasBeenUpdatedFlag) continue;
-      const int slot = lsd_ctx_take_slot(c);
-      if (slot < 0) return slot;
-      if (kf->pendStats >= 0) c->slot_stats_owner[kf->pendStats] = nullptr;
-      kf->pendStats = slot;
-      c->slot_stats_owner[slot] = kf;
-      kfs.push_back(kf);
-      parts.push_back(maps[j]->d_red + 16);
-      outs.push_back((double*)&c->h_slots[slot]);
-    }
     bp = lsd_bprof_begin(c, 3, ms);
     if (bp < -1) return bp;
-    rc = lsd_frame_build_idepth_pyramid_batch(kfs.data(), (int)kfs.size(), parts.data(), (int)(rgrid.x * rgrid.y), outs.data());
+    // At most LSD_NUM_SLOTS keyframes per pyramid launch: taking a slot that still has an owner resolves that owner first, which is only
+    // right once the launch that writes the slot has been queued — with more keyframes than slots in ONE launch the ring wrapped onto
+    // keyframes of the same call, whose statistics were then read before anything had written them (numPoints = 0).
+    int j0 = 0;
+    while (j0 < n) {
+      std::vector<lsdhip_frame*> kfs;
+      std::vector<const double*> parts;
+      std::vector<double*> outs;
+      for (; j0 < n && (int)kfs.size() < LSD_NUM_SLOTS; j0++) {
+        lsdhip_frame* kf = maps[j0]->activeKeyFrame;
+        if (kf->depthHasBeenUpdatedFlag) continue;
+        const int slot = lsd_ctx_take_slot(c);
+        if (slot < 0) return slot;
+        if (kf->pendStats >= 0) c->slot_stats_owner[kf->pendStats] = nullptr;
+        kf->pendStats = slot;
+        c->slot_stats_owner[slot] = kf;
+        kfs.push_back(kf);
+        parts.push_back(maps[j0]->d_red + 16);
+        outs.push_back((double*)&c->h_slots[slot]);
+      }
+      if (kfs.empty()) break;
+      rc = lsd_frame_build_idepth_pyramid_batch(kfs.data(), (int)kfs.size(), parts.data(), (int)(rgrid.x * rgrid.y), outs.data());
+      if (rc) return rc;
+      for (lsdhip_frame* kf : kfs) kf->depthHasBeenUpdatedFlag = true;
+    }
+    rc = lsd_bprof_end(c, bp, ms, (double)nSet * c->w * c->h);
     if (rc) return rc;
-    rc = lsd_bprof_end(c, bp, ms, (double)kfs.size() * c->w * c->h);
-    if (rc) return rc;
-    for (lsdhip_frame* kf : kfs) kf->depthHasBeenUpdatedFlag = true;
   }
   if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
   if (!c->async) {
     HIPCHK(hipStreamSynchronize(ms));
+    c->batchForm[0].synced = true;
     for (int j = 0; j < n; j++) { rc = lsd_frame_resolve(maps[j]->activeKeyFrame); if (rc) return rc; }
   }
   const double dt = now_ms() - t0;
@@ -2513,6 +2529,19 @@ extern "C" int lsdhip_depth_change_keyframe_batch(int n, lsdhip_depthmap** maps,
     if (new_keyframes[j] == dm->activeKeyFrame) { lsd_set_error("keyframe change batch: map %d: the new keyframe is the current one", j); return LSDHIP_E_ARG; }
     for (int i = 0; i < j; i++)
       if (maps[i] == dm || new_keyframes[i] == new_keyframes[j]) { lsd_set_error("keyframe change batch: entry %d appears twice", j); return LSDHIP_E_ARG; }
+  }
+  // A change holds three deferred-result slots per map until its launches are queued, and taking a slot that still has an owner resolves
+  // that owner first — right only once the launch that writes the slot has been queued.  More maps than a third of the ring go in
+  // consecutive parts, so that the ring never wraps onto a map of the part being prepared (it did: the first maps of a call of more than
+  // 85 read their rescale factor and statistics before anything had written them).
+  constexpr int maxPerPart = LSD_NUM_SLOTS / 3;
+  if (n > maxPerPart) {
+    for (int j0 = 0; j0 < n; j0 += maxPerPart) {
+      const int part = n - j0 < maxPerPart ? n - j0 : maxPerPart;
+      if (int rcp = lsdhip_depth_change_keyframe_batch(part, maps + j0, new_keyframes + j0, rescale_out ? rescale_out + j0 : nullptr)) return rcp;
+    }
+    c->batchForm[1].n = n;     // (py: that of the last part)
+    return LSDHIP_OK;
   }
   HIPCHK(hipSetDevice(c->device));
   const double t0 = now_ms();
@@ -2680,6 +2709,7 @@ extern "C" int lsdhip_depth_change_keyframe_batch(int n, lsdhip_depthmap** maps,
   rc = lsd_bprof_end(c, bp, ms, (double)n * npx);
   if (rc) return rc;
   txn.done = true;            // every launch of the change is queued: the new state stands
+  { lsdhip_ctx::BatchForm& bf = c->batchForm[1]; bf = lsdhip_ctx::BatchForm(); bf.n = n; bf.py = tpy; }
   for (int j = 0; j < n; j++) {
     maps[j]->propClean = true;
     pyrFrames[j]->depthHasBeenUpdatedFlag = true;
@@ -3025,5 +3055,30 @@ extern "C" int lsdhip_depth_timings(lsdhip_depthmap* dm, float out[8]) {
   if (!dm || !out) return LSDHIP_E_ARG;
   out[0] = dm->msUpdate; out[1] = dm->msCreate; out[2] = dm->msFinalize; out[3] = dm->msObserve; out[4] = dm->msRegularize;
   out[5] = dm->msPropagate; out[6] = dm->msFillHoles; out[7] = dm->msSetDepth;
+  return LSDHIP_OK;
+}
+
+// what the last batched update / keyframe change on the context ran (include/lsdhip.h); the queue counts of a split update are read
+// from the call's argument record here, on request: the calls themselves keep host-side notes only
+extern "C" int lsdhip_ctx_batch_form(lsdhip_ctx* c, int which, int out[8], int* queueCounts, int maxCounts) {
+  if (!c || !out || which < 0 || which > 1 || (queueCounts && maxCounts < 0)) return LSDHIP_E_ARG;
+  LSD_CTX_LOCK(c);
+  const lsdhip_ctx::BatchForm& bf = c->batchForm[which];
+  out[0] = bf.n; out[1] = bf.split ? 1 : 0; out[2] = bf.candidates ? 1 : 0; out[3] = bf.py; out[4] = bf.nSet; out[5] = bf.walkWorkgroups;
+  out[6] = -1; out[7] = -1;
+  const lsdhip_ctx::ArgRing& r = c->args;
+  const bool readable = bf.n > 0 && bf.split && bf.synced && bf.qcountDev && r.d && bf.argsGen == r.gen &&
+                        r.serial - bf.argsSerial < (unsigned long long)lsdhip_ctx::ArgRing::NS;
+  if (!readable) return LSDHIP_OK;
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<int> cnt((size_t)bf.n);
+  HIPCHK(hipMemcpy(cnt.data(), bf.qcountDev, sizeof(int) * (size_t)bf.n, hipMemcpyDeviceToHost));
+  long long entries = 0, chunks = 0;
+  for (int j = 0; j < bf.n; j++) {
+    entries += cnt[j];
+    chunks += (cnt[j] + 63) >> 6;
+    if (queueCounts && j < maxCounts) queueCounts[j] = cnt[j];
+  }
+  out[6] = (int)entries; out[7] = (int)chunks;
   return LSDHIP_OK;
 }

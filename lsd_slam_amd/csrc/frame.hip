@@ -1459,10 +1459,12 @@ int lsd_args_begin(lsdhip_ctx* c, size_t bytes, void** host_out, void** dev_out)
     HIPCHK(hipHostMalloc((void**)&r.h, want * NS, hipHostMallocDefault));
     HIPCHK(hipMalloc((void**)&r.d, want * NS));
     r.slotBytes = want;
+    r.gen++;
     for (int i = 0; i < NS; i++) { r.used[i] = false; if (!r.ev[i]) HIPCHK(hipEventCreateWithFlags(&r.ev[i], hipEventDisableTiming)); }
   }
   const int i = r.next;
   r.next = (r.next + 1) % NS;
+  r.serial++;
   if (r.used[i]) HIPCHK(hipEventSynchronize(r.ev[i]));   // (NS - 1 uses ago: long finished)
   r.cur = i;
   r.curBytes = bytes;

@@ -278,7 +278,16 @@ struct lsdhip_ctx {
     static constexpr int NS = 32;
     uint8_t* h = nullptr; uint8_t* d = nullptr; size_t slotBytes = 0; int next = 0; hipEvent_t ev[NS] = {}; bool used[NS] = {};
     int cur = -1; size_t curBytes = 0;   // the slot being filled / last committed
+    unsigned long long serial = 0, gen = 0;   // slots handed out so far / times the ring was regrown: a device address handed out at serial s
+                                              // still holds its record while gen is unchanged and serial < s + NS (lsdhip_ctx_batch_form)
   } args;
+  // what the last lsdhip_depth_update_batch [0] / lsdhip_depth_change_keyframe_batch [1] ran (lsdhip_ctx_batch_form): host-side notes only
+  struct BatchForm {
+    int n = 0, py = 0, nSet = 0, walkWorkgroups = 0;
+    bool split = false, candidates = false, synced = false;
+    const int* qcountDev = nullptr;           // the queues' fill counts inside the call's argument record
+    unsigned long long argsSerial = 0, argsGen = 0;
+  } batchForm[2];
   std::vector<struct lsdhip_depthmap*> depthmaps;   // alive on this context: a destroyed frame is unhooked from them
   size_t arena_bytes = 0;
 };

@@ -74,6 +74,18 @@ class Context:
         check(self.L.lsdhip_ctx_intrinsics(self.h_, level, out.ctypes.data))
         return out
 
+    def batchForm(self, which="update"):
+        """the form the last DepthMap.updateKeyframeBatch ("update") / changeKeyframeBatch ("change") on this context took
+        (lsdhip_ctx_batch_form): dict with n, split, candidates, py, nSet, walkWorkgroups, queued, chunks and queueCounts (entries queued
+        per map; None where the counts are not available: not split, asynchronous context, or asked too late)"""
+        out = np.zeros(8, np.int32)
+        counts = np.zeros(512, np.int32)
+        check(self.L.lsdhip_ctx_batch_form(self.h_, {"update": 0, "change": 1}[which], out.ctypes.data, counts.ctypes.data, len(counts)))
+        n = int(out[0])
+        return {"n": n, "split": bool(out[1]), "candidates": bool(out[2]), "py": int(out[3]), "nSet": int(out[4]),
+                "walkWorkgroups": int(out[5]), "queued": int(out[6]), "chunks": int(out[7]),
+                "queueCounts": counts[:n].copy() if out[6] >= 0 else None}
+
     def stream(self):
         return self.L.lsdhip_ctx_stream(self.h_)
 

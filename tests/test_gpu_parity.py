@@ -419,17 +419,8 @@ def test_permaref_paths(oracle, hip):
 # ---------------------------------------------------------------------------------------------------------------
 # depth map stages
 # ---------------------------------------------------------------------------------------------------------------
-def _noisy_map(oracle, hip, ctx, frames, depth0, K, w, h, sigma=0.1, seed=1, op=None):
-    kfo = oracle.Frame(0, frames[0], K)
-    kfg = hip.Frame(ctx, 0, frames[0])
-    kfo.set_depth_gt(depth0)
-    kfg.setDepthFromGroundTruth(depth0)
-    dmo = oracle.DepthMap(w, h, K, params=op)
-    dmg = hip.DepthMap(ctx)
-    dmo.init_gt(kfo)
-    dmg.initializeFromGTDepth(kfg)
-    assert_hyp_equal(dmg.currentDepthMap(), dmo.get(), "initializeFromGTDepth")
-    hyp = dmo.get()
+def _noisy_hyp(hyp, sigma=0.1, seed=1):
+    """the ragged state of _noisy_map, applied to a downloaded map (host arithmetic only: the batch tests build the oracle's side alone first)"""
     rng = np.random.default_rng(seed)
     v = hyp["isValid"] > 0
     noise = rng.normal(0, sigma, hyp.shape).astype(np.float32)
@@ -444,6 +435,20 @@ def _noisy_map(oracle, hip, ctx, frames, depth0, K, w, h, sigma=0.1, seed=1, op=
     hyp["blacklisted"][rng.uniform(size=hyp.shape) < 0.03] = -1
     hyp["validity_counter"] = rng.integers(0, 60, hyp.shape).astype(np.int32)
     hyp["nextStereoFrameMinID"][rng.uniform(size=hyp.shape) < 0.2] = 4.0
+    return hyp
+
+
+def _noisy_map(oracle, hip, ctx, frames, depth0, K, w, h, sigma=0.1, seed=1, op=None, threads=None):
+    kfo = oracle.Frame(0, frames[0], K)
+    kfg = hip.Frame(ctx, 0, frames[0])
+    kfo.set_depth_gt(depth0)
+    kfg.setDepthFromGroundTruth(depth0)
+    dmo = oracle.DepthMap(w, h, K, params=op) if threads is None else oracle.DepthMap(w, h, K, params=op, threads=threads)
+    dmg = hip.DepthMap(ctx)
+    dmo.init_gt(kfo)
+    dmg.initializeFromGTDepth(kfg)
+    assert_hyp_equal(dmg.currentDepthMap(), dmo.get(), "initializeFromGTDepth")
+    hyp = _noisy_hyp(dmo.get(), sigma, seed)
     dmo.set(kfo, hyp)
     dmg.setCurrentDepthMap(kfg, hyp)
     return kfo, kfg, dmo, dmg
@@ -461,17 +466,22 @@ def assert_hyp_equal(g, o, what, float_exact=True, rtol=0.0):
             assert np.allclose(g[k][v], o[k][v], rtol=rtol, atol=0), what + ": " + k
 
 
+def _ref_pose(oracle, gt, i, base=None):
+    """(Sim3 frame i -> keyframe, initialTrackedResidual): the ground-truth pose (relative to frame `base` when the keyframe is not frame
+    0) composed with a small general twist — a pure in-plane translation + roll (the synthetic trajectory) leaves t_z = 0 and zero rotation
+    off-diagonals, which would hide operation-order mismatches"""
+    twist = np.array([0.0, 0.0, 0.003, 0.0008, -0.0006, 0.0004]) * (1 + 0.1 * i)
+    rel = gt[i] if base is None else oracle.se3_mul(oracle.se3_inv(gt[base]), gt[i])
+    return np.concatenate([oracle.se3_mul(rel, oracle.se3_exp(twist)), [1.0]]), float(0.3 + 0.1 * i)
+
+
 def _ref_frames(oracle, hip, ctx, frames, K, gt, kfo, kfg, ids, with_masks=True, seed=5):
     rng = np.random.default_rng(seed)
     fos, fgs = [], []
     for i in ids:
         fo = oracle.Frame(i, frames[i], K)
         fg = hip.Frame(ctx, i, frames[i])
-        # GT pose composed with a small general twist: a pure in-plane translation + roll (the synthetic trajectory)
-        # leaves t_z = 0 and zero rotation off-diagonals, which would hide operation-order mismatches
-        twist = np.array([0.0, 0.0, 0.003, 0.0008, -0.0006, 0.0004]) * (1 + 0.1 * i)
-        sim3 = np.concatenate([oracle.se3_mul(gt[i], oracle.se3_exp(twist)), [1.0]])
-        itr = float(0.3 + 0.1 * i)
+        sim3, itr = _ref_pose(oracle, gt, i)
         fo.set_pose(sim3, kfo, itr)
         fg.setPose(sim3, kfg, itr)
         if with_masks:
@@ -600,6 +610,73 @@ def test_initialize_randomly_draws_the_same_rand_sequence(oracle, hip):
         assert_bit_equal(kfg.idepthVar(lvl), kfo.plane("idepthVar", lvl), "kf idepthVar L%d" % lvl)
 
 
+def oracle_prerescale_after_propagate(dmo):
+    """createKeyFrame behind propagateDepth up to the rescale (oracle/orc_depthmap.cpp DepthMap::createKeyFrame): regularizeDepthMap(true),
+    fill holes, regularizeDepthMap(false) -> the pre-rescale map"""
+    dmo.stage("regularize_occ")
+    dmo.stage("fillholes")
+    dmo.stage("regularize")
+    return dmo.get()
+
+
+def expected_rescale(pre, what=""):
+    """(f, allowed, N): f = float32(N) / float32(S64), S64 the float64 sum of the pre-rescale idepth_smoothed over the N valid pixels.  The
+    device's float64 tree sum lies within N * 2^-53 relative of S64; only if float32(S64) changes inside that interval (S64 that close to a
+    float32 rounding tie) is a neighbouring factor allowed too — reported when it happens."""
+    v = pre["isValid"] > 0
+    N = int(v.sum())
+    assert N > 0, what
+    S64 = float(pre["idepth_smoothed"][v].astype(np.float64).sum())
+    n32 = np.float32(N)
+    f = n32 / np.float32(S64)
+    eps = N * 2.0 ** -53
+    lo, hi = np.float32(S64 * (1 - eps)), np.float32(S64 * (1 + eps))
+    allowed = {float(f)}
+    if lo != hi:
+        print("%s: the float64 sum %.17g lies within N * 2^-53 of a float32 rounding tie: both neighbouring factors are accepted" % (what, S64))
+        allowed |= {float(n32 / lo), float(n32 / hi)}
+    return f, allowed, N
+
+
+def assert_created_keyframe_exact(oracle, what, pre, s_g, s_o, gg, nkg, pose_o, K, nk_image):
+    """createKeyFrame's result against the oracle's PRE-rescale map `pre` (all valid pixels, bit for bit): s_g the device's factor, s_o the
+    oracle's own (sequential float32 sum), gg the device's new map, nkg the device's new keyframe, pose_o the oracle's new keyframe pose."""
+    f_exp, allowed, N = expected_rescale(pre, what)
+    f = np.float32(s_g)
+    assert float(f) == float(s_g) and float(f) in allowed, "%s: rescale factor %r, expected %r (N = %d)" % (what, s_g, sorted(allowed), N)
+    # the oracle's own factor: its float32 running sum is within N * 2^-24 relative of the float64 sum (holds the construction to the oracle)
+    assert abs(float(s_o) - float(f_exp)) <= N * 2.0 ** -24 * float(f_exp), (what, s_o, f_exp, N)
+    assert_bit_equal(gg["isValid"], pre["isValid"], what + ": isValid")
+    assert_bit_equal(gg["blacklisted"], pre["blacklisted"], what + ": blacklisted")
+    v = pre["isValid"] > 0
+    assert_bit_equal(gg["validity_counter"][v], pre["validity_counter"][v], what + ": validity_counter")
+    assert_bit_equal(gg["nextStereoFrameMinID"][v], pre["nextStereoFrameMinID"][v], what + ": nextStereoFrameMinID")
+    f2 = np.float32(f * f)
+    want = {}
+    for k, fac in (("idepth", f), ("idepth_smoothed", f), ("idepth_var", f2), ("idepth_var_smoothed", f2)):
+        want[k] = (pre[k].astype(np.float32) * fac).astype(np.float32)      # one rounded multiply each
+        assert_bit_equal(gg[k][v], want[k][v], what + ": " + k)
+    # the new keyframe: Frame::setDepth's rule on level 0, the pyramid an oracle frame builds from those planes above it
+    ok = v & (want["idepth_smoothed"].astype(np.float64) >= -0.05)
+    id0 = np.where(ok, want["idepth_smoothed"], np.float32(-1)).astype(np.float32)
+    var0 = np.where(ok, want["idepth_var_smoothed"], np.float32(-1)).astype(np.float32)
+    fo = oracle.Frame(0, nk_image, K)
+    fo.set_depth_planes(id0, var0)
+    assert_bit_equal(nkg.idepth(0), id0, what + ": new keyframe idepth L0")
+    assert_bit_equal(nkg.idepthVar(0), var0, what + ": new keyframe idepthVar L0")
+    for lvl in range(1, 5):
+        assert_bit_equal(nkg.idepth(lvl), fo.plane("idepth", lvl), what + ": new keyframe idepth L%d" % lvl)
+        assert_bit_equal(nkg.idepthVar(lvl), fo.plane("idepthVar", lvl), what + ": new keyframe idepthVar L%d" % lvl)
+    sg = nkg.stats()
+    assert sg["numPoints"] == int(ok.sum()), what
+    mean64 = float(id0[ok].astype(np.float64).sum()) / max(int(ok.sum()), 1)
+    assert abs(sg["meanIdepth"] - mean64) <= int(ok.sum()) * 2.0 ** -24 * abs(mean64), (what, sg["meanIdepth"], mean64)
+    pg = np.asarray(nkg.thisToParent_raw())
+    assert np.allclose(pg[:7], np.asarray(pose_o)[:7], atol=1e-12, rtol=0), (what, pg, pose_o)
+    assert pg[7] == float(f), (what, pg[7], f)
+    return want
+
+
 @pytest.mark.parametrize("use_mask", [True, False])
 def test_propagate_and_create_keyframe(oracle, hip, use_mask):
     w, h = 640, 480
@@ -614,16 +691,14 @@ def test_propagate_and_create_keyframe(oracle, hip, use_mask):
     dmo.stage("propagate", [nko])
     dmg.stage("propagate", [nkg])
     assert_hyp_equal(dmg.currentDepthMap(), dmo.get(), "propagateDepth")
+    # ... and on through createKeyFrame's passes up to the rescale: the oracle's pre-rescale map
+    pre = oracle_prerescale_after_propagate(dmo)
     # full createKeyFrame from the same starting state
     dmo.set(kfo, hyp0)
     dmg.setCurrentDepthMap(kfg, hyp0)
     s_o = dmo.create_keyframe(nko)
     s_g = dmg.createKeyFrame(nkg)
-    assert s_g == pytest.approx(s_o, rel=2e-5)     # float32 sequential vs float64 tree sum of ~1e5 terms
-    go, gg = dmo.get(), dmg.currentDepthMap()
-    assert_hyp_equal(gg, go, "createKeyFrame", float_exact=False, rtol=1e-4)
-    po, pg = nko.pose(), nkg.thisToParent_raw()
-    assert np.allclose(pg[:7], po[:7], atol=1e-12) and pg[7] == pytest.approx(po[7], rel=2e-5)
+    assert_created_keyframe_exact(oracle, "createKeyFrame", pre, s_g, s_o, dmg.currentDepthMap(), nkg, nko.pose(), K, frames[9])
     assert nkg.stats()["numPoints"] == nko.stats()["numPoints"]
 
 
