@@ -203,6 +203,11 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
   const int lvlIn_ = S.level, numLaunchesIn_ = S.numLaunches, pendingIn_ = S.pending, ncandIn_ = S.ncand;
   int pcLog_ = -1;
 #endif
+  // A finished job's launches leave here.  The host may have read the summary and gone on already (polled jobs and batches do not drain
+  // the stream), so two things must stay true: (a) every workgroup of a launch queued behind the finishing one returns at this point,
+  // before it touches frame or keyframe memory — the state is all it has read; (b) the finishing launch requests its next strip
+  // (strip_request below) before it knows that it finishes: those loads may read kf_refBlk after the host has seen `done`, and their
+  // result is always discarded (the S.done return behind the finishing phase).
   if (S.done) {
     LAUNCH_LOG(1, pendingIn_, ncandIn_, -1);
     if (MODE != TS_EVAL && leader) { copy_words<sizeof(TrackState) / 4>(next, &S, tid, BLOCK); }   // keep both buffers "done"
@@ -1042,6 +1047,8 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
   };
   for (int guard = 0; guard < 4096; guard++) {
     const int level = S.level;
+    // the same two invariants as at track_step_impl's early-out: once the job is done this workgroup touches no frame or keyframe memory
+    // again, and nothing is requested ahead of this check (every load of a level sits behind it), so there is nothing to discard
     if (S.done) break;
     const TrackLevel& L = job.lv[level];
     const int work = L.w * L.h;
@@ -1332,6 +1339,35 @@ __global__ __launch_bounds__(64) void k_devtest_se3f_lm_step(const float* __rest
 // ---------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------
+// The TrackScratch arena, the one place that knows its layout: four arrays over [job][parity][trial slot], one behind the other — sums
+// (RS_COLS floats per tile row) | topkey (an int4 per row) | topval (96 floats per row) | recs (32 floats per slot).  Offsets in floats.
+struct ScratchLayout { size_t topkey, topval, recs, end; };
+static constexpr ScratchLayout scratch_layout(size_t jobs, size_t trials, size_t rows) {
+  const size_t slots = jobs * 2 * trials;
+  const size_t topkey = slots * RS_COLS * rows, topval = topkey + slots * 4 * rows, recs = topval + slots * 96 * rows;
+  return {topkey, topval, recs, recs + slots * 32};
+}
+// (the two arenas in use — a single job's LSD_SPEC_MAX slots, a batch's LSD_BATCH_SPEC_MAX per job — sized as they always were)
+static_assert(scratch_layout(1, LSD_SPEC_MAX, 304).end * 4 == (size_t)LSD_SPEC_MAX * (2 * RS_COLS * 304 * 4 + 2 * 304 * 16 + 2 * 304 * 96 * 4 + 2 * 32 * 4) &&
+              scratch_layout(8, LSD_BATCH_SPEC_MAX, 304).end * 4 == 8 * (size_t)LSD_BATCH_SPEC_MAX * (2 * RS_COLS * 304 * 4 + 2 * 304 * 16 + 2 * 304 * 96 * 4 + 2 * 32 * 4) &&
+              scratch_layout(8, LSD_BATCH_SPEC_MAX, 304).recs == 8 * (size_t)LSD_BATCH_SPEC_MAX * (2 * RS_COLS * 304 + 2 * 4 * 304 + 2 * 96 * 304),
+              "scratch arena: byte count and offsets");
+// the arena at `base` as the kernels take it; cmax = the trial slots per parity they index with (<= trials; 1: no speculation, no recs)
+static TrackScratch scratch_at(const lsdhip_tracker* t, float* base, size_t jobs, size_t trials, int cmax) {
+  const ScratchLayout lay = scratch_layout(jobs, trials, (size_t)t->max_blocks);
+  TrackScratch sc;
+  sc.sums = base;
+  sc.topkey = (int4*)(base + lay.topkey);
+  sc.topval = base + lay.topval;
+  sc.recs = cmax > 1 ? base + lay.recs : nullptr;
+  sc.max_rows = t->max_blocks;
+  sc.cmax = cmax;
+#ifdef LSD_PHASE_TRACE
+  sc.trace = t->d_trace;
+#endif
+  return sc;
+}
+
 extern "C" int lsdhip_tracker_create(lsdhip_ctx* c, lsdhip_tracker** out) {
   if (!c || !out) return LSDHIP_E_ARG;
   HIPCHK(hipSetDevice(c->device));
@@ -1355,8 +1391,7 @@ extern "C" int lsdhip_tracker_create(lsdhip_ctx* c, lsdhip_tracker** out) {
     if (t->grid_cap > 80 * nslice) t->grid_cap = (80 * nslice) & ~7;
   }
   t->max_blocks = t->grid_cap;
-  const size_t rows = (size_t)t->max_blocks;
-  const size_t scratch_bytes = (size_t)LSD_SPEC_MAX * (2 * RS_COLS * rows * 4 + 2 * rows * 16 + 2 * rows * 96 * 4 + 2 * 32 * 4);
+  const size_t partials_bytes = scratch_layout(1, LSD_SPEC_MAX, (size_t)t->max_blocks).end * sizeof(float);
   if (const char* e = getenv("LSDHIP_SPEC")) t->specC = atoi(e);
   if (t->specC < 1) t->specC = 1;
   if (t->specC > LSD_SPEC_MAX) t->specC = LSD_SPEC_MAX;
@@ -1374,8 +1409,8 @@ extern "C" int lsdhip_tracker_create(lsdhip_ctx* c, lsdhip_tracker** out) {
   t->maskStride = (((size_t)c->wl[LSD_TRACK_MIN_LEVEL] * c->hl[LSD_TRACK_MIN_LEVEL]) + 255) & ~(size_t)255;
   HIPCHK(hipMalloc((void**)&t->d_maskSide, 2 * t->maskStride * (LSD_SPEC_MAX - 1)));
   HIPCHK(hipMemsetAsync(t->d_maskSide, 0, 2 * t->maskStride * (LSD_SPEC_MAX - 1), c->stream));
-  HIPCHK(hipMalloc((void**)&t->d_partials, scratch_bytes));
-  HIPCHK(hipMemsetAsync(t->d_partials, 0, scratch_bytes, c->stream));
+  HIPCHK(hipMalloc((void**)&t->d_partials, partials_bytes));
+  HIPCHK(hipMemsetAsync(t->d_partials, 0, partials_bytes, c->stream));
 #ifdef LSD_ORDER_CHECK
   {
     const size_t nd = 8 + 2 * 8192;
@@ -1547,8 +1582,33 @@ static const float MIN_GOODPERGOODBAD_PIXEL = 0.5f;
 static const float MIN_GOODPERALL_PIXEL = 0.04f;
 static const float MIN_GOODPERALL_PIXEL_ABSMIN = 0.01f;
 
-static void fill_level(lsdhip_tracker* t, TrackJob& job, int level, lsdhip_frame* kf, lsdhip_frame* frame, const float* pts_pos,
-                       const float* pts_colvar, int npts) {
+// The batch a job is described for: how many jobs share its launches, and the workgroups each of them may use at a level.  With many
+// jobs in flight the other jobs hide a job's latency, so each job gets fewer, fatter workgroups: the per-workgroup LM replay (the price
+// of the launch needing no inter-workgroup communication) shrinks accordingly.  {0, 0}: a single job on the tracker's own grid_cap.
+struct BatchShape { int jobs, cap; };
+static BatchShape batch_shape(const lsdhip_tracker* t, int n) {
+  if (n <= 1) return {0, 0};
+  const int cap = (t->grid_cap / n) & ~7;
+  return {n, cap < 16 ? 16 : cap};
+}
+
+// Developer switches of the batch path (sweeps and A/Bs; tools/gpu.sh ab sets them per process): read once, at the first batch.
+static long long env_num(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
+struct BatchEnv {
+  int specMax = (int)std::clamp<long long>(env_num("LSDHIP_BATCH_SPEC", LSD_BATCH_SPEC_MAX), 1, LSD_BATCH_SPEC_MAX);   // most trials per step (1: off)
+  long long specPixels = env_num("LSDHIP_BATCH_SPEC_PIXELS", LSD_BATCH_SPEC_PIXELS);
+  int fused = (int)env_num("LSDHIP_BATCH_FUSED", 2);   // 0 = LM launch + evaluation launch per round (round 6), 1 = the fused form without speculation
+  int margin = (int)env_num("LSDHIP_BATCH_MARGIN", 3);   // rounds queued beyond what the recent batches needed
+  bool poll = !(getenv("LSDHIP_BATCH_POLL") && getenv("LSDHIP_BATCH_POLL")[0] == '0');   // 0: synchronise the stream instead of polling the summaries
+  int soloMin = (int)env_num("LSDHIP_BATCH_SOLO_MIN", LSD_SOLO_MIN_JOBS);   // (0: never)
+  int stripWgs = (int)env_num("LSDHIP_BATCH_WGS", LSD_BATCH_STRIP_WORKGROUPS);   // strips x jobs of a throughput-mode evaluation launch
+  int traceWg = (int)env_num("LSDHIP_TRACE_WG", 0);      // LSD_PHASE_TRACE builds: the traced workgroup
+};
+static const BatchEnv& batch_env() { static const BatchEnv env; return env; }
+
+// one level of a job: planes, intrinsics, LM settings and its tiling for the batch `shape`.  Fails only if the level-0 planes cannot be built.
+static int fill_level(lsdhip_tracker* t, TrackJob& job, BatchShape shape, int level, lsdhip_frame* kf, lsdhip_frame* frame, const float* pts_pos,
+                      const float* pts_colvar, int npts) {
   lsdhip_ctx* c = t->ctx;
   LSD_CTX_LOCK(c);
   TrackLevel& L = job.lv[level];
@@ -1556,7 +1616,7 @@ static void fill_level(lsdhip_tracker* t, TrackJob& job, int level, lsdhip_frame
   L.w = c->wl[level]; L.h = c->hl[level];
   L.fx = in.fx; L.fy = in.fy; L.cx = in.cx; L.cy = in.cy; L.fxi = in.fxi; L.fyi = in.fyi; L.cxi = in.cxi; L.cyi = in.cyi;
   L.fr_grad = frame->d_grad[level];
-  if (level == 0) (void)lsd_frame_require_level0_for_tracking(frame);   // (levels >= 1 are what a tracked frame has: the level-0 texels on demand)
+  if (level == 0) { if (int rc = lsd_frame_require_level0_for_tracking(frame)) return rc; }   // (levels >= 1 are what a tracked frame has: the level-0 texels on demand)
   if (npts >= 0) {
     L.pts_pos = pts_pos; L.pts_colvar = pts_colvar; L.npts = npts;
     L.kf_idepth = L.kf_idepthVar = L.kf_image = nullptr;
@@ -1569,17 +1629,17 @@ static void fill_level(lsdhip_tracker* t, TrackJob& job, int level, lsdhip_frame
   int work = npts >= 0 ? npts : L.w * L.h;
   L.nblocks = (work + t->block - 1) / t->block;
   if (L.nblocks >= 16) L.nblocks = (L.nblocks + 7) & ~7;   // multiples of 8: one contiguous band of tiles per XCD
-  const int cap = t->cap_override > 0 ? t->cap_override : t->grid_cap;
+  const int cap = shape.cap > 0 ? shape.cap : t->grid_cap;
   if (L.nblocks > cap) L.nblocks = cap;                     // larger levels grid-stride
   if (L.nblocks < 1) L.nblocks = 1;
   L.singlePass = (long long)L.nblocks * t->block >= work ? 1 : 0;
   L.tilePx = 0;
-  if (t->batch_jobs >= LSD_BATCH_THROUGHPUT_MIN_JOBS && npts < 0 && L.kf_refBlk != nullptr) {   // (levels >= 1: level 0 has no reference blocks)
+  if (shape.jobs >= LSD_BATCH_THROUGHPUT_MIN_JOBS && npts < 0 && L.kf_refBlk != nullptr) {   // (levels >= 1: level 0 has no reference blocks)
     // throughput mode: strips of tilePx pixels, compacted in the workgroup; enough strips over all jobs to fill the chip
-    static const int wgTarget = getenv("LSDHIP_BATCH_WGS") ? atoi(getenv("LSDHIP_BATCH_WGS")) : LSD_BATCH_STRIP_WORKGROUPS;   // developer sweep
+    const int wgTarget = batch_env().stripWgs;
     // strips x jobs = the chip's 768 workgroup slots (3 per CU) where the level is large enough: one full round of equal strips;
     // a strip is a multiple of 256 pixels (the lanes take 4 consecutive pixels each)
-    long long px = (((long long)work * t->batch_jobs + wgTarget - 1) / wgTarget + 255) & ~255LL;
+    long long px = (((long long)work * shape.jobs + wgTarget - 1) / wgTarget + 255) & ~255LL;
     if (px < 1024) px = 1024;
     if (px > 8192) px = 8192;                                  // the strip's list lives in the reduction's LDS (10545 words)
     if ((work + px - 1) / px <= t->max_blocks) {               // (levels beyond 2.4 Mpixel keep the grid-stride form)
@@ -1592,6 +1652,7 @@ static void fill_level(lsdhip_tracker* t, TrackJob& job, int level, lsdhip_frame
   L.maxIts = t->maxItsPerLvl[level];
   L.minWarped = MIN_GOODPERALL_PIXEL_ABSMIN * (c->w >> level) * (c->h >> level);
   L.writeMask = 0;
+  return LSDHIP_OK;
 }
 static void fill_job_common(lsdhip_tracker* t, TrackJob& job) {
   lsdhip_ctx* c = t->ctx;
@@ -1604,21 +1665,35 @@ static void fill_job_common(lsdhip_tracker* t, TrackJob& job) {
   job.lambdaFailFac = t->lambdaFailFac;
   job.useAffine = c->params.useAffineLightningEstimation;
 }
-
-static TrackScratch scratch_of(lsdhip_tracker* t) {
-  TrackScratch sc;
-  const size_t rows = (size_t)t->max_blocks, C = LSD_SPEC_MAX;
-  sc.sums = t->d_partials;
-  sc.topkey = (int4*)(t->d_partials + C * 2 * RS_COLS * rows);
-  sc.topval = t->d_partials + C * 2 * RS_COLS * rows + C * 2 * 4 * rows;
-  sc.recs = t->d_partials + C * 2 * RS_COLS * rows + C * 2 * 4 * rows + C * 2 * 96 * rows;
-  sc.max_rows = t->max_blocks;
-  sc.cmax = LSD_SPEC_MAX;
-#ifdef LSD_PHASE_TRACE
-  sc.trace = t->d_trace;
-#endif
-  return sc;
+// a pose as the C ABI passes it in floats: q (w x y z), t
+static lsdm::SE3fH pose_from7(const float* T7) {
+  lsdm::SE3fH T;
+  T.q = {T7[0], T7[1], T7[2], T7[3]};
+  T.t[0] = T7[4]; T.t[1] = T7[5]; T.t[2] = T7[6];
+  return T;
 }
+// referenceToFrame a job ended at
+static lsdm::SE3fH pose_of(const TrackSummary* S) {
+  const float T7[7] = {S->q[0], S->q[1], S->q[2], S->q[3], S->t[0], S->t[1], S->t[2]};
+  return pose_from7(T7);
+}
+// what a finished LM job leaves in the tracker's public members (SE3Tracker.h:82-93, 185-186)
+static void take_summary(lsdhip_tracker* t, const TrackSummary* S) {
+  t->numEvaluations = S->numEvaluations;
+  t->numWarpUpdates = S->numWarpUpdates;
+  t->pointUsage = S->pointUsage; t->lastGoodCount = S->goodCount; t->lastBadCount = S->badCount; t->lastMeanRes = S->meanRes;
+  t->affineEstimation_a = S->aff_a; t->affineEstimation_b = S->aff_b;
+  t->affineEstimation_a_lastIt = S->aff_a_lastIt; t->affineEstimation_b_lastIt = S->aff_b_lastIt;
+  t->lastResidual = S->lastResidual;
+}
+// trackingWasGood of a job that ended at `level` (SE3Tracker.cpp:267-269, 475-477), from the counts the tracker holds
+static bool tracking_was_good(const lsdhip_tracker* t, int level) {
+  const lsdhip_ctx* c = t->ctx;
+  return t->lastGoodCount / (c->wl[level] * c->hl[level]) > MIN_GOODPERALL_PIXEL &&
+         t->lastGoodCount / (t->lastGoodCount + t->lastBadCount) > MIN_GOODPERGOODBAD_PIXEL;
+}
+
+static TrackScratch scratch_of(lsdhip_tracker* t) { return scratch_at(t, t->d_partials, 1, LSD_SPEC_MAX, LSD_SPEC_MAX); }
 static void launch_step(lsdhip_tracker* t, const TrackJob& job, int grid, int parity, int first) {
   lsdhip_ctx* c = t->ctx;
   LSD_CTX_LOCK(c);
@@ -1725,6 +1800,7 @@ static int evaluate_pose(lsdhip_tracker* t, TrackJob& job, const lsdm::SE3fH& T,
     c->prof_launches++;
     c->prof_bytes += S->bytes;
   }
+  // (not take_summary: the accepted affine pair, the warp updates and the last residual belong to the host's LM loop around this evaluation)
   t->numEvaluations++;
   t->pointUsage = S->pointUsage; t->lastGoodCount = S->goodCount; t->lastBadCount = S->badCount; t->lastMeanRes = S->meanRes;
   t->affineEstimation_a_lastIt = S->aff_a_lastIt; t->affineEstimation_b_lastIt = S->aff_b_lastIt;
@@ -2038,14 +2114,8 @@ static int track_device(lsdhip_tracker* t, TrackJob& job, int topLevel, const ls
   t->numLaunches = S->numLaunches;
   t->recent[3] = t->recent[2]; t->recent[2] = t->recent[1]; t->recent[1] = t->recent[0]; t->recent[0] = t->numLaunches;
   for (int l = 0; l < LSD_LEVELS; l++) t->levelEvaluations[l] = S->levelEvals[l];
-  t->numEvaluations = S->numEvaluations;
-  t->numWarpUpdates = S->numWarpUpdates;
-  t->pointUsage = S->pointUsage; t->lastGoodCount = S->goodCount; t->lastBadCount = S->badCount; t->lastMeanRes = S->meanRes;
-  t->affineEstimation_a = S->aff_a; t->affineEstimation_b = S->aff_b;
-  t->affineEstimation_a_lastIt = S->aff_a_lastIt; t->affineEstimation_b_lastIt = S->aff_b_lastIt;
-  t->lastResidual = S->lastResidual;
-  Tout->q = {S->q[0], S->q[1], S->q[2], S->q[3]};
-  Tout->t[0] = S->t[0]; Tout->t[1] = S->t[1]; Tout->t[2] = S->t[2];
+  take_summary(t, S);
+  *Tout = pose_of(S);
   return S->diverged ? LSDHIP_DIVERGED : LSDHIP_OK;
 }
 
@@ -2058,11 +2128,19 @@ static void fill_result(lsdhip_tracker* t, const lsdm::SE3dH& T, lsdhip_track_re
   out->numEvaluations = t->numEvaluations; out->numWarpUpdates = t->numWarpUpdates;
 }
 static lsdm::SE3dH identity_d() { lsdm::SE3dH I; I.q = {1, 0, 0, 0}; I.t[0] = I.t[1] = I.t[2] = 0; return I; }
+// a diverged job's flags and result: the identity, like the reference (SE3Tracker.cpp:324-329)
+static int finish_diverged(lsdhip_tracker* t, lsdhip_track_result* out) {
+  t->diverged = true;
+  t->trackingWasGood = false;
+  fill_result(t, identity_d(), out);
+  return LSDHIP_DIVERGED;
+}
 
 // trackFrame job description (SE3Tracker.cpp:280-322): levels SE3TRACKING_MAX_LEVEL-1 .. SE3TRACKING_MIN_LEVEL
-static int fill_trackframe_job(lsdhip_tracker* t, TrackJob& job, lsdhip_frame* kf, lsdhip_frame* frame) {
+static int fill_trackframe_job(lsdhip_tracker* t, TrackJob& job, BatchShape shape, lsdhip_frame* kf, lsdhip_frame* frame) {
   fill_job_common(t, job);
-  for (int lvl = LSD_TRACK_MIN_LEVEL; lvl < LSD_TRACK_MAX_LEVEL; lvl++) fill_level(t, job, lvl, kf, frame, nullptr, nullptr, -1);
+  for (int lvl = LSD_TRACK_MIN_LEVEL; lvl < LSD_TRACK_MAX_LEVEL; lvl++)
+    if (int rcl = fill_level(t, job, shape, lvl, kf, frame, nullptr, nullptr, -1)) return rcl;
   job.lv[LSD_TRACK_MIN_LEVEL].writeMask = 1;
   int rc = lsd_frame_ensure_wasgood(frame);
   if (rc) return rc;
@@ -2071,31 +2149,59 @@ static int fill_trackframe_job(lsdhip_tracker* t, TrackJob& job, lsdhip_frame* k
   job.trackFrameSemantics = 1;
   return LSDHIP_OK;
 }
+// one evaluation (calcResidualAndBuffers .. calcWeightsAndResidual, the normal equations) at `level`, pose T7 and the affine pair
+static int fill_eval_job(lsdhip_tracker* t, TrackJob& job, BatchShape shape, lsdhip_frame* kf, lsdhip_frame* frame, int level, const float T7[7],
+                         float aff_a, float aff_b) {
+  fill_job_common(t, job);
+  if (int rcl = fill_level(t, job, shape, level, kf, frame, nullptr, nullptr, -1)) return rcl;
+  if (level == LSD_TRACK_MIN_LEVEL) {
+    if (int rc = lsd_frame_ensure_wasgood(frame)) return rc;
+    job.wasGood = frame->d_wasGood;
+    job.lv[level].writeMask = 1;
+  }
+  job.trackFrameSemantics = 1;
+  job.evalOnly = 1;
+  job.lastLevel = level;
+  job.topLevel = level;
+  job.T0 = pose_from7(T7);
+  job.aff_a0 = aff_a; job.aff_b0 = aff_b;
+  return LSDHIP_OK;
+}
+// trackFrameOnPermaref job description (SE3Tracker.cpp:162-272): `npts` reference points against the frame at QUICK_KF_CHECK_LVL, from T0
+static int fill_permaref_job(lsdhip_tracker* t, TrackJob& job, BatchShape shape, const float* pts_pos, const float* pts_colvar, int npts,
+                             lsdhip_frame* frame, const lsdm::SE3fH& T0) {
+  const int L = LSD_QUICK_KF_CHECK_LVL;
+  fill_job_common(t, job);
+  if (int rcl = fill_level(t, job, shape, L, nullptr, frame, pts_pos, pts_colvar, npts)) return rcl;
+  job.lv[L].lambdaInitial = t->lambdaInitialTestTrack; job.lv[L].stepSizeMin = t->stepSizeMinTestTrack;
+  job.lv[L].convergenceEps = t->convergenceEpsTestTrack; job.lv[L].maxIts = (int)t->maxItsTestTrack;
+  job.lastLevel = L;
+  job.topLevel = L;
+  job.trackFrameSemantics = 0;
+  job.evalOnly = 0;
+  job.T0 = T0;
+  job.aff_a0 = 1.0f; job.aff_b0 = 0.0f;
+  return LSDHIP_OK;
+}
+// epilogue of trackFrameOnPermaref (SE3Tracker.cpp:254-272) from the counters the job left in the tracker
+static int finish_permaref(lsdhip_tracker* t, bool diverged, const lsdm::SE3fH& referenceToFrame, lsdhip_track_result* out) {
+  if (diverged) return finish_diverged(t, out);
+  t->diverged = false;
+  t->trackingWasGood = tracking_was_good(t, LSD_QUICK_KF_CHECK_LVL);   // (the reference's `!diverged &&` is this branch)
+  fill_result(t, lsdm::se3d_from_f(referenceToFrame), out);
+  return LSDHIP_OK;
+}
 // epilogue of trackFrame (SE3Tracker.cpp:451-485) from the job's summary: flags, frame / keyframe side effects, result
 static int finish_trackframe(lsdhip_tracker* t, const TrackSummary* S, lsdhip_frame* kf, lsdhip_frame* frame, lsdhip_track_result* out) {
   lsdhip_ctx* c = t->ctx;
   LSD_CTX_LOCK(c);
-  t->numEvaluations = S->numEvaluations;
-  t->numWarpUpdates = S->numWarpUpdates;
-  t->pointUsage = S->pointUsage; t->lastGoodCount = S->goodCount; t->lastBadCount = S->badCount; t->lastMeanRes = S->meanRes;
-  t->affineEstimation_a = S->aff_a; t->affineEstimation_b = S->aff_b;
-  t->affineEstimation_a_lastIt = S->aff_a_lastIt; t->affineEstimation_b_lastIt = S->aff_b_lastIt;
-  t->lastResidual = S->lastResidual;
-  if (S->diverged) {
-    t->diverged = true;
-    t->trackingWasGood = false;
-    fill_result(t, identity_d(), out);
-    return LSDHIP_DIVERGED;
-  }
+  take_summary(t, S);
+  if (S->diverged) return finish_diverged(t, out);
   t->diverged = false;
-  lsdm::SE3fH referenceToFrame;
-  referenceToFrame.q = {S->q[0], S->q[1], S->q[2], S->q[3]};
-  referenceToFrame.t[0] = S->t[0]; referenceToFrame.t[1] = S->t[1]; referenceToFrame.t[2] = S->t[2];
-  t->trackingWasGood = t->lastGoodCount / (c->wl[LSD_TRACK_MIN_LEVEL] * c->hl[LSD_TRACK_MIN_LEVEL]) > MIN_GOODPERALL_PIXEL &&
-                       t->lastGoodCount / (t->lastGoodCount + t->lastBadCount) > MIN_GOODPERGOODBAD_PIXEL;
+  t->trackingWasGood = tracking_was_good(t, LSD_TRACK_MIN_LEVEL);
   if (t->trackingWasGood) kf->numFramesTrackedOnThis++;
   frame->initialTrackedResidual = t->lastResidual / t->pointUsage;
-  lsdm::SE3dH f2r = lsdm::se3d_from_f(lsdm::se3f_inverse(referenceToFrame));
+  lsdm::SE3dH f2r = lsdm::se3d_from_f(lsdm::se3f_inverse(pose_of(S)));
   frame->thisToParent_raw.q = f2r.q;
   lsdm::q_normalize(frame->thisToParent_raw.q);   // sim3FromSE3 -> Sim3::setScale normalises the quaternion (rxso3.hpp:332-335)
   frame->thisToParent_raw.t[0] = f2r.t[0]; frame->thisToParent_raw.t[1] = f2r.t[1]; frame->thisToParent_raw.t[2] = f2r.t[2];
@@ -2126,7 +2232,7 @@ extern "C" int lsdhip_tracker_track(lsdhip_tracker* t, lsdhip_frame* kf, lsdhip_
     if (kf->depthSeq > need) need = kf->depthSeq;
     if (int rcw = lsd_t_wait_m(c, need)) return rcw;
   }
-  int rc = fill_trackframe_job(t, job, kf, frame);
+  int rc = fill_trackframe_job(t, job, BatchShape{}, kf, frame);
   if (rc) return rc;
   if (int rcg = lsd_gate_open(c)) return rcg;
   if (int rcd = lsd_pipe_dummy(c)) return rcd;
@@ -2157,12 +2263,7 @@ extern "C" int lsdhip_tracker_track(lsdhip_tracker* t, lsdhip_frame* kf, lsdhip_
     for (int lvl = LSD_TRACK_MAX_LEVEL - 1; lvl >= LSD_TRACK_MIN_LEVEL && rc == LSDHIP_OK; lvl--)
       rc = lm_level_host(t, job, lvl, referenceToFrame, &last_residual);
     t->lastResidual = last_residual;
-    if (rc == LSDHIP_DIVERGED) {
-      t->diverged = true;
-      t->trackingWasGood = false;
-      fill_result(t, identity_d(), out);
-      return LSDHIP_DIVERGED;
-    }
+    if (rc == LSDHIP_DIVERGED) return finish_diverged(t, out);
     if (rc) return rc;
     // host-LM debugging path: build the summary the common epilogue expects
     TrackSummary S = *t->h_summary;
@@ -2249,45 +2350,24 @@ static int batch_reserve(lsdhip_tracker* t, int n) {
   HIPCHK(hipStreamSynchronize(c->stream));
   if (t->d_bjobs) { (void)hipFree(t->d_bjobs); (void)hipFree(t->d_bstate); (void)hipFree(t->d_bscratch); (void)hipHostFree(t->h_bjobs); (void)hipHostFree(t->h_bsummary); }
   t->batch_capacity = n < 8 ? 8 : n;
-  const size_t B = (size_t)t->batch_capacity, rows = (size_t)t->max_blocks;
-  const size_t per_job = (size_t)LSD_BATCH_SPEC_MAX * (2 * RS_COLS * rows * 4 + 2 * rows * 16 + 2 * rows * 96 * 4 + 2 * 32 * 4);
+  const size_t B = (size_t)t->batch_capacity, bytes = scratch_layout(B, LSD_BATCH_SPEC_MAX, (size_t)t->max_blocks).end * sizeof(float);
   HIPCHK(hipMalloc((void**)&t->d_bjobs, B * sizeof(TrackJob)));
   HIPCHK(hipMalloc((void**)&t->d_bstate, B * 2 * sizeof(TrackState)));
-  HIPCHK(hipMalloc((void**)&t->d_bscratch, B * per_job));
-  HIPCHK(hipMemsetAsync(t->d_bscratch, 0, B * per_job, c->stream));
+  HIPCHK(hipMalloc((void**)&t->d_bscratch, bytes));
+  HIPCHK(hipMemsetAsync(t->d_bscratch, 0, bytes, c->stream));
   HIPCHK(hipHostMalloc((void**)&t->h_bjobs, B * sizeof(TrackJob), hipHostMallocDefault));
   HIPCHK(hipHostMalloc((void**)&t->h_bsummary, B * sizeof(TrackSummary), hipHostMallocMapped));
   return LSDHIP_OK;
 }
 // scratch of a batch: arrays over [job][parity][trial]; cmax = trial slots per parity (1: no speculation)
 static TrackScratch batch_scratch(lsdhip_tracker* t, int cmax) {
-  TrackScratch sc;
-  const size_t B = (size_t)t->batch_capacity, rows = (size_t)t->max_blocks, C = (size_t)LSD_BATCH_SPEC_MAX;
-  sc.sums = t->d_bscratch;
-  sc.topkey = (int4*)(t->d_bscratch + B * C * 2 * RS_COLS * rows);
-  sc.topval = t->d_bscratch + B * C * 2 * RS_COLS * rows + B * C * 2 * 4 * rows;
-  sc.recs = cmax > 1 ? t->d_bscratch + B * C * 2 * RS_COLS * rows + B * C * 2 * 4 * rows + B * C * 2 * 96 * rows : nullptr;
-  sc.max_rows = t->max_blocks;
-  sc.cmax = cmax;
-#ifdef LSD_PHASE_TRACE
-  sc.trace = t->d_trace;
-#endif
-  return sc;
-}
-// With many jobs in flight the other jobs hide a job's latency, so each job gets fewer, fatter workgroups: the
-// per-workgroup LM replay (the price of the launch needing no inter-workgroup communication) shrinks accordingly.
-static void batch_begin(lsdhip_tracker* t, int n) {
-  t->batch_jobs = n;
-  t->cap_override = (t->grid_cap / n) & ~7;
-  if (t->cap_override < 16) t->cap_override = 16;
-  if (n == 1) t->cap_override = 0;
+  return scratch_at(t, t->d_bscratch, (size_t)t->batch_capacity, LSD_BATCH_SPEC_MAX, cmax);
 }
 // runs the n jobs described in t->h_bjobs[0..n) to completion; summaries in t->h_bsummary
 static int batch_run(lsdhip_tracker* t, int n, bool callHook = false) {
   lsdhip_ctx* c = t->ctx;
   LSD_CTX_LOCK(c);
-  t->cap_override = 0;
-  t->batch_jobs = 0;
+  const BatchEnv& env = batch_env();
   int grid = 1;
   bool split = false;
   for (int j = 0; j < n; j++) {
@@ -2305,13 +2385,12 @@ static int batch_run(lsdhip_tracker* t, int n, bool callHook = false) {
   // (a round must not cost more than the rounds it saves); one at the level that writes refPixelWasGood (no side planes in batches).
   TrackSpec spec = TrackSpec{};
 #ifdef LSD_PHASE_TRACE
-  spec.traceWg = getenv("LSDHIP_TRACE_WG") ? atoi(getenv("LSDHIP_TRACE_WG")) : 0;
+  spec.traceWg = env.traceWg;
 #endif
   int lmGrid = 1;
-  static const int specMaxEnv = getenv("LSDHIP_BATCH_SPEC") ? atoi(getenv("LSDHIP_BATCH_SPEC")) : LSD_BATCH_SPEC_MAX;   // developer A/B (1: off)
-  int specMax = specMaxEnv < 1 ? 1 : (specMaxEnv > LSD_BATCH_SPEC_MAX ? LSD_BATCH_SPEC_MAX : specMaxEnv);
+  int specMax = env.specMax;
   if (t->specC < specMax) specMax = t->specC;        // lsdhip_tracker_set_speculation(t, 1, 0): one evaluation per step, batches too
-  if (getenv("LSDHIP_BATCH_FUSED") && atoi(getenv("LSDHIP_BATCH_FUSED")) == 1) specMax = 1;   // developer A/B: the fused form without speculation
+  if (env.fused == 1) specMax = 1;
   if (split && specMax > 1) {
     for (int l = 0; l < LSD_LEVELS; l++) spec.trials[l] = 1;
     const TrackJob& j0 = t->h_bjobs[0];
@@ -2319,8 +2398,7 @@ static int batch_run(lsdhip_tracker* t, int n, bool callHook = false) {
       bool ok = true;
       for (int j = 0; j < n; j++) ok = ok && t->h_bjobs[j].lv[l].tilePx > 0 && !t->h_bjobs[j].lv[l].writeMask && t->h_bjobs[j].lastLevel <= l && t->h_bjobs[j].topLevel >= l;
       if (!ok) continue;
-      static const long long specPixels = getenv("LSDHIP_BATCH_SPEC_PIXELS") ? atoll(getenv("LSDHIP_BATCH_SPEC_PIXELS")) : LSD_BATCH_SPEC_PIXELS;   // developer sweep
-      long long tr = specPixels / ((long long)j0.lv[l].w * j0.lv[l].h * n);
+      long long tr = env.specPixels / ((long long)j0.lv[l].w * j0.lv[l].h * n);
       if (tr > specMax) tr = specMax;
       if (tr < 1) tr = 1;
       spec.trials[l] = (int)tr;
@@ -2343,17 +2421,14 @@ static int batch_run(lsdhip_tracker* t, int n, bool callHook = false) {
   if (split && t->batchRecent[0] > 0) {
     budget = 0;
     for (int i = 0; i < 4; i++) if (t->batchRecent[i] > budget) budget = t->batchRecent[i];
-    static const int marginEnv = getenv("LSDHIP_BATCH_MARGIN") ? atoi(getenv("LSDHIP_BATCH_MARGIN")) : 3;   // developer sweep
-    budget += marginEnv;
+    budget += env.margin;
   }
   int parity = 0, first = 1, guard = 0;
-  static const int fusedEnv = getenv("LSDHIP_BATCH_FUSED") ? atoi(getenv("LSDHIP_BATCH_FUSED")) : 2;   // developer A/B (round 6): 0 = LM launch + evaluation launch per round
   // Fused rounds: the host polls the jobs' summaries in pinned memory (as lsdhip_tracker_track does for one job) instead of draining the
   // stream: the budget's launches behind the last job's finishing step (~3 us each, a handful per batch) then run while the host is
   // already reading the results and queueing what follows.  `done` carries the batch's tag, the record is taken once it adds up to its
   // check word; the budget's last launch reports a job it leaves unfinished (`exhausted`).
-  static const bool pollEnv = !(getenv("LSDHIP_BATCH_POLL") && getenv("LSDHIP_BATCH_POLL")[0] == '0');   // developer A/B
-  const bool polled = split && fusedEnv && t->spinWait && pollEnv;
+  const bool polled = split && env.fused && t->spinWait && env.poll;
   if (polled) {
     t->batchTag = t->batchTag >= 0x3FFFFFFF ? 2 : t->batchTag + 1;
     if (t->batchTag < 2) t->batchTag = 2;
@@ -2361,9 +2436,8 @@ static int batch_run(lsdhip_tracker* t, int n, bool callHook = false) {
     for (int j = 0; j < n; j++) t->h_bsummary[j].exhausted = 0;
   }
   // the coarse levels of every job inside one workgroup (k_track_solo), then lock-step rounds for the rest
-  static const int soloMinEnv = getenv("LSDHIP_BATCH_SOLO_MIN") ? atoi(getenv("LSDHIP_BATCH_SOLO_MIN")) : LSD_SOLO_MIN_JOBS;   // developer A/B (0: never)
-  const int soloMin = t->soloMinJobs >= 0 ? t->soloMinJobs : soloMinEnv;     // lsdhip_tracker_set_batch_coarse_min_jobs
-  bool soloDue = split && fusedEnv && soloMin > 0 && n >= soloMin;
+  const int soloMin = t->soloMinJobs >= 0 ? t->soloMinJobs : env.soloMin;     // lsdhip_tracker_set_batch_coarse_min_jobs
+  bool soloDue = split && env.fused && soloMin > 0 && n >= soloMin;
   if (soloDue) {
     // (nothing to walk if no job's top level fits the tile — 1280x1024: level 4 is 80x64 = 5120 pixels —: the launch would only copy states)
     bool any = false;
@@ -2384,7 +2458,7 @@ static int batch_run(lsdhip_tracker* t, int n, bool callHook = false) {
     }
     for (int i = 0; i < budget; i++) {
       spec.last = (polled && i == budget - 1) ? 1 : 0;
-      if (split && fusedEnv) {
+      if (split && env.fused) {
         hipLaunchKernelGGL((k_track_step<256, true, TS_FUSED>), dim3(grid, n), dim3(256), 0, c->stream, t->h_bjobs[0], (const TrackJob*)t->d_bjobs,
                            t->d_bstate, sc, d_sum, parity, first, spec);
       } else if (split) {
@@ -2475,7 +2549,8 @@ extern "C" int lsdhip_tracker_track_batch(lsdhip_tracker* t, int n, lsdhip_frame
   if (c->pipeline) {
     // as lsdhip_tracker_track: the tracking stream waits for the mapping-stream points its inputs were complete at (the frames'
     // pyramids, the keyframes' PUBLISHED depth) and for nothing queued behind them — the mapping iterations of OTHER sequences run
-    // beside this batch (SlamLoopBatch::setOverlapped).  batch_run leaves the tracking stream drained.
+    // beside this batch (SlamLoopBatch::setOverlapped).  When batch_run returns only the summaries are complete: the launches of its budget
+    // behind the last job's finishing step may still be queued on the tracking stream (they leave at once, see track_step_impl).
     long long need = 0;
     for (int j = 0; j < n; j++) {
       need = std::max(need, std::max(frames[j]->readySeq, std::max(keyframes[j]->readySeq, keyframes[j]->depthSeq)));
@@ -2485,11 +2560,11 @@ extern "C" int lsdhip_tracker_track_batch(lsdhip_tracker* t, int n, lsdhip_frame
   if (n >= LSD_BATCH_THROUGHPUT_MIN_JOBS) { if (int rcb = lsd_frames_require_ref_blocks(keyframes, n, c->stream)) return rcb; }   // the strips read them
   int rc = batch_reserve(t, n);
   if (rc) return rc;
-  batch_begin(t, n);
+  const BatchShape shape = batch_shape(t, n);
   for (int j = 0; j < n; j++) {
     TrackJob& job = t->h_bjobs[j];
-    rc = fill_trackframe_job(t, job, keyframes[j], frames[j]);
-    if (rc) { t->cap_override = 0; t->batch_jobs = 0; return rc; }
+    rc = fill_trackframe_job(t, job, shape, keyframes[j], frames[j]);
+    if (rc) return rc;
     job.evalOnly = 0;
     job.topLevel = LSD_TRACK_MAX_LEVEL - 1;
     job.T0 = lsdm::se3f_from_d(lsdm::se3d_inverse(lsdm::se3d_from7(inits + 7 * (size_t)j)));
@@ -2525,33 +2600,16 @@ extern "C" int lsdhip_tracker_eval_throughput(lsdhip_tracker* t, int n, lsdhip_f
   if (int rcb = lsd_frames_require_ref_blocks(keyframes, n, c->stream)) return rcb;
   int rc = batch_reserve(t, n);
   if (rc) return rc;
-  batch_begin(t, n);
+  const BatchShape shape = batch_shape(t, n);
   int grid = 1;
   for (int j = 0; j < n; j++) {
-    if (!keyframes[j] || !frames[j] || !keyframes[j]->hasIDepth) { t->cap_override = 0; t->batch_jobs = 0; return LSDHIP_E_ARG; }
     TrackJob& job = t->h_bjobs[j];
-    fill_job_common(t, job);
-    fill_level(t, job, level, keyframes[j], frames[j], nullptr, nullptr, -1);
-    if (level == LSD_TRACK_MIN_LEVEL) {
-      rc = lsd_frame_ensure_wasgood(frames[j]);
-      if (rc) { t->cap_override = 0; t->batch_jobs = 0; return rc; }
-      job.wasGood = frames[j]->d_wasGood;
-      job.lv[level].writeMask = 1;
-    }
-    job.trackFrameSemantics = 1;
-    job.evalOnly = 1;
-    job.lastLevel = level;
-    job.topLevel = level;
-    const float* T7 = refToFrame + 7 * (size_t)j;
-    job.T0.q = {T7[0], T7[1], T7[2], T7[3]};
-    job.T0.t[0] = T7[4]; job.T0.t[1] = T7[5]; job.T0.t[2] = T7[6];
-    job.aff_a0 = 1.0f; job.aff_b0 = 0.0f;
+    rc = fill_eval_job(t, job, shape, keyframes[j], frames[j], level, refToFrame + 7 * (size_t)j, 1.0f, 0.0f);
+    if (rc) return rc;
     if (job.lv[level].nblocks > grid) grid = job.lv[level].nblocks;
-    if (job.lv[level].tilePx == 0) { t->cap_override = 0; t->batch_jobs = 0; lsd_set_error("lsdhip_tracker_eval_throughput: level %d is not in throughput mode", level); return LSDHIP_E_STATE; }
+    if (job.lv[level].tilePx == 0) { lsd_set_error("lsdhip_tracker_eval_throughput: level %d is not in throughput mode", level); return LSDHIP_E_STATE; }
     t->h_bsummary[j].done = 0;
   }
-  t->cap_override = 0;
-  t->batch_jobs = 0;
   HIPCHK(hipMemcpyAsync(t->d_bjobs, t->h_bjobs, (size_t)n * sizeof(TrackJob), hipMemcpyHostToDevice, c->stream));
   const TrackScratch sc = batch_scratch(t, 1);
   TrackSummary* d_sum = nullptr;
@@ -2599,22 +2657,12 @@ extern "C" int lsdhip_tracker_evaluate(lsdhip_tracker* t, lsdhip_frame* kf, lsdh
   LSD_CTX_LOCK(t->ctx);
   LsdTrackJobScope tjob_(t->ctx, true);
   if (tjob_.rc) return tjob_.rc;
-  lsdm::SE3fH T;
-  T.q = {T7[0], T7[1], T7[2], T7[3]};
-  T.t[0] = T7[4]; T.t[1] = T7[5]; T.t[2] = T7[6];
-  t->affineEstimation_a = aff_a; t->affineEstimation_b = aff_b;
+  t->affineEstimation_a = aff_a; t->affineEstimation_b = aff_b;   // (evaluate_pose evaluates at the tracker's pair)
   TrackJob job;
-  fill_job_common(t, job);
-  fill_level(t, job, level, kf, frame, nullptr, nullptr, -1);
-  if (level == LSD_TRACK_MIN_LEVEL) {
-    int rc = lsd_frame_ensure_wasgood(frame);
-    if (rc) return rc;
-    job.wasGood = frame->d_wasGood;
-    job.lv[level].writeMask = 1;
-  }
-  job.trackFrameSemantics = 1;
+  int rc = fill_eval_job(t, job, BatchShape{}, kf, frame, level, T7, aff_a, aff_b);
+  if (rc) return rc;
   EvalOut ev;
-  int rc = evaluate_pose(t, job, T, level, &ev);
+  rc = evaluate_pose(t, job, job.T0, level, &ev);
   if (rc) return rc;
   record_of(t->h_summary, out);
   return LSDHIP_OK;
@@ -2642,25 +2690,10 @@ extern "C" int lsdhip_tracker_evaluate_batch(lsdhip_tracker* t, int n, lsdhip_fr
   if (n >= LSD_BATCH_THROUGHPUT_MIN_JOBS) { if (int rcb = lsd_frames_require_ref_blocks(keyframes, n, c->stream)) return rcb; }   // the strips read them
   int rc = batch_reserve(t, n);
   if (rc) return rc;
-  batch_begin(t, n);
+  const BatchShape shape = batch_shape(t, n);
   for (int j = 0; j < n; j++) {
-    TrackJob& job = t->h_bjobs[j];
-    fill_job_common(t, job);
-    fill_level(t, job, level, keyframes[j], frames[j], nullptr, nullptr, -1);
-    if (level == LSD_TRACK_MIN_LEVEL) {
-      rc = lsd_frame_ensure_wasgood(frames[j]);
-      if (rc) { t->cap_override = 0; t->batch_jobs = 0; return rc; }
-      job.wasGood = frames[j]->d_wasGood;
-      job.lv[level].writeMask = 1;
-    }
-    job.trackFrameSemantics = 1;
-    job.evalOnly = 1;
-    job.lastLevel = level;
-    job.topLevel = level;
-    const float* T7 = refToFrame + 7 * (size_t)j;
-    job.T0.q = {T7[0], T7[1], T7[2], T7[3]};
-    job.T0.t[0] = T7[4]; job.T0.t[1] = T7[5]; job.T0.t[2] = T7[6];
-    job.aff_a0 = affine[2 * (size_t)j]; job.aff_b0 = affine[2 * (size_t)j + 1];
+    rc = fill_eval_job(t, t->h_bjobs[j], shape, keyframes[j], frames[j], level, refToFrame + 7 * (size_t)j, affine[2 * (size_t)j], affine[2 * (size_t)j + 1]);
+    if (rc) return rc;
   }
   // what batch_run leaves in the tracker besides the summaries: the rounds of recent batches (the next batch's budget) and launch_stats
   int recent[4];
@@ -2709,12 +2742,8 @@ extern "C" int lsdhip_tracker_track_permaref(lsdhip_tracker* t, const float* pos
   t->numEvaluations = 0; t->numWarpUpdates = 0;
   const int L = LSD_QUICK_KF_CHECK_LVL;
   TrackJob job;
-  fill_job_common(t, job);
-  fill_level(t, job, L, nullptr, frame, t->d_pts, t->d_pts + (size_t)t->pts_capacity * 3, n);
-  job.lv[L].lambdaInitial = t->lambdaInitialTestTrack; job.lv[L].stepSizeMin = t->stepSizeMinTestTrack;
-  job.lv[L].convergenceEps = t->convergenceEpsTestTrack; job.lv[L].maxIts = (int)t->maxItsTestTrack;
-  job.lastLevel = L;
-  job.trackFrameSemantics = 0;
+  rc = fill_permaref_job(t, job, BatchShape{}, t->d_pts, t->d_pts + (size_t)t->pts_capacity * 3, n, frame, referenceToFrame);
+  if (rc) return rc;
   if (t->hostLM) {
     float lastErr = 0;
     rc = lm_level_host(t, job, L, referenceToFrame, &lastErr);
@@ -2722,16 +2751,8 @@ extern "C" int lsdhip_tracker_track_permaref(lsdhip_tracker* t, const float* pos
   } else {
     rc = track_device(t, job, L, referenceToFrame, &referenceToFrame);
   }
-  if (rc == LSDHIP_DIVERGED) {
-    t->diverged = true; t->trackingWasGood = false;
-    fill_result(t, identity_d(), out);
-    return LSDHIP_DIVERGED;
-  }
-  if (rc) return rc;
-  t->trackingWasGood = !t->diverged && t->lastGoodCount / (c->wl[L] * c->hl[L]) > MIN_GOODPERALL_PIXEL &&
-                       t->lastGoodCount / (t->lastGoodCount + t->lastBadCount) > MIN_GOODPERGOODBAD_PIXEL;
-  fill_result(t, lsdm::se3d_from_f(referenceToFrame), out);
-  return LSDHIP_OK;
+  if (rc != LSDHIP_OK && rc != LSDHIP_DIVERGED) return rc;
+  return finish_permaref(t, rc == LSDHIP_DIVERGED, referenceToFrame, out);
 }
 
 // SE3Tracker::trackFrameOnPermaref (SE3Tracker.cpp:162-272) for n permanent references against frames[j] in the same
@@ -2752,21 +2773,12 @@ extern "C" int lsdhip_tracker_track_permaref_batch(lsdhip_tracker* t, int n, con
   if (rc) return rc;
   rc = batch_reserve(t, n);
   if (rc) return rc;
-  batch_begin(t, n);
-  const int L = LSD_QUICK_KF_CHECK_LVL;
+  const BatchShape shape = batch_shape(t, n);
   int off = 0;
   for (int j = 0; j < n; j++) {
-    TrackJob& job = t->h_bjobs[j];
-    fill_job_common(t, job);
-    fill_level(t, job, L, nullptr, frames[j], t->d_pts + (size_t)off * 3, t->d_pts + (size_t)t->pts_capacity * 3 + (size_t)off * 2, counts[j]);
-    job.lv[L].lambdaInitial = t->lambdaInitialTestTrack; job.lv[L].stepSizeMin = t->stepSizeMinTestTrack;
-    job.lv[L].convergenceEps = t->convergenceEpsTestTrack; job.lv[L].maxIts = (int)t->maxItsTestTrack;
-    job.lastLevel = L;
-    job.topLevel = L;
-    job.trackFrameSemantics = 0;
-    job.evalOnly = 0;
-    job.T0 = lsdm::se3f_from_d(lsdm::se3d_from7(refToFrame + 7 * (size_t)j));
-    job.aff_a0 = 1.0f; job.aff_b0 = 0.0f;
+    rc = fill_permaref_job(t, t->h_bjobs[j], shape, t->d_pts + (size_t)off * 3, t->d_pts + (size_t)t->pts_capacity * 3 + (size_t)off * 2, counts[j],
+                           frames[j], lsdm::se3f_from_d(lsdm::se3d_from7(refToFrame + 7 * (size_t)j)));
+    if (rc) return rc;
     off += counts[j];
   }
   rc = batch_run(t, n);
@@ -2774,23 +2786,8 @@ extern "C" int lsdhip_tracker_track_permaref_batch(lsdhip_tracker* t, int n, con
   int rcAll = LSDHIP_OK;
   for (int j = 0; j < n; j++) {
     const TrackSummary* S = &t->h_bsummary[j];
-    t->numEvaluations = S->numEvaluations; t->numWarpUpdates = S->numWarpUpdates;
-    t->pointUsage = S->pointUsage; t->lastGoodCount = S->goodCount; t->lastBadCount = S->badCount; t->lastMeanRes = S->meanRes;
-    t->affineEstimation_a = S->aff_a; t->affineEstimation_b = S->aff_b;
-    t->lastResidual = S->lastResidual;
-    if (S->diverged) {
-      t->diverged = true; t->trackingWasGood = false;
-      fill_result(t, identity_d(), &results[j]);
-      rcAll = LSDHIP_DIVERGED;
-      continue;
-    }
-    t->diverged = false;
-    t->trackingWasGood = t->lastGoodCount / (c->wl[L] * c->hl[L]) > MIN_GOODPERALL_PIXEL &&
-                         t->lastGoodCount / (t->lastGoodCount + t->lastBadCount) > MIN_GOODPERGOODBAD_PIXEL;
-    lsdm::SE3fH T;
-    T.q = {S->q[0], S->q[1], S->q[2], S->q[3]};
-    T.t[0] = S->t[0]; T.t[1] = S->t[1]; T.t[2] = S->t[2];
-    fill_result(t, lsdm::se3d_from_f(T), &results[j]);
+    take_summary(t, S);   // (with the affine pair of the last iteration, which only the host-LM loop reads, behind an evaluation of its own)
+    if (finish_permaref(t, S->diverged != 0, pose_of(S), &results[j]) == LSDHIP_DIVERGED) rcAll = LSDHIP_DIVERGED;
   }
   return rcAll;
 }

@@ -14,7 +14,7 @@ mask within 0.2 %) cannot see small errors the LM loop absorbs; here every job o
 
 gamma = depth of one term on its way into the total + the record's division (1) + per-term roundings.  The depth per form:
   small batch (k_track_step<256, true>, fewer than 8 jobs): P sequential additions in a lane, P = pixels per lane of the grid-stride loop
-    = ceil(w h / (256 nb)), min(16, ceil(w h / 256)) <= nb <= ceil(w h / 256) rounded up to 8 workgroups (batch_begin: at least 16); the LDS fold: a run of
+    = ceil(w h / (256 nb)), min(16, ceil(w h / 256)) <= nb <= ceil(w h / 256) rounded up to 8 workgroups (batch_shape: at least 16); the LDS fold: a run of
     RRUN = ceil(256 / RSLICE) = 43 lanes (RSLICE = 256 / RS_END = 6 slices of the 41 columns, CPP = RS_END), then the 6 slices (5); the
     finishing launch: K = ceil(nb / 16) rows per row slot (K), the 16 slots (15); the subtraction of up to 3 tail points (3).
     nb is not reported, so P + K is taken at its largest over the nb the rule allows.
