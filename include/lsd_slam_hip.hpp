@@ -240,6 +240,75 @@ class Frame {
   double timestamp_;
 };
 
+// The vendored Sophus stores a Sim3 as a non-unit quaternion (x, y, z, w) whose norm is the scale (thirdparty/Sophus/
+// sophus/rxso3.hpp:311-313), followed by the translation (sim3.hpp:740-754); ROSOutput3DWrapper memcpys those 7 floats.
+inline void sim3ToWire(const Sim3& T, float out[7]) {
+  const double r = T.s;
+  out[0] = (float)(T.q[1] * r); out[1] = (float)(T.q[2] * r); out[2] = (float)(T.q[3] * r); out[3] = (float)(T.q[0] * r);
+  out[4] = (float)T.t[0]; out[5] = (float)T.t[1]; out[6] = (float)T.t[2];
+}
+
+// The viewer's accumulated point cloud (KeyFrameDisplay::flushPC per keyframe, lsd_slam_viewer/src/KeyFrameDisplay.cpp:269-340) in device
+// memory: appendKeyframe queues the filter + back-projection + ordered compaction of one finalised keyframe on the context's mapping
+// stream and returns; nothing waits until total() / stored() / segments() / download() ask.  Points are (x, y, z, intensity), in row-major
+// pixel order within a keyframe, keyframes in call order; equal bit for bit to flushPointCloud of lsd_slam_hip_io.hpp on the same planes.
+// Points beyond `capacityPoints` are counted (total()) but not stored; keyframes beyond `maxKeyframes` get no segment row.
+class PointCloud {
+ public:
+  struct Segment { int id; int64_t first; int count; };
+  PointCloud(std::shared_ptr<Context> ctx, int64_t capacityPoints, int maxKeyframes) : ctx_(std::move(ctx)) {
+    check(lsdhip_cloud_create(ctx_->handle(), capacityPoints, maxKeyframes, &h_), "lsdhip_cloud_create");
+  }
+  PointCloud(const PointCloud&) = delete;
+  PointCloud& operator=(const PointCloud&) = delete;
+  ~PointCloud() { lsdhip_cloud_destroy(h_); }
+  // the viewer's defaults (lsd_slam_viewer/src/settings.cpp:36-40); false once the segment table is full.  `kf` may be dropped right after the call.
+  bool appendKeyframe(Frame& kf, const Sim3& camToWorld, float scaledTH = 1.f, float absTH = 1.f, int minNearSupport = 5) {
+    float wire[7];
+    sim3ToWire(camToWorld, wire);
+    return check(lsdhip_cloud_append_keyframe(h_, kf.handle(), wire, scaledTH, absTH, minNearSupport), "lsdhip_cloud_append_keyframe") != LSDHIP_CLOUD_TABLE_FULL;
+  }
+  // n keyframes into n different clouds of one context in the launches of one (lsdhip_cloud_append_batch)
+  static void appendBatch(const std::vector<PointCloud*>& clouds, const std::vector<Frame*>& kfs, const std::vector<Sim3>& camToWorld,
+                          float scaledTH = 1.f, float absTH = 1.f, int minNearSupport = 5) {
+    const size_t n = clouds.size();
+    if (n == 0) return;
+    if (kfs.size() != n || camToWorld.size() != n) throw Error(LSDHIP_E_ARG, "PointCloud::appendBatch: one frame and one pose per cloud");
+    std::vector<lsdhip_cloud*> cs(n);
+    std::vector<lsdhip_frame*> fs(n);
+    std::vector<float> poses(7 * n);
+    for (size_t j = 0; j < n; j++) { cs[j] = clouds[j]->h_; fs[j] = kfs[j]->handle(); sim3ToWire(camToWorld[j], &poses[7 * j]); }
+    check(lsdhip_cloud_append_batch(clouds[0]->ctx_->handle(), (int)n, cs.data(), fs.data(), poses.data(), scaledTH, absTH, minNearSupport),
+          "lsdhip_cloud_append_batch");
+  }
+  int64_t total() const { int64_t t = 0, s = 0; check(lsdhip_cloud_count(h_, &t, &s), "lsdhip_cloud_count"); return t; }
+  int64_t stored() const { int64_t t = 0, s = 0; check(lsdhip_cloud_count(h_, &t, &s), "lsdhip_cloud_count"); return s; }
+  std::vector<Segment> segments() const {
+    int n = 0;
+    check(lsdhip_cloud_segments(h_, 0, nullptr, nullptr, nullptr, &n), "lsdhip_cloud_segments");
+    std::vector<int> ids((size_t)n), cnt((size_t)n);
+    std::vector<int64_t> first((size_t)n);
+    int n2 = 0;
+    check(lsdhip_cloud_segments(h_, n, ids.data(), first.data(), cnt.data(), &n2), "lsdhip_cloud_segments");
+    std::vector<Segment> out;
+    for (int i = 0; i < n && i < n2; i++) out.push_back(Segment{ids[(size_t)i], first[(size_t)i], cnt[(size_t)i]});
+    return out;
+  }
+  // stored points [first, first + n) as x y z intensity; n < 0: all from `first`
+  std::vector<float> download(int64_t first = 0, int64_t n = -1) const {
+    if (n < 0) { n = stored() - first; if (n < 0) n = 0; }
+    std::vector<float> v((size_t)n * 4);
+    check(lsdhip_cloud_download(h_, first, n, v.data()), "lsdhip_cloud_download");
+    return v;
+  }
+  void reset() { check(lsdhip_cloud_reset(h_), "lsdhip_cloud_reset"); }
+  lsdhip_cloud* handle() const { return h_; }
+
+ private:
+  std::shared_ptr<Context> ctx_;
+  lsdhip_cloud* h_ = nullptr;
+};
+
 // Tracking/TrackingReference.h — on the device the point cloud is generated inside the residual kernel, so this object
 // only remembers which keyframe it refers to; makePointCloud() exports the compacted arrays in the reference's order.
 class TrackingReference {
@@ -614,6 +683,11 @@ class SlamLoop {
   }
   // called with the keyframe that has just been finalised (before the next one replaces it): output hook (PLY, messages)
   std::function<void(Frame&, DepthMap&)> onKeyframeFinished;
+  // Second output hook: called AFTER the keyframe change (DepthMap::changeKeyframe, or createKeyFrame on the split path) with the keyframe
+  // that was just finalised.  Meant for stream-ordered work (PointCloud::appendKeyframe queues three launches and returns): the planes of
+  // that keyframe stay as finalised.  A hook that waits for the device (a download, makeKeyframeMsgDevice) is still correct, but stalls the
+  // loop for that wait once per keyframe.  Setting the hook leaves the loop on the shared keyframe change.
+  std::function<void(Frame&)> onKeyframeFinishedAsync;
   // track one frame, then one mapping iteration; returns frameToKeyframe (of the keyframe the frame was tracked on).  Throws when
   // tracking diverges.
   SE3 step(const unsigned char* image) { return step(image, [](double) {}); }
@@ -662,6 +736,7 @@ class SlamLoop {
           map.finalizeKeyFrame();
           numKeyframesFinished_++;
           if (onKeyframeFinished) onKeyframeFinished(*keyframe, map);
+          if (onKeyframeFinishedAsync) onKeyframeFinishedAsync(*keyframe);
         }   // else discardCurrentKeyframe (:428-456): nothing of it is kept
         map.invalidate();
       }
@@ -719,6 +794,7 @@ class SlamLoop {
       } else {
         map.changeKeyframe(frame.get());
       }
+      if (onKeyframeFinishedAsync) onKeyframeFinishedAsync(*keyframe);
       keyframe = frame;
       if (keepKeyframes) keyframeLog.push_back(frame);
       liveQueue_.clear();
@@ -818,6 +894,7 @@ class SlamLoopBatch {
     bool trackingLost = false, newKeyframe = false;
     lsdhip_track_result last = lsdhip_track_result();
     std::vector<std::shared_ptr<Frame>> keyframeLog;   // every keyframe this sequence promoted (SlamLoopBatch::keepKeyframes)
+    std::shared_ptr<Frame> replacedFirst;              // ... and the keyframe its first keyframe change replaced while keepKeyframes was on (not in the log: it was never promoted)
   };
   // firstImages / gtDepth0: S pointers each (gtDepth0 == null or gtDepth0[s] == null: random initialisation of that sequence)
   SlamLoopBatch(int w, int h, const Mat3f& K, int S, const unsigned char* const* firstImages, bool imagesOnDevice,
@@ -980,6 +1057,16 @@ class SlamLoopBatch {
   // queues the mapping work the last step left (a pipelined loop keeps it back for the next tracking batch's enqueue hook); call after the
   // last step() before reading maps or statistics
   void flush() { MapWork w = std::move(deferred_); deferred_ = MapWork(); mapGroup(w); }
+  // Per-sequence output: sinks[s] (null: none) receives every keyframe sequence s finalises at a keyframe change, with camToWorld =
+  // poseOf(s, keyframe).  The keyframes that change in one step go into ONE PointCloud::appendBatch queued behind the keyframe change;
+  // nothing waits.  The clouds must be pairwise different and outlive the loop's use of them.
+  void setCloudSinks(std::vector<PointCloud*> sinks, std::function<Sim3(int, Frame&)> poseOf) {
+    if (!sinks.empty() && ((int)sinks.size() != size() || !poseOf)) throw Error(LSDHIP_E_ARG, "SlamLoopBatch::setCloudSinks: one sink per sequence and a pose function");
+    cloudSinks_ = std::move(sinks);
+    cloudPoseOf_ = std::move(poseOf);
+  }
+  float cloudScaledTH = 1.f, cloudAbsTH = 1.f;   // thresholds of the sinks' appends (the viewer's defaults)
+  int cloudMinNearSupport = 5;
   SE3Tracker tracker;
   bool keepKeyframes = false;         // keep every promoted keyframe alive in its sequence's keyframeLog (validation: rescale factors, point counts)
   bool sharedKeyframeChange = true;   // the keyframe changes of a step in shared launches (DepthMap::changeKeyframeBatch); false: per-sequence
@@ -1084,14 +1171,23 @@ class SlamLoopBatch {
       for (int i = 0; i < nkf; i++) { kfMaps.push_back(&seqs_[work.kfChange[i].first]->map); kfFrames.push_back(work.kfChange[i].second.get()); }
       DepthMap::changeKeyframeBatch(kfMaps, kfFrames);
     }
+    std::vector<std::shared_ptr<Frame>> finished;     // the keyframes this step finalises, for the cloud sinks
+    std::vector<PointCloud*> sinkClouds;
+    std::vector<Sim3> sinkPoses;
     for (int i = 0; i < nkf; i++) {
       Sequence& q = *seqs_[work.kfChange[i].first];
       const std::shared_ptr<Frame>& frame = work.kfChange[i].second;
+      if (!cloudSinks_.empty() && cloudSinks_[(size_t)work.kfChange[i].first]) {
+        finished.push_back(q.keyframe);
+        sinkClouds.push_back(cloudSinks_[(size_t)work.kfChange[i].first]);
+        sinkPoses.push_back(cloudPoseOf_(work.kfChange[i].first, *q.keyframe));
+      }
       if (lanes) ctx->laneSelect(i % lanes);
       if (!sharedKeyframeChange) q.map.finalizeKeyFrame();
       q.numKeyframesFinished++;
       q.mappedOnKF = 0;
       if (!sharedKeyframeChange) q.map.createKeyFrame(frame.get());
+      if (keepKeyframes && q.keyframeLog.empty() && !q.replacedFirst) q.replacedFirst = q.keyframe;
       q.keyframe = frame;
       if (keepKeyframes) q.keyframeLog.push_back(frame);
       q.sinceKF = 0;
@@ -1105,6 +1201,11 @@ class SlamLoopBatch {
       }
     }
     region.end();
+    if (!finished.empty()) {
+      std::vector<Frame*> fs;
+      for (auto& f : finished) fs.push_back(f.get());
+      PointCloud::appendBatch(sinkClouds, fs, sinkPoses, cloudScaledTH, cloudAbsTH, cloudMinNearSupport);
+    }
     for (size_t k = 0; k < work.updSeq.size(); k++) {
       Sequence& q = *seqs_[work.updSeq[k]];
       q.mappedOnKF++;
@@ -1112,6 +1213,8 @@ class SlamLoopBatch {
       work.updFrames[k]->clear_refPixelWasGood();
     }
   }
+  std::vector<PointCloud*> cloudSinks_;
+  std::function<Sim3(int, Frame&)> cloudPoseOf_;
   bool pipelined_ = false;
   std::vector<std::shared_ptr<Frame>> prefetched_;
   int prefetchedId_ = -1;

@@ -5,7 +5,10 @@
 //   * the keyframe message of lsd_slam_viewer (msg/keyframeMsg.msg; InputPointDense payload V/KeyFrameDisplay.h:39-44,
 //     filled as C/IOWrapper/ROS/ROSOutput3DWrapper.cpp:70-111) in ROS 1 wire serialisation;
 //   * the viewer's point-cloud export (V/KeyFrameDisplay.cpp:269-340 flushPC + V/KeyFrameGraphDisplay.cpp:60-94 PLY header).
-// Plain host code: nothing here touches pixels on the hot path.
+// The formats and their host-side fill loops (makeKeyframeMsg, flushPointCloud) are plain host code and the yardstick of the device
+// export: makeKeyframeMsgDevice packs the payload on the GPU (lsdhip_frame_pack_keyframe_points) and PointCloud (lsd_slam_hip.hpp)
+// builds the viewer's cloud there, both held bit for bit to the host functions below; cloudConstants is the one place the per-keyframe
+// constants of the cloud are computed, for both paths.
 #ifndef LSD_SLAM_HIP_IO_HPP
 #define LSD_SLAM_HIP_IO_HPP
 
@@ -16,6 +19,7 @@
 #include <vector>
 
 #include "lsd_slam_hip.hpp"
+#include "lsd_slam_hip_cloud_constants.hpp"
 
 namespace lsd_slam_hip {
 
@@ -95,13 +99,7 @@ struct KeyframeMsg {
   std::vector<InputPointDense> pointcloud;
 };
 
-// The vendored Sophus stores a Sim3 as a non-unit quaternion (x, y, z, w) whose norm is the scale (thirdparty/Sophus/
-// sophus/rxso3.hpp:311-313), followed by the translation (sim3.hpp:740-754); ROSOutput3DWrapper memcpys those 7 floats.
-inline void sim3ToWire(const Sim3& T, float out[7]) {
-  const double r = T.s;
-  out[0] = (float)(T.q[1] * r); out[1] = (float)(T.q[2] * r); out[2] = (float)(T.q[3] * r); out[3] = (float)(T.q[0] * r);
-  out[4] = (float)T.t[0]; out[5] = (float)T.t[1]; out[6] = (float)T.t[2];
-}
+// (sim3ToWire, the Sim3 -> 7 float conversion of the message, lives in lsd_slam_hip.hpp: PointCloud uses it too)
 
 // ROSOutput3DWrapper::publishKeyframe (ROSOutput3DWrapper.cpp:70-111) at publishLvl 0, from the device planes
 inline KeyframeMsg makeKeyframeMsg(const Frame& kf, const Sim3& camToWorld, const Mat3f& K) {
@@ -122,6 +120,20 @@ inline KeyframeMsg makeKeyframeMsg(const Frame& kf, const Sim3& camToWorld, cons
   return m;
 }
 
+// The same message with the payload packed on the device (lsdhip_frame_pack_keyframe_points): one launch and one copy of 12 bytes per
+// pixel instead of three plane downloads and a host loop; serialises to the same bytes as makeKeyframeMsg's.
+inline KeyframeMsg makeKeyframeMsgDevice(const Frame& kf, const Sim3& camToWorld, const Mat3f& K) {
+  KeyframeMsg m;
+  m.id = kf.id();
+  m.time = kf.timestamp();
+  sim3ToWire(camToWorld, m.camToWorld);
+  m.fx = K.fx(); m.fy = K.fy(); m.cx = K.cx(); m.cy = K.cy();
+  m.width = (uint32_t)kf.width(0); m.height = (uint32_t)kf.height(0);
+  m.pointcloud.resize((size_t)m.width * m.height);
+  check(lsdhip_frame_pack_keyframe_points(kf.handle(), (uint8_t*)m.pointcloud.data()), "lsdhip_frame_pack_keyframe_points");
+  return m;
+}
+
 // ROS 1 serialisation of keyframeMsg (little-endian fields in declaration order, uint8[] with a uint32 length prefix)
 inline std::vector<unsigned char> serializeKeyframeMsg(const KeyframeMsg& m) {
   std::vector<unsigned char> b;
@@ -138,16 +150,15 @@ inline std::vector<unsigned char> serializeKeyframeMsg(const KeyframeMsg& m) {
   return b;
 }
 
+// (CloudConstants / cloudConstants, the per-keyframe constants of flushPC for the host loop below and for the device append, come from
+// lsd_slam_hip_cloud_constants.hpp: a header without dependencies, because liblsdhip itself includes it)
+
 // KeyFrameDisplay::flushPC (V/KeyFrameDisplay.cpp:269-340) with the viewer's default thresholds (V/settings.cpp:36-40:
 // scaledDepthVarTH = absDepthVarTH = 1, minNearSupport = 5, sparsifyFactor = 1); appends (x, y, z, intensity) floats.
 inline int flushPointCloud(const KeyframeMsg& m, std::vector<float>& xyzi, float scaledTH = 1.f, float absTH = 1.f, int minNearSupport = 5) {
   const int w = (int)m.width, h = (int)m.height;
-  const float fxi = 1 / m.fx, fyi = 1 / m.fy, cxi = -m.cx / m.fx, cyi = -m.cy / m.fy;
-  // camToWorld: rotation-and-scale quaternion (x y z w) + translation
-  const float qx = m.camToWorld[0], qy = m.camToWorld[1], qz = m.camToWorld[2], qw = m.camToWorld[3];
-  const float n = std::sqrt(qx * qx + qy * qy + qz * qz + qw * qw);
-  const float scale = n;
-  const float ux = qx / n, uy = qy / n, uz = qz / n, uw = qw / n;
+  const CloudConstants k = cloudConstants(m.fx, m.fy, m.cx, m.cy, m.camToWorld);
+  const float fxi = k.fxi, fyi = k.fyi, cxi = k.cxi, cyi = k.cyi, scale = k.scale, ux = k.ux, uy = k.uy, uz = k.uz, uw = k.uw;
   int num = 0;
   for (int y = 1; y < h - 1; y++)
     for (int x = 1; x < w - 1; x++) {

@@ -36,11 +36,14 @@ extern "C" {
 #define LSDHIP_E_HIP (-2)
 #define LSDHIP_E_STATE (-3)
 #define LSDHIP_E_CAPACITY (-4)
+#define LSDHIP_CLOUD_TABLE_FULL 2   /* lsdhip_cloud_append_*: the cloud's segment table has no free row left after this call */
+#define LSDHIP_CLOUD_GUARD_POINTS 64 /* points allocated behind a cloud's capacity that no append ever writes (lsdhip_cloud_download reads them) */
 
 typedef struct lsdhip_ctx lsdhip_ctx;
 typedef struct lsdhip_frame lsdhip_frame;
 typedef struct lsdhip_tracker lsdhip_tracker;
 typedef struct lsdhip_depthmap lsdhip_depthmap;
+typedef struct lsdhip_cloud lsdhip_cloud;
 
 /* The mutable globals of C/util/settings.cpp:77-88 that the hot path reads. */
 typedef struct lsdhip_params {
@@ -480,6 +483,47 @@ int lsdhip_depth_gpu_times(lsdhip_depthmap* dm, double ms_out[3], long long call
  * DepthMap.cpp:1622-1744).  bench.py: stereo_steps_per_s, roofline_depth on the bytes of searched pixels.  Synchronises. */
 int lsdhip_depth_observe_work(lsdhip_depthmap* dm, double out[3]);
 int lsdhip_depth_observe_time(lsdhip_depthmap* dm, double* ms_out, long long* calls_out);
+
+/* ---- keyframe export ------------------------------------------------------------ */
+/* The payload of a keyframeMsg as ROSOutput3DWrapper::publishKeyframe fills it at publishLvl 0 (C/IOWrapper/ROS/ROSOutput3DWrapper.cpp:70-111):
+ * w x h InputPointDense records (V/KeyFrameDisplay.h:39-44: float idepth, float idepth_var, uchar color[4] = the level-0 image value four
+ * times), 12 bytes each, packed on the device from the frame's level-0 image and its latest level-0 idepth / idepthVar planes (what
+ * lsdhip_frame_download what = 3 / 4 returns).  Synchronous like lsdhip_frame_download: one launch and one device-to-host copy of
+ * w * h * 12 bytes.  LSDHIP_E_STATE when the frame has no depth. */
+int lsdhip_frame_pack_keyframe_points(lsdhip_frame* f, uint8_t* out_host);
+/* The viewer's accumulated point cloud (KeyFrameDisplay::flushPC for every keyframe, V/KeyFrameDisplay.cpp:269-340, written out by
+ * KeyFrameGraphDisplay::draw, V/KeyFrameGraphDisplay.cpp:60-94) kept in device memory: capacity_points float4 (x, y, z, intensity), a
+ * running total, and a table of (frame id, first, count) per appended keyframe with max_keyframes rows.  LSDHIP_CLOUD_GUARD_POINTS
+ * further points behind the buffer are filled with 0xFF bytes at creation and never written again. */
+int lsdhip_cloud_create(lsdhip_ctx* ctx, int64_t capacity_points, int max_keyframes, lsdhip_cloud** out);
+void lsdhip_cloud_destroy(lsdhip_cloud* cloud);   /* waits for the context's streams; destroy clouds before their context */
+/* KeyFrameDisplay::flushPC (V/KeyFrameDisplay.cpp:269-340) with sparsifyFactor = 1 for one finalised keyframe, appended behind the points
+ * the cloud holds: the pixels with 1 <= x <= w - 2, 1 <= y <= h - 2 and idepth > 0 that pass var * depth^4 <= scaledTH,
+ * var * depth^4 * scale^2 <= absTH and (minNearSupport > 1) the 3x3 support count, back-projected with the context's level-0 intrinsics,
+ * scaled, rotated and translated by camToWorld, intensity = colour / 255; in row-major pixel order.  camToWorld: the 7 floats of the
+ * keyframeMsg (Sophus Sim3f::data(): quaternion x y z w with norm = scale, then the translation).  Same single-precision operations in
+ * the same order as flushPointCloud of include/lsd_slam_hip_io.hpp: equal bit for bit.  Reads the frame's level-0 image and its latest
+ * level-0 depth planes.  Three launches queued on the context's mapping stream (lsdhip_ctx_map_stream); returns without waiting, the host
+ * never sees a count: the base of every append is the cloud's device-resident running total, so consecutive appends chain in stream
+ * order.  The frame may be destroyed right after the call (its memory is reused in the order of that stream).
+ * Overflow is a condition, not a fault: point i of the concatenated sequence is stored iff i < capacity; the total keeps counting.  The
+ * segment table stops growing at max_keyframes rows (the points of later keyframes are still appended); the call that takes the last
+ * row, and every later one, returns LSDHIP_CLOUD_TABLE_FULL. */
+int lsdhip_cloud_append_keyframe(lsdhip_cloud* cloud, lsdhip_frame* frame, const float camToWorld[7], float scaledTH, float absTH,
+                                 int minNearSupport);
+/* n appends (clouds[j], frames[j], poses[7 j ..]) into pairwise different clouds of one context in the same three launches (blockIdx.y =
+ * job), whatever n: the keyframes that several sequences finish in one step.  Every cloud ends as after the single call.  LSDHIP_E_ARG
+ * (and nothing changed) if two jobs name one cloud. */
+int lsdhip_cloud_append_batch(lsdhip_ctx* ctx, int n, lsdhip_cloud** clouds, lsdhip_frame** frames, const float* poses, float scaledTH,
+                              float absTH, int minNearSupport);
+/* These three wait for the mapping stream.  total: points appended so far, also those beyond the capacity; stored = min(total, capacity).
+ * segments: n = rows recorded; the first min(n, max) rows are copied out (any output array may be NULL).  download: points
+ * [first, first + n) as 4 floats each; first + n <= capacity + LSDHIP_CLOUD_GUARD_POINTS. */
+int lsdhip_cloud_count(lsdhip_cloud* cloud, int64_t* total, int64_t* stored);
+int lsdhip_cloud_segments(lsdhip_cloud* cloud, int max, int* ids, int64_t* first, int* count, int* n);
+int lsdhip_cloud_download(lsdhip_cloud* cloud, int64_t first, int64_t n, float* xyzi_host);
+/* back to empty (total 0, no segments), ordered behind the appends queued so far; the buffer's contents are left as they are */
+int lsdhip_cloud_reset(lsdhip_cloud* cloud);
 
 /* ---- measurement hooks ---------------------------------------------------------------------------- */
 /* Accumulated HIP-event time (ms) and launch count of the residual kernel on the context's stream since the last

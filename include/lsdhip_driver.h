@@ -114,6 +114,18 @@ int lsdloopbatch_keep_keyframes(lsdloopbatch* l, int on);
 int lsdloopbatch_keyframe_log(lsdloopbatch* l, int sequence, double* scales_out, long long* points_out, int max);
 int lsdloopbatch_last_result(lsdloopbatch* l, int sequence, lsdhip_track_result* out);
 int lsdloopbatch_download_map(lsdloopbatch* l, int sequence, lsdhip_hypothesis* out);   /* frames of a sequence tracked on a replaced keyframe (pipelined): not mapped */
+/* VALIDATION ONLY (tests/test_cloud_gpu.py drives lsd_slam_hip::SlamLoopBatch::setCloudSinks through these; a C++ caller uses the class
+ * and passes its own pose function).  From now on every keyframe a sequence finalises at a keyframe change is appended to that sequence's
+ * cloud (capacity_points, max_keyframes each), all keyframes of a step in one lsdhip_cloud_append_batch behind the keyframe change;
+ * capacity_points <= 0 removes the sinks.  This driver keeps no pose graph: the camToWorld of keyframe frame_id of sequence s is a fixed,
+ * made-up function of the two, which lsdloopbatch_cloud_pose reports in the wire form.
+ * lsdloopbatch_cloud: the lsdhip_cloud* of a sequence (owned by the loop); lsdloopbatch_keyframe_handle: the lsdhip_frame* of entry k of
+ * the sequence's kept keyframes (lsdloopbatch_keep_keyframes), k = -1: the keyframe the sequence's first keyframe change replaced (kept
+ * under the same switch); NULL where there is none. */
+int lsdloopbatch_set_cloud_sinks(lsdloopbatch* l, long long capacity_points, int max_keyframes);
+void* lsdloopbatch_cloud(lsdloopbatch* l, int sequence);
+int lsdloopbatch_cloud_pose(lsdloopbatch* l, int sequence, int frame_id, float out7[7]);
+void* lsdloopbatch_keyframe_handle(lsdloopbatch* l, int sequence, int k);
 const char* lsdloop_last_error(void);
 /* ---- row-band decomposition of the regulariser (BASELINE.json configs[4]) ----------------------------
  * `world` bands over an H-row map; this process holds bands [first_band, first_band + n_local) as windows of

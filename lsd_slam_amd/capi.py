@@ -187,6 +187,15 @@ def _signatures():
         "lsdhip_prof_read": (i, [vp, C.POINTER(C.c_double), C.POINTER(C.c_longlong), C.POINTER(C.c_double)]),
         "lsdhip_ctx_batch_prof_read": (i, [vp, vp, vp, vp, vp]),
         "lsdhip_prof_reset": (i, [vp]),
+        "lsdhip_frame_pack_keyframe_points": (i, [vp, vp]),
+        "lsdhip_cloud_create": (i, [vp, C.c_int64, i, pvp]),
+        "lsdhip_cloud_destroy": (None, [vp]),
+        "lsdhip_cloud_append_keyframe": (i, [vp, vp, vp, f, f, i]),
+        "lsdhip_cloud_append_batch": (i, [vp, i, pvp, pvp, vp, f, f, i]),
+        "lsdhip_cloud_count": (i, [vp, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "lsdhip_cloud_segments": (i, [vp, i, vp, vp, vp, C.POINTER(C.c_int)]),
+        "lsdhip_cloud_download": (i, [vp, C.c_int64, C.c_int64, vp]),
+        "lsdhip_cloud_reset": (i, [vp]),
     }
 
 

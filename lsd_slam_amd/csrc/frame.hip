@@ -658,6 +658,7 @@ extern "C" void lsdhip_ctx_destroy(lsdhip_ctx* c) {
   for (int i = 0; i < LSD_BPROF_SLOTS; i++) if (c->bprof[i].a) { (void)hipEventDestroy(c->bprof[i].a); (void)hipEventDestroy(c->bprof[i].b); }
   if (c->d_obsBatchAcc) (void)hipFree(c->d_obsBatchAcc);
   if (c->d_gtStage) (void)hipFree(c->d_gtStage);
+  if (c->d_kfPoints) (void)hipFree(c->d_kfPoints);
   if (c->d_flagArrive) (void)hipFree(c->d_flagArrive);
   if (c->d_gate) (void)hipFree(c->d_gate);
   if (c->ev_a) (void)hipEventDestroy(c->ev_a);

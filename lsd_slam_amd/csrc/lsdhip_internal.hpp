@@ -272,6 +272,7 @@ struct lsdhip_ctx {
   std::vector<void*> free_arenas;
   size_t arena_keep = 16;                // arenas of destroyed frames kept for reuse (grows with the batch width of lsdhip_frame_create_batch)
   float* d_gtStage = nullptr;                        // w x h floats: staging of lsdhip_frame_set_depth_gt
+  uint8_t* d_kfPoints = nullptr;                     // w x h x 12 bytes: staging of lsdhip_frame_pack_keyframe_points (cloud.hip)
   // kernel-argument arrays of the batched launches (several sequences per launch): pinned staging slots and their device twins,
   // reused round-robin; a slot is rewritten only after the launches that read it have completed (lsd_args_push / lsd_args_release)
   struct ArgRing {

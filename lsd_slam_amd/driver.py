@@ -24,7 +24,8 @@ EXPORTED_SYMBOLS = ["lsdloop_create", "lsdloop_destroy", "lsdloop_run", "lsdloop
                     "lsdloop_gather_keyframes", "lsdband_create", "lsdband_destroy", "lsdband_window_rows", "lsdband_layout", "lsdband_load",
                     "lsdband_get", "lsdband_comm_init", "lsdband_run", "lsdband_synchronize", "lsdband_halo_bytes_per_pass", "lsdband_set_packed_exchange", "lsdband_set_overlap", "lsdband_tile_runs", "lsdband_plan", "lsdband_ipc_init", "lsdband_ipc_connect", "lsdband_ipc_failed", "lsdloop_gather_counts", "lsdloop_ipc_init", "lsdloop_ipc_connect", "lsdloop_ipc_result", "lsdloop_observe_work",
                     "lsdloopbatch_create", "lsdloopbatch_destroy", "lsdloopbatch_run", "lsdloopbatch_get_stats", "lsdloopbatch_ctx", "lsdloopbatch_set_keyframe_phases", "lsdloopbatch_set_pipeline", "lsdloopbatch_set_coarse_min_jobs", "lsdloopbatch_dropped",
-                    "lsdloopbatch_keep_keyframes", "lsdloopbatch_keyframe_log", "lsdloopbatch_last_result", "lsdloopbatch_download_map"]
+                    "lsdloopbatch_keep_keyframes", "lsdloopbatch_keyframe_log", "lsdloopbatch_last_result", "lsdloopbatch_download_map",
+                    "lsdloopbatch_set_cloud_sinks", "lsdloopbatch_cloud", "lsdloopbatch_cloud_pose", "lsdloopbatch_keyframe_handle"]
 
 
 def lib():
@@ -115,6 +116,14 @@ def lib():
         L.lsdloopbatch_last_result.argtypes = [vp, i, vp]
         L.lsdloopbatch_download_map.restype = i
         L.lsdloopbatch_download_map.argtypes = [vp, i, vp]
+        L.lsdloopbatch_set_cloud_sinks.restype = i
+        L.lsdloopbatch_set_cloud_sinks.argtypes = [vp, C.c_longlong, i]
+        L.lsdloopbatch_cloud.restype = vp
+        L.lsdloopbatch_cloud.argtypes = [vp, i]
+        L.lsdloopbatch_cloud_pose.restype = i
+        L.lsdloopbatch_cloud_pose.argtypes = [vp, i, i, vp]
+        L.lsdloopbatch_keyframe_handle.restype = vp
+        L.lsdloopbatch_keyframe_handle.argtypes = [vp, i, i]
         L.lsdloop_last_error.restype = C.c_char_p
         L.lsdloop_last_error.argtypes = []
         _lib = L
@@ -184,6 +193,29 @@ class DriverLoopBatch:
 
     def keep_keyframes(self, on=True):
         _check(self.L.lsdloopbatch_keep_keyframes(self.h_, int(on)))
+
+    def set_cloud_sinks(self, capacity_points, max_keyframes=1024):
+        """one device point cloud per sequence, fed by every keyframe change (SlamLoopBatch::setCloudSinks); 0 points: off"""
+        self._cloud_capacity = int(capacity_points)
+        _check(self.L.lsdloopbatch_set_cloud_sinks(self.h_, int(capacity_points), int(max_keyframes)))
+
+    def cloud(self, s, ctx):
+        """sequence s's cloud as a slam.PointCloud view (owned by the loop); ctx: a slam.Context view of ctx_handle()"""
+        from . import slam
+        return slam.PointCloud.view(ctx, self.L.lsdloopbatch_cloud(self.h_, int(s)), self._cloud_capacity)
+
+    def cloud_pose(self, s, frame_id):
+        """the camToWorld (wire form, 7 floats) the sinks use for keyframe frame_id of sequence s"""
+        out = np.zeros(7, np.float32)
+        _check(self.L.lsdloopbatch_cloud_pose(self.h_, int(s), int(frame_id), out.ctypes.data))
+        return out
+
+    def kept_keyframe(self, s, k, ctx):
+        """entry k of sequence s's kept keyframes as a slam.Frame view (None beyond the log); k = -1: the keyframe the sequence's first
+        keyframe change replaced.  Validation only, like set_cloud_sinks / cloud_pose."""
+        from . import slam
+        h_ = self.L.lsdloopbatch_keyframe_handle(self.h_, int(s), int(k))
+        return slam.Frame.view(ctx, h_) if h_ else None
 
     def keyframe_log(self, s, max_entries=1024):
         """(rescale factors, point counts) of the keyframes sequence s promoted since keep_keyframes(True); synchronises"""

@@ -4,8 +4,16 @@
 // through include/lsd_slam_hip.hpp.  Outputs: a trajectory text file, one keyframeMsg (ROS 1 wire format) per finished
 // keyframe, and the viewer's PLY point cloud.
 //
-//   dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1]
+//   dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both]
+//                [--cloud-capacity POINTS]
 //
+// --cloud host (default): pc.ply and keyframe_<id>.msg from the host functions (three plane downloads and a host loop per keyframe).
+// --cloud device: every finished keyframe is appended to one PointCloud on the GPU behind the keyframe change (no split of the change; the
+//   append waits for nothing), downloaded once at the end into pc.ply; keyframe_<id>.msg comes from makeKeyframeMsgDevice, which does
+//   wait once per keyframe: the file needs the payload on the host (one launch and one copy of 12 bytes per pixel).
+// --cloud both: the host path writes pc.ply / keyframe_<id>.msg and the device path pc_device.ply / keyframe_<id>_device.msg, in the same
+//   run on the same keyframes: the like-for-like mode (a host run and a device run go through different keyframe-change paths, whose
+//   rescale factors differ in the last bits).
 // --constraints 1 additionally aligns every new keyframe with the keyframe it replaces by Sim3Tracker::trackFrameSim3 (the
 // tracking-parent edge the reference's constraint search always tests, C/SlamSystem.cpp:1253-1262) and writes constraints.txt.
 #include <cstdlib>
@@ -37,15 +45,21 @@ static Sim3 sim3_mul(const Sim3& a, const Sim3& b) {
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::cerr << "usage: dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1]\n";
+    std::cerr << "usage: dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both] [--cloud-capacity POINTS]\n";
     return 2;
   }
   int kfEvery = 0, device = 0, constraints = 0;
+  std::string cloudMode = "host";
+  long long cloudCapacity = 0;
   for (int i = 4; i + 1 < argc; i += 2) {
     if (!strcmp(argv[i], "--kf-every")) kfEvery = atoi(argv[i + 1]);
     if (!strcmp(argv[i], "--device")) device = atoi(argv[i + 1]);
     if (!strcmp(argv[i], "--constraints")) constraints = atoi(argv[i + 1]);
+    if (!strcmp(argv[i], "--cloud")) cloudMode = argv[i + 1];
+    if (!strcmp(argv[i], "--cloud-capacity")) cloudCapacity = atoll(argv[i + 1]);
   }
+  if (cloudMode != "host" && cloudMode != "device" && cloudMode != "both") { std::cerr << "--cloud takes host, device or both\n"; return 2; }
+  const bool hostCloud = cloudMode != "device", devCloud = cloudMode != "host";
   try {
     const Calibration cal = parseCalibration(argv[1]);
     std::vector<std::string> files;
@@ -68,13 +82,30 @@ int main(int argc, char** argv) {
     std::vector<float> cloud;
     int nKeyframes = 0;
     int keyframeId = 0;
-    loop.onKeyframeFinished = [&](Frame& kf, DepthMap&) {
-      KeyframeMsg m = makeKeyframeMsg(kf, kfToWorld, cal.K);
+    auto writeMsg = [&](const KeyframeMsg& m, const std::string& suffix) {
       const std::vector<unsigned char> wire = serializeKeyframeMsg(m);
-      std::ofstream f(outDir + "/keyframe_" + std::to_string(kf.id()) + ".msg", std::ios::binary);
+      std::ofstream f(outDir + "/keyframe_" + std::to_string(m.id) + suffix + ".msg", std::ios::binary);
       f.write((const char*)wire.data(), (std::streamsize)wire.size());
+    };
+    // device cloud: at most one point per pixel and keyframe; the default capacity covers that up to 2^26 points (1 GiB)
+    std::unique_ptr<PointCloud> dcloud;
+    if (devCloud) {
+      long long cap = cloudCapacity > 0 ? cloudCapacity : (long long)files.size() * w * h;
+      if (cloudCapacity <= 0 && cap > (1ll << 26)) cap = 1ll << 26;
+      dcloud.reset(new PointCloud(Context::get(w, h, cal.K), cap, (int)files.size()));
+    }
+    if (hostCloud) loop.onKeyframeFinished = [&](Frame& kf, DepthMap&) {
+      KeyframeMsg m = makeKeyframeMsg(kf, kfToWorld, cal.K);
+      writeMsg(m, "");
       flushPointCloud(m, cloud);
       nKeyframes++;
+    };
+    // behind the keyframe change, with the keyframe that was just finalised (kfToWorld is still its pose): the append only queues work;
+    // writing the message file WAITS for the device (the payload has to reach the host: one launch and one copy)
+    if (devCloud) loop.onKeyframeFinishedAsync = [&](Frame& kf) {
+      dcloud->appendKeyframe(kf, kfToWorld);
+      writeMsg(makeKeyframeMsgDevice(kf, kfToWorld, cal.K), hostCloud ? "_device" : "");
+      if (!hostCloud) nKeyframes++;
     };
     int good = 0, nConstraints = 0;
     std::unique_ptr<Sim3Tracker> sim3;
@@ -123,9 +154,20 @@ int main(int argc, char** argv) {
     }
     // the last keyframe: SlamSystem::finalize -> finishCurrentKeyframe
     loop.map.finalizeKeyFrame();
-    loop.onKeyframeFinished(*loop.keyframe, loop.map);
-    writePLY(outDir + "/pc.ply", cloud);
-    std::cout << "frames " << files.size() - 1 << " tracked_good " << good << " keyframes " << nKeyframes << " points " << cloud.size() / 4
+    if (hostCloud) loop.onKeyframeFinished(*loop.keyframe, loop.map);
+    if (devCloud) loop.onKeyframeFinishedAsync(*loop.keyframe);
+    long long points = (long long)cloud.size() / 4;
+    if (hostCloud) writePLY(outDir + "/pc.ply", cloud);
+    if (devCloud) {
+      const long long total = dcloud->total(), stored = dcloud->stored();
+      if (total > stored) std::cerr << "dataset_slam: the device cloud holds " << stored << " of " << total << " points (--cloud-capacity)\n";
+      writePLY(outDir + (hostCloud ? "/pc_device.ply" : "/pc.ply"), dcloud->download());
+      std::ofstream seg(outDir + (hostCloud ? "/segments_device.txt" : "/segments.txt"));
+      seg << "# keyframe first count\n";
+      for (const PointCloud::Segment& sg : dcloud->segments()) seg << sg.id << " " << sg.first << " " << sg.count << "\n";
+      if (!hostCloud) points = stored;
+    }
+    std::cout << "frames " << files.size() - 1 << " tracked_good " << good << " keyframes " << nKeyframes << " points " << points
               << " constraints " << nConstraints << "\n";
     return 0;
   } catch (const Error& e) {

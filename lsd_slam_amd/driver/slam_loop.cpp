@@ -125,7 +125,21 @@ struct lsdloopbatch {
   std::shared_ptr<Context> ctx;
   std::unique_ptr<lsd_slam_hip::SlamLoopBatch> loop;
   std::vector<long long> keyframes;
+  std::vector<std::unique_ptr<PointCloud>> clouds;   // lsdloopbatch_set_cloud_sinks
 };
+// VALIDATION ONLY (tests/test_cloud_gpu.py): camToWorld the cloud sinks of a batch loop use for keyframe `frameId` of sequence s.  This
+// driver keeps no pose graph, so the pose is a fixed function of (s, frameId) — a different rotation, scale and translation per keyframe,
+// which is what the export has to get right; a real caller of SlamLoopBatch::setCloudSinks passes its own pose function.
+static Sim3 batch_cloud_pose(int s, int frameId) {
+  const double ax[3] = {0.2, 1.0, 0.1}, nrm = std::sqrt(ax[0] * ax[0] + ax[1] * ax[1] + ax[2] * ax[2]);
+  const double ang = 0.3 * s + 0.05 * frameId;
+  Sim3 T;
+  T.q[0] = std::cos(ang / 2);
+  for (int k = 0; k < 3; k++) T.q[1 + k] = std::sin(ang / 2) * ax[k] / nrm;
+  T.t[0] = 0.5 * s; T.t[1] = 0.1 * frameId; T.t[2] = 1.0;
+  T.s = 1.0 + 0.5 * (s % 3);
+  return T;
+}
 extern "C" int lsdloopbatch_create(int device, int w, int h, const float K4[4], int S, const uint8_t* const* first_images, int images_on_device,
                                    const float* const* gt_depth0_host, int kf_every, lsdloopbatch** out) {
   if (!K4 || !first_images || !out || kf_every < 1 || S < 1) return LSDHIP_E_ARG;
@@ -207,10 +221,40 @@ extern "C" long long lsdloopbatch_dropped(lsdloopbatch* l, int s) {
   if (!l || s < 0 || s >= l->loop->size()) return -1;
   return l->loop->sequence(s).numDropped;
 }
+extern "C" int lsdloopbatch_set_cloud_sinks(lsdloopbatch* l, long long capacity_points, int max_keyframes) {
+  if (!l) return LSDHIP_E_ARG;
+  try {
+    l->loop->setCloudSinks({}, nullptr);
+    l->clouds.clear();
+    if (capacity_points <= 0) return LSDHIP_OK;
+    std::vector<PointCloud*> sinks;
+    for (int s = 0; s < l->loop->size(); s++) {
+      l->clouds.emplace_back(new PointCloud(l->ctx, capacity_points, max_keyframes));
+      sinks.push_back(l->clouds.back().get());
+    }
+    l->loop->setCloudSinks(sinks, [](int s, Frame& kf) { return batch_cloud_pose(s, kf.id()); });
+    return LSDHIP_OK;
+  } catch (const Error& e) { g_err = e.what(); return e.status < 0 ? e.status : LSDHIP_E_STATE; }
+}
+extern "C" void* lsdloopbatch_cloud(lsdloopbatch* l, int s) {
+  return l && s >= 0 && s < (int)l->clouds.size() ? (void*)l->clouds[(size_t)s]->handle() : nullptr;
+}
+extern "C" int lsdloopbatch_cloud_pose(lsdloopbatch* l, int s, int frame_id, float out7[7]) {
+  if (!l || !out7 || s < 0 || s >= l->loop->size()) return LSDHIP_E_ARG;
+  sim3ToWire(batch_cloud_pose(s, frame_id), out7);
+  return LSDHIP_OK;
+}
+extern "C" void* lsdloopbatch_keyframe_handle(lsdloopbatch* l, int s, int k) {
+  if (!l || s < 0 || s >= l->loop->size()) return nullptr;
+  const auto& q = l->loop->sequence(s);
+  if (k == -1) return q.replacedFirst ? (void*)q.replacedFirst->handle() : nullptr;
+  const auto& log = q.keyframeLog;
+  return k >= 0 && k < (int)log.size() ? (void*)log[(size_t)k]->handle() : nullptr;
+}
 extern "C" int lsdloopbatch_keep_keyframes(lsdloopbatch* l, int on) {
   if (!l) return LSDHIP_E_ARG;
   l->loop->keepKeyframes = on != 0;
-  if (!on) for (int s = 0; s < l->loop->size(); s++) l->loop->sequence(s).keyframeLog.clear();
+  if (!on) for (int s = 0; s < l->loop->size(); s++) { l->loop->sequence(s).keyframeLog.clear(); l->loop->sequence(s).replacedFirst.reset(); }
   return LSDHIP_OK;
 }
 extern "C" int lsdloopbatch_keyframe_log(lsdloopbatch* l, int s, double* scales_out, long long* points_out, int max) {

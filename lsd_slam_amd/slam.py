@@ -20,6 +20,8 @@ from . import capi
 from .capi import HYP_DTYPE, check
 
 IDENTITY = np.array([1.0, 0, 0, 0, 0, 0, 0])
+KEYFRAME_POINT_DTYPE = np.dtype([("idepth", "<f4"), ("idepth_var", "<f4"), ("color", "u1", 4)])   # InputPointDense, 12 bytes
+assert KEYFRAME_POINT_DTYPE.itemsize == 12
 
 
 class Context:
@@ -39,10 +41,17 @@ class Context:
               allow_positive=False)
         self.h_ = h_
 
+    @classmethod
+    def view(cls, handle, w, h):
+        """a context owned by somebody else (the C++ driver loops), for Frame.view / PointCloud.view: never destroyed from here"""
+        c = cls.__new__(cls)
+        c.L, c.w, c.h, c.h_, c._borrowed = capi.lib(), int(w), int(h), C.c_void_p(handle if isinstance(handle, int) else handle.value), True
+        return c
+
     def close(self):
-        if getattr(self, "h_", None):
+        if getattr(self, "h_", None) and not getattr(self, "_borrowed", False):
             self.L.lsdhip_ctx_destroy(self.h_)
-            self.h_ = None
+        self.h_ = None
 
     def synchronize(self):
         check(self.L.lsdhip_ctx_synchronize(self.h_))
@@ -142,11 +151,19 @@ class Frame:
             frames.append(f)
         return frames
 
+    @classmethod
+    def view(cls, ctx, handle):
+        """a frame owned by somebody else (a keyframe a C++ driver loop keeps): never destroyed from here"""
+        f = cls.__new__(cls)
+        f.ctx, f.L, f.h_, f._parent, f._borrowed = ctx, ctx.L, C.c_void_p(handle), None, True
+        f._id = ctx.L.lsdhip_frame_id(f.h_)
+        return f
+
     def __del__(self):
         self.close()
 
     def close(self):
-        if getattr(self, "h_", None) and getattr(self.ctx, "h_", None):
+        if getattr(self, "h_", None) and getattr(self.ctx, "h_", None) and not getattr(self, "_borrowed", False):
             self.L.lsdhip_frame_destroy(self.h_)
         self.h_ = None
 
@@ -179,6 +196,13 @@ class Frame:
 
     def idepthVar(self, level=0):
         return self._plane(4, level)
+
+    def keyframePoints(self):
+        """the keyframeMsg payload packed on the device (lsdhip_frame_pack_keyframe_points): structured array [h, w] of
+        (idepth f4, idepth_var f4, color u1 x 4), the InputPointDense records of V/KeyFrameDisplay.h:39-44"""
+        out = np.zeros((self.height(0), self.width(0)), KEYFRAME_POINT_DTYPE)
+        check(self.L.lsdhip_frame_pack_keyframe_points(self.h_, out.ctypes.data), False)
+        return out
 
     def referenceBlocks(self, level):
         """(offsets uint8 [blocks, 256], counts int32 [blocks]) of the level's reference blocks (lsdhip_frame_download what = 5): per 256
@@ -261,6 +285,82 @@ class Frame:
     def setCounters(self, numFramesTrackedOnThis, numMappedOnThis, numMappedOnThisTotal, depthHasBeenUpdatedFlag):
         check(self.L.lsdhip_frame_set_counters(self.h_, numFramesTrackedOnThis, numMappedOnThis, numMappedOnThisTotal,
                                                int(depthHasBeenUpdatedFlag)))
+
+
+class PointCloud:
+    """The viewer's accumulated point cloud in device memory (lsdhip_cloud_*; KeyFrameDisplay::flushPC per keyframe,
+    V/KeyFrameDisplay.cpp:269-340).  appendKeyframe only queues work on the context's mapping stream; total / stored / segments /
+    download wait for it.  camToWorld: the 7 floats of the keyframeMsg (quaternion x y z w with norm = scale, translation)."""
+    GUARD_POINTS = 64     # LSDHIP_CLOUD_GUARD_POINTS
+    TABLE_FULL = 2        # LSDHIP_CLOUD_TABLE_FULL
+
+    def __init__(self, ctx, capacity_points, max_keyframes):
+        self.ctx = ctx
+        self.L = ctx.L
+        self.capacity = int(capacity_points)
+        h_ = C.c_void_p()
+        check(self.L.lsdhip_cloud_create(ctx.h_, self.capacity, int(max_keyframes), C.byref(h_)), False)
+        self.h_ = h_
+
+    def __del__(self):
+        self.close()
+
+    @classmethod
+    def view(cls, ctx, handle, capacity_points):
+        """a cloud owned by somebody else (the sinks of a C++ driver loop): never destroyed from here"""
+        q = cls.__new__(cls)
+        q.ctx, q.L, q.capacity, q.h_, q._borrowed = ctx, ctx.L, int(capacity_points), C.c_void_p(handle), True
+        return q
+
+    def close(self):
+        if getattr(self, "h_", None) and getattr(self.ctx, "h_", None) and not getattr(self, "_borrowed", False):
+            self.L.lsdhip_cloud_destroy(self.h_)
+        self.h_ = None
+
+    def appendKeyframe(self, frame, camToWorld, scaledTH=1.0, absTH=1.0, minNearSupport=5):
+        """returns False once the segment table is full"""
+        p = np.ascontiguousarray(camToWorld, dtype=np.float32)
+        assert p.shape == (7,)
+        return check(self.L.lsdhip_cloud_append_keyframe(self.h_, frame.h_, p.ctypes.data, scaledTH, absTH, int(minNearSupport))) != self.TABLE_FULL
+
+    @staticmethod
+    def appendBatch(clouds, frames, camToWorlds, scaledTH=1.0, absTH=1.0, minNearSupport=5):
+        n = len(clouds)
+        p = np.ascontiguousarray(camToWorlds, dtype=np.float32).reshape(n, 7)
+        cs = (C.c_void_p * n)(*[c.h_.value for c in clouds])
+        fs = (C.c_void_p * n)(*[f.h_.value for f in frames])
+        ctx = clouds[0].ctx
+        return check(ctx.L.lsdhip_cloud_append_batch(ctx.h_, n, cs, fs, p.ctypes.data, scaledTH, absTH, int(minNearSupport)))
+
+    def _count(self):
+        t, s = C.c_int64(), C.c_int64()
+        check(self.L.lsdhip_cloud_count(self.h_, C.byref(t), C.byref(s)), False)
+        return t.value, s.value
+
+    def total(self):
+        return self._count()[0]
+
+    def stored(self):
+        return self._count()[1]
+
+    def segments(self, max_rows=4096):
+        """list of (frame id, first, count) per appended keyframe"""
+        ids, cnt, first, n = np.zeros(max_rows, np.int32), np.zeros(max_rows, np.int32), np.zeros(max_rows, np.int64), C.c_int()
+        check(self.L.lsdhip_cloud_segments(self.h_, max_rows, ids.ctypes.data, first.ctypes.data, cnt.ctypes.data, C.byref(n)), False)
+        k = min(n.value, max_rows)
+        return [(int(ids[i]), int(first[i]), int(cnt[i])) for i in range(k)]
+
+    def download(self, first=0, n=None):
+        """points [first, first + n) as float32 [n, 4] (x, y, z, intensity); n = None: the stored points from `first`.  Reading up to
+        capacity + GUARD_POINTS is allowed (the guard behind the buffer keeps its 0xFF fill)."""
+        if n is None:
+            n = max(self.stored() - first, 0)
+        out = np.zeros((int(n), 4), np.float32)
+        check(self.L.lsdhip_cloud_download(self.h_, int(first), int(n), out.ctypes.data), False)
+        return out
+
+    def reset(self):
+        check(self.L.lsdhip_cloud_reset(self.h_), False)
 
 
 class TrackingReference:
