@@ -1363,12 +1363,23 @@ struct RescaleItem {
   LSD_G double* statPartials;        // (sum, count) per workgroup of this launch
   int n;
 };
+// The developer switches of this file, read once per process (as BatchEnv in tracker.hip)
+struct DepthEnv {
+  int regPy = getenv("LSDHIP_REG_PY") ? atoi(getenv("LSDHIP_REG_PY")) : 0;     // A/B: 1 or 2 forces the regulariser's tile height
+  // map rows per k_observe workgroup: 8, 4, else 2 — 64-thread workgroups measured best (+2.5 % Mpixel/s over 256)
+  int obsRows = [] { const char* e = getenv("LSDHIP_OBS_ROWS"); const int r = e ? atoi(e) : 2; return (r == 8 || r == 4) ? r : 2; }();
+  bool obsSplit = !(getenv("LSDHIP_OBS_SPLIT") && getenv("LSDHIP_OBS_SPLIT")[0] == '0');   // 0: batched updates never take select + walk (A/B of round 5)
+  bool obsCand = !(getenv("LSDHIP_OBS_CAND") && getenv("LSDHIP_OBS_CAND")[0] == '0');      // 0: the select pass always scans every pixel (A/B of round 6)
+  int walkWaves = getenv("LSDHIP_OBS_WALK_WAVES") ? atoi(getenv("LSDHIP_OBS_WALK_WAVES")) : LSD_OBS_WALK_WAVES;   // sweep of the walk launch's size
+  bool eventsAll = getenv("LSDHIP_DEPTH_EVENTS_ALL") != nullptr;   // every mapping call is bracketed by events: A/B of the sampling itself
+};
+static const DepthEnv& depth_env() { static const DepthEnv env; return env; }
 // Tile height of a regulariser launch: workgroups that own 32 x 16 pixels (PY = 2) move a quarter less through LDS per owned pixel and
 // recompute a sixth less of K5 than 32 x 8 ones — where the launch has enough of them to fill the chip (several maps, large frames:
 // -19 % for the 32-map pass, -6 % at 3840x2160); one 640x480 map is 1200 short workgroups or 600 long ones on 256 CUs, and the short ones
 // win there (keyframe change 0.085 against 0.097 ms).  32 x 32 (PY = 4, 33.6 KB of LDS) lost everywhere.  profiles/r06_notes.md section 5.
 static inline int lsd_reg_py(long long workgroups_at_py1) {
-  static const int forced = getenv("LSDHIP_REG_PY") ? atoi(getenv("LSDHIP_REG_PY")) : 0;     // developer A/B
+  const int forced = depth_env().regPy;
   if (forced == 1 || forced == 2) return forced;
   return workgroups_at_py1 >= 2048 ? 2 : 1;
 }
@@ -1651,21 +1662,42 @@ __global__ __launch_bounds__(256) void k_from_react(HypPlanes m, const float* __
 // ---------------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------------
+static size_t up256(size_t v) { return (v + 255) / 256 * 256; }
+// 256-thread workgroups of a launch with one thread per level-0 pixel
+static unsigned px_blocks(const lsdhip_ctx* c) { return (unsigned)(((size_t)c->w * c->h + 255) / 256); }
+// The launch shape of a regulariser pass over `units` tile rows (8 map rows each) of nMaps maps, one map per grid z.  The tile height is
+// chosen for unitsInAll tile rows (lsd_reg_py); where the maps bring different row counts it is their sum, otherwise units x nMaps.
+struct RegGrid {
+  int tx, units, py;
+  dim3 grid;
+  int tiles() const { return (int)(grid.x * grid.y); }   // per map: one (sum, count) partial each
+};
+static int tile_rows(const lsdhip_ctx* c) { return (c->h + 7) / 8; }
+static RegGrid reg_grid(const lsdhip_ctx* c, int units, int nMaps, long long unitsInAll = 0) {
+  const int tx = (c->w + 31) / 32, py = lsd_reg_py((long long)tx * (unitsInAll ? unitsInAll : (long long)units * nMaps));
+  return RegGrid{tx, units, py, dim3(tx, lsd_reg_grid_rows(units, py), nMaps)};
+}
+// every mapping call ends here: the record point of a pipelined context, and unless the context is asynchronous the call's work is done
+static int map_call_end(lsdhip_ctx* c) {
+  if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
+  if (!c->async) HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));   // asynchronous contexts: ordered on the stream, see lsdhip_ctx_synchronize
+  return LSDHIP_OK;
+}
+
 static int alloc_planes(HypPlanes& p, size_t n, void** base_out) {
   char* base = nullptr;
   size_t bytes = n * 29 + 8 * 256;
   HIPCHK(hipMalloc((void**)&base, bytes));
   HIPCHK(hipMemset(base, 0, bytes));
   HIPCHK(hipStreamSynchronize(nullptr));   // (hipMemset runs on the null stream, which this library's non-blocking streams do not wait for)
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
   size_t off = 0;
-  p.blacklisted = lsd_g((int32_t*)(base + off)); off = up(off + n * 4);
-  p.nextID = lsd_g((float*)(base + off)); off = up(off + n * 4);
-  p.validity = lsd_g((int32_t*)(base + off)); off = up(off + n * 4);
-  p.idepth = lsd_g((float*)(base + off)); off = up(off + n * 4);
-  p.var = lsd_g((float*)(base + off)); off = up(off + n * 4);
-  p.idepth_s = lsd_g((float*)(base + off)); off = up(off + n * 4);
-  p.var_s = lsd_g((float*)(base + off)); off = up(off + n * 4);
+  p.blacklisted = lsd_g((int32_t*)(base + off)); off = up256(off + n * 4);
+  p.nextID = lsd_g((float*)(base + off)); off = up256(off + n * 4);
+  p.validity = lsd_g((int32_t*)(base + off)); off = up256(off + n * 4);
+  p.idepth = lsd_g((float*)(base + off)); off = up256(off + n * 4);
+  p.var = lsd_g((float*)(base + off)); off = up256(off + n * 4);
+  p.idepth_s = lsd_g((float*)(base + off)); off = up256(off + n * 4);
+  p.var_s = lsd_g((float*)(base + off)); off = up256(off + n * 4);
   p.valid = lsd_g((uint8_t*)(base + off));
   *base_out = base;
   return LSDHIP_OK;
@@ -1688,8 +1720,8 @@ static int depth_create_impl(lsdhip_ctx* c, lsdhip_depthmap* dm) {
   HIPCHK(hipMalloc((void**)&dm->d_cand, n * 16));
   HIPCHK(hipMalloc((void**)&dm->d_flags, 64));
   HIPCHK(hipMemsetAsync(dm->d_flags, 0, 64, lsd_map_stream(c)));
-  int nb = (int)((n + 255) / 256);
-  const int ntiles = ((c->w + 31) / 32) * ((c->h + 7) / 8);   // partials of the fused regulariser: one pair per 32x8 tile
+  const int nb = (int)px_blocks(c);
+  const int ntiles = ((c->w + 31) / 32) * tile_rows(c);   // partials of the fused regulariser: one pair per 32x8 tile
   // (sum, count) partials: [16, ...) the setDepth / rescale passes of the single calls; the keyframe change in shared launches keeps
   // three sets alive at once (old keyframe's setDepth | rescale sums | new keyframe's setDepth)
   dm->redStride = (size_t)2 * (nb > ntiles ? nb : ntiles);
@@ -1772,9 +1804,8 @@ static int set_depth(lsdhip_depthmap* dm) {
   lsdhip_ctx* c = dm->ctx;
   LSD_CTX_LOCK(c);
   lsdhip_frame* kf = dm->activeKeyFrame;
-  int n = c->w * c->h;
-  int nb = (n + 255) / 256;
-  hipLaunchKernelGGL(k_set_depth, dim3(nb), dim3(256), 0, lsd_map_stream(c), dm->cur, lsd_depth_w(kf)[0], lsd_depthvar_w(kf)[0], n, dm->d_red + 16);
+  const int nb = (int)px_blocks(c);
+  hipLaunchKernelGGL(k_set_depth, dim3(nb), dim3(256), 0, lsd_map_stream(c), dm->cur, lsd_depth_w(kf)[0], lsd_depthvar_w(kf)[0], c->w * c->h, dm->d_red + 16);
   return set_depth_finish(dm, nb);
 }
 // second half of Frame::setDepth: mean inverse depth / point count from the (sum, count) partials, idepth pyramid
@@ -1782,11 +1813,8 @@ static int set_depth_finish(lsdhip_depthmap* dm, int nPartials) {
   lsdhip_ctx* c = dm->ctx;
   LSD_CTX_LOCK(c);
   lsdhip_frame* kf = dm->activeKeyFrame;
-  const int slot = lsd_ctx_take_slot(c);
+  const int slot = lsd_ctx_claim_stats_slot(c, kf);
   if (slot < 0) return slot;
-  if (kf->pendStats >= 0) c->slot_stats_owner[kf->pendStats] = nullptr;   // superseded by this setDepth
-  kf->pendStats = slot;
-  c->slot_stats_owner[slot] = kf;
   // the (sum, count) reduction rides on the pyramid launch (one extra workgroup): both depend only on the level-0 planes
   int rc = lsd_frame_build_idepth_pyramid(kf, dm->d_red + 16, nPartials, (double*)&c->h_slots[slot]);
   if (rc) return rc;
@@ -1812,12 +1840,23 @@ static RegArgs reg_args(lsdhip_depthmap* dm, int validityTH) {
   return a;
 }
 static void swap_valid(lsdhip_depthmap* dm) { uint8_t* v = (uint8_t*)dm->cur.valid; dm->cur.valid = lsd_g(dm->d_validSnap); dm->d_validSnap = v; }
+// One map's record of a batched regulariser pass on the planes as they stand (it reads cur.valid and writes the spare plane: the caller
+// swaps them, as fill_regularize does).  setDepthOf: the keyframe whose level-0 planes the pass also writes (Frame::setDepth), or null.
+static RegBatchItem reg_item(lsdhip_depthmap* dm, lsdhip_frame* setDepthOf, double* partials) {
+  RegBatchItem r;
+  memset((void*)&r, 0, sizeof(r));
+  r.a = reg_args(dm, VAL_SUM_MIN_FOR_KEEP);
+  r.id0 = lsd_g(setDepthOf ? lsd_depth_w(setDepthOf)[0] : nullptr);
+  r.var0 = lsd_g(setDepthOf ? lsd_depthvar_w(setDepthOf)[0] : nullptr);
+  r.partials = lsd_g(partials);
+  return r;
+}
 
 static int fill_holes(lsdhip_depthmap* dm) {
   lsdhip_ctx* c = dm->ctx;
   LSD_CTX_LOCK(c);
   RegArgs a = reg_args(dm, 0);
-  hipLaunchKernelGGL(k_fill_holes, dim3((c->w + 31) / 32, (c->h + 7) / 8), dim3(256), 0, lsd_map_stream(c), a);
+  hipLaunchKernelGGL(k_fill_holes, dim3((c->w + 31) / 32, tile_rows(c)), dim3(256), 0, lsd_map_stream(c), a);
   HIPCHK(hipGetLastError());
   swap_valid(dm);
   return LSDHIP_OK;
@@ -1826,11 +1865,10 @@ static int regularize(lsdhip_depthmap* dm, bool removeOcclusions, int validityTH
   lsdhip_ctx* c = dm->ctx;
   LSD_CTX_LOCK(c);
   RegArgs a = reg_args(dm, validityTH);
-  const int tx = (c->w + 31) / 32, units = (c->h + 7) / 8, py = lsd_reg_py((long long)tx * units);
-  dim3 grid(tx, lsd_reg_grid_rows(units, py));
-  LSD_REG_DISPATCH(py,
-    if (removeOcclusions) hipLaunchKernelGGL((k_reg_fused<false, true, false, PYV>), grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr);
-    else hipLaunchKernelGGL((k_reg_fused<false, false, false, PYV>), grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr));
+  const RegGrid g = reg_grid(c, tile_rows(c), 1);
+  LSD_REG_DISPATCH(g.py,
+    if (removeOcclusions) hipLaunchKernelGGL((k_reg_fused<false, true, false, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr);
+    else hipLaunchKernelGGL((k_reg_fused<false, false, false, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr));
   HIPCHK(hipGetLastError());
   swap_valid(dm);
   return LSDHIP_OK;
@@ -1841,16 +1879,15 @@ static int fill_regularize(lsdhip_depthmap* dm, int validityTH, bool setDepth) {
   LSD_CTX_LOCK(c);
   lsdhip_frame* kf = dm->activeKeyFrame;
   RegArgs a = reg_args(dm, validityTH);
-  const int tx = (c->w + 31) / 32, units = (c->h + 7) / 8, py = lsd_reg_py((long long)tx * units);
-  dim3 grid(tx, lsd_reg_grid_rows(units, py));
-  LSD_REG_DISPATCH(py,
+  const RegGrid g = reg_grid(c, tile_rows(c), 1);
+  LSD_REG_DISPATCH(g.py,
     if (setDepth)
-      hipLaunchKernelGGL((k_reg_fused<true, false, true, PYV>), grid, dim3(256), 0, lsd_map_stream(c), a, lsd_depth_w(kf)[0], lsd_depthvar_w(kf)[0], dm->d_red + 16);
+      hipLaunchKernelGGL((k_reg_fused<true, false, true, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, lsd_depth_w(kf)[0], lsd_depthvar_w(kf)[0], dm->d_red + 16);
     else
-      hipLaunchKernelGGL((k_reg_fused<true, false, false, PYV>), grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr));
+      hipLaunchKernelGGL((k_reg_fused<true, false, false, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr));
   HIPCHK(hipGetLastError());
   swap_valid(dm);
-  if (setDepth) return set_depth_finish(dm, (int)(grid.x * grid.y));
+  if (setDepth) return set_depth_finish(dm, g.tiles());
   return LSDHIP_OK;
 }
 
@@ -1859,18 +1896,23 @@ static int fill_regularize(lsdhip_depthmap* dm, int validityTH, bool setDepth) {
 // was invalid in the snapshot, so nobody reads the fields its owner rewrites) and writes the other validity plane; `last` swaps the
 // two once all parts are queued.  Rows outside the parts keep whatever the second validity plane held: the caller refreshes them
 // (row-band decomposition: rows another band owns arrive with the halo exchange).
+// a part of a pass names tile rows of the map; minRows = 0 where an empty part is allowed
+static int check_tile_rows(const lsdhip_ctx* c, int tileRow0, int nTileRows, int minRows) {
+  const int T = tile_rows(c);
+  if (tileRow0 >= 0 && nTileRows >= minRows && tileRow0 + nTileRows <= T) return LSDHIP_OK;
+  lsd_set_error("depth stage rows: tile rows [%d, %d) outside [0, %d)", tileRow0, tileRow0 + nTileRows, T);
+  return LSDHIP_E_ARG;
+}
 static int fill_regularize_rows(lsdhip_depthmap* dm, int validityTH, int tileRow0, int nTileRows, bool last) {
   lsdhip_ctx* c = dm->ctx;
   LSD_CTX_LOCK(c);
-  const int T = (c->h + 7) / 8;
-  if (tileRow0 < 0 || nTileRows < 0 || tileRow0 + nTileRows > T) { lsd_set_error("depth stage rows: tile rows [%d, %d) outside [0, %d)", tileRow0, tileRow0 + nTileRows, T); return LSDHIP_E_ARG; }
+  if (int rcr = check_tile_rows(c, tileRow0, nTileRows, 0)) return rcr;
   if (nTileRows > 0) {
     RegArgs a = reg_args(dm, validityTH);
     a.tileRow0 = tileRow0;
     a.tileRows = nTileRows;
-    const int tx = (c->w + 31) / 32, py = lsd_reg_py((long long)tx * nTileRows);
-    dim3 grid(tx, lsd_reg_grid_rows(nTileRows, py));
-    LSD_REG_DISPATCH(py, hipLaunchKernelGGL((k_reg_fused<true, false, false, PYV>), grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr));
+    const RegGrid g = reg_grid(c, nTileRows, 1);
+    LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL((k_reg_fused<true, false, false, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr));
     HIPCHK(hipGetLastError());
   }
   if (last) swap_valid(dm);
@@ -1940,38 +1982,41 @@ static void observe_args_common(lsdhip_depthmap* dm, ObserveArgs& a) {
   a.qcount = nullptr;
 }
 
-static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n) {
+// a map is updated with frames that were tracked on its active keyframe
+static int check_tracked_on(const lsdhip_frame* ref, const lsdhip_frame* kf) {
+  if (ref->trackingParentID == kf->id) return LSDHIP_OK;
+  // DepthMap.cpp:1099 needs getScaledCamToWorld() from the pose graph, which stays on the host side of the boundary
+  lsd_set_error("updateKeyframe: frame %d was tracked on keyframe %d, active keyframe is %d (pose-graph path is out of scope)",
+                ref->id, ref->trackingParentID, kf->id);
+  return LSDHIP_E_STATE;
+}
+// k_observe's arguments for one reference frame (blockUntilMapped): it travels inside the record, no staging copy
+static void observe_args_one(lsdhip_depthmap* dm, lsdhip_frame* ref, ObserveArgs& a) {
+  memset((void*)&a, 0, sizeof(a));
+  prepare_stereo(dm, ref, a.one);
+  a.nByID = 1; a.byIDOffset = ref->id; a.nRefs = 1;
+  observe_args_common(dm, a);
+}
+
+// countWork: the launch also counts its searches and walk steps (sampled while profiling)
+static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n, bool countWork) {
   lsdhip_ctx* c = dm->ctx;
   LSD_CTX_LOCK(c);
   lsdhip_frame* kf = dm->activeKeyFrame;
   if (n <= 0) { lsd_set_error("updateKeyframe: empty reference deque"); return LSDHIP_E_ARG; }
-  for (int i = 0; i < n; i++) {
-    if (refs[i]->trackingParentID != kf->id) {
-      // DepthMap.cpp:1099 needs getScaledCamToWorld() from the pose graph, which stays on the host side of the boundary
-      lsd_set_error("updateKeyframe: frame %d was tracked on keyframe %d, active keyframe is %d (pose-graph path is out of scope)",
-                    refs[i]->id, refs[i]->trackingParentID, kf->id);
-      return LSDHIP_E_STATE;
-    }
-  }
-  size_t nByID = 0;
-  const int offset = refs[0]->id;
+  for (int i = 0; i < n; i++) if (int rct = check_tracked_on(refs[i], kf)) return rct;
   ObserveArgs a;
   if (n == 1) {
-    // one reference frame (blockUntilMapped): it travels in the kernel arguments
-    prepare_stereo(dm, refs[0], a.one);
-    nByID = 1;
-    dm->d_refs = nullptr;
-    dm->d_refByID = nullptr;
+    observe_args_one(dm, refs[0], a);
   } else {
+    size_t nByID = 0;
+    const int offset = refs[0]->id;
     // host staging lives in one pinned block (refs | refByID); it is reused by the next call, which must not start
     // before this copy has been consumed
-    size_t byIDCount = 0;
-    {
-      int last = offset - 1;
-      for (int i = 0; i < n; i++) if (refs[i]->id > last) last = refs[i]->id;
-      byIDCount = (size_t)(last - offset + 1);
-    }
-    const size_t refsBytes = (sizeof(StereoRef) * (size_t)n + 255) / 256 * 256;
+    int last = offset - 1;
+    for (int i = 0; i < n; i++) if (refs[i]->id > last) last = refs[i]->id;
+    const size_t byIDCount = (size_t)(last - offset + 1);
+    const size_t refsBytes = up256(sizeof(StereoRef) * (size_t)n);
     const size_t need = refsBytes + sizeof(int) * byIDCount;
     HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));
     if (need > dm->stage_bytes) {
@@ -1990,20 +2035,17 @@ static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n) {
       while ((int)nByID + offset <= refs[i]->id) byID[nByID++] = i;
     }
     HIPCHK(hipMemcpyAsync(dm->d_stage, dm->h_stage, refsBytes + sizeof(int) * nByID, hipMemcpyHostToDevice, lsd_map_stream(c)));
-    dm->d_refs = (StereoRef*)dm->d_stage;
-    dm->d_refByID = (int*)(dm->d_stage + refsBytes);
-    memset(&a.one, 0, sizeof(a.one));
+    memset((void*)&a, 0, sizeof(a));
+    a.refs = lsd_g((const StereoRef*)dm->d_stage);
+    a.refByID = lsd_g((const int*)(dm->d_stage + refsBytes));
+    a.nByID = (int)nByID;
+    a.byIDOffset = offset;
+    a.nRefs = n;
+    observe_args_common(dm, a);
   }
-
-  a.refs = lsd_g(dm->d_refs);
-  a.refByID = lsd_g(dm->d_refByID);
-  a.nByID = (int)nByID;
-  a.byIDOffset = offset;
-  a.nRefs = n;
-  observe_args_common(dm, a);
 #ifdef LSD_PHASE_TRACE
   {
-    const size_t words = (size_t)((c->w + 31) / 32) * ((c->h + 7) / 8) * 16;
+    const size_t words = (size_t)((c->w + 31) / 32) * tile_rows(c) * 16;
     if (!dm->d_obs_trace) HIPCHK(hipMalloc((void**)&dm->d_obs_trace, words * 8));
     HIPCHK(hipMemsetAsync(dm->d_obs_trace, 0, words * 8, lsd_map_stream(c)));
     a.trace = (decltype(a.trace))dm->d_obs_trace;
@@ -2014,12 +2056,12 @@ static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n) {
 #ifdef LSD_PHASE_TRACE
     constexpr int rows = 8;   // the trace buffer is laid out for 32x8 tiles
 #else
-    static const int rows = [] { const char* e = getenv("LSDHIP_OBS_ROWS"); int r = e ? atoi(e) : 2; return (r == 8 || r == 4) ? r : 2; }();   // 64-thread workgroups measured best (+2.5 % Mpixel/s over 256)
+    const int rows = depth_env().obsRows;
 #endif
     const dim3 grid((c->w + 31) / 32, (c->h + rows - 1) / rows);
     const int nwaves = (int)(grid.x * grid.y) * (rows * 32 / 64);
-    if (dm->countNext) {
-      // sampled launch while profiling: searches and walk steps, per wave, summed behind the launch (bench.py: stereo_steps_per_s,
+    if (countWork) {
+      // searches and walk steps, per wave, summed behind the launch (bench.py: stereo_steps_per_s,
       // roofline_depth on the bytes of the pixels that were actually searched)
       if (!dm->d_obsCounters) {
         HIPCHK(hipMalloc((void**)&dm->d_obsCounters, (size_t)nwaves * 16 + 32));
@@ -2046,8 +2088,26 @@ static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n) {
   return LSDHIP_OK;
 }
 
+// oldToNew_SE3 = se3FromSim3(new_keyframe->pose->thisToParent_raw).inverse() (DepthMap.cpp:1230), in double
+static lsdm::SE3dH old_to_new(const lsdhip_frame* nk) {
+  lsdm::SE3dH newToOld;
+  // se3FromSim3 = SE3(sim3.quaternion(), translation): the SCALED quaternion, normalised by the SO3 constructor (so3.hpp:630-633)
+  newToOld.q = nk->thisToParent_raw.q;
+  { const double s_ = nk->thisToParent_raw.s; newToOld.q.w *= s_; newToOld.q.x *= s_; newToOld.q.y *= s_; newToOld.q.z *= s_; }
+  lsdm::q_normalize(newToOld.q);
+  for (int i = 0; i < 3; i++) newToOld.t[i] = nk->thisToParent_raw.t[i];
+  return lsdm::se3d_inverse(newToOld);
+}
+// the new keyframe's pose becomes sim3FromSE3(oldToNew.inverse()): its scale follows with the rescale factor (DepthMap.cpp:1305, lsd_frame_resolve)
+static void drop_pose_scale(lsdhip_frame* nk, const lsdm::SE3dH& oldToNew) {
+  const lsdm::SE3dH back = lsdm::se3d_inverse(oldToNew);
+  nk->thisToParent_raw.q = back.q;
+  lsdm::q_normalize(nk->thisToParent_raw.q);   // sim3FromSE3 -> Sim3::setScale normalises the quaternion (rxso3.hpp:332-335)
+  for (int i = 0; i < 3; i++) nk->thisToParent_raw.t[i] = back.t[i];
+}
+
 // propagateDepth's arguments for the map's current keyframe -> nk (source = currentDepthMap, target = otherDepthMap)
-static void prop_args(lsdhip_depthmap* dm, lsdhip_frame* nk, PropArgs& a) {
+static void prop_args(lsdhip_depthmap* dm, lsdhip_frame* nk, const lsdm::SE3dH& oldToNew, PropArgs& a) {
   lsdhip_ctx* c = dm->ctx;
   lsdhip_frame* old = dm->activeKeyFrame;
   size_t n = (size_t)c->w * c->h;
@@ -2068,32 +2128,28 @@ static void prop_args(lsdhip_depthmap* dm, lsdhip_frame* nk, PropArgs& a) {
   const LevelIntr& in = c->intr[0];
   a.fx = in.fx; a.fy = in.fy; a.cx = in.cx; a.cy = in.cy; a.fxi = in.fxi; a.fyi = in.fyi; a.cxi = in.cxi; a.cyi = in.cyi;
   a.minUseGrad = c->params.minUseGrad;
-  // oldToNew_SE3 = se3FromSim3(new_keyframe->pose->thisToParent_raw).inverse() (double), cast to float
-  lsdm::SE3dH newToOld;
-  // se3FromSim3 = SE3(sim3.quaternion(), translation): the SCALED quaternion, normalised by the SO3 constructor (so3.hpp:630-633)
-  newToOld.q = nk->thisToParent_raw.q;
-  { const double s_ = nk->thisToParent_raw.s; newToOld.q.w *= s_; newToOld.q.x *= s_; newToOld.q.y *= s_; newToOld.q.z *= s_; }
-  lsdm::q_normalize(newToOld.q);
-  for (int i = 0; i < 3; i++) newToOld.t[i] = nk->thisToParent_raw.t[i];
-  lsdm::SE3dH oldToNew = lsdm::se3d_inverse(newToOld);
-  double Rd[9];
+  double Rd[9];   // (computed in double, cast to float)
   lsdm::quatd_to_rot(oldToNew.q, Rd);
   for (int i = 0; i < 9; i++) a.R[i] = (float)Rd[i];
   for (int i = 0; i < 3; i++) a.t[i] = (float)oldToNew.t[i];
 }
-static int propagate(lsdhip_depthmap* dm, lsdhip_frame* nk, bool checkOverflowNow) {
+// the rest state of the K7 scratch: slot counts, chain heads, flags
+static int clear_prop_scratch(lsdhip_depthmap* dm, hipStream_t s) {
+  const size_t n = (size_t)dm->ctx->w * dm->ctx->h;
+  HIPCHK(hipMemsetAsync(dm->d_slotCount, 0, n * 4, s));
+  HIPCHK(hipMemsetAsync(dm->d_ovfHead, 0xFF, n * 4, s));
+  HIPCHK(hipMemsetAsync(dm->d_flags, 0, 64, s));
+  return LSDHIP_OK;
+}
+static int propagate(lsdhip_depthmap* dm, lsdhip_frame* nk, const lsdm::SE3dH& oldToNew, bool checkOverflowNow) {
   lsdhip_ctx* c = dm->ctx;
   LSD_CTX_LOCK(c);
-  size_t n = (size_t)c->w * c->h;
   PropArgs a;
-  prop_args(dm, nk, a);
-
-  HIPCHK(hipMemsetAsync(dm->d_slotCount, 0, n * 4, lsd_map_stream(c)));
-  HIPCHK(hipMemsetAsync(dm->d_ovfHead, 0xFF, n * 4, lsd_map_stream(c)));
-  HIPCHK(hipMemsetAsync(dm->d_flags, 0, 64, lsd_map_stream(c)));
+  prop_args(dm, nk, oldToNew, a);
+  if (int rcc = clear_prop_scratch(dm, lsd_map_stream(c))) return rcc;
   dm->propClean = false;      // (the flags stay set until somebody has read them: lsdhip_depth_change_keyframe_batch then clears first)
-  hipLaunchKernelGGL(k_prop_candidates, dim3((c->w + 31) / 32, (c->h + 7) / 8), dim3(256), 0, lsd_map_stream(c), a);
-  hipLaunchKernelGGL(k_prop_resolve, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lsd_map_stream(c), a);
+  hipLaunchKernelGGL(k_prop_candidates, dim3((c->w + 31) / 32, tile_rows(c)), dim3(256), 0, lsd_map_stream(c), a);
+  hipLaunchKernelGGL(k_prop_resolve, dim3(px_blocks(c)), dim3(256), 0, lsd_map_stream(c), a);
   if (checkOverflowNow) {
     int flag = 0;
     HIPCHK(hipMemcpyAsync(&flag, dm->d_flags, 4, hipMemcpyDeviceToHost, lsd_map_stream(c)));
@@ -2107,13 +2163,6 @@ static int propagate(lsdhip_depthmap* dm, lsdhip_frame* nk, bool checkOverflowNo
   return LSDHIP_OK;
 }
 
-struct StageTimer {
-  hipEvent_t a, b;
-  lsdhip_ctx* c;
-  bool ok;
-  StageTimer(lsdhip_ctx* c_) : c(c_) { ok = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess; }
-  ~StageTimer() { if (ok) { (void)hipEventDestroy(a); (void)hipEventDestroy(b); } }
-};
 static double now_ms() { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 // GPU-side duration of a mapping call: an event pair on the stream, read back lazily (kind 0 update, 1 create, 2 finalize)
@@ -2138,8 +2187,7 @@ static void timing_collect(lsdhip_depthmap* dm, bool all) {
 constexpr int EV_SKIP = -1000;
 static int timing_begin(lsdhip_depthmap* dm, int kind) {
   if (kind < 3) {
-    static const bool every = getenv("LSDHIP_DEPTH_EVENTS_ALL") != nullptr;   // developer switch: A/B of the sampling itself
-    const unsigned period = every ? 1u : (kind == 0 ? 7u : 2u);
+    const unsigned period = depth_env().eventsAll ? 1u : (kind == 0 ? 7u : 2u);
     if ((dm->ev_tick[kind]++ % period) != 0) return EV_SKIP;
   }
   const int i = dm->ev_next;
@@ -2170,12 +2218,10 @@ extern "C" int lsdhip_depth_init_gt(lsdhip_depthmap* dm, lsdhip_frame* kf) {
   dm->lowGradHypPossible = true;
   dm->activeKeyFrame = kf;
   dm->activeKeyFrameIsReactivated = false;
-  int n = c->w * c->h;
   if (int rcb = lsd_m_begin(c)) return rcb;
-  hipLaunchKernelGGL(k_init_gt, dim3((n + 255) / 256), dim3(256), 0, lsd_map_stream(c), dm->cur, kf->d_idepth[0], n);
-  int rc = set_depth(dm);
-  if (rc == LSDHIP_OK && lsd_m_record(c) < 0) rc = LSDHIP_E_HIP;
-  return rc;
+  hipLaunchKernelGGL(k_init_gt, dim3(px_blocks(c)), dim3(256), 0, lsd_map_stream(c), dm->cur, kf->d_idepth[0], c->w * c->h);
+  if (int rc = set_depth(dm)) return rc;
+  return map_call_end(c);
 }
 
 extern "C" int lsdhip_depth_init_random(lsdhip_depthmap* dm, lsdhip_frame* kf) {
@@ -2211,8 +2257,8 @@ extern "C" int lsdhip_depth_init_random(lsdhip_depthmap* dm, lsdhip_frame* kf) {
   rc = lsdhip_depth_upload(dm, kf, hyp.data(), 0);
   if (rc) return rc;
   rc = set_depth(dm);
-  if (rc == LSDHIP_OK && lsd_m_record(c) < 0) rc = LSDHIP_E_HIP;
-  return rc;
+  if (rc) return rc;
+  return map_call_end(c);
 }
 
 extern "C" int lsdhip_depth_set_from_existing(lsdhip_depthmap* dm, lsdhip_frame* kf) {
@@ -2227,10 +2273,9 @@ extern "C" int lsdhip_depth_set_from_existing(lsdhip_depthmap* dm, lsdhip_frame*
   kf->numMappedOnThis = 0;
   kf->numFramesTrackedOnThis = 0;
   dm->activeKeyFrameIsReactivated = true;
-  int n = c->w * c->h;
   if (int rcb = lsd_m_begin(c)) return rcb;
-  hipLaunchKernelGGL(k_from_react, dim3((n + 255) / 256), dim3(256), 0, lsd_map_stream(c), dm->cur, kf->d_idepth_reAct, kf->d_idepthVar_reAct,
-                     kf->d_validity_reAct, n);
+  hipLaunchKernelGGL(k_from_react, dim3(px_blocks(c)), dim3(256), 0, lsd_map_stream(c), dm->cur, kf->d_idepth_reAct, kf->d_idepthVar_reAct,
+                     kf->d_validity_reAct, c->w * c->h);
   int rc = regularize(dm, false, VAL_SUM_MIN_FOR_KEEP);
   if (rc) return rc;
   HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));
@@ -2255,9 +2300,7 @@ extern "C" int lsdhip_depth_update(lsdhip_depthmap* dm, lsdhip_frame** refs, int
   int evo = -1;
   if (sampleObs) { evo = timing_begin(dm, 3); if (evo < 0) return evo; }
   lsdhip_host_mark(10);
-  dm->countNext = sampleObs;
-  int rc = observe(dm, refs, n);
-  dm->countNext = false;
+  int rc = observe(dm, refs, n, sampleObs);
   if (rc) return rc;
   lsdhip_host_mark(11);
   if (sampleObs) { rc = timing_end(dm, evo); if (rc) return rc; }
@@ -2284,12 +2327,114 @@ extern "C" int lsdhip_depth_update(lsdhip_depthmap* dm, lsdhip_frame** refs, int
     lsd_trace_sum(c, lsd_map_stream(c), 39, fid, lsd_depthvar_latest(kf)[1], npx);
   }
 #endif
-  if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
-  if (!c->async) HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));
+  rc = map_call_end(c);
+  if (rc) return rc;
   dm->msUpdate = ema(dm->msUpdate, now_ms() - t0);   // host wall time of the call (enqueue time only in async mode)
   kf->numMappedOnThis++;
   kf->numMappedOnThisTotal++;
   return LSDHIP_OK;
+}
+
+// The jobs of one lsd_frame_build_idepth_pyramid_batch launch: a keyframe, the (sum, count) partials of its level-0 planes and the
+// deferred-result slot its statistics go to
+struct PyramidJobs {
+  std::vector<lsdhip_frame*> frames; std::vector<const double*> parts; std::vector<int> nParts; std::vector<double*> outs;
+  explicit PyramidJobs(size_t n) : frames(n), parts(n), nParts(n), outs(n) {}
+  void set(size_t i, lsdhip_frame* f, const double* partials, int nPartials, int slot) {
+    frames[i] = f; parts[i] = partials; nParts[i] = nPartials; outs[i] = (double*)&f->ctx->h_slots[slot];
+  }
+  int launch() { return lsd_frame_build_idepth_pyramid_batch(frames.data(), (int)frames.size(), parts.data(), 0, outs.data(), nParts.data()); }
+};
+
+// The argument record of a batched update, sub-records on 256-byte boundaries: ObserveArgs x n | RegBatchItem x n | int x n (the search
+// queues' fill counts).  One layout for the pinned host copy and its device twin: the views take either base.
+struct UpdateRecord {
+  size_t regOff, qcountOff, bytes;
+  explicit UpdateRecord(int n)
+      : regOff(up256(sizeof(ObserveArgs) * (size_t)n)), qcountOff(regOff + up256(sizeof(RegBatchItem) * (size_t)n)), bytes(qcountOff + sizeof(int) * (size_t)n) {}
+  ObserveArgs* obs(void* base) const { return (ObserveArgs*)base; }
+  RegBatchItem* reg(void* base) const { return (RegBatchItem*)((uint8_t*)base + regOff); }
+  int* qcount(void* base) const { return (int*)((uint8_t*)base + qcountOff); }
+};
+
+static int update_batch_check(lsdhip_ctx* c, int n, lsdhip_depthmap** maps, lsdhip_frame** refs) {
+  for (int j = 0; j < n; j++) {
+    lsdhip_depthmap* dm = maps[j];
+    if (dm->ctx != c || refs[j]->ctx != c) { lsd_set_error("updateKeyframe batch: maps and frames of one batch live on one context"); return LSDHIP_E_ARG; }
+    if (!dm->activeKeyFrame) { lsd_set_error("updateKeyframe batch: depth map %d has no active keyframe", j); return LSDHIP_E_STATE; }
+    for (int i = 0; i < j; i++) if (maps[i] == dm) { lsd_set_error("updateKeyframe batch: depth map %d appears twice", j); return LSDHIP_E_ARG; }
+    if (int rct = check_tracked_on(refs[j], dm->activeKeyFrame)) return rct;
+  }
+  return LSDHIP_OK;
+}
+// Fills the host copy of the record: per map what observe() and fill_regularize() would pass.  due: the maps whose keyframe is due for
+// Frame::setDepth; *candidates is cleared unless every map of the call qualifies for the select pass over the keyframes' gradient candidates.
+static void update_batch_items(int n, lsdhip_depthmap** maps, lsdhip_frame** refs, const UpdateRecord& L, void* host, void* dev, bool split,
+                               std::vector<int>& due, bool* candidates) {
+  for (int j = 0; j < n; j++) {
+    lsdhip_depthmap* dm = maps[j];
+    lsdhip_frame* kf = dm->activeKeyFrame;
+    ObserveArgs& a = L.obs(host)[j];
+    observe_args_one(dm, refs[j], a);
+    a.queue = lsd_g(split ? dm->d_obsQueue : nullptr);
+    a.qcount = lsd_g(L.qcount(dev) + j);
+    a.gradCand = lsd_g((const uint16_t*)kf->d_gradCand);
+    if (dm->lowGradHypPossible || kf->gradCandTh != a.minUseGrad) *candidates = false;
+    L.qcount(host)[j] = 0;       // the queues' fill counts start from the zeros copied here
+    const bool setDepth = !kf->depthHasBeenUpdatedFlag;
+    L.reg(host)[j] = reg_item(dm, setDepth ? kf : nullptr, dm->d_red + 16);
+    if (setDepth) due.push_back(j);
+  }
+}
+// the observe pass in the form `form` names: select + walk (the select over every pixel or over the gradient candidates), or one launch
+static int update_batch_observe(lsdhip_ctx* c, int n, const ObserveArgs* dobs, const lsdhip_ctx::BatchForm& form, hipStream_t ms) {
+  const int bp = lsd_bprof_begin(c, 1, ms);
+  if (bp < -1) return bp;
+  if (form.split) {
+    unsigned long long* acc = nullptr;
+    if (bp >= 0) {     // a sampled call also counts its searches and walk steps
+      if (!c->d_obsBatchAcc) { HIPCHK(hipMalloc((void**)&c->d_obsBatchAcc, 66 * 8)); HIPCHK(hipMemsetAsync(c->d_obsBatchAcc, 0, 66 * 8, ms)); }
+      acc = c->d_obsBatchAcc;
+    }
+    if (form.candidates) hipLaunchKernelGGL(k_observe_select_cand_batch, dim3((lsd_gradcand_groups(c->w * c->h) + 3) / 4, 1, n), dim3(256), 0, ms, dobs);
+    else hipLaunchKernelGGL(k_observe_select_batch, dim3((c->w + 63) / 64, (c->h + 15) / 16, n), dim3(256), 0, ms, dobs);
+    hipLaunchKernelGGL(k_observe_walk_batch, dim3(form.walkWorkgroups), dim3(64), 0, ms, dobs, form.qcountDev, n, acc);
+  } else {
+    hipLaunchKernelGGL((k_observe_batch<2>), dim3((c->w + 31) / 32, (c->h + 1) / 2, n), dim3(64), 0, ms, dobs);
+  }
+  return lsd_bprof_end(c, bp, ms, (double)n * c->w * c->h);
+}
+// the regulariser pass: the maps whose keyframe is due for Frame::setDepth in one launch, the others in its twin
+static int update_batch_regularize(lsdhip_ctx* c, int n, const RegBatchItem* dreg, const RegGrid& g, int nSet, hipStream_t ms) {
+  const int bp = lsd_bprof_begin(c, 2, ms);
+  if (bp < -1) return bp;
+  LSD_REG_DISPATCH(g.py,
+    if (nSet > 0) hipLaunchKernelGGL((k_reg_fused_batch<true, PYV>), g.grid, dim3(256), 0, ms, dreg);
+    if (nSet < n) hipLaunchKernelGGL((k_reg_fused_batch<false, PYV>), g.grid, dim3(256), 0, ms, dreg));
+  if (int rc = lsd_bprof_end(c, bp, ms, (double)n * c->w * c->h)) return rc;
+  HIPCHK(hipGetLastError());
+  return LSDHIP_OK;
+}
+// Frame::setDepth's second half for the keyframes that were due.  At most LSD_NUM_SLOTS keyframes per pyramid launch: claiming a slot that
+// still has an owner resolves that owner first, which is only right once the launch that writes the slot has been queued — with more
+// keyframes than slots in ONE launch the ring wrapped onto keyframes of the same call, whose statistics were then read before anything had
+// written them (numPoints = 0).
+static int update_batch_set_depth(lsdhip_ctx* c, lsdhip_depthmap** maps, const std::vector<int>& due, int nPartials, hipStream_t ms) {
+  if (due.empty()) return LSDHIP_OK;
+  const int bp = lsd_bprof_begin(c, 3, ms);
+  if (bp < -1) return bp;
+  for (size_t i0 = 0; i0 < due.size(); i0 += LSD_NUM_SLOTS) {
+    PyramidJobs pyr(std::min<size_t>(LSD_NUM_SLOTS, due.size() - i0));
+    for (size_t i = 0; i < pyr.frames.size(); i++) {
+      lsdhip_depthmap* dm = maps[due[i0 + i]];
+      const int slot = lsd_ctx_claim_stats_slot(c, dm->activeKeyFrame);
+      if (slot < 0) return slot;
+      pyr.set(i, dm->activeKeyFrame, dm->d_red + 16, nPartials, slot);
+    }
+    if (int rc = pyr.launch()) return rc;
+    for (lsdhip_frame* kf : pyr.frames) kf->depthHasBeenUpdatedFlag = true;
+  }
+  return lsd_bprof_end(c, bp, ms, (double)due.size() * c->w * c->h);
 }
 
 // DepthMap::updateKeyframe for the maps of n sequences, one tracked frame each (the blockUntilMapped deque), in three launches for
@@ -2300,147 +2445,41 @@ extern "C" int lsdhip_depth_update_batch(int n, lsdhip_depthmap** maps, lsdhip_f
   for (int j = 0; j < n; j++) if (!maps[j] || !refs[j]) return LSDHIP_E_ARG;
   lsdhip_ctx* c = maps[0]->ctx;
   LSD_CTX_LOCK(c);
-  for (int j = 0; j < n; j++) {
-    lsdhip_depthmap* dm = maps[j];
-    if (dm->ctx != c || refs[j]->ctx != c) { lsd_set_error("updateKeyframe batch: maps and frames of one batch live on one context"); return LSDHIP_E_ARG; }
-    if (!dm->activeKeyFrame) { lsd_set_error("updateKeyframe batch: depth map %d has no active keyframe", j); return LSDHIP_E_STATE; }
-    for (int i = 0; i < j; i++) if (maps[i] == dm) { lsd_set_error("updateKeyframe batch: depth map %d appears twice", j); return LSDHIP_E_ARG; }
-    if (refs[j]->trackingParentID != dm->activeKeyFrame->id) {
-      lsd_set_error("updateKeyframe: frame %d was tracked on keyframe %d, active keyframe is %d (pose-graph path is out of scope)",
-                    refs[j]->id, refs[j]->trackingParentID, dm->activeKeyFrame->id);
-      return LSDHIP_E_STATE;
-    }
-  }
+  if (int rcv = update_batch_check(c, n, maps, refs)) return rcv;
   HIPCHK(hipSetDevice(c->device));
   double t0 = now_ms();
   if (int rcb = lsd_m_begin(c)) return rcb;
   const hipStream_t ms = lsd_map_stream(c);
-  // ---- observe ---------------------------------------------------------------------------------------------------------------------
-  const size_t obsBytes = (sizeof(ObserveArgs) * (size_t)n + 255) / 256 * 256;
-  const size_t regBytes = (sizeof(RegBatchItem) * (size_t)n + 255) / 256 * 256;
-  static const bool splitOff = getenv("LSDHIP_OBS_SPLIT") && getenv("LSDHIP_OBS_SPLIT")[0] == '0';   // A/B of round 5
-  const bool split = !splitOff && n >= LSD_OBS_SPLIT_MIN_MAPS && n <= LSD_OBS_WALK_MAX_MAPS;
-  if (split)
+  const DepthEnv& env = depth_env();
+  lsdhip_ctx::BatchForm form;     // what this call runs: becomes c->batchForm[0] once everything is queued
+  form.n = n;
+  form.split = env.obsSplit && n >= LSD_OBS_SPLIT_MIN_MAPS && n <= LSD_OBS_WALK_MAX_MAPS;
+  form.walkWorkgroups = form.split ? env.walkWaves : 0;
+  if (form.split)
     for (int j = 0; j < n; j++)
       if (!maps[j]->d_obsQueue) HIPCHK(hipMalloc((void**)&maps[j]->d_obsQueue, (size_t)c->w * c->h * sizeof(float4)));
-  void* hostBlob = nullptr;
-  void* dev = nullptr;
-  int rc = lsd_args_begin(c, obsBytes + regBytes + sizeof(int) * (size_t)n, &hostBlob, &dev);
-  if (rc) return rc;
-  ObserveArgs* oa = (ObserveArgs*)hostBlob;
-  RegBatchItem* ra = (RegBatchItem*)((uint8_t*)hostBlob + obsBytes);
-  int* qcountHost = (int*)((uint8_t*)hostBlob + obsBytes + regBytes);       // the queues' fill counts start from the zeros copied here
-  int* qcountDev = (int*)((uint8_t*)dev + obsBytes + regBytes);
-  const unsigned long long argsSerial = c->args.serial, argsGen = c->args.gen;   // (the record's place in the ring: lsdhip_ctx_batch_form)
-  int nSet = 0;
-  static const bool candOff = getenv("LSDHIP_OBS_CAND") && getenv("LSDHIP_OBS_CAND")[0] == '0';   // developer A/B (round 6)
-  bool candidates = !candOff;     // the select pass walks the keyframes' gradient candidates: every map of the call must qualify
-  for (int j = 0; j < n; j++) {
-    lsdhip_depthmap* dm = maps[j];
-    lsdhip_frame* kf = dm->activeKeyFrame;
-    ObserveArgs& a = oa[j];
-    memset((void*)&a, 0, sizeof(a));
-    prepare_stereo(dm, refs[j], a.one);
-    a.refs = nullptr; a.refByID = nullptr; a.nByID = 1; a.byIDOffset = refs[j]->id; a.nRefs = 1;
-    observe_args_common(dm, a);
-#ifdef LSD_PHASE_TRACE
-    a.trace = nullptr;
-#endif
-    a.queue = lsd_g(split ? dm->d_obsQueue : nullptr);
-    a.qcount = lsd_g(qcountDev + j);
-    a.gradCand = lsd_g((const uint16_t*)kf->d_gradCand);
-    if (dm->lowGradHypPossible || kf->gradCandTh != a.minUseGrad) candidates = false;
-    qcountHost[j] = 0;
-    dm->d_refs = nullptr;
-    dm->d_refByID = nullptr;
-    // the regulariser pass that follows: reads cur.valid, writes the spare plane (swapped below, as fill_regularize does)
-    RegBatchItem& r = ra[j];
-    r.a = reg_args(dm, VAL_SUM_MIN_FOR_KEEP);
-    const bool setDepth = !kf->depthHasBeenUpdatedFlag;
-    r.id0 = lsd_g(setDepth ? lsd_depth_w(kf)[0] : nullptr);
-    r.var0 = lsd_g(setDepth ? lsd_depthvar_w(kf)[0] : nullptr);
-    r.partials = lsd_g(dm->d_red + 16);
-    if (setDepth) nSet++;
-  }
-  rc = lsd_args_commit(c, ms);
-  if (rc) return rc;
-  const double mapPixels = (double)n * c->w * c->h;
-  int bp = lsd_bprof_begin(c, 1, ms);
-  if (bp < -1) return bp;
-  if (split) {
-    static const int walkWaves = getenv("LSDHIP_OBS_WALK_WAVES") ? atoi(getenv("LSDHIP_OBS_WALK_WAVES")) : LSD_OBS_WALK_WAVES;   // developer sweep
-    unsigned long long* acc = nullptr;
-    if (bp >= 0) {     // a sampled call also counts its searches and walk steps
-      if (!c->d_obsBatchAcc) { HIPCHK(hipMalloc((void**)&c->d_obsBatchAcc, 66 * 8)); HIPCHK(hipMemsetAsync(c->d_obsBatchAcc, 0, 66 * 8, ms)); }
-      acc = c->d_obsBatchAcc;
-    }
-    if (candidates) hipLaunchKernelGGL(k_observe_select_cand_batch, dim3((lsd_gradcand_groups(c->w * c->h) + 3) / 4, 1, n), dim3(256), 0, ms, (const ObserveArgs*)dev);
-    else hipLaunchKernelGGL(k_observe_select_batch, dim3((c->w + 63) / 64, (c->h + 15) / 16, n), dim3(256), 0, ms, (const ObserveArgs*)dev);
-    hipLaunchKernelGGL(k_observe_walk_batch, dim3(walkWaves), dim3(64), 0, ms, (const ObserveArgs*)dev, (const int*)qcountDev, n, acc);
-    c->batchForm[0].walkWorkgroups = walkWaves;
-  } else {
-    hipLaunchKernelGGL((k_observe_batch<2>), dim3((c->w + 31) / 32, (c->h + 1) / 2, n), dim3(64), 0, ms, (const ObserveArgs*)dev);
-  }
-  rc = lsd_bprof_end(c, bp, ms, mapPixels);
-  if (rc) return rc;
-  const RegBatchItem* dra = (const RegBatchItem*)((const uint8_t*)dev + obsBytes);
-  const int rpy = lsd_reg_py((long long)((c->w + 31) / 32) * ((c->h + 7) / 8) * n);
-  const dim3 rgrid((c->w + 31) / 32, lsd_reg_grid_rows((c->h + 7) / 8, rpy), n);
-  {
-    lsdhip_ctx::BatchForm& bf = c->batchForm[0];
-    bf.n = n; bf.py = rpy; bf.nSet = nSet; bf.split = split; bf.candidates = split && candidates; bf.synced = false;
-    if (!split) bf.walkWorkgroups = 0;
-    bf.qcountDev = qcountDev; bf.argsSerial = argsSerial; bf.argsGen = argsGen;
-  }
-  bp = lsd_bprof_begin(c, 2, ms);
-  if (bp < -1) return bp;
-  LSD_REG_DISPATCH(rpy,
-    if (nSet > 0) hipLaunchKernelGGL((k_reg_fused_batch<true, PYV>), rgrid, dim3(256), 0, ms, dra);
-    if (nSet < n) hipLaunchKernelGGL((k_reg_fused_batch<false, PYV>), rgrid, dim3(256), 0, ms, dra));
-  rc = lsd_bprof_end(c, bp, ms, mapPixels);
-  if (rc) return rc;
-  HIPCHK(hipGetLastError());
-  rc = lsd_args_release(c, dev, ms);
-  if (rc) return rc;
+  const UpdateRecord L(n);
+  void *host = nullptr, *dev = nullptr;
+  if (int rc = lsd_args_begin(c, L.bytes, &host, &dev)) return rc;
+  form.qcountDev = L.qcount(dev); form.argsSerial = c->args.serial; form.argsGen = c->args.gen;   // (the record's place in the ring: lsdhip_ctx_batch_form)
+  std::vector<int> due;
+  bool candidates = env.obsCand;
+  update_batch_items(n, maps, refs, L, host, dev, form.split, due, &candidates);
+  form.nSet = (int)due.size();
+  form.candidates = form.split && candidates;
+  if (int rc = lsd_args_commit(c, ms)) return rc;
+  const RegGrid g = reg_grid(c, tile_rows(c), n);
+  form.py = g.py;
+  if (int rc = update_batch_observe(c, n, L.obs(dev), form, ms)) return rc;
+  if (int rc = update_batch_regularize(c, n, L.reg(dev), g, form.nSet, ms)) return rc;
+  if (int rc = lsd_args_release(c, dev, ms)) return rc;
   for (int j = 0; j < n; j++) { swap_valid(maps[j]); maps[j]->lowGradHypPossible = false; }   // (every form of the observe pass drops a hypothesis below the threshold)
-  // ---- Frame::setDepth's second half for the keyframes that were due -------------------------------------------------------------------
-  if (nSet > 0) {
-    bp = lsd_bprof_begin(c, 3, ms);
-    if (bp < -1) return bp;
-    // At most LSD_NUM_SLOTS keyframes per pyramid launch: taking a slot that still has an owner resolves that owner first, which is only
-    // right once the launch that writes the slot has been queued — with more keyframes than slots in ONE launch the ring wrapped onto
-    // keyframes of the same call, whose statistics were then read before anything had written them (numPoints = 0).
-    int j0 = 0;
-    while (j0 < n) {
-      std::vector<lsdhip_frame*> kfs;
-      std::vector<const double*> parts;
-      std::vector<double*> outs;
-      for (; j0 < n && (int)kfs.size() < LSD_NUM_SLOTS; j0++) {
-        lsdhip_frame* kf = maps[j0]->activeKeyFrame;
-        if (kf->depthHasBeenUpdatedFlag) continue;
-        const int slot = lsd_ctx_take_slot(c);
-        if (slot < 0) return slot;
-        if (kf->pendStats >= 0) c->slot_stats_owner[kf->pendStats] = nullptr;
-        kf->pendStats = slot;
-        c->slot_stats_owner[slot] = kf;
-        kfs.push_back(kf);
-        parts.push_back(maps[j0]->d_red + 16);
-        outs.push_back((double*)&c->h_slots[slot]);
-      }
-      if (kfs.empty()) break;
-      rc = lsd_frame_build_idepth_pyramid_batch(kfs.data(), (int)kfs.size(), parts.data(), (int)(rgrid.x * rgrid.y), outs.data());
-      if (rc) return rc;
-      for (lsdhip_frame* kf : kfs) kf->depthHasBeenUpdatedFlag = true;
-    }
-    rc = lsd_bprof_end(c, bp, ms, (double)nSet * c->w * c->h);
-    if (rc) return rc;
-  }
-  if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
-  if (!c->async) {
-    HIPCHK(hipStreamSynchronize(ms));
-    c->batchForm[0].synced = true;
-    for (int j = 0; j < n; j++) { rc = lsd_frame_resolve(maps[j]->activeKeyFrame); if (rc) return rc; }
-  }
+  if (int rc = update_batch_set_depth(c, maps, due, g.tiles(), ms)) return rc;
+  if (int rc = map_call_end(c)) return rc;
+  form.synced = !c->async;
+  c->batchForm[0] = form;
+  if (!c->async)
+    for (int j = 0; j < n; j++) if (int rc = lsd_frame_resolve(maps[j]->activeKeyFrame)) return rc;
   const double dt = now_ms() - t0;
   for (int j = 0; j < n; j++) {
     lsdhip_depthmap* dm = maps[j];
@@ -2459,19 +2498,13 @@ extern "C" int lsdhip_depth_create_keyframe(lsdhip_depthmap* dm, lsdhip_frame* n
   LSD_CTX_LOCK(c);
   HIPCHK(hipSetDevice(c->device));
   double t0 = now_ms();
-  lsdm::SE3dH newToOld;
-  // se3FromSim3 = SE3(sim3.quaternion(), translation): the SCALED quaternion, normalised by the SO3 constructor (so3.hpp:630-633)
-  newToOld.q = nk->thisToParent_raw.q;
-  { const double s_ = nk->thisToParent_raw.s; newToOld.q.w *= s_; newToOld.q.x *= s_; newToOld.q.y *= s_; newToOld.q.z *= s_; }
-  lsdm::q_normalize(newToOld.q);
-  for (int i = 0; i < 3; i++) newToOld.t[i] = nk->thisToParent_raw.t[i];
-  lsdm::SE3dH oldToNew = lsdm::se3d_inverse(newToOld);
+  const lsdm::SE3dH oldToNew = old_to_new(nk);
 
   if (int rcb = lsd_m_begin(c)) return rcb;
   const int ev = timing_begin(dm, 1);
   if (ev < 0 && ev != EV_SKIP) return ev;
   if (int rcl = lsd_frame_require_level0(nk)) return rcl;   // the new keyframe's maxGradients(0): propagateDepth reads it (DepthMap.cpp:758)
-  int rc = propagate(dm, nk, false);
+  int rc = propagate(dm, nk, oldToNew, false);
   if (rc) return rc;
   dm->msPropagate = ema(dm->msPropagate, now_ms() - t0);
   dm->activeKeyFrame = nk;
@@ -2483,21 +2516,15 @@ extern "C" int lsdhip_depth_create_keyframe(lsdhip_depthmap* dm, lsdhip_frame* n
 
   // make mean inverse depth be one (DepthMap.cpp:1285-1304): the factor is formed on the device (k_rescale), the host
   // copy of (sum, count) and the propagation overflow flag are a deferred result of the new keyframe
-  int n = c->w * c->h;
-  int nb = (n + 255) / 256;
-  const int slot = lsd_ctx_take_slot(c);
+  const int n = c->w * c->h;
+  const int nb = (int)px_blocks(c);
+  const int slot = lsd_ctx_claim_rescale_slot(c, nk);
   if (slot < 0) return slot;
   hipLaunchKernelGGL(k_sum_valid_idepth, dim3(nb), dim3(256), 0, lsd_map_stream(c), dm->cur, n, dm->d_red + 16);
   hipLaunchKernelGGL(k_reduce_pairs, dim3(1), dim3(256), 0, lsd_map_stream(c), dm->d_red + 16, nb, (double*)&c->h_slots[slot], dm->d_red,
                      (const int*)dm->d_flags);
   hipLaunchKernelGGL(k_rescale, dim3(nb), dim3(256), 0, lsd_map_stream(c), dm->cur, n, dm->d_red);
-  lsdm::SE3dH back = lsdm::se3d_inverse(oldToNew);
-  nk->thisToParent_raw.q = back.q;
-  lsdm::q_normalize(nk->thisToParent_raw.q);   // sim3FromSE3 -> Sim3::setScale normalises the quaternion (rxso3.hpp:332-335)
-  for (int i = 0; i < 3; i++) nk->thisToParent_raw.t[i] = back.t[i];
-  if (nk->pendRescale >= 0) c->slot_rescale_owner[nk->pendRescale] = nullptr;
-  nk->pendRescale = slot;
-  c->slot_rescale_owner[slot] = nk;
+  drop_pose_scale(nk, oldToNew);
   rc = set_depth(dm);
   if (rc) return rc;
   rc = timing_end(dm, ev);
@@ -2512,6 +2539,179 @@ extern "C" int lsdhip_depth_create_keyframe(lsdhip_depthmap* dm, lsdhip_frame* n
   return LSDHIP_OK;
 }
 
+// A keyframe change edits host-side state of the maps, of both keyframes and of the context's slot ring while it builds the launches'
+// arguments, and several steps can fail (a slot, the argument ring, a launch).  The edits are undone unless the call gets as far as its
+// last launch: an error leaves every map on its old keyframe with its planes where they were, not half-way.
+struct ChangeTxn {
+  lsdhip_ctx* c; int n; lsdhip_depthmap** maps; lsdhip_frame** nks;
+  struct M { HypPlanes cur, oth; uint8_t* snap; lsdhip_frame* kf; bool react; bool propClean; int oldStats; int nkRescale, nkStats; lsdm::Sim3dH nkPose; };
+  std::vector<M> m;
+  std::vector<int> slots;      // slots claimed by this call
+  int slotNext; int ev = EV_SKIP; bool timing = false; bool done = false;
+  ChangeTxn(lsdhip_ctx* c_, int n_, lsdhip_depthmap** maps_, lsdhip_frame** nks_) : c(c_), n(n_), maps(maps_), nks(nks_), m((size_t)n_), slotNext(c_->slot_next) {
+    for (int j = 0; j < n; j++) {
+      lsdhip_depthmap* dm = maps[j];
+      m[j] = M{dm->cur, dm->oth, dm->d_validSnap, dm->activeKeyFrame, dm->activeKeyFrameIsReactivated, dm->propClean, dm->activeKeyFrame->pendStats,
+               nks[j]->pendRescale, nks[j]->pendStats, nks[j]->thisToParent_raw};
+    }
+  }
+  int stats_slot(lsdhip_frame* f) { const int s = lsd_ctx_claim_stats_slot(c, f); if (s >= 0) slots.push_back(s); return s; }
+  int rescale_slot(lsdhip_frame* f) { const int s = lsd_ctx_claim_rescale_slot(c, f); if (s >= 0) slots.push_back(s); return s; }
+  ~ChangeTxn() {
+    if (done) return;
+    for (int s : slots) { c->slot_stats_owner[s] = nullptr; c->slot_rescale_owner[s] = nullptr; }
+    c->slot_next = slotNext;
+    for (int j = 0; j < n; j++) {
+      lsdhip_depthmap* dm = maps[j];
+      dm->cur = m[j].cur; dm->oth = m[j].oth; dm->d_validSnap = m[j].snap; dm->activeKeyFrame = m[j].kf; dm->activeKeyFrameIsReactivated = m[j].react;
+      dm->propClean = false;                       // (the K7 scratch may have been written: the next call clears it)
+      m[j].kf->pendStats = m[j].oldStats;
+      if (m[j].oldStats >= 0) c->slot_stats_owner[m[j].oldStats] = m[j].kf;
+      nks[j]->pendRescale = m[j].nkRescale; nks[j]->pendStats = m[j].nkStats;
+      if (m[j].nkRescale >= 0) c->slot_rescale_owner[m[j].nkRescale] = nks[j];
+      if (m[j].nkStats >= 0) c->slot_stats_owner[m[j].nkStats] = nks[j];
+      nks[j]->thisToParent_raw = m[j].nkPose;
+    }
+    if (timing) (void)timing_end(maps[0], ev);     // (keeps the event pair of the timing sample balanced)
+  }
+};
+// The argument record of a keyframe change, sub-records on 256-byte boundaries: KfItem x n | RegBatchItem x n (the pass that removes
+// occlusions) | RegBatchItem x n (fill holes + regularise) | RescaleItem x n.  One layout for the pinned host copy and its device twin.
+struct ChangeRecord {
+  size_t occOff, fillOff, resOff, bytes;
+  explicit ChangeRecord(int n)
+      : occOff(up256(sizeof(KfItem) * (size_t)n)), fillOff(occOff + up256(sizeof(RegBatchItem) * (size_t)n)),
+        resOff(fillOff + up256(sizeof(RegBatchItem) * (size_t)n)), bytes(resOff + up256(sizeof(RescaleItem) * (size_t)n)) {}
+  KfItem* kf(void* base) const { return (KfItem*)base; }
+  RegBatchItem* occ(void* base) const { return (RegBatchItem*)((uint8_t*)base + occOff); }
+  RegBatchItem* fill(void* base) const { return (RegBatchItem*)((uint8_t*)base + fillOff); }
+  RescaleItem* res(void* base) const { return (RescaleItem*)((uint8_t*)base + resOff); }
+};
+
+static int change_keyframe_check(lsdhip_ctx* c, int n, lsdhip_depthmap** maps, lsdhip_frame** nks) {
+  for (int j = 0; j < n; j++) {
+    lsdhip_depthmap* dm = maps[j];
+    if (dm->ctx != c || nks[j]->ctx != c) { lsd_set_error("keyframe change batch: maps and frames of one batch live on one context"); return LSDHIP_E_ARG; }
+    if (!dm->activeKeyFrame) { lsd_set_error("keyframe change batch: depth map %d has no active keyframe", j); return LSDHIP_E_STATE; }
+    if (!nks[j]->trackingParent) { lsd_set_error("createKeyFrame: new keyframe has no tracking parent"); return LSDHIP_E_STATE; }
+    if (nks[j] == dm->activeKeyFrame) { lsd_set_error("keyframe change batch: map %d: the new keyframe is the current one", j); return LSDHIP_E_ARG; }
+    for (int i = 0; i < j; i++)
+      if (maps[i] == dm || nks[i] == nks[j]) { lsd_set_error("keyframe change batch: entry %d appears twice", j); return LSDHIP_E_ARG; }
+  }
+  return LSDHIP_OK;
+}
+// Map j's records of the change, and the host-side state of the map and of both keyframes as the six launches will leave it.  The order
+// of swap_valid, std::swap(cur, oth) and the three reg_args snapshots is what the launches depend on: each record describes the planes as
+// the launch before it leaves them.  pyr: jobs j (old keyframe) and n + j (new keyframe) of the pyramid launch.
+static int change_build_map(ChangeTxn& txn, int j, const ChangeRecord& L, void* host, int ntiles, int nwg5, PyramidJobs& pyr) {
+  lsdhip_depthmap* dm = txn.maps[j];
+  lsdhip_frame* old = dm->activeKeyFrame;
+  lsdhip_frame* nk = txn.nks[j];
+  double* setA = dm->d_red + 16;
+  double* setB = setA + dm->redStride;
+  double* setC = setB + dm->redStride;
+  const lsdm::SE3dH oldToNew = old_to_new(nk);
+  // finalizeKeyFrame: the pass on the old keyframe's map, its Frame::setDepth (level 0 + partials), re-activation data; phase A of
+  // propagateDepth into otherDepthMap
+  KfItem& k = L.kf(host)[j];
+  memset((void*)&k, 0, sizeof(k));
+  k.a = reg_args(dm, VAL_SUM_MIN_FOR_KEEP);
+  k.id0 = lsd_g(lsd_depth_w(old)[0]); k.var0 = lsd_g(lsd_depthvar_w(old)[0]); k.partials = lsd_g(setA);
+  k.x.reactId = lsd_g(old->d_idepth_reAct); k.x.reactVar = lsd_g(old->d_idepthVar_reAct); k.x.reactVal = lsd_g(old->d_validity_reAct);
+  prop_args(dm, nk, oldToNew, k.x.prop);
+  swap_valid(dm);
+  int slot = txn.stats_slot(old);
+  if (slot < 0) return slot;
+  pyr.set(j, old, setA, ntiles, slot);
+  // createKeyFrame: the new keyframe's map becomes the current one
+  std::swap(dm->cur, dm->oth);
+  dm->activeKeyFrame = nk;
+  dm->activeKeyFrameIsReactivated = false;
+  L.occ(host)[j] = reg_item(dm, nullptr, nullptr);
+  swap_valid(dm);
+  L.fill(host)[j] = reg_item(dm, nullptr, setB);
+  swap_valid(dm);
+  RescaleItem& r = L.res(host)[j];
+  memset((void*)&r, 0, sizeof(r));
+  r.m = dm->cur;
+  r.sumPartials = lsd_g(setB); r.nSumPartials = ntiles;
+  r.flags = lsd_g(dm->d_flags);
+  slot = txn.rescale_slot(nk);
+  if (slot < 0) return slot;
+  r.slot = lsd_g((double*)&txn.c->h_slots[slot]);
+  r.id0 = lsd_g(lsd_depth_w(nk)[0]); r.var0 = lsd_g(lsd_depthvar_w(nk)[0]);
+  r.statPartials = lsd_g(setC);
+  r.n = txn.c->w * txn.c->h;
+  slot = txn.stats_slot(nk);
+  if (slot < 0) return slot;
+  pyr.set(txn.n + j, nk, setC, nwg5, slot);
+  drop_pose_scale(nk, oldToNew);
+  return LSDHIP_OK;
+}
+// five of the six launches of the change (kernels above); the pyramid launch follows
+static int change_launch(lsdhip_ctx* c, int n, const ChangeRecord& L, void* dev, const RegGrid& g, int nwg5, hipStream_t ms) {
+  const KfItem* dkf = L.kf(dev);
+  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL(k_kf_finalize_prop<PYV>, g.grid, dim3(256), 0, ms, dkf));
+  hipLaunchKernelGGL(k_prop_resolve_batch, dim3(px_blocks(c), n), dim3(256), 0, ms, dkf);
+  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL((k_kf_reg<false, true, PYV>), g.grid, dim3(256), 0, ms, (const RegBatchItem*)L.occ(dev)));
+  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL((k_kf_reg<true, false, PYV>), g.grid, dim3(256), 0, ms, (const RegBatchItem*)L.fill(dev)));
+  hipLaunchKernelGGL(k_kf_rescale_setdepth, dim3(nwg5, n), dim3(256), 0, ms, (const RescaleItem*)L.res(dev));
+  HIPCHK(hipGetLastError());
+  return LSDHIP_OK;
+}
+// the change of at most LSD_NUM_SLOTS / 3 maps (validated by the caller)
+static int change_keyframe_part(lsdhip_ctx* c, int n, lsdhip_depthmap** maps, lsdhip_frame** new_keyframes, float* rescale_out) {
+  HIPCHK(hipSetDevice(c->device));
+  const double t0 = now_ms();
+  if (int rcb = lsd_m_begin(c)) return rcb;
+  const hipStream_t ms = lsd_map_stream(c);
+  const RegGrid g = reg_grid(c, tile_rows(c), n);
+  const int nwg5 = (c->w * c->h + LSD_RESCALE_PX - 1) / LSD_RESCALE_PX;
+  ChangeTxn txn(c, n, maps, new_keyframes);
+  for (int j = 0; j < n; j++) {
+    lsdhip_depthmap* dm = maps[j];
+    // (a single-call propagation, or a failed call, left the K7 scratch in use)
+    if (!dm->propClean) { if (int rcc = clear_prop_scratch(dm, ms)) return rcc; }
+    dm->propClean = false;
+  }
+  const int ev = timing_begin(maps[0], 1);
+  if (ev < 0 && ev != EV_SKIP) return ev;
+  txn.ev = ev; txn.timing = true;
+  if (int rcl = lsd_frames_require_level0(new_keyframes, n)) return rcl;   // the new keyframes' gradients(0) / maxGradients(0), one launch pair
+  const ChangeRecord L(n);
+  void *host = nullptr, *dev = nullptr;
+  if (int rc = lsd_args_begin(c, L.bytes, &host, &dev)) return rc;
+  PyramidJobs pyr((size_t)2 * n);
+  for (int j = 0; j < n; j++) if (int rc = change_build_map(txn, j, L, host, g.tiles(), nwg5, pyr)) return rc;
+  if (int rc = lsd_args_commit(c, ms)) return rc;
+  const int bp = lsd_bprof_begin(c, 4, ms);
+  if (bp < -1) return bp;
+  if (int rc = change_launch(c, n, L, dev, g, nwg5, ms)) return rc;
+  if (int rc = lsd_args_release(c, dev, ms)) return rc;
+  if (int rc = pyr.launch()) return rc;
+  if (int rc = lsd_bprof_end(c, bp, ms, (double)n * c->w * c->h)) return rc;
+  txn.done = true;            // every launch of the change is queued: the new state stands
+  { lsdhip_ctx::BatchForm& bf = c->batchForm[1]; bf = lsdhip_ctx::BatchForm(); bf.n = n; bf.py = g.py; }
+  for (int j = 0; j < n; j++) {
+    maps[j]->propClean = true;
+    txn.m[j].kf->depthHasBeenUpdatedFlag = true;
+    txn.m[j].kf->reActValid = true;
+    new_keyframes[j]->depthHasBeenUpdatedFlag = true;
+  }
+  if (int rc = timing_end(maps[0], ev)) return rc;
+  if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
+  if (!c->async || rescale_out) {
+    for (int j = 0; j < n; j++) {
+      if (!c->async) { if (int rc = lsd_frame_resolve(txn.m[j].kf)) return rc; }
+      if (int rc = lsd_frame_resolve(new_keyframes[j])) return rc;
+      if (rescale_out) rescale_out[j] = (float)new_keyframes[j]->thisToParent_raw.s;
+    }
+  }
+  const double dt = now_ms() - t0;
+  for (int j = 0; j < n; j++) maps[j]->msCreate = ema(maps[j]->msCreate, dt / n);
+  return LSDHIP_OK;
+}
+
 // DepthMap::finalizeKeyFrame (DepthMap.cpp:1363-1395) on the current keyframes of n maps followed by DepthMap::createKeyFrame(new_keyframes[j])
 // (:1222-1327), in six launches shared by all maps (kernels above).  Per map every plane, the re-activation data, both keyframes' idepth
 // pyramids and the deferred results (mean inverse depth / point counts, rescale factor, overflow flag) are those of
@@ -2521,214 +2721,17 @@ extern "C" int lsdhip_depth_change_keyframe_batch(int n, lsdhip_depthmap** maps,
   for (int j = 0; j < n; j++) if (!maps[j] || !new_keyframes[j]) return LSDHIP_E_ARG;
   lsdhip_ctx* c = maps[0]->ctx;
   LSD_CTX_LOCK(c);
-  for (int j = 0; j < n; j++) {
-    lsdhip_depthmap* dm = maps[j];
-    if (dm->ctx != c || new_keyframes[j]->ctx != c) { lsd_set_error("keyframe change batch: maps and frames of one batch live on one context"); return LSDHIP_E_ARG; }
-    if (!dm->activeKeyFrame) { lsd_set_error("keyframe change batch: depth map %d has no active keyframe", j); return LSDHIP_E_STATE; }
-    if (!new_keyframes[j]->trackingParent) { lsd_set_error("createKeyFrame: new keyframe has no tracking parent"); return LSDHIP_E_STATE; }
-    if (new_keyframes[j] == dm->activeKeyFrame) { lsd_set_error("keyframe change batch: map %d: the new keyframe is the current one", j); return LSDHIP_E_ARG; }
-    for (int i = 0; i < j; i++)
-      if (maps[i] == dm || new_keyframes[i] == new_keyframes[j]) { lsd_set_error("keyframe change batch: entry %d appears twice", j); return LSDHIP_E_ARG; }
-  }
-  // A change holds three deferred-result slots per map until its launches are queued, and taking a slot that still has an owner resolves
+  if (int rcv = change_keyframe_check(c, n, maps, new_keyframes)) return rcv;
+  // A change holds three deferred-result slots per map until its launches are queued, and claiming a slot that still has an owner resolves
   // that owner first — right only once the launch that writes the slot has been queued.  More maps than a third of the ring go in
   // consecutive parts, so that the ring never wraps onto a map of the part being prepared (it did: the first maps of a call of more than
   // 85 read their rescale factor and statistics before anything had written them).
   constexpr int maxPerPart = LSD_NUM_SLOTS / 3;
-  if (n > maxPerPart) {
-    for (int j0 = 0; j0 < n; j0 += maxPerPart) {
-      const int part = n - j0 < maxPerPart ? n - j0 : maxPerPart;
-      if (int rcp = lsdhip_depth_change_keyframe_batch(part, maps + j0, new_keyframes + j0, rescale_out ? rescale_out + j0 : nullptr)) return rcp;
-    }
-    c->batchForm[1].n = n;     // (py: that of the last part)
-    return LSDHIP_OK;
+  for (int j0 = 0; j0 < n; j0 += maxPerPart) {
+    const int part = n - j0 < maxPerPart ? n - j0 : maxPerPart;
+    if (int rcp = change_keyframe_part(c, part, maps + j0, new_keyframes + j0, rescale_out ? rescale_out + j0 : nullptr)) return rcp;
   }
-  HIPCHK(hipSetDevice(c->device));
-  const double t0 = now_ms();
-  if (int rcb = lsd_m_begin(c)) return rcb;
-  const hipStream_t ms = lsd_map_stream(c);
-  const int npx = c->w * c->h;
-  const int tpy = lsd_reg_py((long long)((c->w + 31) / 32) * ((c->h + 7) / 8) * n);
-  const dim3 tgrid((c->w + 31) / 32, lsd_reg_grid_rows((c->h + 7) / 8, tpy), n);
-  const int ntiles = (int)(tgrid.x * tgrid.y);
-  const int nwg5 = (npx + LSD_RESCALE_PX - 1) / LSD_RESCALE_PX;
-  // Everything below edits host-side state of the maps, of both keyframes and of the context's slot ring while it builds the launches'
-  // arguments, and several steps can fail (a slot, the argument ring, a launch).  The edits are undone unless the call gets as far as its
-  // last launch: an error leaves every map on its old keyframe with its planes where they were, not half-way.
-  struct Txn {
-    lsdhip_ctx* c; int n; lsdhip_depthmap** maps; lsdhip_frame** nks;
-    struct M { HypPlanes cur, oth; uint8_t* snap; lsdhip_frame* kf; bool react; bool propClean; int oldStats; int nkRescale, nkStats; lsdm::Sim3dH nkPose; };
-    std::vector<M> m;
-    std::vector<int> slots;      // slots taken by this call
-    int slotNext; int ev = EV_SKIP; bool timing = false; bool done = false;
-    Txn(lsdhip_ctx* c_, int n_, lsdhip_depthmap** maps_, lsdhip_frame** nks_) : c(c_), n(n_), maps(maps_), nks(nks_), m((size_t)n_), slotNext(c_->slot_next) {
-      for (int j = 0; j < n; j++) {
-        lsdhip_depthmap* dm = maps[j];
-        m[j] = M{dm->cur, dm->oth, dm->d_validSnap, dm->activeKeyFrame, dm->activeKeyFrameIsReactivated, dm->propClean, dm->activeKeyFrame->pendStats,
-                 nks[j]->pendRescale, nks[j]->pendStats, nks[j]->thisToParent_raw};
-      }
-    }
-    ~Txn() {
-      if (done) return;
-      for (int s : slots) { c->slot_stats_owner[s] = nullptr; c->slot_rescale_owner[s] = nullptr; }
-      c->slot_next = slotNext;
-      for (int j = 0; j < n; j++) {
-        lsdhip_depthmap* dm = maps[j];
-        dm->cur = m[j].cur; dm->oth = m[j].oth; dm->d_validSnap = m[j].snap; dm->activeKeyFrame = m[j].kf; dm->activeKeyFrameIsReactivated = m[j].react;
-        dm->propClean = false;                       // (the K7 scratch may have been written: the next call clears it)
-        m[j].kf->pendStats = m[j].oldStats;
-        if (m[j].oldStats >= 0) c->slot_stats_owner[m[j].oldStats] = m[j].kf;
-        nks[j]->pendRescale = m[j].nkRescale; nks[j]->pendStats = m[j].nkStats;
-        if (m[j].nkRescale >= 0) c->slot_rescale_owner[m[j].nkRescale] = nks[j];
-        if (m[j].nkStats >= 0) c->slot_stats_owner[m[j].nkStats] = nks[j];
-        nks[j]->thisToParent_raw = m[j].nkPose;
-      }
-      if (timing) (void)timing_end(maps[0], ev);     // (keeps the event pair of the timing sample balanced)
-    }
-  } txn(c, n, maps, new_keyframes);
-  for (int j = 0; j < n; j++) {
-    lsdhip_depthmap* dm = maps[j];
-    if (!dm->propClean) {     // (a single-call propagation, or a failed call, left the K7 scratch in use)
-      HIPCHK(hipMemsetAsync(dm->d_slotCount, 0, (size_t)npx * 4, ms));
-      HIPCHK(hipMemsetAsync(dm->d_ovfHead, 0xFF, (size_t)npx * 4, ms));
-      HIPCHK(hipMemsetAsync(dm->d_flags, 0, 64, ms));
-    }
-    dm->propClean = false;
-  }
-  const int ev = timing_begin(maps[0], 1);
-  if (ev < 0 && ev != EV_SKIP) return ev;
-  txn.ev = ev; txn.timing = true;
-  if (int rcl = lsd_frames_require_level0(new_keyframes, n)) return rcl;   // the new keyframes' gradients(0) / maxGradients(0), one launch pair
-  auto up = [](size_t v) { return (v + 255) / 256 * 256; };
-  const size_t kfBytes = up(sizeof(KfItem) * (size_t)n), regBytes = up(sizeof(RegBatchItem) * (size_t)n), resBytes = up(sizeof(RescaleItem) * (size_t)n);
-  void* hostBlob = nullptr;
-  void* dev = nullptr;
-  int rc = lsd_args_begin(c, kfBytes + 2 * regBytes + resBytes, &hostBlob, &dev);
-  if (rc) return rc;
-  KfItem* kf = (KfItem*)hostBlob;
-  RegBatchItem* regOcc = (RegBatchItem*)((uint8_t*)hostBlob + kfBytes);
-  RegBatchItem* regFill = (RegBatchItem*)((uint8_t*)hostBlob + kfBytes + regBytes);
-  RescaleItem* res = (RescaleItem*)((uint8_t*)hostBlob + kfBytes + 2 * regBytes);
-  std::vector<lsdhip_frame*> pyrFrames((size_t)2 * n);
-  std::vector<const double*> pyrParts((size_t)2 * n);
-  std::vector<double*> pyrOuts((size_t)2 * n);
-  std::vector<int> pyrN((size_t)2 * n);
-  for (int j = 0; j < n; j++) {
-    lsdhip_depthmap* dm = maps[j];
-    lsdhip_frame* old = dm->activeKeyFrame;
-    lsdhip_frame* nk = new_keyframes[j];
-    double* setA = dm->d_red + 16;
-    double* setB = setA + dm->redStride;
-    double* setC = setB + dm->redStride;
-    // finalizeKeyFrame: the pass on the old keyframe's map, its Frame::setDepth (level 0 + partials), re-activation data; phase A of
-    // propagateDepth into otherDepthMap
-    KfItem& k = kf[j];
-    memset((void*)&k, 0, sizeof(k));
-    k.a = reg_args(dm, VAL_SUM_MIN_FOR_KEEP);
-    k.id0 = lsd_g(lsd_depth_w(old)[0]); k.var0 = lsd_g(lsd_depthvar_w(old)[0]); k.partials = lsd_g(setA);
-    k.x.reactId = lsd_g(old->d_idepth_reAct); k.x.reactVar = lsd_g(old->d_idepthVar_reAct); k.x.reactVal = lsd_g(old->d_validity_reAct);
-    prop_args(dm, nk, k.x.prop);
-    swap_valid(dm);
-    {
-      const int slot = lsd_ctx_take_slot(c);
-      if (slot < 0) return slot;
-      txn.slots.push_back(slot);
-      if (old->pendStats >= 0) c->slot_stats_owner[old->pendStats] = nullptr;
-      old->pendStats = slot;
-      c->slot_stats_owner[slot] = old;
-      pyrFrames[j] = old; pyrParts[j] = setA; pyrN[j] = ntiles; pyrOuts[j] = (double*)&c->h_slots[slot];
-    }
-    // createKeyFrame: the new keyframe's map becomes the current one
-    std::swap(dm->cur, dm->oth);
-    dm->activeKeyFrame = nk;
-    dm->activeKeyFrameIsReactivated = false;
-    memset((void*)&regOcc[j], 0, sizeof(RegBatchItem));
-    regOcc[j].a = reg_args(dm, VAL_SUM_MIN_FOR_KEEP);
-    swap_valid(dm);
-    memset((void*)&regFill[j], 0, sizeof(RegBatchItem));
-    regFill[j].a = reg_args(dm, VAL_SUM_MIN_FOR_KEEP);
-    regFill[j].partials = lsd_g(setB);
-    swap_valid(dm);
-    RescaleItem& r = res[j];
-    memset((void*)&r, 0, sizeof(r));
-    r.m = dm->cur;
-    r.sumPartials = lsd_g(setB); r.nSumPartials = ntiles;
-    r.flags = lsd_g(dm->d_flags);
-    {
-      const int slot = lsd_ctx_take_slot(c);
-      if (slot < 0) return slot;
-      txn.slots.push_back(slot);
-      if (nk->pendRescale >= 0) c->slot_rescale_owner[nk->pendRescale] = nullptr;
-      nk->pendRescale = slot;
-      c->slot_rescale_owner[slot] = nk;
-      r.slot = lsd_g((double*)&c->h_slots[slot]);
-    }
-    r.id0 = lsd_g(lsd_depth_w(nk)[0]); r.var0 = lsd_g(lsd_depthvar_w(nk)[0]);
-    r.statPartials = lsd_g(setC);
-    r.n = npx;
-    {
-      const int slot = lsd_ctx_take_slot(c);
-      if (slot < 0) return slot;
-      txn.slots.push_back(slot);
-      if (nk->pendStats >= 0) c->slot_stats_owner[nk->pendStats] = nullptr;
-      nk->pendStats = slot;
-      c->slot_stats_owner[slot] = nk;
-      pyrFrames[n + j] = nk; pyrParts[n + j] = setC; pyrN[n + j] = nwg5; pyrOuts[n + j] = (double*)&c->h_slots[slot];
-    }
-    // the new keyframe's pose: sim3FromSE3(se3FromSim3(thisToParent_raw)) — the scale follows with the rescale factor (DepthMap.cpp:1305)
-    {
-      lsdm::SE3dH newToOld;
-      newToOld.q = nk->thisToParent_raw.q;
-      { const double s_ = nk->thisToParent_raw.s; newToOld.q.w *= s_; newToOld.q.x *= s_; newToOld.q.y *= s_; newToOld.q.z *= s_; }
-      lsdm::q_normalize(newToOld.q);
-      for (int i = 0; i < 3; i++) newToOld.t[i] = nk->thisToParent_raw.t[i];
-      const lsdm::SE3dH back = lsdm::se3d_inverse(lsdm::se3d_inverse(newToOld));
-      nk->thisToParent_raw.q = back.q;
-      lsdm::q_normalize(nk->thisToParent_raw.q);
-      for (int i = 0; i < 3; i++) nk->thisToParent_raw.t[i] = back.t[i];
-    }
-  }
-  rc = lsd_args_commit(c, ms);
-  if (rc) return rc;
-  const int bp = lsd_bprof_begin(c, 4, ms);
-  if (bp < -1) return bp;
-  const KfItem* dkf = (const KfItem*)dev;
-  const RegBatchItem* dOcc = (const RegBatchItem*)((const uint8_t*)dev + kfBytes);
-  const RegBatchItem* dFill = (const RegBatchItem*)((const uint8_t*)dev + kfBytes + regBytes);
-  const RescaleItem* dRes = (const RescaleItem*)((const uint8_t*)dev + kfBytes + 2 * regBytes);
-  LSD_REG_DISPATCH(tpy, hipLaunchKernelGGL(k_kf_finalize_prop<PYV>, tgrid, dim3(256), 0, ms, dkf));
-  hipLaunchKernelGGL(k_prop_resolve_batch, dim3((unsigned)((npx + 255) / 256), n), dim3(256), 0, ms, dkf);
-  LSD_REG_DISPATCH(tpy, hipLaunchKernelGGL((k_kf_reg<false, true, PYV>), tgrid, dim3(256), 0, ms, dOcc));
-  LSD_REG_DISPATCH(tpy, hipLaunchKernelGGL((k_kf_reg<true, false, PYV>), tgrid, dim3(256), 0, ms, dFill));
-  hipLaunchKernelGGL(k_kf_rescale_setdepth, dim3(nwg5, n), dim3(256), 0, ms, dRes);
-  HIPCHK(hipGetLastError());
-  rc = lsd_args_release(c, dev, ms);
-  if (rc) return rc;
-  rc = lsd_frame_build_idepth_pyramid_batch(pyrFrames.data(), 2 * n, pyrParts.data(), 0, pyrOuts.data(), pyrN.data());
-  if (rc) return rc;
-  rc = lsd_bprof_end(c, bp, ms, (double)n * npx);
-  if (rc) return rc;
-  txn.done = true;            // every launch of the change is queued: the new state stands
-  { lsdhip_ctx::BatchForm& bf = c->batchForm[1]; bf = lsdhip_ctx::BatchForm(); bf.n = n; bf.py = tpy; }
-  for (int j = 0; j < n; j++) {
-    maps[j]->propClean = true;
-    pyrFrames[j]->depthHasBeenUpdatedFlag = true;
-    pyrFrames[j]->reActValid = true;
-    pyrFrames[n + j]->depthHasBeenUpdatedFlag = true;
-  }
-  rc = timing_end(maps[0], ev);
-  if (rc) return rc;
-  if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
-  if (!c->async || rescale_out) {
-    for (int j = 0; j < n; j++) {
-      if (!c->async) { rc = lsd_frame_resolve(pyrFrames[j]); if (rc) return rc; }
-      rc = lsd_frame_resolve(pyrFrames[n + j]);
-      if (rc) return rc;
-      if (rescale_out) rescale_out[j] = (float)pyrFrames[n + j]->thisToParent_raw.s;
-    }
-  }
-  const double dt = now_ms() - t0;
-  for (int j = 0; j < n; j++) maps[j]->msCreate = ema(maps[j]->msCreate, dt / n);
+  c->batchForm[1].n = n;     // (py: that of the last part)
   return LSDHIP_OK;
 }
 
@@ -2745,13 +2748,12 @@ extern "C" int lsdhip_depth_finalize(lsdhip_depthmap* dm) {
   int rc = fill_regularize(dm, VAL_SUM_MIN_FOR_KEEP, true);
   if (rc) return rc;
   lsdhip_frame* kf = dm->activeKeyFrame;
-  size_t n = (size_t)c->w * c->h;
-  hipLaunchKernelGGL(k_take_react, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, lsd_map_stream(c), dm->cur, kf->d_idepth_reAct,
-                     kf->d_idepthVar_reAct, kf->d_validity_reAct, (int)n);
+  hipLaunchKernelGGL(k_take_react, dim3(px_blocks(c)), dim3(256), 0, lsd_map_stream(c), dm->cur, kf->d_idepth_reAct,
+                     kf->d_idepthVar_reAct, kf->d_validity_reAct, c->w * c->h);
   rc = timing_end(dm, ev);
   if (rc) return rc;
-  if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
-  if (!c->async) HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));
+  rc = map_call_end(c);
+  if (rc) return rc;
   kf->reActValid = true;
   dm->msFinalize = ema(dm->msFinalize, now_ms() - t0);
   return LSDHIP_OK;
@@ -2858,23 +2860,21 @@ extern "C" int lsdhip_depth_stage(lsdhip_depthmap* dm, int stage, lsdhip_frame**
   int rc = LSDHIP_E_ARG;
   if (int rcb = lsd_m_begin(c)) return rcb;
   switch (stage) {
-    case 0: rc = observe(dm, refs, n); break;
+    case 0: rc = observe(dm, refs, n, false); break;
     case 1: rc = fill_holes(dm); break;
     case 2: rc = regularize(dm, false, VAL_SUM_MIN_FOR_KEEP); break;
     case 3: rc = regularize(dm, true, VAL_SUM_MIN_FOR_KEEP); break;
     case 4:
       if (!refs || n < 1) return LSDHIP_E_ARG;
       rc = lsd_frame_require_level0(refs[0]);
-      if (rc == LSDHIP_OK) rc = propagate(dm, refs[0], true);
+      if (rc == LSDHIP_OK) rc = propagate(dm, refs[0], old_to_new(refs[0]), true);
       if (rc == LSDHIP_OK) { dm->activeKeyFrame = refs[0]; dm->activeKeyFrameIsReactivated = false; }
       break;
     case 5: rc = fill_regularize(dm, VAL_SUM_MIN_FOR_KEEP, false); break;
     default: return LSDHIP_E_ARG;
   }
   if (rc) return rc;
-  if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
-  if (!c->async) HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));   // asynchronous contexts: ordered on the stream
-  return LSDHIP_OK;
+  return map_call_end(c);
 }
 
 extern "C" int lsdhip_depth_stage_rows(lsdhip_depthmap* dm, int stage, int tile_row0, int n_tile_rows, int last) {
@@ -2894,13 +2894,14 @@ extern "C" int lsdhip_depth_stage_rows_batch(lsdhip_ctx* c, int n, lsdhip_depthm
   if (n == 0) return LSDHIP_OK;
   LSD_CTX_LOCK(c);
   HIPCHK(hipSetDevice(c->device));
-  const int T = (c->h + 7) / 8;
   int maxRows = 0;
+  long long rowsInAll = 0;
   for (int k = 0; k < n; k++) {
     if (!maps[k] || maps[k]->ctx != c) return LSDHIP_E_ARG;
     if (!maps[k]->activeKeyFrame) { lsd_set_error("depth stage: no active keyframe"); return LSDHIP_E_STATE; }
-    if (tile_row0[k] < 0 || n_tile_rows[k] <= 0 || tile_row0[k] + n_tile_rows[k] > T) { lsd_set_error("depth stage rows: tile rows [%d, %d) outside [0, %d)", tile_row0[k], tile_row0[k] + n_tile_rows[k], T); return LSDHIP_E_ARG; }
+    if (int rcr = check_tile_rows(c, tile_row0[k], n_tile_rows[k], 1)) return rcr;
     if (n_tile_rows[k] > maxRows) maxRows = n_tile_rows[k];
+    rowsInAll += n_tile_rows[k];
   }
   void* host = nullptr;
   void* dev = nullptr;
@@ -2908,18 +2909,15 @@ extern "C" int lsdhip_depth_stage_rows_batch(lsdhip_ctx* c, int n, lsdhip_depthm
   if (rc) return rc;
   RegBatchItem* items = (RegBatchItem*)host;
   for (int k = 0; k < n; k++) {
-    memset((void*)&items[k], 0, sizeof(RegBatchItem));
-    items[k].a = reg_args(maps[k], VAL_SUM_MIN_FOR_KEEP);
+    items[k] = reg_item(maps[k], nullptr, nullptr);
     items[k].a.tileRow0 = tile_row0[k];
     items[k].a.tileRows = n_tile_rows[k];
   }
   const hipStream_t ms = lsd_map_stream(c);
   rc = lsd_args_commit(c, ms);
   if (rc) return rc;
-  long long wg1 = 0;
-  for (int k = 0; k < n; k++) wg1 += (long long)((c->w + 31) / 32) * n_tile_rows[k];
-  const int bpy = lsd_reg_py(wg1);
-  LSD_REG_DISPATCH(bpy, hipLaunchKernelGGL(k_reg_rows_batch<PYV>, dim3((c->w + 31) / 32, lsd_reg_grid_rows(maxRows, bpy), n), dim3(256), 0, ms, (const RegBatchItem*)dev));
+  const RegGrid g = reg_grid(c, maxRows, n, rowsInAll);
+  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL(k_reg_rows_batch<PYV>, g.grid, dim3(256), 0, ms, (const RegBatchItem*)dev));
   HIPCHK(hipGetLastError());
   rc = lsd_args_release(c, dev, ms);
   if (rc) return rc;
@@ -2937,9 +2935,7 @@ extern "C" int lsdhip_depth_copy_planes_dev(lsdhip_depthmap* dm, float* idepth_d
   if (int rcb = lsd_m_begin(c)) return rcb;
   HIPCHK(hipMemcpyAsync(idepth_dev, lsd_depth_latest(dm->activeKeyFrame)[0], n * 4, hipMemcpyDeviceToDevice, lsd_map_stream(c)));
   HIPCHK(hipMemcpyAsync(var_dev, lsd_depthvar_latest(dm->activeKeyFrame)[0], n * 4, hipMemcpyDeviceToDevice, lsd_map_stream(c)));
-  if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
-  if (!c->async) HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));   // asynchronous contexts: ordered on the stream, see lsdhip_ctx_synchronize
-  return LSDHIP_OK;
+  return map_call_end(c);
 }
 
 // Rows [row0, row0 + nrows) of the eight hypothesis planes <-> one packed device buffer (plane after plane: isValid u8,

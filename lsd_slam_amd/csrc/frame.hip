@@ -1123,6 +1123,22 @@ int lsd_ctx_take_slot(lsdhip_ctx* c) {
   c->slot_mseq[i] = c->mSeq + 1;     // pipelined contexts: the calling DepthMap entry ends with the record point of this number
   return i;
 }
+int lsd_ctx_claim_stats_slot(lsdhip_ctx* c, lsdhip_frame* f) {
+  const int slot = lsd_ctx_take_slot(c);
+  if (slot < 0) return slot;
+  if (f->pendStats >= 0) c->slot_stats_owner[f->pendStats] = nullptr;
+  f->pendStats = slot;
+  c->slot_stats_owner[slot] = f;
+  return slot;
+}
+int lsd_ctx_claim_rescale_slot(lsdhip_ctx* c, lsdhip_frame* f) {
+  const int slot = lsd_ctx_take_slot(c);
+  if (slot < 0) return slot;
+  if (f->pendRescale >= 0) c->slot_rescale_owner[f->pendRescale] = nullptr;
+  f->pendRescale = slot;
+  c->slot_rescale_owner[slot] = f;
+  return slot;
+}
 int lsd_frame_resolve(lsdhip_frame* f) {
   if (f->pendStats < 0 && f->pendRescale < 0) return LSDHIP_OK;
   lsdhip_ctx* c = f->ctx;

@@ -461,8 +461,6 @@ struct lsdhip_depthmap {
   void* bases[3] = {nullptr, nullptr, nullptr};  // arena base pointers (for hipFree)
   lsdhip_frame* activeKeyFrame = nullptr;
   bool activeKeyFrameIsReactivated = false;
-  StereoRef* d_refs = nullptr;     // views into d_stage
-  int* d_refByID = nullptr;
   char* h_stage = nullptr;         // pinned staging block (refs | refByID) and its device twin
   char* d_stage = nullptr;
   size_t stage_bytes = 0;
@@ -492,7 +490,6 @@ struct lsdhip_depthmap {
   double gpu_ms[4] = {0, 0, 0, 0};    // update, createKeyFrame, finalizeKeyFrame, k_observe alone (sampled while profiling)
   long long gpu_calls[4] = {0, 0, 0, 0};
   unsigned obs_tick = 0;
-  bool countNext = false;                        // the next k_observe launch counts its searches / walk steps (sampled while profiling)
   unsigned long long* d_obsCounters = nullptr;   // per wave (searches, steps) of the last counted launch | d_obsAcc: totals (searches, steps, launches)
   unsigned long long* d_obsAcc = nullptr;
   int obsCounterWaves = 0;
@@ -582,3 +579,7 @@ int lsd_bprof_begin(lsdhip_ctx* c, int kind, hipStream_t s);               // sl
 int lsd_bprof_end(lsdhip_ctx* c, int slot, hipStream_t s, double units);
 int lsd_frame_resolve(lsdhip_frame* f);        // reads the frame's deferred results (synchronises the stream if any)
 int lsd_ctx_take_slot(lsdhip_ctx* c);          // next slot of the ring (resolving whoever still waits on it)
+// The next slot of the ring becomes the home of f's statistics (Frame::setDepth: mean inverse depth, point count) / of f's rescale factor
+// and overflow flag (createKeyFrame); a result of that kind that f still waited for is superseded.  Returns the slot, or an error (< 0).
+int lsd_ctx_claim_stats_slot(lsdhip_ctx* c, lsdhip_frame* f);
+int lsd_ctx_claim_rescale_slot(lsdhip_ctx* c, lsdhip_frame* f);
