@@ -36,11 +36,13 @@ enum {
 #define S3_NTAIL (S3_END - S3_TAIL0)        // 46 contributions per point
 static_assert(S3_END == 54 && S3_NTAIL == 46, "layout");
 
-struct Sim3Job {
+struct Sim3Lvl {                            // one pyramid level of a (keyframe, frame) pair: what does not change during a job (sim3_level)
   const float* kf_idepth; const float* kf_idepthVar; const float* kf_image; const float4* kf_grad;
   const float4* fr_grad; const float* fr_idepth; const float* fr_idepthVar;
   int w, h, nblocks, ppl;                   // nblocks strips of ppl * 256 pixels (ppl: pixels per lane)
   float fx, fy, cx, cy, fxi, fyi, cxi, cyi;
+};
+struct Sim3Job : Sim3Lvl {                  // one evaluation: its level, then the request
   float R[9], t[3];                         // rxso3().matrix() (scale * rotation) and translation, cast to float
   float xRoll0, xRoll1, yRoll0, yRoll1;     // in-plane rotation of the reference gradients (ESM, Sim3Tracker.cpp:455-464)
   float aff_a, aff_b, cameraPixelNoise2, var_weight, huber_d;
@@ -348,6 +350,38 @@ S3_HD Sim3H sim3_mul(const Sim3H& a, const Sim3H& b) {   // sim3.hpp:160-163
   r.s = a.s * b.s;
   return r;
 }
+S3_HD void sim3_out8(const Sim3H& T, double p[8]) { p[0] = T.q.w; p[1] = T.q.x; p[2] = T.q.y; p[3] = T.q.z; p[4] = T.t[0]; p[5] = T.t[1]; p[6] = T.t[2]; p[7] = T.s; }
+// the requested transformation as the evaluation kernel wants it: rxso3().matrix() and translation in float, the in-plane roll of the
+// reference gradients (ESM, Sim3Tracker.cpp:455-464)
+S3_HD void sim3_request_of(const Sim3H& T, float R[9], float t[3], float roll[4]) {
+  double Rd[9];
+  lsdm::quatd_to_rot(T.q, Rd);
+  float Ru[9];
+  for (int i = 0; i < 9; i++) { R[i] = (float)(T.s * Rd[i]); Ru[i] = (float)Rd[i]; }
+  for (int i = 0; i < 3; i++) t[i] = (float)T.t[i];
+  // Quaternionf::setFromTwoVectors(R * (0,0,-1), (0,0,-1)).toRotationMatrix() * R
+  const float rf[3] = {Ru[0] * 0.f + Ru[1] * 0.f + Ru[2] * -1.f, Ru[3] * 0.f + Ru[4] * 0.f + Ru[5] * -1.f, Ru[6] * 0.f + Ru[7] * 0.f + Ru[8] * -1.f};
+  const float n0 = sqrtf(rf[0] * rf[0] + (rf[1] * rf[1] + rf[2] * rf[2]));
+  const float v0[3] = {rf[0] / n0, rf[1] / n0, rf[2] / n0};
+  const float v1[3] = {0, 0, -1};
+  const float cdot = v1[0] * v0[0] + (v1[1] * v0[1] + v1[2] * v0[2]);
+  lsdm::Quatf q;
+  if (cdot < -1.0f + 1e-5f) {
+    q = {0, 1, 0, 0};
+  } else {
+    const float ax = v0[1] * v1[2] - v0[2] * v1[1], ay = v0[2] * v1[0] - v0[0] * v1[2], az = v0[0] * v1[1] - v0[1] * v1[0];
+    const float sq = sqrtf((1.0f + cdot) * 2.0f);
+    const float invs = 1.0f / sq;
+    q = {sq * 0.5f, ax * invs, ay * invs, az * invs};
+  }
+  float Q[9];
+  lsdm::quatf_to_rot(q, Q);
+  // rows 0 and 1, columns 0 and 1 of Q * R
+  roll[0] = (Q[0] * Ru[0] + Q[1] * Ru[3]) + Q[2] * Ru[6];
+  roll[1] = (Q[0] * Ru[1] + Q[1] * Ru[4]) + Q[2] * Ru[7];
+  roll[2] = (Q[3] * Ru[0] + Q[4] * Ru[3]) + Q[5] * Ru[6];
+  roll[3] = (Q[3] * Ru[1] + Q[4] * Ru[4]) + Q[5] * Ru[7];
+}
 // the five transcendental values of an increment's exponential (the device computes them in different lanes: k_sim3_fused)
 struct Sim3Trig { double sin_theta, cos_theta, sin_half, cos_half, exp_sigma; };
 S3_HD double sim3_theta(const double a[7]) { return std::sqrt(a[3] * a[3] + (a[4] * a[4] + a[5] * a[5])); }
@@ -522,17 +556,16 @@ struct lsdhip_sim3tracker {
   int recentRounds = 0;        // evaluations the longest job of the last call needed: the next call's launch budget
 };
 
+// all of a tracker's storage (defined behind the job structures it holds: "the tracker's storage" below)
+static int sim3_storage_reserve(lsdhip_sim3tracker* t, bool tracking);
+static void sim3_storage_release(lsdhip_sim3tracker* t);
+
 extern "C" int lsdhip_sim3tracker_create(lsdhip_ctx* c, lsdhip_sim3tracker** out) {
   if (!c || !out) return LSDHIP_E_ARG;
   HIPCHK(hipSetDevice(c->device));
   lsdhip_sim3tracker* t = new lsdhip_sim3tracker();
   t->ctx = c;
-  const size_t mb = (size_t)S3_NBMAX * S3_MAXB * 2;
-  HIPCHK(hipMalloc((void**)&t->d_rows, mb * 64 * 4));
-  HIPCHK(hipMalloc((void**)&t->d_topkey, mb * 16));
-  HIPCHK(hipHostMalloc((void**)&t->h_record, S3_MAXB * 64 * 4, hipHostMallocMapped));
-  memset(t->h_record, 0, S3_MAXB * 64 * 4);
-  HIPCHK(hipHostGetDevicePointer((void**)&t->d_record, t->h_record, 0));
+  if (int rc = sim3_storage_reserve(t, false)) { sim3_storage_release(t); return rc; }
   *out = t;
   return LSDHIP_OK;
 }
@@ -540,10 +573,7 @@ extern "C" void lsdhip_sim3tracker_destroy(lsdhip_sim3tracker* t) {
   if (!t) return;
   (void)hipSetDevice(t->ctx->device);
   (void)hipStreamSynchronize(t->ctx->stream);
-  (void)hipFree(t->d_rows); (void)hipFree(t->d_topkey); (void)hipHostFree(t->h_record);
-  (void)hipFree(t->d_sets);      // (one block: level descriptions + states, as they are uploaded)
-  (void)hipHostFree(t->h_sets); (void)hipHostFree(t->h_results); (void)hipHostFree(t->h_done);
-  delete t;
+  sim3_storage_release(t);
 }
 extern "C" int lsdhip_sim3tracker_set_max_its(lsdhip_sim3tracker* t, const int its[LSD_LEVELS]) {
   if (!t || !its) return LSDHIP_E_ARG;
@@ -551,64 +581,99 @@ extern "C" int lsdhip_sim3tracker_set_max_its(lsdhip_sim3tracker* t, const int i
   return LSDHIP_OK;
 }
 
+// ---- what the entry points refuse ------------------------------------------------------------------------------------------------
+static int sim3_check_pair(const lsdhip_frame* kf, const lsdhip_frame* frame) {
+  if (!kf || !frame) return LSDHIP_E_ARG;
+  if (!kf->hasIDepth || !frame->hasIDepth) { lsd_set_error("Sim3 tracking needs inverse depth on both frames"); return LSDHIP_E_STATE; }
+  return LSDHIP_OK;
+}
+static int sim3_check_levels(int startLevel, int finalLevel) {
+  return startLevel < finalLevel || finalLevel < 0 || startLevel >= LSD_LEVELS ? LSDHIP_E_ARG : LSDHIP_OK;
+}
+
+// ---- what an evaluation reads and writes: stated once for the single evaluation and the fused loop ---------------------------------
 static void sim3_strips(int npix, int* nblocks, int* ppl) {
   *ppl = (npix + S3_BLOCK * S3_NBMAX - 1) / (S3_BLOCK * S3_NBMAX);
   *nblocks = (npix + S3_BLOCK * *ppl - 1) / (S3_BLOCK * *ppl);
 }
+static Sim3Lvl sim3_level(const lsdhip_sim3tracker* t, const lsdhip_frame* kf, const lsdhip_frame* frame, int l) {
+  const lsdhip_ctx* c = t->ctx;
+  Sim3Lvl L;
+  L.kf_idepth = kf->d_idepth[l]; L.kf_idepthVar = kf->d_idepthVar[l]; L.kf_image = kf->d_image[l]; L.kf_grad = kf->d_grad[l];
+  L.fr_grad = frame->d_grad[l]; L.fr_idepth = frame->d_idepth[l]; L.fr_idepthVar = frame->d_idepthVar[l];
+  L.w = c->wl[l]; L.h = c->hl[l];
+  sim3_strips(L.w * L.h, &L.nblocks, &L.ppl);
+  const LevelIntr& in = c->intr[l];
+  L.fx = in.fx; L.fy = in.fy; L.cx = in.cx; L.cy = in.cy; L.fxi = in.fxi; L.fyi = in.fyi; L.cxi = in.cxi; L.cyi = in.cyi;
+  return L;
+}
+// level-0 texels are built on demand: once per pair, before its level 0 is described
+static int sim3_require_level0(lsdhip_frame* kf, lsdhip_frame* frame) {
+  if (int rc = lsd_frame_require_level0_for_tracking(kf)) return rc;
+  return lsd_frame_require_level0_for_tracking(frame);
+}
+// the tracker-wide constants of the weights (Sim3Job and Sim3Set name them alike)
+template <class D>
+static void sim3_noise(const lsdhip_sim3tracker* t, D& d) {
+  d.cameraPixelNoise2 = t->ctx->params.cameraPixelNoise2; d.var_weight = t->var_weight; d.huber_d = t->huber_d;
+}
+// the rows and order keys a batch slot's evaluation leaves, per launch parity (the single evaluation: parity 0)
+static void sim3_scratch(const lsdhip_sim3tracker* t, int slot, int parity, float** rows, int4** topkey) {
+  const size_t at = ((size_t)parity * S3_MAXB + slot) * S3_NBMAX;
+  *rows = t->d_rows + at * 64;
+  *topkey = t->d_topkey + at;
+}
+
+// ---- waiting for pinned words ----------------------------------------------------------------------------------------------------
+// The host polls pinned memory instead of sleeping in hipStreamSynchronize (whose wake-up costs more than an evaluation).  Time limits of
+// the three waits, in seconds: the record of a single evaluation, the flags of a launch budget, a finished job's result record
+enum { S3_EVAL_WAIT_S = 5, S3_FLAG_WAIT_S = 10, S3_RESULT_WAIT_S = 2 };
+typedef std::chrono::steady_clock::time_point Sim3Deadline;
+static Sim3Deadline sim3_deadline(int seconds) { return std::chrono::steady_clock::now() + std::chrono::seconds(seconds); }
+// Spins until settled() holds.  No stream query in the wait but as a safety net: each one puts a marker packet into the queue the
+// launches run through (profiles/r03_notes.md §2b).  Past the deadline the stream is drained and settled() has its last word.
+template <class Pred>
+static int sim3_spin_until(lsdhip_ctx* c, Pred settled, Sim3Deadline deadline, const char* failure) {
+  for (unsigned spins = 1; !settled(); spins++) {
+    if ((spins & 0xFFFFFu) == 0) {
+      hipError_t q = hipStreamQuery(c->stream);
+      if (q != hipSuccess && q != hipErrorNotReady) { lsd_set_error("hipStreamQuery failed: %s", hipGetErrorString(q)); return LSDHIP_E_HIP; }
+      if (std::chrono::steady_clock::now() > deadline) {
+        HIPCHK(hipStreamSynchronize(c->stream));
+        if (!settled()) { lsd_set_error("%s", failure); return LSDHIP_E_STATE; }
+        break;
+      }
+    }
+    __builtin_ia32_pause();
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return LSDHIP_OK;
+}
+// A pinned record of n words is whole when seed + the position-weighted sum of its words equals the check word the device stored with
+// it: whole record or nothing.  (They are separate posted writes: the words of such a record have been seen to land after the flag stored
+// behind the fence, profiles/r06_notes.md section 1.)  `late` counts the records that were not whole at the first look.
+static int sim3_wait_record(lsdhip_ctx* c, const void* record, unsigned n, unsigned seed, const void* check, Sim3Deadline deadline,
+                            const char* failure, long long* late = nullptr) {
+  volatile const unsigned* w = (volatile const unsigned*)record;
+  auto whole = [&]() { unsigned chk = seed; for (unsigned i = 0; i < n; i++) chk += lsd_summary_term(i, w[i]); return *(volatile const unsigned*)check == chk; };
+  if (late && !whole()) ++*late;
+  return sim3_spin_until(c, whole, deadline, failure);
+}
+
 // one evaluation = calcSim3Buffers + calcSim3WeightsAndResidualSSE + calcSim3LGSSSE at one transformation.
 // Description of the evaluation for batch slot `slot`:
 static int sim3_build_job(lsdhip_sim3tracker* t, int slot, lsdhip_frame* kf, lsdhip_frame* frame, const Sim3H& referenceToFrame, int level,
                           float aff_a, float aff_b, Sim3Job* out) {
-  lsdhip_ctx* c = t->ctx;
-  LSD_CTX_LOCK(c);
+  LSD_CTX_LOCK(t->ctx);
+  if (level == 0) { if (int rc = sim3_require_level0(kf, frame)) return rc; }
   Sim3Job a;
-  if (level == 0) {   // level-0 texels on demand
-    if (int rc = lsd_frame_require_level0_for_tracking(kf)) return rc;
-    if (int rc = lsd_frame_require_level0_for_tracking(frame)) return rc;
-  }
-  a.kf_idepth = kf->d_idepth[level]; a.kf_idepthVar = kf->d_idepthVar[level]; a.kf_image = kf->d_image[level]; a.kf_grad = kf->d_grad[level];
-  a.fr_grad = frame->d_grad[level]; a.fr_idepth = frame->d_idepth[level]; a.fr_idepthVar = frame->d_idepthVar[level];
-  a.w = c->wl[level]; a.h = c->hl[level];
-  sim3_strips(a.w * a.h, &a.nblocks, &a.ppl);
-  const LevelIntr& in = c->intr[level];
-  a.fx = in.fx; a.fy = in.fy; a.cx = in.cx; a.cy = in.cy; a.fxi = in.fxi; a.fyi = in.fyi; a.cxi = in.cxi; a.cyi = in.cyi;
-  double Rd[9];
-  lsdm::quatd_to_rot(referenceToFrame.q, Rd);
-  float Ru[9];
-  for (int i = 0; i < 9; i++) { a.R[i] = (float)(referenceToFrame.s * Rd[i]); Ru[i] = (float)Rd[i]; }
-  for (int i = 0; i < 3; i++) a.t[i] = (float)referenceToFrame.t[i];
-  {
-    // Quaternionf::setFromTwoVectors(R * (0,0,-1), (0,0,-1)).toRotationMatrix() * R   (Sim3Tracker.cpp:455-464)
-    const float rf[3] = {Ru[0] * 0.f + Ru[1] * 0.f + Ru[2] * -1.f, Ru[3] * 0.f + Ru[4] * 0.f + Ru[5] * -1.f, Ru[6] * 0.f + Ru[7] * 0.f + Ru[8] * -1.f};
-    const float n0 = sqrtf(rf[0] * rf[0] + (rf[1] * rf[1] + rf[2] * rf[2]));
-    const float v0[3] = {rf[0] / n0, rf[1] / n0, rf[2] / n0};
-    const float v1[3] = {0, 0, -1};
-    const float cdot = v1[0] * v0[0] + (v1[1] * v0[1] + v1[2] * v0[2]);
-    lsdm::Quatf q;
-    if (cdot < -1.0f + 1e-5f) {
-      q = {0, 1, 0, 0};
-    } else {
-      const float ax = v0[1] * v1[2] - v0[2] * v1[1], ay = v0[2] * v1[0] - v0[0] * v1[2], az = v0[0] * v1[1] - v0[1] * v1[0];
-      const float s = sqrtf((1.0f + cdot) * 2.0f);
-      const float invs = 1.0f / s;
-      q = {s * 0.5f, ax * invs, ay * invs, az * invs};
-    }
-    float Q[9];
-    lsdm::quatf_to_rot(q, Q);
-    float roll[9];
-    for (int i = 0; i < 3; i++)
-      for (int j = 0; j < 3; j++) {
-        float acc = Q[i * 3 + 0] * Ru[0 * 3 + j];
-        acc += Q[i * 3 + 1] * Ru[1 * 3 + j];
-        acc += Q[i * 3 + 2] * Ru[2 * 3 + j];
-        roll[i * 3 + j] = acc;
-      }
-    a.xRoll0 = roll[0]; a.xRoll1 = roll[1]; a.yRoll0 = roll[3]; a.yRoll1 = roll[4];
-  }
+  static_cast<Sim3Lvl&>(a) = sim3_level(t, kf, frame, level);
+  float roll[4];
+  sim3_request_of(referenceToFrame, a.R, a.t, roll);
+  a.xRoll0 = roll[0]; a.xRoll1 = roll[1]; a.yRoll0 = roll[2]; a.yRoll1 = roll[3];
   a.aff_a = aff_a; a.aff_b = aff_b;
-  a.cameraPixelNoise2 = c->params.cameraPixelNoise2; a.var_weight = t->var_weight; a.huber_d = t->huber_d;
-  a.rows = t->d_rows + (size_t)slot * S3_NBMAX * 64;
-  a.topkey = t->d_topkey + (size_t)slot * S3_NBMAX;
+  sim3_noise(t, a);
+  sim3_scratch(t, slot, 0, &a.rows, &a.topkey);
   a.record = t->d_record + (size_t)slot * 64;
   a.seq = 0;
   *out = a;
@@ -631,35 +696,21 @@ static int sim3_run_batch(lsdhip_sim3tracker* t, Sim3Batch& batch, int nslots) {
   hipLaunchKernelGGL(k_sim3_eval, dim3(grid, nslots), dim3(S3_BLOCK), 0, c->stream, batch);
   hipLaunchKernelGGL(k_sim3_finalize, dim3(1, nslots), dim3(256), 0, c->stream, batch);
   HIPCHK(hipGetLastError());
-  const auto tStart = std::chrono::steady_clock::now();
+  const Sim3Deadline deadline = sim3_deadline(S3_EVAL_WAIT_S);
   for (int k = 0; k < nslots; k++) {
     if (batch.j[k].nblocks <= 0) continue;
-    volatile const unsigned* rec = (volatile const unsigned*)(t->h_record + (size_t)k * 64);
-    // word 63 = seq + position-weighted sum of the words before it (k_sim3_finalize): whole record or nothing
-    auto landed = [&]() { unsigned chk = (unsigned)seq; for (unsigned i = 0; i < 63; i++) chk += lsd_summary_term(i, rec[i]); return rec[63] == chk; };
-    unsigned spins = 0;
-    while (!landed()) {
-      if ((++spins & 0xFFFFFu) == 0) {   // safety net only: a stream query puts a marker packet into the queue (profiles/r03_notes.md §2b)
-        hipError_t q = hipStreamQuery(c->stream);
-        if (q != hipSuccess && q != hipErrorNotReady) { lsd_set_error("hipStreamQuery failed: %s", hipGetErrorString(q)); return LSDHIP_E_HIP; }
-        if (std::chrono::steady_clock::now() - tStart > std::chrono::seconds(5)) { HIPCHK(hipStreamSynchronize(c->stream)); break; }
-      }
-      __builtin_ia32_pause();
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    if (!landed()) { lsd_set_error("Sim3 evaluation did not complete"); return LSDHIP_E_STATE; }
+    const float* rec = t->h_record + (size_t)k * 64;      // word 63 = seq + the weighted sum of the 63 words before it (k_sim3_finalize)
+    if (int rc = sim3_wait_record(c, rec, 63, (unsigned)seq, rec + 63, deadline, "Sim3 evaluation did not complete")) return rc;
   }
   return LSDHIP_OK;
 }
-static void sim3_read_eval(lsdhip_sim3tracker* t, int slot, Eval* ev) { sim3_eval_from_totals(t->h_record + (size_t)slot * 64, ev); }
 
 static Sim3H sim3_in(const double p[8]) { Sim3H T; T.q = {p[0], p[1], p[2], p[3]}; T.t[0] = p[4]; T.t[1] = p[5]; T.t[2] = p[6]; T.s = p[7]; return T; }
-static void sim3_out(const Sim3H& T, double p[8]) { p[0] = T.q.w; p[1] = T.q.x; p[2] = T.q.y; p[3] = T.q.z; p[4] = T.t[0]; p[5] = T.t[1]; p[6] = T.t[2]; p[7] = T.s; }
 
 // host-side algebra of the LM step, exported for CPU tests of the product's own arithmetic (no device involved)
 extern "C" int lsdhip_host_sim3_step(const double increment[7], const double referenceToFrame[8], double out[8]) {
   if (!increment || !referenceToFrame || !out) return LSDHIP_E_ARG;
-  sim3_out(sim3_mul(sim3_exp(increment), sim3_in(referenceToFrame)), out);
+  sim3_out8(sim3_mul(sim3_exp(increment), sim3_in(referenceToFrame)), out);
   return LSDHIP_OK;
 }
 extern "C" int lsdhip_host_ldlt7(const float A[49], const float b[7], float x[7]) {
@@ -671,8 +722,8 @@ extern "C" int lsdhip_host_ldlt7(const float A[49], const float b[7], float x[7]
 
 extern "C" int lsdhip_sim3tracker_evaluate(lsdhip_sim3tracker* t, lsdhip_frame* kf, lsdhip_frame* frame, const double refToFrame[8], int level,
                                            float aff_a, float aff_b, lsdhip_sim3_eval_record* out) {
-  if (!t || !kf || !frame || !refToFrame || !out || level < 0 || level >= LSD_LEVELS) return LSDHIP_E_ARG;
-  if (!kf->hasIDepth || !frame->hasIDepth) { lsd_set_error("Sim3 tracking needs inverse depth on both frames"); return LSDHIP_E_STATE; }
+  if (!t || !kf || !frame || !refToFrame || !out || sim3_check_levels(level, level)) return LSDHIP_E_ARG;
+  if (int rc = sim3_check_pair(kf, frame)) return rc;
   HIPCHK(hipSetDevice(t->ctx->device));
   Sim3Batch batch;
   memset(&batch, 0, sizeof(batch));
@@ -681,7 +732,7 @@ extern "C" int lsdhip_sim3tracker_evaluate(lsdhip_sim3tracker* t, lsdhip_frame* 
   rc = sim3_run_batch(t, batch, 1);
   if (rc) return rc;
   Eval ev;
-  sim3_read_eval(t, 0, &ev);
+  sim3_eval_from_totals(t->h_record, &ev);
   out->warped_size = ev.M; out->pointUsage = ev.pointUsage; out->affine_a_lastIt = ev.aff_a_lastIt; out->affine_b_lastIt = ev.aff_b_lastIt;
   out->sumResD = ev.res.sumResD; out->sumResP = ev.res.sumResP; out->numTermsD = ev.res.numTermsD; out->numTermsP = ev.res.numTermsP;
   out->meanD = ev.res.meanD; out->meanP = ev.res.meanP; out->mean = ev.res.mean;
@@ -724,40 +775,8 @@ struct Sim3Track {                  // plain data: lives in HBM between the laun
 static_assert(sizeof(Sim3Track) % 4 == 0, "copied by words");
 struct Sim3Scratch { float inc[7]; int solve; float m[7][8]; Sim3Trig trig; };
 
-// the requested transformation as the evaluation kernel wants it: rxso3().matrix() and translation in float, the in-plane roll of the
-// reference gradients (ESM, Sim3Tracker.cpp:455-464)
-S3_HD void sim3_request(Sim3Track& J) {
-  const Sim3H& T = J.reqPose;
-  double Rd[9];
-  lsdm::quatd_to_rot(T.q, Rd);
-  float Ru[9];
-  for (int i = 0; i < 9; i++) { J.reqR[i] = (float)(T.s * Rd[i]); Ru[i] = (float)Rd[i]; }
-  for (int i = 0; i < 3; i++) J.reqT[i] = (float)T.t[i];
-  // Quaternionf::setFromTwoVectors(R * (0,0,-1), (0,0,-1)).toRotationMatrix() * R
-  const float rf[3] = {Ru[0] * 0.f + Ru[1] * 0.f + Ru[2] * -1.f, Ru[3] * 0.f + Ru[4] * 0.f + Ru[5] * -1.f, Ru[6] * 0.f + Ru[7] * 0.f + Ru[8] * -1.f};
-  const float n0 = sqrtf(rf[0] * rf[0] + (rf[1] * rf[1] + rf[2] * rf[2]));
-  const float v0[3] = {rf[0] / n0, rf[1] / n0, rf[2] / n0};
-  const float v1[3] = {0, 0, -1};
-  const float cdot = v1[0] * v0[0] + (v1[1] * v0[1] + v1[2] * v0[2]);
-  lsdm::Quatf q;
-  if (cdot < -1.0f + 1e-5f) {
-    q = {0, 1, 0, 0};
-  } else {
-    const float ax = v0[1] * v1[2] - v0[2] * v1[1], ay = v0[2] * v1[0] - v0[0] * v1[2], az = v0[0] * v1[1] - v0[1] * v1[0];
-    const float sq = sqrtf((1.0f + cdot) * 2.0f);
-    const float invs = 1.0f / sq;
-    q = {sq * 0.5f, ax * invs, ay * invs, az * invs};
-  }
-  float Q[9];
-  lsdm::quatf_to_rot(q, Q);
-  // rows 0 and 1, columns 0 and 1 of Q * R
-  J.reqRoll[0] = (Q[0] * Ru[0] + Q[1] * Ru[3]) + Q[2] * Ru[6];
-  J.reqRoll[1] = (Q[0] * Ru[1] + Q[1] * Ru[4]) + Q[2] * Ru[7];
-  J.reqRoll[2] = (Q[3] * Ru[0] + Q[4] * Ru[3]) + Q[5] * Ru[6];
-  J.reqRoll[3] = (Q[3] * Ru[1] + Q[4] * Ru[4]) + Q[5] * Ru[7];
-}
-
-S3_HD void sim3_out8(const Sim3H& T, double p[8]) { p[0] = T.q.w; p[1] = T.q.x; p[2] = T.q.y; p[3] = T.q.z; p[4] = T.t[0]; p[5] = T.t[1]; p[6] = T.t[2]; p[7] = T.s; }
+// the evaluation this job waits for, as the strips read it
+S3_HD void sim3_request(Sim3Track& J) { sim3_request_of(J.reqPose, J.reqR, J.reqT, J.reqRoll); }
 S3_HD void sim3_finish(Sim3Track& J) {
   lsdhip_sim3_result* out = &J.res;
   for (int i = 0; i < 49; i++) out->lastSim3Hessian[i] = J.cur.A[i];
@@ -873,12 +892,6 @@ S3_HD void sim3_advance(const Sim3LM& P, Sim3Track& J, const Eval& ev, Sim3Scrat
 }  // namespace
 
 // ---- the job on the device ---------------------------------------------------------------------------------------------------------
-struct Sim3Lvl {                  // what does not change during a job, per pyramid level
-  const float* kf_idepth; const float* kf_idepthVar; const float* kf_image; const float4* kf_grad;
-  const float4* fr_grad; const float* fr_idepth; const float* fr_idepthVar;
-  int w, h, nblocks, ppl;
-  float fx, fy, cx, cy, fxi, fyi, cxi, cyi;
-};
 struct Sim3Set {
   Sim3Lvl lv[LSD_LEVELS];
   float cameraPixelNoise2, var_weight, huber_d;
@@ -888,11 +901,7 @@ struct Sim3Set {
   int seq;                        // ends with the job unfinished (the host then queues another budget)
 };
 __device__ __forceinline__ void sim3_job_view(const Sim3Set& set, const Sim3Track& J, const int parity, Sim3Job& a) {
-  const Sim3Lvl& L = set.lv[J.reqLevel];
-  a.kf_idepth = L.kf_idepth; a.kf_idepthVar = L.kf_idepthVar; a.kf_image = L.kf_image; a.kf_grad = L.kf_grad;
-  a.fr_grad = L.fr_grad; a.fr_idepth = L.fr_idepth; a.fr_idepthVar = L.fr_idepthVar;
-  a.w = L.w; a.h = L.h; a.nblocks = L.nblocks; a.ppl = L.ppl;
-  a.fx = L.fx; a.fy = L.fy; a.cx = L.cx; a.cy = L.cy; a.fxi = L.fxi; a.fyi = L.fyi; a.cxi = L.cxi; a.cyi = L.cyi;
+  static_cast<Sim3Lvl&>(a) = set.lv[J.reqLevel];
 #pragma unroll
   for (int i = 0; i < 9; i++) a.R[i] = J.reqR[i];
 #pragma unroll
@@ -1093,22 +1102,42 @@ __global__ __launch_bounds__(S3_BLOCK) void k_sim3_fused(const Sim3Set* __restri
   S3_MARK(7);
 }
 
-// the device-side job storage of a tracker (first trackFrameSim3 call)
-static int sim3_device_storage(lsdhip_sim3tracker* t) {
-  if (t->d_sets) return LSDHIP_OK;
-  // one block on each side — [S3_MAXB] level descriptions, then the states ([2][S3_MAXB] on the device) — so that a call uploads both in one copy
-  static_assert((sizeof(Sim3Set) * S3_MAXB) % alignof(Sim3Track) == 0, "the states behind the level descriptions keep their alignment");
-  uint8_t *dblk = nullptr, *hblk = nullptr;
-  HIPCHK(hipMalloc((void**)&dblk, sizeof(Sim3Set) * S3_MAXB + sizeof(Sim3Track) * S3_MAXB * 2));
-  HIPCHK(hipHostMalloc((void**)&hblk, sizeof(Sim3Set) * S3_MAXB + sizeof(Sim3Track) * S3_MAXB, hipHostMallocDefault));
-  t->d_sets = (Sim3Set*)dblk; t->d_states = (Sim3Track*)(dblk + sizeof(Sim3Set) * S3_MAXB);
-  t->h_sets = (Sim3Set*)hblk; t->h_states = (Sim3Track*)(hblk + sizeof(Sim3Set) * S3_MAXB);
-  HIPCHK(hipHostMalloc((void**)&t->h_results, sizeof(lsdhip_sim3_result) * S3_MAXB, hipHostMallocMapped));
+// ---- the tracker's storage -------------------------------------------------------------------------------------------------------
+// What a chunk of jobs uploads, one block on each side so that one copy carries both: [S3_MAXB] level descriptions, then the jobs' states
+// ([S3_MAXB] in the pinned staging block, [2][S3_MAXB] on the device: launch parities)
+static_assert((sizeof(Sim3Set) * S3_MAXB) % alignof(Sim3Track) == 0, "the states behind the level descriptions keep their alignment");
+static size_t sim3_block_bytes(int nstates) { return sizeof(Sim3Set) * S3_MAXB + sizeof(Sim3Track) * (size_t)nstates; }
+static Sim3Track* sim3_block_states(Sim3Set* sets) { return (Sim3Track*)(sets + S3_MAXB); }
+// The evaluation scratch and record of every tracker; with `tracking` also the job storage of trackFrameSim3 (made by the first such call).
+// Every allocation is behind its own pointer, so a call that failed half-way is repeated or released without a leak.
+static int sim3_storage_reserve(lsdhip_sim3tracker* t, bool tracking) {
+  if (tracking ? t->d_done != nullptr : t->d_record != nullptr) return LSDHIP_OK;
+  const size_t mb = (size_t)S3_NBMAX * S3_MAXB * 2;
+  if (!t->d_rows) HIPCHK(hipMalloc((void**)&t->d_rows, mb * 64 * 4));
+  if (!t->d_topkey) HIPCHK(hipMalloc((void**)&t->d_topkey, mb * 16));
+  if (!t->h_record) {
+    HIPCHK(hipHostMalloc((void**)&t->h_record, S3_MAXB * 64 * 4, hipHostMallocMapped));
+    memset(t->h_record, 0, S3_MAXB * 64 * 4);
+  }
+  HIPCHK(hipHostGetDevicePointer((void**)&t->d_record, t->h_record, 0));
+  if (!tracking) return LSDHIP_OK;
+  if (!t->d_sets) HIPCHK(hipMalloc((void**)&t->d_sets, sim3_block_bytes(2 * S3_MAXB)));
+  if (!t->h_sets) HIPCHK(hipHostMalloc((void**)&t->h_sets, sim3_block_bytes(S3_MAXB), hipHostMallocDefault));
+  t->d_states = sim3_block_states(t->d_sets); t->h_states = sim3_block_states(t->h_sets);
+  if (!t->h_results) HIPCHK(hipHostMalloc((void**)&t->h_results, sizeof(lsdhip_sim3_result) * S3_MAXB, hipHostMallocMapped));
   HIPCHK(hipHostGetDevicePointer((void**)&t->d_results, t->h_results, 0));
-  HIPCHK(hipHostMalloc((void**)&t->h_done, sizeof(int) * S3_MAXB * 2, hipHostMallocMapped));   // [k]: flag, [S3_MAXB + k]: check word of result k
-  memset(t->h_done, 0, sizeof(int) * S3_MAXB * 2);
+  if (!t->h_done) {   // [k]: flag, [S3_MAXB + k]: check word of result k
+    HIPCHK(hipHostMalloc((void**)&t->h_done, sizeof(int) * S3_MAXB * 2, hipHostMallocMapped));
+    memset(t->h_done, 0, sizeof(int) * S3_MAXB * 2);
+  }
   HIPCHK(hipHostGetDevicePointer((void**)&t->d_done, t->h_done, 0));
   return LSDHIP_OK;
+}
+// ... and the tracker itself (the d_* of pinned blocks are aliases)
+static void sim3_storage_release(lsdhip_sim3tracker* t) {
+  (void)hipFree(t->d_rows); (void)hipFree(t->d_topkey); (void)hipHostFree(t->h_record);
+  (void)hipFree(t->d_sets); (void)hipHostFree(t->h_sets); (void)hipHostFree(t->h_results); (void)hipHostFree(t->h_done);
+  delete t;
 }
 static Sim3LM sim3_lm_params(const lsdhip_sim3tracker* t) {
   Sim3LM P;
@@ -1118,190 +1147,154 @@ static Sim3LM sim3_lm_params(const lsdhip_sim3tracker* t) {
   P.useAffine = t->ctx->params.useAffineLightningEstimation; P.w = t->ctx->w; P.h = t->ctx->h;
   return P;
 }
-// n independent trackFrameSim3 jobs: their states and level descriptions go to the device, a budget of (evaluation, step) launch pairs is
-// queued — every pair advances all unfinished jobs by one evaluation (at most S3_MAXB jobs per launch) —, the host waits for the jobs'
-// `done` words (pinned) and tops the budget up if some job needs more
-static int sim3_track_jobs(lsdhip_sim3tracker* t, std::vector<Sim3Track>& jobs, const std::vector<std::pair<lsdhip_frame*, lsdhip_frame*>>& frames) {
+
+// ---- trackFrameSim3 jobs, a chunk of at most S3_MAXB at a time (job k of the chunk in batch slot k) -----------------------------------
+// the done word of a job: seq * 256 + ...
+static int sim3_done_word(int seq, int what) { return seq * 256 + what; }
+// Describe: the chunk's level descriptions and states in the staging block.  *grid: strips of the finest level any unfinished job will
+// reach, *pending: unfinished jobs (a job with no level that has iterations is finished before any evaluation).
+static int sim3_describe_chunk(lsdhip_sim3tracker* t, Sim3Track* jobs, lsdhip_frame* const* kfs, lsdhip_frame* const* frames, int m, int seq,
+                               int* grid, int* pending) {
+  *grid = *pending = 0;
+  for (int k = 0; k < m; k++) {
+    Sim3Track& J = jobs[k];
+    Sim3Set& S = t->h_sets[k];
+    if (int rc = sim3_require_level0(kfs[k], frames[k])) return rc;
+    for (int l = 0; l < LSD_LEVELS; l++) S.lv[l] = sim3_level(t, kfs[k], frames[k], l);
+    sim3_noise(t, S);
+    for (int par = 0; par < 2; par++) sim3_scratch(t, k, par, &S.rows[par], &S.topkey[par]);
+    S.result = t->d_results + k;     // pinned, written by the device when the job ends
+    S.done = t->d_done + k;
+    S.seq = seq;
+    if (J.phase != Sim3Track::DONE) {
+      sim3_request(J);
+      ++*pending;
+      *grid = std::max(*grid, S.lv[J.finalLevel].nblocks);
+    }
+    J.pendingEval = 0;
+    t->h_states[k] = J;
+  }
+  return LSDHIP_OK;
+}
+// Run: a budget of launches is queued — every launch advances all unfinished jobs by one evaluation; evaluations + 1 launches end a job —,
+// the host waits for the jobs' done words and tops the budget up while some job needs more.  Every pending job raises its word when it
+// finishes or when the budget's last launch leaves it unfinished.
+static int sim3_run_budgets(lsdhip_sim3tracker* t, const Sim3LM& P, const Sim3Track* jobs, int m, int seq, int grid) {
+  lsdhip_ctx* c = t->ctx;
+  int budget = t->recentRounds > 0 ? t->recentRounds + 3 : 24, parity = 0;
+  for (int b = 0; b < 250; b++, budget = 8) {
+    for (int i = 0; i < budget; i++, parity ^= 1)
+      hipLaunchKernelGGL(k_sim3_fused, dim3(grid, m), dim3(S3_BLOCK), 0, c->stream, (const Sim3Set*)t->d_sets, t->d_states, P, parity,
+                         i == budget - 1 ? b : -1, b == 0 ? i : -1);
+    HIPCHK(hipGetLastError());
+    const Sim3Deadline deadline = sim3_deadline(S3_FLAG_WAIT_S);
+    bool unfinished = false;
+    for (int k = 0; k < m; k++) {
+      if (jobs[k].phase == Sim3Track::DONE) continue;
+      volatile const int* flag = t->h_done + k;
+      int v;
+      auto settled = [&]() { v = *flag; return v == sim3_done_word(seq, 255) || v == sim3_done_word(seq, 254) || v == sim3_done_word(seq, b); };
+      if (int rc = sim3_spin_until(c, settled, deadline, "Sim3 tracking did not complete")) return rc;
+      if (v == sim3_done_word(seq, b)) unfinished = true;
+    }
+    if (!unfinished) return LSDHIP_OK;
+  }
+  lsd_set_error("Sim3 tracking did not terminate");
+  return LSDHIP_E_STATE;
+}
+// Collect: the pinned records the device wrote before it raised the words (launches of the budget still queued behind a job's end leave
+// at once; the stream orders them before whatever comes next).  A record is taken once it is whole under the job's done word.
+static int sim3_collect_chunk(lsdhip_sim3tracker* t, Sim3Track* jobs, int m, int seq) {
+  int rounds = 0;
+  for (int k = 0; k < m; k++) {
+    Sim3Track& J = jobs[k];
+    if (J.phase == Sim3Track::DONE) continue;             // finished before any evaluation
+    const int word = ((volatile const int*)t->h_done)[k];
+    if (int rc = sim3_wait_record(t->ctx, &t->h_results[k], sizeof(lsdhip_sim3_result) / 4, (unsigned)word, t->h_done + S3_MAXB + k,
+                                  sim3_deadline(S3_RESULT_WAIT_S), "Sim3 result record in pinned memory never became consistent", &t->lateRecords))
+      return rc;
+    *J.hostOut = t->h_results[k];
+    J.rc = word == sim3_done_word(seq, 255) ? LSDHIP_OK : LSDHIP_DIVERGED;
+    J.phase = Sim3Track::DONE;
+    rounds = std::max(rounds, J.hostOut->numEvaluations);
+  }
+  t->recentRounds = rounds;
+  return LSDHIP_OK;
+}
+#ifdef LSD_DEVTOOLS
+// LSDHIP_S3_TRACE=1: where the launches of the chunk's first budget spent their time
+static int sim3_print_trace(lsdhip_sim3tracker* t) {
+  if (!getenv("LSDHIP_S3_TRACE")) return LSDHIP_OK;
+  HIPCHK(hipStreamSynchronize(t->ctx->stream));
+  static unsigned long long h[64][8];
+  HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_s3trace), sizeof(h)));
+  const char* names[7] = {"state", "totals", "system+advance", "solve", "finish+request", "publish", "strip"};
+  double sum[8] = {0}; int cnt = 0; double span = 0;
+  for (int i = 1; i + 1 < t->recentRounds && i < 63; i++) {     // launches with a pending evaluation and a strip of their own
+    for (int k = 0; k < 7; k++) sum[k] += (double)(h[i][k + 1] - h[i][k]) * 0.01;
+    span += (double)(h[i + 1][0] - h[i][0]) * 0.01;
+    cnt++;
+  }
+  if (cnt) {
+    fprintf(stderr, "[s3trace] %d launches, start-to-start %.2f us:", cnt, span / cnt);
+    for (int k = 0; k < 7; k++) fprintf(stderr, " %s %.2f", names[k], sum[k] / cnt);
+    fprintf(stderr, " (us, workgroup 0 of job 0)\n");
+  }
+  return LSDHIP_OK;
+}
+#endif
+// n independent trackFrameSim3 jobs: per chunk describe, upload (one copy), run, collect
+static int sim3_track_jobs(lsdhip_sim3tracker* t, const Sim3LM& P, int n, Sim3Track* jobs, lsdhip_frame* const* kfs, lsdhip_frame* const* frames) {
   lsdhip_ctx* c = t->ctx;
   LSD_CTX_LOCK(c);
-  const int n = (int)jobs.size();
-  const Sim3LM P = sim3_lm_params(t);
   LsdTrackJobScope tjob_(c, true);   // pipelined contexts: behind the mapping stream's products, and a record point for it afterwards
   if (tjob_.rc) return tjob_.rc;
-  { int rc = sim3_device_storage(t); if (rc) return rc; }
+  if (int rc = sim3_storage_reserve(t, true)) return rc;
   for (int base = 0; base < n; base += S3_MAXB) {
     const int m = std::min(S3_MAXB, n - base);
     const int seq = t->seq = (t->seq % 0x3FFFFF) + 1;
-    int grid = 0, pending = 0;
-    for (int k = 0; k < m; k++) {
-      Sim3Track& J = jobs[base + k];
-      Sim3Set& S = t->h_sets[k];
-      for (int l = 0; l < LSD_LEVELS; l++) {
-        Sim3Lvl& L = S.lv[l];
-        lsdhip_frame* kf = frames[base + k].first;
-        lsdhip_frame* fr = frames[base + k].second;
-        if (l == 0) {
-          if (int rc = lsd_frame_require_level0_for_tracking(kf)) return rc;
-          if (int rc = lsd_frame_require_level0_for_tracking(fr)) return rc;
-        }
-        L.kf_idepth = kf->d_idepth[l]; L.kf_idepthVar = kf->d_idepthVar[l]; L.kf_image = kf->d_image[l]; L.kf_grad = kf->d_grad[l];
-        L.fr_grad = fr->d_grad[l]; L.fr_idepth = fr->d_idepth[l]; L.fr_idepthVar = fr->d_idepthVar[l];
-        L.w = c->wl[l]; L.h = c->hl[l];
-        sim3_strips(L.w * L.h, &L.nblocks, &L.ppl);
-        const LevelIntr& in = c->intr[l];
-        L.fx = in.fx; L.fy = in.fy; L.cx = in.cx; L.cy = in.cy; L.fxi = in.fxi; L.fyi = in.fyi; L.cxi = in.cxi; L.cyi = in.cyi;
-        if (l == J.finalLevel && J.phase != Sim3Track::DONE && L.nblocks > grid) grid = L.nblocks;
-      }
-      S.cameraPixelNoise2 = c->params.cameraPixelNoise2; S.var_weight = t->var_weight; S.huber_d = t->huber_d;
-      for (int par = 0; par < 2; par++) {
-        S.rows[par] = t->d_rows + ((size_t)par * S3_MAXB + k) * S3_NBMAX * 64;
-        S.topkey[par] = t->d_topkey + ((size_t)par * S3_MAXB + k) * S3_NBMAX;
-      }
-      S.result = t->d_results + k;     // pinned, written by the device when the job ends
-      S.done = t->d_done + k;
-      S.seq = seq;
-      if (J.phase != Sim3Track::DONE) { sim3_request(J); pending++; }
-      J.pendingEval = 0;
-      t->h_states[k] = J;
-    }
+    int grid, pending;
+    if (int rc = sim3_describe_chunk(t, jobs + base, kfs + base, frames + base, m, seq, &grid, &pending)) return rc;
     if (!pending) continue;
-    HIPCHK(hipMemcpyAsync(t->d_sets, t->h_sets, sizeof(Sim3Set) * S3_MAXB + sizeof(Sim3Track) * (size_t)m, hipMemcpyHostToDevice, c->stream));
-    int budget = t->recentRounds > 0 ? t->recentRounds + 3 : 24, parity = 0;   // evaluations + 1 launches end a job
-    for (int b = 0;; b++) {
-      if (b >= 250) { lsd_set_error("Sim3 tracking did not terminate"); return LSDHIP_E_STATE; }
-      for (int i = 0; i < budget; i++, parity ^= 1)
-        hipLaunchKernelGGL(k_sim3_fused, dim3(grid, m), dim3(S3_BLOCK), 0, c->stream, (const Sim3Set*)t->d_sets, t->d_states, P, parity,
-                           i == budget - 1 ? b : -1, b == 0 ? i : -1);
-      HIPCHK(hipGetLastError());
-      // every pending job raises its word when it finishes or when the budget's last step leaves it unfinished; no stream query in
-      // the wait (each one puts a marker packet into the queue the chain runs through) but as a safety net
-      const auto tStart = std::chrono::steady_clock::now();
-      bool unfinished = false;
-      for (int k = 0; k < m; k++) {
-        if (jobs[base + k].phase == Sim3Track::DONE) continue;
-        volatile const int* flag = (volatile const int*)t->h_done + k;
-        unsigned spins = 0;
-        int v;
-        auto settled = [&](int x) { return x == seq * 256 + 255 || x == seq * 256 + 254 || x == seq * 256 + b; };
-        while (!settled(v = *flag)) {
-          if ((++spins & 0xFFFFFu) == 0) {
-            hipError_t q = hipStreamQuery(c->stream);
-            if (q != hipSuccess && q != hipErrorNotReady) { lsd_set_error("hipStreamQuery failed: %s", hipGetErrorString(q)); return LSDHIP_E_HIP; }
-            if (std::chrono::steady_clock::now() - tStart > std::chrono::seconds(10)) {
-              HIPCHK(hipStreamSynchronize(c->stream));
-              if (!settled(v = *flag)) { lsd_set_error("Sim3 tracking did not complete"); return LSDHIP_E_STATE; }
-              break;
-            }
-          }
-          __builtin_ia32_pause();
-        }
-        if (v == seq * 256 + b) unfinished = true;
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      if (!unfinished) break;
-      budget = 8;
-    }
-    // results: the pinned records the device wrote before it raised the words (launches of the budget still queued behind a job's end
-    // leave at once; the stream orders them before whatever comes next)
-    int rounds = 0;
-    for (int k = 0; k < m; k++) {
-      Sim3Track& J = jobs[base + k];
-      if (J.phase == Sim3Track::DONE) continue;             // finished before any evaluation (no level with iterations)
-      {
-        // the record is taken once its words add up to the check word the device stored with it (they are separate posted writes: the
-        // flag has been seen to overtake the tail of such a record, profiles/r06_notes.md section 1)
-        const unsigned word = (unsigned)((volatile int*)t->h_done)[k];
-        volatile const unsigned* rw = (volatile const unsigned*)&t->h_results[k];
-        const auto tv0 = std::chrono::steady_clock::now();
-        for (unsigned spins = 0;; spins++) {
-          unsigned chk = word;
-          for (unsigned i = 0; i < (unsigned)(sizeof(lsdhip_sim3_result) / 4); i++) chk += lsd_summary_term(i, rw[i]);
-          if (chk == ((volatile unsigned*)t->h_done)[S3_MAXB + k]) break;
-          if (spins == 0) t->lateRecords++;
-          if ((spins & 0xFFFFu) == 0xFFFFu && std::chrono::steady_clock::now() - tv0 > std::chrono::seconds(2)) {
-            lsd_set_error("Sim3 result record in pinned memory never became consistent"); return LSDHIP_E_STATE;
-          }
-          __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-      }
-      *J.hostOut = t->h_results[k];
-      J.rc = ((volatile int*)t->h_done)[k] == seq * 256 + 255 ? LSDHIP_OK : LSDHIP_DIVERGED;
-      J.phase = Sim3Track::DONE;
-      if (J.hostOut->numEvaluations > rounds) rounds = J.hostOut->numEvaluations;
-    }
-    t->recentRounds = rounds;
+    HIPCHK(hipMemcpyAsync(t->d_sets, t->h_sets, sim3_block_bytes(m), hipMemcpyHostToDevice, c->stream));
+    if (int rc = sim3_run_budgets(t, P, jobs + base, m, seq, grid)) return rc;
+    if (int rc = sim3_collect_chunk(t, jobs + base, m, seq)) return rc;
 #ifdef LSD_DEVTOOLS
-    if (getenv("LSDHIP_S3_TRACE")) {
-      HIPCHK(hipStreamSynchronize(c->stream));
-      static unsigned long long h[64][8];
-      HIPCHK(hipMemcpyFromSymbol(h, HIP_SYMBOL(g_s3trace), sizeof(h)));
-      const char* names[7] = {"state", "totals", "system+advance", "solve", "finish+request", "publish", "strip"};
-      double sum[8] = {0}; int cnt = 0; double span = 0;
-      for (int i = 1; i + 1 < rounds && i < 63; i++) {     // launches with a pending evaluation and a strip of their own
-        for (int k = 0; k < 7; k++) sum[k] += (double)(h[i][k + 1] - h[i][k]) * 0.01;
-        span += (double)(h[i + 1][0] - h[i][0]) * 0.01;
-        cnt++;
-      }
-      if (cnt) {
-        fprintf(stderr, "[s3trace] %d launches, start-to-start %.2f us:", cnt, span / cnt);
-        for (int k = 0; k < 7; k++) fprintf(stderr, " %s %.2f", names[k], sum[k] / cnt);
-        fprintf(stderr, " (us, workgroup 0 of job 0)\n");
-      }
-    }
+    if (int rc = sim3_print_trace(t)) return rc;
 #endif
   }
   return LSDHIP_OK;
 }
-static int sim3_init_job(lsdhip_sim3tracker* t, Sim3Track& J, lsdhip_frame* kf, lsdhip_frame* frame, const double init[8], int startLevel,
-                         int finalLevel, lsdhip_sim3_result* out) {
-  if (!kf || !frame || !init || !out) return LSDHIP_E_ARG;
-  if (!kf->hasIDepth || !frame->hasIDepth) { lsd_set_error("Sim3 tracking needs inverse depth on both frames"); return LSDHIP_E_STATE; }
+// a job before its first evaluation (the pair and the levels have been checked)
+static void sim3_init_job(const Sim3LM& P, Sim3Track& J, const double init[8], int startLevel, int finalLevel, lsdhip_sim3_result* out) {
   memset(out, 0, sizeof(*out));
   out->frameToReference[0] = 1; out->frameToReference[7] = 1;   // Sim3() on failure
   memset(&J, 0, sizeof(J));
   J.res = *out; J.hostOut = out;
   J.phase = Sim3Track::DONE;
+  J.rc = LSDHIP_OK;
   J.aff_a = 1; J.aff_b = 0;
   J.referenceToFrame = sim3_inverse(sim3_in(init));
-  memset(&J.cur, 0, sizeof(J.cur));
-  memset(&J.finalResidual, 0, sizeof(J.finalResidual));
-  memset(&J.lastErr, 0, sizeof(J.lastErr));
-  J.warp_update_up_to_date = 0;
-  J.numEvaluations = 0;
   J.lvl = startLevel; J.finalLevel = finalLevel;
-  J.rc = LSDHIP_OK;
-  sim3_next_level(sim3_lm_params(t), J);
+  sim3_next_level(P, J);
   if (J.phase == Sim3Track::DONE) *out = J.res;   // no level with iterations
-  return LSDHIP_OK;
 }
 
 extern "C" int lsdhip_sim3tracker_track(lsdhip_sim3tracker* t, lsdhip_frame* kf, lsdhip_frame* frame, const double init[8], int startLevel,
                                         int finalLevel, lsdhip_sim3_result* out) {
-  if (!t || !kf || !frame || !init || !out || startLevel < finalLevel || finalLevel < 0 || startLevel >= LSD_LEVELS) return LSDHIP_E_ARG;
-  HIPCHK(hipSetDevice(t->ctx->device));
-  std::vector<Sim3Track> jobs(1);
-  int rc = sim3_init_job(t, jobs[0], kf, frame, init, startLevel, finalLevel, out);
-  if (rc) return rc;
-  rc = sim3_track_jobs(t, jobs, {{kf, frame}});
-  if (rc) return rc;
-  return jobs[0].rc;
+  return lsdhip_sim3tracker_track_batch(t, 1, &kf, &frame, init, startLevel, finalLevel, out);   // (its verdict: the one job's)
 }
 
+// every job is checked before any result is written or any work queued: a refused call leaves results[] as it was
 extern "C" int lsdhip_sim3tracker_track_batch(lsdhip_sim3tracker* t, int n, lsdhip_frame** keyframes, lsdhip_frame** frames, const double* inits,
                                               int startLevel, int finalLevel, lsdhip_sim3_result* results) {
-  if (!t || n <= 0 || !keyframes || !frames || !inits || !results || startLevel < finalLevel || finalLevel < 0 || startLevel >= LSD_LEVELS)
-    return LSDHIP_E_ARG;
+  if (!t || n <= 0 || !keyframes || !frames || !inits || !results || sim3_check_levels(startLevel, finalLevel)) return LSDHIP_E_ARG;
   HIPCHK(hipSetDevice(t->ctx->device));
+  for (int j = 0; j < n; j++) { if (int rc = sim3_check_pair(keyframes[j], frames[j])) return rc; }
+  const Sim3LM P = sim3_lm_params(t);
   std::vector<Sim3Track> jobs((size_t)n);
-  std::vector<std::pair<lsdhip_frame*, lsdhip_frame*>> pairs((size_t)n);
-  for (int j = 0; j < n; j++) {
-    int rc = sim3_init_job(t, jobs[j], keyframes[j], frames[j], inits + 8 * (size_t)j, startLevel, finalLevel, &results[j]);
-    if (rc) return rc;
-    pairs[j] = {keyframes[j], frames[j]};
-  }
-  int rc = sim3_track_jobs(t, jobs, pairs);
-  if (rc) return rc;
+  for (int j = 0; j < n; j++) sim3_init_job(P, jobs[j], inits + 8 * (size_t)j, startLevel, finalLevel, &results[j]);
+  if (int rc = sim3_track_jobs(t, P, n, jobs.data(), keyframes, frames)) return rc;
   int rcAll = LSDHIP_OK;
   for (int j = 0; j < n; j++) if (jobs[j].rc == LSDHIP_DIVERGED) rcAll = LSDHIP_DIVERGED;
   return rcAll;
