@@ -57,17 +57,18 @@ def changed_pixels(a, b):
 
 
 def build_twins(oracle, w, h, n, kind="S1", params=None, seed0=100, sigma=0.1, far=False, reactivated=(), regularize=False, nseq=4,
-                nframes=N_FRAMES):
+                nframes=N_FRAMES, source=sequence):
     """n ragged oracle maps (test_gpu_parity._noisy_hyp with a per-map seed) on keyframes of `nseq` rendered sequences, plus hypotheses
     planted on 2 % of the pixels below minUseGrad (initializeFromGTDepth leaves none there: without them nothing would tell an
-    every-pixel select pass, which drops them, from the candidate select, which never sees them)."""
+    every-pixel select pass, which drops them, from the candidate select, which never sees them).  source: common.sequence or another
+    callable with its arguments and results (tests/test_observe_motions_gpu.py: frames of general camera motions)."""
     op = oracle_params(oracle, params)
     for s in range(min(n, nseq)):
-        sequence(w, h, nframes, s, kind)      # (rendered once per size, before the pool asks for them)
+        source(w, h, nframes, s, kind)      # (rendered once per size, before the pool asks for them)
 
     def one(j):
         t = Twin()
-        t.frames, t.depth0, t.K, t.gt = sequence(w, h, nframes, j % nseq, kind)
+        t.frames, t.depth0, t.K, t.gt = source(w, h, nframes, j % nseq, kind)
         t.w, t.h, t.base, t.react, t.op = w, h, 0, j in reactivated, op
         t.kf = oracle.Frame(0, t.frames[0], t.K)
         t.kf.set_depth_gt(t.depth0)
