@@ -684,13 +684,10 @@ extern "C" int lsdhip_ctx_free_dev(lsdhip_ctx* c, void* p) {
 extern "C" int lsdhip_ctx_synchronize(lsdhip_ctx* c) {
   if (!c) return LSDHIP_E_ARG;
   LSD_CTX_LOCK(c);
-  if (c) {
-    for (int i = 0; i < LSD_NUM_SLOTS; i++) {   // pick up every deferred result
-      if (c->slot_stats_owner[i]) { int rc = lsd_frame_resolve(c->slot_stats_owner[i]); if (rc) return rc; }
-      if (c->slot_rescale_owner[i]) { int rc = lsd_frame_resolve(c->slot_rescale_owner[i]); if (rc) return rc; }
-    }
+  for (int i = 0; i < LSD_NUM_SLOTS; i++) {   // pick up every deferred result
+    if (c->slot_stats_owner[i]) { int rc = lsd_frame_resolve(c->slot_stats_owner[i]); if (rc) return rc; }
+    if (c->slot_rescale_owner[i]) { int rc = lsd_frame_resolve(c->slot_rescale_owner[i]); if (rc) return rc; }
   }
-  if (!c) return LSDHIP_E_ARG;
   if (c->aux_stream) HIPCHK(hipStreamSynchronize(c->aux_stream));
   return lsd_sync_all(c);
 }
@@ -1264,76 +1261,38 @@ extern "C" int lsdhip_prof_read(lsdhip_ctx* c, double* ms, long long* launches, 
   return LSDHIP_OK;
 }
 
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
+// ---- frames: arena, pyramids, planes on demand ------------------------------------------------------------------------------------------
+// One arena per frame, out of the context's pool where it holds one.  Which planes it has and where: lsd_frame_planes (frame_layout.hpp).
 static int frame_alloc(lsdhip_ctx* c, int id, lsdhip_frame** out) {
   LSD_CTX_LOCK(c);
+  LsdFrameLayout& lay = c->frameLayout;
+  if (lay.n == 0) {
+    lay = lsd_frame_layout<lsdhip_frame>(c->wl, c->hl);
+    c->arena_bytes = lay.bytes;
+  }
+  if (lay.n > LsdFrameLayout::MAX_PLANES) { lsd_set_error("frame_alloc: %d planes do not fit the layout table", lay.n); return LSDHIP_E_STATE; }
+  char* base = nullptr;
+  if (!c->free_arenas.empty()) {
+    base = (char*)c->free_arenas.back();
+    c->free_arenas.pop_back();
+  } else {
+    hipError_t e = hipMalloc((void**)&base, c->arena_bytes);
+    if (e != hipSuccess) { lsd_set_error("hipMalloc(%zu) failed: %s", c->arena_bytes, hipGetErrorString(e)); return LSDHIP_E_HIP; }
+  }
   lsdhip_frame* f = new lsdhip_frame();
   f->ctx = c;
   f->id = id;
   f->thisToParent_raw.q = {1, 0, 0, 0};
   f->thisToParent_raw.t[0] = f->thisToParent_raw.t[1] = f->thisToParent_raw.t[2] = 0;
   f->thisToParent_raw.s = 1;
-  // one arena per frame: gray | image[l] | grad[l] | absgrad | maxgrad | idepth[l] | idepthVar[l] | wasGood
-  size_t off = 0, offs[64];
-  int k = 0;
-  auto take = [&](size_t bytes) { off = align_up(off, 256); offs[k++] = off; off += bytes; };
-  size_t n0 = (size_t)c->w * c->h;
-  take(n0);
-  for (int l = 0; l < LSD_LEVELS; l++) take((size_t)c->wl[l] * c->hl[l] * 4);
-  for (int l = 0; l < LSD_LEVELS; l++) take((size_t)c->wl[l] * c->hl[l] * 16);
-  take(n0 * 4);
-  take(n0 * 4);
-  for (int l = 0; l < LSD_LEVELS; l++) take((size_t)c->wl[l] * c->hl[l] * 4);
-  for (int l = 0; l < LSD_LEVELS; l++) take((size_t)c->wl[l] * c->hl[l] * 4);
-  take((size_t)c->wl[1] * c->hl[1]);
-  take(n0 * 4);   // re-activation data (Frame::takeReActivationData): idepth, idepthVar, validity
-  take(n0 * 4);
-  take(n0);
-  for (int l = 0; l < LSD_LEVELS; l++) take((size_t)c->wl[l] * c->hl[l] * 4);   // second depth plane set (pipelined contexts)
-  for (int l = 0; l < LSD_LEVELS; l++) take((size_t)c->wl[l] * c->hl[l] * 4);
-  for (int s2 = 0; s2 < 2; s2++)                                                 // reference blocks of levels >= 1, one set per depth plane set
-    for (int l = 1; l < LSD_LEVELS; l++) take(lsd_refblk_bytes(c->wl[l] * c->hl[l]));
-  take(lsd_gradcand_bytes((int)n0));                                             // gradient candidates (keyframes)
-  char* base = nullptr;
-  c->arena_bytes = align_up(off, 256);
-  if (!c->free_arenas.empty()) {
-    base = (char*)c->free_arenas.back();
-    c->free_arenas.pop_back();
-  } else {
-    hipError_t e = hipMalloc((void**)&base, c->arena_bytes);
-    if (e != hipSuccess) { lsd_set_error("hipMalloc(%zu) failed: %s", off, hipGetErrorString(e)); delete f; return LSDHIP_E_HIP; }
-  }
-  k = 0;
-  f->d_gray = (uint8_t*)(base + offs[k++]);
-  for (int l = 0; l < LSD_LEVELS; l++) f->d_image[l] = (float*)(base + offs[k++]);
-  for (int l = 0; l < LSD_LEVELS; l++) f->d_grad[l] = (float4*)(base + offs[k++]);
-  f->d_absgrad = (float*)(base + offs[k++]);
-  f->d_maxgrad = (float*)(base + offs[k++]);
-  for (int l = 0; l < LSD_LEVELS; l++) f->d_idepth[l] = (float*)(base + offs[k++]);
-  for (int l = 0; l < LSD_LEVELS; l++) f->d_idepthVar[l] = (float*)(base + offs[k++]);
-  f->d_wasGood = (uint8_t*)(base + offs[k++]);
-  f->d_idepth_reAct = (float*)(base + offs[k++]);
-  f->d_idepthVar_reAct = (float*)(base + offs[k++]);
-  f->d_validity_reAct = (uint8_t*)(base + offs[k++]);
-  for (int l = 0; l < LSD_LEVELS; l++) f->d_idepthW[l] = (float*)(base + offs[k++]);
-  for (int l = 0; l < LSD_LEVELS; l++) f->d_idepthVarW[l] = (float*)(base + offs[k++]);
-  for (int l = 1; l < LSD_LEVELS; l++) f->d_refBlk[l] = (uint8_t*)(base + offs[k++]);
-  for (int l = 1; l < LSD_LEVELS; l++) f->d_refBlkW[l] = (uint8_t*)(base + offs[k++]);
-  f->d_gradCand = (uint16_t*)(base + offs[k++]);
+  lsd_frame_bind(*f, lay, c->wl, c->hl, base);
   *out = f;
   return LSDHIP_OK;
 }
 
-int lsd_frame_build_pyramids(lsdhip_frame* f, const uint8_t* src, hipStream_t stream) {
-  lsdhip_ctx* c = f->ctx;
-  LSD_CTX_LOCK(c);
-  if (!stream) stream = lsd_map_stream(c);
-  dim3 grid(c->w / 16, c->h / 16);
-  lsdhip_host_mark(21);
-  hipLaunchKernelGGL(k_image_pyramid, grid, dim3(256), 0, stream, src ? src : f->d_gray, f->d_image[0], f->d_image[1], f->d_image[2],
-                     f->d_image[3], f->d_image[4], c->w, c->h, (float4*)nullptr, (float*)nullptr);
-  f->level0Ready = false; f->gradCandTh = -1.0f;
+// The gradient launch of a new frame: levels 1..4 as ranges of 256-pixel blocks, and the level-1 mask words it fills with 0xFF
+static GradMaxArgs grad_max_args(const lsdhip_frame* f) {
+  const lsdhip_ctx* c = f->ctx;
   GradMaxArgs ga;
   int nb = 0;
   for (int l = 0; l < LSD_LEVELS; l++) {
@@ -1343,12 +1302,117 @@ int lsd_frame_build_pyramids(lsdhip_frame* f, const uint8_t* src, hipStream_t st
   }
   ga.blk0[LSD_LEVELS] = nb;
   ga.wasGoodWords = lsd_g((uint32_t*)f->d_wasGood); ga.nMaskWords = (c->wl[1] * c->hl[1] + 3) / 4;
+  return ga;
+}
+// What the pyramid launches leave: a frame that owns nothing its (recycled) arena held before
+static void frame_pyramids_queued(lsdhip_frame* f) {
+  f->level0Ready = false; f->gradCandTh = -1.0f;   // keyframe planes and candidates: on demand (lsd_frames_require_level0)
+  f->wasGoodPristine = true;                       // the mask holds the gradient launch's 0xFF fill
+}
+
+int lsd_frame_build_pyramids(lsdhip_frame* f, const uint8_t* src, hipStream_t stream) {
+  lsdhip_ctx* c = f->ctx;
+  LSD_CTX_LOCK(c);
+  if (!stream) stream = lsd_map_stream(c);
+  lsdhip_host_mark(21);
+  hipLaunchKernelGGL(k_image_pyramid, dim3(c->w / 16, c->h / 16), dim3(256), 0, stream, src ? src : f->d_gray, f->d_image[0], f->d_image[1],
+                     f->d_image[2], f->d_image[3], f->d_image[4], c->w, c->h, (float4*)nullptr, (float*)nullptr);
+  const GradMaxArgs ga = grad_max_args(f);
   lsdhip_host_mark(22);
-  hipLaunchKernelGGL(k_gradients_max, dim3(nb), dim3(256), 0, stream, ga);   // the gradient blocks only: maxGradients is a keyframe plane (lsd_frames_require_level0)
+  hipLaunchKernelGGL(k_gradients_max, dim3(ga.blk0[LSD_LEVELS]), dim3(256), 0, stream, ga);   // the gradient blocks only: maxGradients is a keyframe plane (lsd_frames_require_level0)
   lsdhip_host_mark(23);
   HIPCHK(hipGetLastError());
-  f->wasGoodPristine = true;
+  frame_pyramids_queued(f);
   return LSDHIP_OK;
+}
+
+// Two item arrays in one argument record (one copy for both launches of a pair): A[n] at its start, B[n] from the next 256-byte boundary
+// on.  Filled in place between args_pair_begin and lsd_args_commit; lsd_args_release(dev) behind the launches.
+template <class A, class B> struct ArgPair {
+  A* a; B* b;                      // the pinned record, to be filled
+  const A* devA; const B* devB;    // what the launches read
+  void* dev;
+};
+template <class A, class B> static int args_pair_begin(lsdhip_ctx* c, int n, ArgPair<A, B>& p) {
+  const size_t bOff = lsd_align_up(sizeof(A) * (size_t)n, 256);
+  void* host = nullptr;
+  if (int rc = lsd_args_begin(c, bOff + sizeof(B) * (size_t)n, &host, &p.dev)) return rc;
+  p.a = (A*)host; p.b = (B*)((uint8_t*)host + bOff);
+  p.devA = (const A*)p.dev; p.devB = (const B*)((const uint8_t*)p.dev + bOff);
+  return LSDHIP_OK;
+}
+// ... and one array
+template <class T> static int args_items_begin(lsdhip_ctx* c, size_t n, T** items, const T** dev) {
+  void *h = nullptr, *d = nullptr;
+  if (int rc = lsd_args_begin(c, sizeof(T) * n, &h, &d)) return rc;
+  *items = (T*)h; *dev = (const T*)d;
+  return LSDHIP_OK;
+}
+
+// The pyramids of n new frames in two launches (blockIdx.z / .y = frame).  devGray: the images where they are on the device already
+// (else each frame's own uint8 plane, uploaded by the caller).
+static int frames_build_pyramids_batch(lsdhip_ctx* c, lsdhip_frame** fs, int n, const uint8_t* const* devGray) {
+  const hipStream_t ms = lsd_map_stream(c);
+  ArgPair<ImagePyrItem, GradMaxArgs> args;
+  if (int rc = args_pair_begin(c, n, args)) return rc;
+  for (int j = 0; j < n; j++) {
+    ImagePyrItem& pi = args.a[j];
+    pi.gray = lsd_g(devGray ? devGray[j] : fs[j]->d_gray);
+    for (int l = 0; l < LSD_LEVELS; l++) pi.img[l] = lsd_g(fs[j]->d_image[l]);
+    pi.grad0 = nullptr; pi.absgrad0 = nullptr;   // keyframe planes: lsd_frames_require_level0
+    args.b[j] = grad_max_args(fs[j]);
+  }
+  const int gradBlocks = args.b[0].blk0[LSD_LEVELS];
+  if (int rc = lsd_args_commit(c, ms)) return rc;
+  const int bp = lsd_bprof_begin(c, 0, ms);
+  if (bp < -1) return bp;
+  hipLaunchKernelGGL(k_image_pyramid_batch, dim3(c->w / 16, c->h / 16, n), dim3(256), 0, ms, args.devA, c->w, c->h);
+  hipLaunchKernelGGL(k_gradients_max_batch, dim3(gradBlocks, n), dim3(256), 0, ms, args.devB);
+  if (int rc = lsd_bprof_end(c, bp, ms, (double)n * (c->w * c->h))) return rc;
+  HIPCHK(hipGetLastError());
+  if (int rc = lsd_args_release(c, args.dev, ms)) return rc;
+  for (int j = 0; j < n; j++) frame_pyramids_queued(fs[j]);
+  return LSDHIP_OK;
+}
+
+// The frames of fs[0 .. n) that still need something, each once (null entries are skipped)
+template <class Needs> static std::vector<lsdhip_frame*> frames_that_need(lsdhip_frame** fs, int n, Needs needs) {
+  std::vector<lsdhip_frame*> todo;
+  for (int j = 0; j < n; j++)
+    if (fs[j] && needs(fs[j]) && std::find(todo.begin(), todo.end(), fs[j]) == todo.end()) todo.push_back(fs[j]);
+  return todo;
+}
+
+// The depth planes of a frame and the reference blocks that go with them: the PUBLISHED set (what the tracking side reads), the set a
+// Frame::setDepth WRITES (the second one on pipelined contexts, until lsd_frame_publish_depth swaps them), or the LATEST written,
+// published or not
+enum class DepthSet { Published, Written, Latest };
+struct DepthPlaneSet { float** id; float** var; uint8_t** blk; bool* blkValid; };
+static DepthPlaneSet depth_plane_set(lsdhip_frame* f, DepthSet which) {
+  const bool second = which == DepthSet::Written ? f->ctx->pipeline : which == DepthSet::Latest ? f->depthPending : false;
+  if (second) return {f->d_idepthW, f->d_idepthVarW, f->d_refBlkW, &f->refBlkValidW};
+  return {f->d_idepth, f->d_idepthVar, f->d_refBlk, &f->refBlkValid};
+}
+// The record k_idepth_pyramid and k_ref_blocks (and their batch forms) read; red*: the pyramid's optional passenger
+static DepthPyrArgs depth_pyr_args(lsdhip_frame* f, DepthSet which, const double* redPartials = nullptr, int redN = 0, double* redOut = nullptr) {
+  const DepthPlaneSet s = depth_plane_set(f, which);
+  DepthPyrArgs a;
+  for (int l = 0; l < LSD_LEVELS; l++) { a.id[l] = lsd_g(s.id[l]); a.var[l] = lsd_g(s.var[l]); a.blk[l] = lsd_g(s.blk[l]); }
+  a.w0 = f->ctx->w; a.h0 = f->ctx->h;
+  a.redPartials = lsd_g(redPartials); a.redN = redN; a.redOut = lsd_g(redOut);
+  return a;
+}
+static dim3 depth_pyr_grid(const lsdhip_ctx* c, bool passenger, int n) { return dim3((c->w + 31) / 32, (c->h + 31) / 32 + (passenger ? 1 : 0), n); }
+// An idepth pyramid (with the reference blocks, where the context builds them) has been queued into the frame's written set
+static void depth_pyramid_queued(lsdhip_frame* f) {
+  lsdhip_ctx* c = f->ctx;
+  *depth_plane_set(f, DepthSet::Written).blkValid = c->refBlocksWanted;
+  if (c->pipeline) {
+    f->depthPending = true; f->depthPendingSeq = c->mSeq + 1;   // complete at the caller's record point; the version changes when the planes are published
+  } else {
+    f->hasIDepth = true;
+    f->depthVersion++;   // a tracking job that is topped up from here on would read the new planes (tracker.hip)
+  }
 }
 
 // The reference blocks of the PUBLISHED depth planes of the keyframes of a throughput-mode tracking batch, where they are missing: a context
@@ -1359,21 +1423,14 @@ int lsd_frames_require_ref_blocks(lsdhip_frame** kfs, int n, hipStream_t stream)
   lsdhip_ctx* c = kfs[0]->ctx;
   LSD_CTX_LOCK(c);
   c->refBlocksWanted = true;
-  std::vector<lsdhip_frame*> todo;
-  for (int j = 0; j < n; j++)
-    if (kfs[j] && !kfs[j]->refBlkValid && std::find(todo.begin(), todo.end(), kfs[j]) == todo.end()) todo.push_back(kfs[j]);
+  const std::vector<lsdhip_frame*> todo = frames_that_need(kfs, n, [](const lsdhip_frame* f) { return !f->refBlkValid; });
   if (todo.empty()) return LSDHIP_OK;
-  std::vector<DepthPyrArgs> items(todo.size());
-  for (size_t j = 0; j < todo.size(); j++) {
-    lsdhip_frame* f = todo[j];
-    DepthPyrArgs& a = items[j];
-    memset((void*)&a, 0, sizeof(a));
-    for (int l = 0; l < LSD_LEVELS; l++) { a.id[l] = lsd_g(f->d_idepth[l]); a.var[l] = lsd_g(f->d_idepthVar[l]); a.blk[l] = lsd_g(f->d_refBlk[l]); }
-    a.w0 = c->w; a.h0 = c->h;
-  }
-  void* dev = nullptr;
-  if (int rc = lsd_args_push(c, items.data(), sizeof(DepthPyrArgs) * items.size(), stream, &dev)) return rc;
-  hipLaunchKernelGGL(k_ref_blocks_batch, dim3(lsd_refblk_grid(c), 1, (unsigned)todo.size()), dim3(256), 0, stream, (const DepthPyrArgs*)dev);
+  DepthPyrArgs* items = nullptr;
+  const DepthPyrArgs* dev = nullptr;
+  if (int rc = args_items_begin(c, todo.size(), &items, &dev)) return rc;
+  for (size_t j = 0; j < todo.size(); j++) items[j] = depth_pyr_args(todo[j], DepthSet::Published);
+  if (int rc = lsd_args_commit(c, stream)) return rc;
+  hipLaunchKernelGGL(k_ref_blocks_batch, dim3(lsd_refblk_grid(c), 1, (unsigned)todo.size()), dim3(256), 0, stream, dev);
   HIPCHK(hipGetLastError());
   if (int rc = lsd_args_release(c, dev, stream)) return rc;
   for (lsdhip_frame* f : todo) f->refBlkValid = true;
@@ -1388,9 +1445,7 @@ int lsd_frames_require_level0(lsdhip_frame** fs, int n) {
   if (n <= 0) return LSDHIP_OK;
   lsdhip_ctx* c = fs[0]->ctx;
   LSD_CTX_LOCK(c);
-  std::vector<lsdhip_frame*> todo;
-  for (int j = 0; j < n; j++)
-    if (fs[j] && !fs[j]->level0Ready && std::find(todo.begin(), todo.end(), fs[j]) == todo.end()) todo.push_back(fs[j]);
+  const std::vector<lsdhip_frame*> todo = frames_that_need(fs, n, [](const lsdhip_frame* f) { return !f->level0Ready; });
   if (todo.empty()) return LSDHIP_OK;
   const hipStream_t ms = lsd_map_stream(c);
   const int n0 = c->w * c->h, m = (int)todo.size();
@@ -1405,15 +1460,13 @@ int lsd_frames_require_level0(lsdhip_frame** fs, int n) {
     hipLaunchKernelGGL(k_level0_gradients, dim3((n0 + 255) / 256), dim3(256), 0, ms, it, c->w, c->h);
     hipLaunchKernelGGL(k_maxgrad_candidates, dim3(lsd_gradcand_groups(n0)), dim3(1024), 0, ms, mc, c->w, c->h, c->params.minUseGrad);
   } else {
-    const size_t itBytes = align_up(sizeof(Level0Item) * (size_t)m, 256);
-    std::vector<uint8_t> blob(itBytes + sizeof(MaxCandItem) * (size_t)m);
-    for (int j = 0; j < m; j++) fill(todo[j], ((Level0Item*)blob.data())[j], ((MaxCandItem*)(blob.data() + itBytes))[j]);
-    void* dev = nullptr;
-    if (int rc = lsd_args_push(c, blob.data(), blob.size(), ms, &dev)) return rc;
-    hipLaunchKernelGGL(k_level0_gradients_batch, dim3((n0 + 255) / 256, m), dim3(256), 0, ms, (const Level0Item*)dev, c->w, c->h);
-    hipLaunchKernelGGL(k_maxgrad_candidates_batch, dim3(lsd_gradcand_groups(n0), m), dim3(1024), 0, ms,
-                       (const MaxCandItem*)((const uint8_t*)dev + itBytes), c->w, c->h, c->params.minUseGrad);
-    if (int rc = lsd_args_release(c, dev, ms)) return rc;
+    ArgPair<Level0Item, MaxCandItem> args;
+    if (int rc = args_pair_begin(c, m, args)) return rc;
+    for (int j = 0; j < m; j++) fill(todo[j], args.a[j], args.b[j]);
+    if (int rc = lsd_args_commit(c, ms)) return rc;
+    hipLaunchKernelGGL(k_level0_gradients_batch, dim3((n0 + 255) / 256, m), dim3(256), 0, ms, args.devA, c->w, c->h);
+    hipLaunchKernelGGL(k_maxgrad_candidates_batch, dim3(lsd_gradcand_groups(n0), m), dim3(1024), 0, ms, args.devB, c->w, c->h, c->params.minUseGrad);
+    if (int rc = lsd_args_release(c, args.dev, ms)) return rc;
   }
   HIPCHK(hipGetLastError());
   for (lsdhip_frame* f : todo) { f->level0Ready = true; f->gradCandTh = c->params.minUseGrad; }
@@ -1437,25 +1490,34 @@ int lsd_frame_require_level0_for_tracking(lsdhip_frame* f) {
   return LSDHIP_OK;
 }
 
+// Frame::setDepth's second half: levels 1..4 of the planes being written, on the mapping stream.  One frame's record travels as a kernel
+// argument, the records of a batch through the argument ring; everything else is the same.
 int lsd_frame_build_idepth_pyramid(lsdhip_frame* f, const double* redPartials, int redN, double* redOut) {
   lsdhip_ctx* c = f->ctx;
   LSD_CTX_LOCK(c);
-  // non-pipelined: a tracking job that is topped up after this point would read the new planes (tracker.hip); pipelined: the job's
-  // planes stay untouched, the version changes when the new ones are published
-  if (!c->pipeline) f->depthVersion++;
-  DepthPyrArgs a;
-  float** id = lsd_depth_w(f);
-  float** var = lsd_depthvar_w(f);
-  for (int l = 0; l < LSD_LEVELS; l++) { a.id[l] = lsd_g(id[l]); a.var[l] = lsd_g(var[l]); }
-  a.w0 = c->w; a.h0 = c->h;
-  a.redPartials = lsd_g(redPartials); a.redN = redN; a.redOut = lsd_g(redOut);
-  for (int l = 0; l < LSD_LEVELS; l++) a.blk[l] = lsd_g(lsd_refblk_w(f)[l]);
-  hipLaunchKernelGGL(k_idepth_pyramid, dim3((c->w + 31) / 32, (c->h + 31) / 32 + (redPartials ? 1 : 0)), dim3(256), 0, lsd_map_stream(c), a);
-  if (c->refBlocksWanted) hipLaunchKernelGGL(k_ref_blocks, dim3(lsd_refblk_grid(c)), dim3(256), 0, lsd_map_stream(c), a);
-  (c->pipeline ? f->refBlkValidW : f->refBlkValid) = c->refBlocksWanted;
+  const hipStream_t ms = lsd_map_stream(c);
+  const DepthPyrArgs a = depth_pyr_args(f, DepthSet::Written, redPartials, redN, redOut);
+  hipLaunchKernelGGL(k_idepth_pyramid, depth_pyr_grid(c, redPartials != nullptr, 1), dim3(256), 0, ms, a);
+  if (c->refBlocksWanted) hipLaunchKernelGGL(k_ref_blocks, dim3(lsd_refblk_grid(c)), dim3(256), 0, ms, a);
   HIPCHK(hipGetLastError());
-  if (c->pipeline) { f->depthPending = true; f->depthPendingSeq = c->mSeq + 1; }   // complete at the caller's record point
-  else f->hasIDepth = true;
+  depth_pyramid_queued(f);
+  return LSDHIP_OK;
+}
+int lsd_frame_build_idepth_pyramid_batch(lsdhip_frame** fs, int n, const double* const* redPartials, int redN, double* const* redOut, const int* redNs) {
+  if (n <= 0) return LSDHIP_OK;
+  lsdhip_ctx* c = fs[0]->ctx;
+  LSD_CTX_LOCK(c);
+  const hipStream_t ms = lsd_map_stream(c);
+  DepthPyrArgs* items = nullptr;
+  const DepthPyrArgs* dev = nullptr;
+  if (int rc = args_items_begin(c, (size_t)n, &items, &dev)) return rc;
+  for (int j = 0; j < n; j++) items[j] = depth_pyr_args(fs[j], DepthSet::Written, redPartials[j], redNs ? redNs[j] : redN, redOut[j]);
+  if (int rc = lsd_args_commit(c, ms)) return rc;
+  hipLaunchKernelGGL(k_idepth_pyramid_batch, depth_pyr_grid(c, true, n), dim3(256), 0, ms, dev);
+  if (c->refBlocksWanted) hipLaunchKernelGGL(k_ref_blocks_batch, dim3(lsd_refblk_grid(c), 1, n), dim3(256), 0, ms, dev);
+  HIPCHK(hipGetLastError());
+  if (int rc = lsd_args_release(c, dev, ms)) return rc;
+  for (int j = 0; j < n; j++) depth_pyramid_queued(fs[j]);
   return LSDHIP_OK;
 }
 
@@ -1472,7 +1534,7 @@ int lsd_args_begin(lsdhip_ctx* c, size_t bytes, void** host_out, void** dev_out)
     if (r.h) { (void)hipHostFree(r.h); r.h = nullptr; }
     if (r.d) { (void)hipFree(r.d); r.d = nullptr; }
     r.slotBytes = 0;
-    const size_t want = align_up(bytes * 2 > 65536 ? bytes * 2 : 65536, 256);
+    const size_t want = lsd_align_up(bytes * 2 > 65536 ? bytes * 2 : 65536, 256);
     HIPCHK(hipHostMalloc((void**)&r.h, want * NS, hipHostMallocDefault));
     HIPCHK(hipMalloc((void**)&r.d, want * NS));
     r.slotBytes = want;
@@ -1520,38 +1582,6 @@ int lsd_args_push(lsdhip_ctx* c, const void* src, size_t bytes, hipStream_t s, v
   return lsd_args_commit(c, s);
 }
 
-int lsd_frame_build_idepth_pyramid_batch(lsdhip_frame** fs, int n, const double* const* redPartials, int redN, double* const* redOut, const int* redNs) {
-  if (n <= 0) return LSDHIP_OK;
-  lsdhip_ctx* c = fs[0]->ctx;
-  LSD_CTX_LOCK(c);
-  std::vector<DepthPyrArgs> items((size_t)n);
-  for (int j = 0; j < n; j++) {
-    lsdhip_frame* f = fs[j];
-    if (!c->pipeline) f->depthVersion++;
-    DepthPyrArgs& a = items[j];
-    float** id = lsd_depth_w(f);
-    float** var = lsd_depthvar_w(f);
-    for (int l = 0; l < LSD_LEVELS; l++) { a.id[l] = lsd_g(id[l]); a.var[l] = lsd_g(var[l]); }
-    a.w0 = c->w; a.h0 = c->h;
-    a.redPartials = lsd_g(redPartials[j]); a.redN = redNs ? redNs[j] : redN; a.redOut = lsd_g(redOut[j]);
-    for (int l = 0; l < LSD_LEVELS; l++) a.blk[l] = lsd_g(lsd_refblk_w(f)[l]);
-  }
-  void* dev = nullptr;
-  int rc = lsd_args_push(c, items.data(), sizeof(DepthPyrArgs) * (size_t)n, lsd_map_stream(c), &dev);
-  if (rc) return rc;
-  hipLaunchKernelGGL(k_idepth_pyramid_batch, dim3((c->w + 31) / 32, (c->h + 31) / 32 + 1, n), dim3(256), 0, lsd_map_stream(c), (const DepthPyrArgs*)dev);
-  if (c->refBlocksWanted) hipLaunchKernelGGL(k_ref_blocks_batch, dim3(lsd_refblk_grid(c), 1, n), dim3(256), 0, lsd_map_stream(c), (const DepthPyrArgs*)dev);
-  for (int j = 0; j < n; j++) (c->pipeline ? fs[j]->refBlkValidW : fs[j]->refBlkValid) = c->refBlocksWanted;
-  HIPCHK(hipGetLastError());
-  rc = lsd_args_release(c, dev, lsd_map_stream(c));
-  if (rc) return rc;
-  for (int j = 0; j < n; j++) {
-    if (c->pipeline) { fs[j]->depthPending = true; fs[j]->depthPendingSeq = c->mSeq + 1; }
-    else fs[j]->hasIDepth = true;
-  }
-  return LSDHIP_OK;
-}
-
 int lsd_frame_ensure_wasgood(lsdhip_frame* f) {
   if (!f->wasGoodValid) {
     if (!f->wasGoodPristine) HIPCHK(hipMemsetAsync(f->d_wasGood, 0xFF, (size_t)f->ctx->wl[1] * f->ctx->hl[1], f->ctx->stream));
@@ -1561,52 +1591,66 @@ int lsd_frame_ensure_wasgood(lsdhip_frame* f) {
   return LSDHIP_OK;
 }
 
-extern "C" int lsdhip_frame_create_from_device(lsdhip_ctx* c, int id, const uint8_t* gray_dev, lsdhip_frame** out) {
-  if (!c || !gray_dev || !out) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
+// ---- frame creation -------------------------------------------------------------------------------------------------------------------------
+// The steps every creator shares, on the mapping stream: arenas, upload of host images, pyramids (two launches per frame, or — batched —
+// two for all), the record point the frames are complete at, and for host images the wait after which the caller may reuse its buffers.
+// gray[j] on the device is read by the pyramid kernel directly (stream-ordered; nothing else needs the uint8 plane).
+static int frames_create_steps(lsdhip_ctx* c, int n, const int* ids, const uint8_t* const* gray, bool onDevice, bool batched, bool wait, lsdhip_frame** fs) {
   HIPCHK(hipSetDevice(c->device));
-  lsdhip_frame* f = nullptr;
-  int rc = frame_alloc(c, id, &f);
-  if (rc) return rc;
-  // the pyramid kernel reads the caller's device image directly (stream-ordered; nothing else needs the uint8 plane)
-  rc = lsd_m_begin(c);
-  if (rc == LSDHIP_OK) rc = lsd_frame_build_pyramids(f, gray_dev, nullptr);
-  if (rc) { lsdhip_frame_destroy(f); return rc; }
-  lsd_trace_sum(c, lsd_map_stream(c), 2, id, f->d_image[0], (size_t)((char*)f->d_idepth[0] - (char*)f->d_image[0]));
-  f->readySeq = lsd_m_record(c);
-  if (f->readySeq < 0) { lsdhip_frame_destroy(f); return LSDHIP_E_HIP; }
-  *out = f;
-  return LSDHIP_OK;
-}
-static int frame_create_host(lsdhip_ctx* c, int id, const uint8_t* gray_host, bool wait, lsdhip_frame** out) {
-  if (!c || !gray_host || !out) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  lsdhip_frame* f = nullptr;
-  int rc = frame_alloc(c, id, &f);
-  if (rc) return rc;
+  for (int j = 0; j < n; j++)
+    if (int rc = frame_alloc(c, ids[j], &fs[j])) return rc;
   const hipStream_t ms = lsd_map_stream(c);
-  rc = lsd_m_begin(c);
-  if (rc) { lsdhip_frame_destroy(f); return rc; }
-  hipError_t e = hipMemcpyAsync(f->d_gray, gray_host, (size_t)c->w * c->h, hipMemcpyHostToDevice, ms);
-  if (e != hipSuccess) { lsd_set_error("lsdhip_frame_create: upload failed: %s", hipGetErrorString(e)); lsdhip_frame_destroy(f); return LSDHIP_E_HIP; }
-  rc = lsd_frame_build_pyramids(f, nullptr, nullptr);
-  if (rc) { lsdhip_frame_destroy(f); return rc; }
-  f->readySeq = lsd_m_record(c);
-  if (f->readySeq < 0) { lsdhip_frame_destroy(f); return LSDHIP_E_HIP; }
+  if (int rc = lsd_m_begin(c)) return rc;
+  if (!onDevice)
+    for (int j = 0; j < n; j++) HIPCHK(hipMemcpyAsync(fs[j]->d_gray, gray[j], (size_t)c->w * c->h, hipMemcpyHostToDevice, ms));
+  if (batched) {
+    if (int rc = frames_build_pyramids_batch(c, fs, n, onDevice ? gray : nullptr)) return rc;
+  } else {
+    if (int rc = lsd_frame_build_pyramids(fs[0], onDevice ? gray[0] : nullptr, nullptr)) return rc;
+    if (onDevice) lsd_trace_sum(c, ms, 2, ids[0], fs[0]->d_image[0], (size_t)((char*)fs[0]->d_idepth[0] - (char*)fs[0]->d_image[0]));
+  }
+  const long long seq = lsd_m_record(c);
+  if (seq < 0) return LSDHIP_E_HIP;
+  for (int j = 0; j < n; j++) fs[j]->readySeq = seq;
   if (wait) {
-    e = hipStreamSynchronize(ms);  // the host buffer may be reused by the caller
-    if (e != hipSuccess) { lsd_set_error("lsdhip_frame_create: %s", hipGetErrorString(e)); lsdhip_frame_destroy(f); return LSDHIP_E_HIP; }
+    HIPCHK(hipStreamSynchronize(ms));
     if (c->pipeline) c->mDoneSeq = c->mSeq;
   }
-  *out = f;
   return LSDHIP_OK;
 }
+// fs[0 .. n) null on entry; a failing call destroys the frames it made and leaves them null
+static int frames_create(lsdhip_ctx* c, int n, const int* ids, const uint8_t* const* gray, bool onDevice, bool batched, bool wait, lsdhip_frame** fs) {
+  LSD_CTX_LOCK(c);
+  const int rc = frames_create_steps(c, n, ids, gray, onDevice, batched, wait, fs);
+  if (rc)
+    for (int j = 0; j < n; j++) { lsdhip_frame_destroy(fs[j]); fs[j] = nullptr; }
+  return rc;
+}
+static int frame_create_one(lsdhip_ctx* c, int id, const uint8_t* gray, bool onDevice, bool wait, lsdhip_frame** out) {
+  if (!c || !gray || !out) return LSDHIP_E_ARG;
+  lsdhip_frame* f = nullptr;
+  const int rc = frames_create(c, 1, &id, &gray, onDevice, false, wait, &f);
+  if (rc == LSDHIP_OK) *out = f;
+  return rc;
+}
+extern "C" int lsdhip_frame_create_from_device(lsdhip_ctx* c, int id, const uint8_t* gray_dev, lsdhip_frame** out) {
+  return frame_create_one(c, id, gray_dev, true, false, out);
+}
 extern "C" int lsdhip_frame_create(lsdhip_ctx* c, int id, const uint8_t* gray_host, lsdhip_frame** out) {
-  return frame_create_host(c, id, gray_host, true, out);
+  return frame_create_one(c, id, gray_host, false, true, out);
 }
 extern "C" int lsdhip_frame_create_async(lsdhip_ctx* c, int id, const uint8_t* gray_host, lsdhip_frame** out) {
-  return frame_create_host(c, id, gray_host, false, out);
+  return frame_create_one(c, id, gray_host, false, false, out);
+}
+// Frame creation for the new frames of n sequences at once: two launches for all of them instead of two per frame.  Same planes, bit
+// for bit, as n lsdhip_frame_create_from_device / lsdhip_frame_create calls.
+extern "C" int lsdhip_frame_create_batch(lsdhip_ctx* c, int n, const int* ids, const uint8_t* const* gray, int images_on_device, lsdhip_frame** out) {
+  if (!c || n <= 0 || !ids || !gray || !out) return LSDHIP_E_ARG;
+  for (int j = 0; j < n; j++) if (!gray[j]) return LSDHIP_E_ARG;
+  LSD_CTX_LOCK(c);
+  if ((size_t)(2 * n + 8) > c->arena_keep) c->arena_keep = (size_t)(2 * n + 8);   // a round of n frames retires n arenas at once
+  for (int j = 0; j < n; j++) out[j] = nullptr;
+  return frames_create(c, n, ids, gray, images_on_device != 0, true, !images_on_device, out);
 }
 // Frame-memory pool (the reference's FrameMemory keeps returned buffers for reuse, util/... FrameMemory.cpp): make sure n arenas are
 // allocated and waiting, so that a loop which keeps its keyframes alive does not pay a hipMalloc (0.5 ms for 20 MB) per keyframe.
@@ -1617,80 +1661,13 @@ extern "C" int lsdhip_ctx_reserve_frames(lsdhip_ctx* c, int n) {
   if ((size_t)n > c->arena_keep) c->arena_keep = (size_t)n;
   std::vector<lsdhip_frame*> tmp;
   int rc = LSDHIP_OK;
-  const size_t have = c->free_arenas.size();
-  for (size_t i = 0; i < (size_t)n && rc == LSDHIP_OK; i++) {   // the first `have` come out of the pool, the rest are new
+  for (int i = 0; i < n && rc == LSDHIP_OK; i++) {   // the pool's arenas first, the rest are new
     lsdhip_frame* f = nullptr;
     rc = frame_alloc(c, -1, &f);
     if (rc == LSDHIP_OK) tmp.push_back(f);
   }
-  (void)have;
   for (lsdhip_frame* f : tmp) lsdhip_frame_destroy(f);
   return rc;
-}
-// Frame creation for the new frames of n sequences at once: two launches for all of them (blockIdx.z / .y = frame) instead of two per
-// frame.  Same planes, bit for bit, as n lsdhip_frame_create_from_device / lsdhip_frame_create calls.
-extern "C" int lsdhip_frame_create_batch(lsdhip_ctx* c, int n, const int* ids, const uint8_t* const* gray, int images_on_device, lsdhip_frame** out) {
-  if (!c || n <= 0 || !ids || !gray || !out) return LSDHIP_E_ARG;
-  for (int j = 0; j < n; j++) if (!gray[j]) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  if ((size_t)(2 * n + 8) > c->arena_keep) c->arena_keep = (size_t)(2 * n + 8);   // a round of n frames retires n arenas at once
-  for (int j = 0; j < n; j++) out[j] = nullptr;
-  auto fail = [&](int rc) { for (int j = 0; j < n; j++) if (out[j]) { lsdhip_frame_destroy(out[j]); out[j] = nullptr; } return rc; };
-  for (int j = 0; j < n; j++) { int rc = frame_alloc(c, ids[j], &out[j]); if (rc) return fail(rc); }
-  const hipStream_t ms = lsd_map_stream(c);
-  int rc = lsd_m_begin(c);
-  if (rc) return fail(rc);
-  std::vector<ImagePyrItem> pi((size_t)n);
-  std::vector<GradMaxArgs> gi((size_t)n);
-  int nb = 0;
-  for (int j = 0; j < n; j++) {
-    lsdhip_frame* f = out[j];
-    if (!images_on_device) {
-      hipError_t e = hipMemcpyAsync(f->d_gray, gray[j], (size_t)c->w * c->h, hipMemcpyHostToDevice, ms);
-      if (e != hipSuccess) { lsd_set_error("lsdhip_frame_create_batch: upload failed: %s", hipGetErrorString(e)); return fail(LSDHIP_E_HIP); }
-    }
-    pi[j].gray = lsd_g(images_on_device ? gray[j] : f->d_gray);
-    for (int l = 0; l < LSD_LEVELS; l++) pi[j].img[l] = lsd_g(f->d_image[l]);
-    pi[j].grad0 = nullptr; pi[j].absgrad0 = nullptr;   // keyframe planes: lsd_frames_require_level0
-    f->level0Ready = false; f->gradCandTh = -1.0f;
-    GradMaxArgs& ga = gi[j];
-    nb = 0;
-    for (int l = 0; l < LSD_LEVELS; l++) {
-      ga.img[l] = lsd_g(f->d_image[l]); ga.grad[l] = lsd_g(f->d_grad[l]); ga.w[l] = c->wl[l]; ga.h[l] = c->hl[l];
-      ga.blk0[l] = nb;
-      if (l >= 1) nb += (c->wl[l] * c->hl[l] + 255) / 256;
-    }
-    ga.blk0[LSD_LEVELS] = nb;
-    ga.wasGoodWords = lsd_g((uint32_t*)f->d_wasGood); ga.nMaskWords = (c->wl[1] * c->hl[1] + 3) / 4;
-    f->wasGoodPristine = true;
-  }
-  const size_t piBytes = align_up(sizeof(ImagePyrItem) * (size_t)n, 256);
-  std::vector<uint8_t> blob(piBytes + sizeof(GradMaxArgs) * (size_t)n);
-  memcpy(blob.data(), pi.data(), sizeof(ImagePyrItem) * (size_t)n);
-  memcpy(blob.data() + piBytes, gi.data(), sizeof(GradMaxArgs) * (size_t)n);
-  void* dev = nullptr;
-  rc = lsd_args_push(c, blob.data(), blob.size(), ms, &dev);
-  if (rc) return fail(rc);
-  const int bp = lsd_bprof_begin(c, 0, ms);
-  if (bp < -1) return fail(bp);
-  hipLaunchKernelGGL(k_image_pyramid_batch, dim3(c->w / 16, c->h / 16, n), dim3(256), 0, ms, (const ImagePyrItem*)dev, c->w, c->h);
-  const int n0 = c->w * c->h;
-  hipLaunchKernelGGL(k_gradients_max_batch, dim3(nb, n), dim3(256), 0, ms, (const GradMaxArgs*)((const uint8_t*)dev + piBytes));
-  rc = lsd_bprof_end(c, bp, ms, (double)n * n0);
-  if (rc) return fail(rc);
-  if (hipGetLastError() != hipSuccess) { lsd_set_error("lsdhip_frame_create_batch: launch failed"); return fail(LSDHIP_E_HIP); }
-  rc = lsd_args_release(c, dev, ms);
-  if (rc) return fail(rc);
-  const long long seq = lsd_m_record(c);
-  if (seq < 0) return fail(LSDHIP_E_HIP);
-  for (int j = 0; j < n; j++) out[j]->readySeq = seq;
-  if (!images_on_device) {
-    hipError_t e = hipStreamSynchronize(ms);   // the host buffers may be reused by the caller
-    if (e != hipSuccess) { lsd_set_error("lsdhip_frame_create_batch: %s", hipGetErrorString(e)); return fail(LSDHIP_E_HIP); }
-    if (c->pipeline) c->mDoneSeq = c->mSeq;
-  }
-  return LSDHIP_OK;
 }
 extern "C" void lsdhip_frame_destroy(lsdhip_frame* f) {
   if (!f) return;
@@ -1713,89 +1690,94 @@ extern "C" void lsdhip_frame_destroy(lsdhip_frame* f) {
 }
 extern "C" int lsdhip_frame_id(lsdhip_frame* f) { return f ? f->id : -1; }
 
+// ---- the host reads and writes planes -----------------------------------------------------------------------------------------------------
+// Before the host touches a frame's planes through the tracking stream, what the mapping side has queued for them is drained: both streams
+// of a pipelined context.  A one-stream context orders everything on `stream` itself, except inside an open lane region, where the mapping
+// calls go to a lane: the entries that may be called there (openLanes) wait for the lane.
+static int drain_for_host(lsdhip_ctx* c, bool openLanes = false) {
+  if (c->pipeline) return lsd_sync_all(c);
+  if (openLanes && lsd_map_stream(c) != c->stream) HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));
+  return LSDHIP_OK;
+}
+static int copy_and_wait(void* dst, const void* src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+  HIPCHK(hipMemcpyAsync(dst, src, bytes, kind, s));
+  HIPCHK(hipStreamSynchronize(s));
+  return LSDHIP_OK;
+}
+
 extern "C" int lsdhip_frame_download(lsdhip_frame* f, int what, int level, float* out) {
   if (!f || !out || level < 0 || level >= LSD_LEVELS) return LSDHIP_E_ARG;
   lsdhip_ctx* c = f->ctx;
   LSD_CTX_LOCK(c);
-  size_t n = (size_t)c->wl[level] * c->hl[level];
+  const size_t n = (size_t)c->wl[level] * c->hl[level];
+  size_t bytes = n * sizeof(float);
   const void* src = nullptr;
   if ((what == 1 && level == 0) || what == 2 || what == 6) { if (int rc = lsd_frame_require_level0_for_tracking(f)) return rc; }   // built on demand
-  if (c->pipeline) { if (int rc = lsd_sync_all(c)) return rc; }
-  else if (lsd_map_stream(c) != c->stream) HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));   // (an open lane region)
+  if (int rc = drain_for_host(c, true)) return rc;
+  const bool hasDepth = f->hasIDepth || f->depthPending;
   switch (what) {
     case 0: src = f->d_image[level]; break;
-    case 1: src = f->d_grad[level]; n *= 4; break;
+    case 1: src = f->d_grad[level]; bytes *= 4; break;
     case 2: if (level != 0) return LSDHIP_E_ARG; src = f->d_maxgrad; break;
     // Frame::idepth / idepthVar: what the last Frame::setDepth left (on pipelined contexts possibly not yet published to the tracker)
-    case 3: if (!f->hasIDepth && !f->depthPending) return LSDHIP_E_STATE; src = lsd_depth_latest(f)[level]; break;
-    case 4: if (!f->hasIDepth && !f->depthPending) return LSDHIP_E_STATE; src = lsd_depthvar_latest(f)[level]; break;
-    // the level's reference blocks (k_ref_blocks), as bytes: ceil(pixels / 256) x 256 offsets, then one int32 count per block
-    case 5:
-      if (!f->hasIDepth && !f->depthPending) return LSDHIP_E_STATE;
+    case 3: if (!hasDepth) return LSDHIP_E_STATE; src = depth_plane_set(f, DepthSet::Latest).id[level]; break;
+    case 4: if (!hasDepth) return LSDHIP_E_STATE; src = depth_plane_set(f, DepthSet::Latest).var[level]; break;
+    // the level's reference blocks (k_ref_blocks), as bytes: ceil(pixels / 256) x 256 offsets, then one int32 count per block — of the
+    // newest planes (published or not), built here if the context has not been building them (everything is drained above)
+    case 5: {
+      if (!hasDepth) return LSDHIP_E_STATE;
       if (level < 1) return LSDHIP_E_ARG;
-      {
-        // of the newest planes (published or not), built here if the context has not been building them (everything is drained above)
-        const bool pend = f->depthPending;
-        bool& valid = pend ? f->refBlkValidW : f->refBlkValid;
-        uint8_t** blk = pend ? f->d_refBlkW : f->d_refBlk;
-        if (!valid) {
-          DepthPyrArgs pa;
-          memset((void*)&pa, 0, sizeof(pa));
-          for (int l = 0; l < LSD_LEVELS; l++) { pa.id[l] = lsd_g(lsd_depth_latest(f)[l]); pa.var[l] = lsd_g(lsd_depthvar_latest(f)[l]); pa.blk[l] = lsd_g(blk[l]); }
-          pa.w0 = c->w; pa.h0 = c->h;
-          hipLaunchKernelGGL(k_ref_blocks, dim3(lsd_refblk_grid(c)), dim3(256), 0, c->stream, pa);
-          valid = true;
-        }
-        src = blk[level];
+      const DepthPlaneSet s = depth_plane_set(f, DepthSet::Latest);
+      if (!*s.blkValid) {
+        hipLaunchKernelGGL(k_ref_blocks, dim3(lsd_refblk_grid(c)), dim3(256), 0, c->stream, depth_pyr_args(f, DepthSet::Latest));
+        *s.blkValid = true;
       }
-      HIPCHK(hipMemcpyAsync(out, src, lsd_refblk_bytes((int)n), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      return LSDHIP_OK;
+      src = s.blk[level]; bytes = lsd_refblk_bytes((int)n);
+      break;
+    }
     // the keyframe planes' gradient candidates (k_grad_candidates), as uint16: ceil(pixels / 1024) groups of 1024 offsets, then one count per group
-    case 6:
-      if (level != 0) return LSDHIP_E_ARG;
-      HIPCHK(hipMemcpyAsync(out, f->d_gradCand, lsd_gradcand_bytes((int)n), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(hipStreamSynchronize(c->stream));
-      return LSDHIP_OK;
+    case 6: if (level != 0) return LSDHIP_E_ARG; src = f->d_gradCand; bytes = lsd_gradcand_bytes((int)n); break;
     default: return LSDHIP_E_ARG;
   }
-  HIPCHK(hipMemcpyAsync(out, src, n * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return LSDHIP_OK;
+  return copy_and_wait(out, src, bytes, hipMemcpyDeviceToHost, c->stream);
 }
 
+// The tail of the synchronous Frame::setDepth entries: level 0 of the written planes is queued on the mapping stream; the pyramid, the
+// wait (the caller may reuse its host buffers), and on pipelined contexts the planes are visible to the tracker at once
+static int set_depth_finish(lsdhip_frame* f) {
+  lsdhip_ctx* c = f->ctx;
+  int rc = lsd_frame_build_idepth_pyramid(f);
+  HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));
+  if (rc == LSDHIP_OK && c->pipeline) { f->depthPendingSeq = 0; rc = lsd_frame_publish_depth(f); }
+  return rc;
+}
 extern "C" int lsdhip_frame_set_depth_gt(lsdhip_frame* f, const float* depth_host, float cov_scale) {
   if (!f || !depth_host) return LSDHIP_E_ARG;
   lsdhip_ctx* c = f->ctx;
   LSD_CTX_LOCK(c);
-  int n0 = c->w * c->h;
+  const int n0 = c->w * c->h;
   // staging plane kept by the context (ground-truth depth arrives once per keyframe in the GT-initialised modes)
   if (!c->d_gtStage) HIPCHK(hipMalloc((void**)&c->d_gtStage, (size_t)n0 * 4));
-  float* d_depth = c->d_gtStage;
-  if (c->pipeline) { if (int rcs = lsd_sync_all(c)) return rcs; }
+  if (int rc = drain_for_host(c)) return rc;
   const hipStream_t ms = lsd_map_stream(c);
-  if (int rcl = lsd_frame_require_level0(f)) return rcl;   // Frame::setDepthFromGroundTruth reads maxGradients(0) (Frame.cpp:259)
-  HIPCHK(hipMemcpyAsync(d_depth, depth_host, (size_t)n0 * 4, hipMemcpyHostToDevice, ms));
-  hipLaunchKernelGGL(k_set_depth_gt, dim3((n0 + 255) / 256), dim3(256), 0, ms, d_depth, f->d_maxgrad, lsd_depth_w(f)[0],
-                     lsd_depthvar_w(f)[0], c->w, c->h, cov_scale, c->params.minUseGrad);
-  int rc = lsd_frame_build_idepth_pyramid(f);
-  HIPCHK(hipStreamSynchronize(ms));   // the host buffer may be reused by the caller
-  if (rc == LSDHIP_OK && c->pipeline) { f->depthPendingSeq = 0; rc = lsd_frame_publish_depth(f); }   // a synchronous call: visible to the tracker at once
-  return rc;
+  if (int rc = lsd_frame_require_level0(f)) return rc;   // Frame::setDepthFromGroundTruth reads maxGradients(0) (Frame.cpp:259)
+  const DepthPlaneSet s = depth_plane_set(f, DepthSet::Written);
+  HIPCHK(hipMemcpyAsync(c->d_gtStage, depth_host, (size_t)n0 * 4, hipMemcpyHostToDevice, ms));
+  hipLaunchKernelGGL(k_set_depth_gt, dim3((n0 + 255) / 256), dim3(256), 0, ms, c->d_gtStage, f->d_maxgrad, s.id[0], s.var[0], c->w, c->h,
+                     cov_scale, c->params.minUseGrad);
+  return set_depth_finish(f);
 }
 extern "C" int lsdhip_frame_set_depth_planes(lsdhip_frame* f, const float* id, const float* var) {
   if (!f || !id || !var) return LSDHIP_E_ARG;
   lsdhip_ctx* c = f->ctx;
   LSD_CTX_LOCK(c);
-  size_t n0 = (size_t)c->w * c->h;
-  if (c->pipeline) { if (int rcs = lsd_sync_all(c)) return rcs; }
+  const size_t n0 = (size_t)c->w * c->h;
+  if (int rc = drain_for_host(c)) return rc;
   const hipStream_t ms = lsd_map_stream(c);
-  HIPCHK(hipMemcpyAsync(lsd_depth_w(f)[0], id, n0 * 4, hipMemcpyHostToDevice, ms));
-  HIPCHK(hipMemcpyAsync(lsd_depthvar_w(f)[0], var, n0 * 4, hipMemcpyHostToDevice, ms));
-  int rc = lsd_frame_build_idepth_pyramid(f);
-  HIPCHK(hipStreamSynchronize(ms));
-  if (rc == LSDHIP_OK && c->pipeline) { f->depthPendingSeq = 0; rc = lsd_frame_publish_depth(f); }
-  return rc;
+  const DepthPlaneSet s = depth_plane_set(f, DepthSet::Written);
+  HIPCHK(hipMemcpyAsync(s.id[0], id, n0 * 4, hipMemcpyHostToDevice, ms));
+  HIPCHK(hipMemcpyAsync(s.var[0], var, n0 * 4, hipMemcpyHostToDevice, ms));
+  return set_depth_finish(f);
 }
 // Test / synthetic-benchmark hook: overwrite the level-0 maxGradients plane (scene S3 of SURVEY.md §8(d) generates
 // hypothesis maps and gradient masks directly, without images)
@@ -1804,16 +1786,13 @@ extern "C" int lsdhip_frame_set_maxgrad(lsdhip_frame* f, const float* maxgrad_ho
   lsdhip_ctx* c = f->ctx;
   LSD_CTX_LOCK(c);
   HIPCHK(hipSetDevice(c->device));
-  if (int rcl = lsd_frame_require_level0_for_tracking(f)) return rcl;   // (the planes count as built from here on: the overwrite below must be the last word)
-  if (c->pipeline) { if (int rcs = lsd_sync_all(c)) return rcs; }
-  else if (lsd_map_stream(c) != c->stream) HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));
+  if (int rc = lsd_frame_require_level0_for_tracking(f)) return rc;   // (the planes count as built from here on: the overwrite below must be the last word)
+  if (int rc = drain_for_host(c, true)) return rc;
   HIPCHK(hipMemcpyAsync(f->d_maxgrad, maxgrad_host, (size_t)c->w * c->h * 4, hipMemcpyHostToDevice, c->stream));
-  {
-    GradCandItem gc;     // the keyframe's gradient candidates follow the plane
-    gc.maxgrad = lsd_g((const float*)f->d_maxgrad); gc.cand = lsd_g(f->d_gradCand);
-    hipLaunchKernelGGL(k_grad_candidates, dim3(lsd_gradcand_groups(c->w * c->h)), dim3(256), 0, c->stream, gc, c->w, c->h, c->params.minUseGrad);
-    f->gradCandTh = c->params.minUseGrad;
-  }
+  GradCandItem gc;     // the keyframe's gradient candidates follow the plane
+  gc.maxgrad = lsd_g((const float*)f->d_maxgrad); gc.cand = lsd_g(f->d_gradCand);
+  hipLaunchKernelGGL(k_grad_candidates, dim3(lsd_gradcand_groups(c->w * c->h)), dim3(256), 0, c->stream, gc, c->w, c->h, c->params.minUseGrad);
+  f->gradCandTh = c->params.minUseGrad;
   HIPCHK(hipStreamSynchronize(c->stream));
   return LSDHIP_OK;
 }
@@ -1822,18 +1801,16 @@ extern "C" int lsdhip_frame_get_wasgood(lsdhip_frame* f, uint8_t* out) {
   if (!f->wasGoodValid) return 0;
   lsdhip_ctx* c = f->ctx;
   LSD_CTX_LOCK(c);
-  if (c->pipeline) { if (int rcs = lsd_sync_all(c)) return rcs; }
-  HIPCHK(hipMemcpyAsync(out, f->d_wasGood, (size_t)c->wl[1] * c->hl[1], hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int rc = drain_for_host(c)) return rc;
+  if (int rc = copy_and_wait(out, f->d_wasGood, (size_t)c->wl[1] * c->hl[1], hipMemcpyDeviceToHost, c->stream)) return rc;
   return 1;
 }
 extern "C" int lsdhip_frame_set_wasgood(lsdhip_frame* f, const uint8_t* in) {
   if (!f || !in) return LSDHIP_E_ARG;
   lsdhip_ctx* c = f->ctx;
   LSD_CTX_LOCK(c);
-  if (c->pipeline) { if (int rcs = lsd_sync_all(c)) return rcs; }
-  HIPCHK(hipMemcpyAsync(f->d_wasGood, in, (size_t)c->wl[1] * c->hl[1], hipMemcpyHostToDevice, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int rc = drain_for_host(c)) return rc;
+  if (int rc = copy_and_wait(f->d_wasGood, in, (size_t)c->wl[1] * c->hl[1], hipMemcpyHostToDevice, c->stream)) return rc;
   f->wasGoodValid = true;
   f->wasGoodPristine = false;
   return LSDHIP_OK;
@@ -1913,13 +1890,13 @@ extern "C" int lsdhip_ref_pointcloud(lsdhip_frame* kf, int level, float* pos, fl
   LSD_CTX_LOCK(c);
   int w = c->wl[level], h = c->hl[level];
   size_t nmax = (size_t)w * h;
-  if (c->pipeline) { if (int rcs = lsd_sync_all(c)) return rcs; }
+  if (int rc = drain_for_host(c)) return rc;
   char* scratch = nullptr;
   size_t bytes = (size_t)(w + 1) * 4 + nmax * (12 + 8 + 8 + 4) + 1024;
   HIPCHK(hipMalloc((void**)&scratch, bytes));
   int* d_col = (int*)scratch;
   int* d_total = d_col + w;
-  float* d_pos = (float*)(scratch + align_up((size_t)(w + 1) * 4, 256));
+  float* d_pos = (float*)(scratch + lsd_align_up((size_t)(w + 1) * 4, 256));
   float* d_cv = d_pos + nmax * 3;
   float* d_gr = d_cv + nmax * 2;
   int* d_idx = (int*)(d_gr + nmax * 2);
@@ -1929,8 +1906,7 @@ extern "C" int lsdhip_ref_pointcloud(lsdhip_frame* kf, int level, float* pos, fl
   hipLaunchKernelGGL(k_pc_write, dim3((w + 255) / 256), dim3(256), 0, c->stream, kf->d_idepth[level], kf->d_idepthVar[level],
                      kf->d_image[level], kf->d_grad[level], w, h, in.fxi, in.fyi, in.cxi, in.cyi, d_col, d_pos, d_cv, d_gr, d_idx);
   int total = 0;
-  HIPCHK(hipMemcpyAsync(&total, d_total, 4, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
+  if (int rc = copy_and_wait(&total, d_total, 4, hipMemcpyDeviceToHost, c->stream)) return rc;
   if (pos) HIPCHK(hipMemcpy(pos, d_pos, (size_t)total * 12, hipMemcpyDeviceToHost));
   if (colvar) HIPCHK(hipMemcpy(colvar, d_cv, (size_t)total * 8, hipMemcpyDeviceToHost));
   if (grad) HIPCHK(hipMemcpy(grad, d_gr, (size_t)total * 8, hipMemcpyDeviceToHost));

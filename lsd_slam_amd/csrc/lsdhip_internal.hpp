@@ -29,6 +29,7 @@ void lsd_set_error(const char* fmt, ...);
 
 #include "pose_math.hpp"  // lsdm:: pose algebra (host + device)
 
+#include "frame_layout.hpp"   // the arena of a frame, lsd_refblk_* / lsd_gradcand_* sizes (plain C++: tests/cpp/frame_layout_test.cpp)
 #include "rcp_exact.hpp"   // lsd_rcp_exact: 1.0f / x bit for bit in 4 instructions (its own header: tools/rcp_exhaustive.hip checks the same code)
 
 // ---- device-visible parameter blocks --------------------------------------------------------------------
@@ -290,6 +291,7 @@ struct lsdhip_ctx {
     unsigned long long argsSerial = 0, argsGen = 0;
   } batchForm[2];
   std::vector<struct lsdhip_depthmap*> depthmaps;   // alive on this context: a destroyed frame is unhooked from them
+  LsdFrameLayout frameLayout;            // where a frame's planes lie in its arena (frame_alloc computes it once: n == 0 until then)
   size_t arena_bytes = 0;
 };
 
@@ -536,11 +538,6 @@ inline void lsd_trace_val(lsdhip_ctx*, int, int, unsigned long long) {}
 // depth planes a Frame::setDepth writes / the most recently written ones (== d_idepth on non-pipelined contexts)
 inline float** lsd_depth_w(lsdhip_frame* f) { return f->ctx->pipeline ? f->d_idepthW : f->d_idepth; }
 inline float** lsd_depthvar_w(lsdhip_frame* f) { return f->ctx->pipeline ? f->d_idepthVarW : f->d_idepthVar; }
-inline uint8_t** lsd_refblk_w(lsdhip_frame* f) { return f->ctx->pipeline ? f->d_refBlkW : f->d_refBlk; }
-inline int lsd_gradcand_groups(int pixels) { return (pixels + 1023) >> 10; }
-inline size_t lsd_gradcand_bytes(int pixels) { return ((size_t)lsd_gradcand_groups(pixels) * 1024 + (size_t)lsd_gradcand_groups(pixels)) * 2; }
-inline int lsd_refblk_blocks(int pixels) { return (pixels + 255) >> 8; }
-inline size_t lsd_refblk_bytes(int pixels) { return (size_t)lsd_refblk_blocks(pixels) * (256 + 4); }
 inline float** lsd_depth_latest(lsdhip_frame* f) { return f->depthPending ? f->d_idepthW : f->d_idepth; }
 inline float** lsd_depthvar_latest(lsdhip_frame* f) { return f->depthPending ? f->d_idepthVarW : f->d_idepthVar; }
 int lsd_frame_publish_depth(lsdhip_frame* f);

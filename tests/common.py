@@ -44,3 +44,20 @@ def pose_distance(pa, pb, po):
     """|log(Ta^-1 Tb)| split into (translation, rotation) norms; po = oracle.pyoracle (SE3 helpers)."""
     d = po.se3_log(po.se3_mul(po.se3_inv(pa), pb))
     return float(np.linalg.norm(d[:3])), float(np.linalg.norm(d[3:]))
+
+
+def assert_reference_blocks_list(offs, cnts, idl, varl, lvl):
+    """(offs, cnts) = Frame.referenceBlocks(lvl) against the level's planes: per 256 consecutive pixels exactly the pixels the reference's
+    makePointCloud test takes — inside the one-pixel border, idepthVar > 0, idepth != 0 (TrackingReference.cpp:120-131) — in pixel order."""
+    hl, wl = idl.shape
+    ok = (varl > 0) & (idl != 0)
+    ok[0, :] = ok[-1, :] = False
+    ok[:, 0] = ok[:, -1] = False
+    flat = ok.reshape(-1)
+    nblk = (wl * hl + 255) // 256
+    assert offs.shape == (nblk, 256) and cnts.shape == (nblk,)
+    for b in range(nblk):
+        want = np.flatnonzero(flat[b * 256:(b + 1) * 256])
+        assert cnts[b] == len(want), "level %d block %d: count" % (lvl, b)
+        assert np.array_equal(offs[b, :len(want)], want.astype(np.uint8)), "level %d block %d: offsets" % (lvl, b)
+    assert int(cnts.sum()) == int(flat.sum())

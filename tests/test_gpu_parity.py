@@ -7,7 +7,7 @@ import os
 import numpy as np
 import pytest
 
-from common import ODOMETRY_ITS, assert_bit_equal, pose_distance, sequence
+from common import ODOMETRY_ITS, assert_bit_equal, assert_reference_blocks_list, pose_distance, sequence
 from se3_terms import oracle_terms64 as _oracle_terms64
 
 pytestmark = pytest.mark.gpu
@@ -105,20 +105,10 @@ def test_reference_blocks_list_the_oracles_reference_pixels(oracle, hip, w, h):
     fo.set_depth_planes(idp, var)
     fg.setDepthPlanes(idp, var)
     for lvl in range(1, 5):
-        wl, hl = w >> lvl, h >> lvl
         idl, varl = fo.plane("idepth", lvl), fo.plane("idepthVar", lvl)
-        ok = (varl > 0) & (idl != 0)
-        ok[0, :] = ok[-1, :] = False
-        ok[:, 0] = ok[:, -1] = False
-        flat = ok.reshape(-1)
+        assert idl.shape == (h >> lvl, w >> lvl)
         offs, cnts = fg.referenceBlocks(lvl)
-        nblk = (wl * hl + 255) // 256
-        assert offs.shape == (nblk, 256) and cnts.shape == (nblk,)
-        for b in range(nblk):
-            want = np.flatnonzero(flat[b * 256:(b + 1) * 256])
-            assert cnts[b] == len(want), "level %d block %d: count" % (lvl, b)
-            assert np.array_equal(offs[b, :len(want)], want.astype(np.uint8)), "level %d block %d: offsets" % (lvl, b)
-        assert int(cnts.sum()) == int(flat.sum())
+        assert_reference_blocks_list(offs, cnts, idl, varl, lvl)
 
 
 @pytest.mark.parametrize("w,h", [(160, 128), (640, 480), (656, 496)])
