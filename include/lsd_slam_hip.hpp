@@ -602,6 +602,26 @@ class DepthMap {
     check(lsdhip_depth_download(h_, v.data()), "lsdhip_depth_download");
     return v;
   }
+  // DepthMap::debugPlotDepthMap (DepthMap.cpp:1400-1428): the keyframe in grey with the hypotheses painted over it, drawn on the device
+  // into debugImageDepth (uint8 [h][w][3]); debugDisplay is the reference's global of that name (util/settings.cpp:35).  Waits for the
+  // mapping stream (one launch and a copy of 3 bytes per pixel).  Returns 1, as the reference does.
+  int debugPlotDepthMap(int debugDisplay = 0) {
+    if (!isValid()) return 1;
+    debugImageDepth.resize((size_t)ctx_->width() * ctx_->height() * 3);
+    check(lsdhip_depth_debug_plot(h_, debugDisplay, debugImageDepth.data()), "lsdhip_depth_debug_plot");
+    return 1;
+  }
+  // the same image into device memory (3 * w * h bytes, 4-byte aligned): queued behind the map's calls, nothing waits
+  void debugPlotDepthMapDevice(unsigned char* dev, int debugDisplay) { check(lsdhip_depth_debug_plot_dev(h_, debugDisplay, dev), "lsdhip_depth_debug_plot_dev"); }
+  // ... of several maps of one context in one launch (lsdhip_depth_debug_plot_batch)
+  static void debugPlotDepthMapBatch(const std::vector<DepthMap*>& maps, const std::vector<unsigned char*>& devs, int debugDisplay) {
+    if (maps.empty()) return;
+    if (devs.size() != maps.size()) throw Error(LSDHIP_E_ARG, "DepthMap::debugPlotDepthMapBatch: one device buffer per map");
+    std::vector<lsdhip_depthmap*> ms;
+    for (DepthMap* m : maps) ms.push_back(m->h_);
+    check(lsdhip_depth_debug_plot_batch((int)ms.size(), ms.data(), debugDisplay, devs.data()), "lsdhip_depth_debug_plot_batch");
+  }
+  std::vector<unsigned char> debugImageDepth;
   // smoothed idepth / variance planes of the active keyframe, device to device (payload of the multi-GPU gather)
   void copyPlanesToDevice(float* idepth_dev, float* idepthVar_dev) { check(lsdhip_depth_copy_planes_dev(h_, idepth_dev, idepthVar_dev), "lsdhip_depth_copy_planes_dev"); }
 
@@ -688,6 +708,11 @@ class SlamLoop {
   // that keyframe stay as finalised.  A hook that waits for the device (a download, makeKeyframeMsgDevice) is still correct, but stalls the
   // loop for that wait once per keyframe.  Setting the hook leaves the loop on the shared keyframe change.
   std::function<void(Frame&)> onKeyframeFinishedAsync;
+  // called right after a frame's mapping iteration (updateKeyframe, or the keyframe change) has been queued: where
+  // SlamSystem::doMappingIteration calls debugDisplayDepthMap (SlamSystem.cpp:777-797).  Meant for stream-ordered work
+  // (DepthMap::debugPlotDepthMapDevice queues one launch and returns); a hook that waits (debugPlotDepthMap) stalls the loop for that wait
+  // once per frame.  Unset, the loop is unchanged.
+  std::function<void(DepthMap&)> onMappingIteration;
   // track one frame, then one mapping iteration; returns frameToKeyframe (of the keyframe the frame was tracked on).  Throws when
   // tracking diverges.
   SE3 step(const unsigned char* image) { return step(image, [](double) {}); }
@@ -808,6 +833,7 @@ class SlamLoop {
       }
       sinceKF_ = 0;
       newKeyframe = true;
+      if (onMappingIteration) onMappingIteration(map);
     } else if (pipelined_ && deferMapping) {
       deferredMap_ = frame;       // queued from the next tracking job's enqueue hook (or flushDeferredMapping)
     } else {
@@ -848,6 +874,7 @@ class SlamLoop {
     frame->clear_refPixelWasGood();
     numUpdates++;
     lsdhip_host_mark(14);
+    if (onMappingIteration) onMappingIteration(map);
   }
   std::shared_ptr<Frame> deferredMap_;
   std::shared_ptr<Frame> makeFrame(int id, const unsigned char* img, bool mayDefer = false) {

@@ -4,7 +4,9 @@
 //   * binary PGM (P5) image files for the image-folder driver (the reference reads through OpenCV, which is not here);
 //   * the keyframe message of lsd_slam_viewer (msg/keyframeMsg.msg; InputPointDense payload V/KeyFrameDisplay.h:39-44,
 //     filled as C/IOWrapper/ROS/ROSOutput3DWrapper.cpp:70-111) in ROS 1 wire serialisation;
-//   * the viewer's point-cloud export (V/KeyFrameDisplay.cpp:269-340 flushPC + V/KeyFrameGraphDisplay.cpp:60-94 PLY header).
+//   * the viewer's point-cloud export (V/KeyFrameDisplay.cpp:269-340 flushPC + V/KeyFrameGraphDisplay.cpp:60-94 PLY header);
+//   * the depth map's debug image (C/DepthEstimation/DepthMap.cpp:1400-1428 debugPlotDepthMap) as plotDepthMap, and binary PPM (P6) files
+//     for it: the yardstick of DepthMap::debugPlotDepthMap (lsdhip_depth_debug_plot), which draws the same bytes on the device.
 // The formats and their host-side fill loops (makeKeyframeMsg, flushPointCloud) are plain host code and the yardstick of the device
 // export: makeKeyframeMsgDevice packs the payload on the GPU (lsdhip_frame_pack_keyframe_points) and PointCloud (lsd_slam_hip.hpp)
 // builds the viewer's cloud there, both held bit for bit to the host functions below; cloudConstants is the one place the per-keyframe
@@ -12,6 +14,7 @@
 #ifndef LSD_SLAM_HIP_IO_HPP
 #define LSD_SLAM_HIP_IO_HPP
 
+#include <cmath>
 #include <cstdio>
 #include <fstream>
 #include <sstream>
@@ -78,6 +81,60 @@ inline bool writePGM(const std::string& path, int w, int h, const unsigned char*
   bool ok = fwrite(data, 1, (size_t)w * h, f) == (size_t)w * h;
   fclose(f);
   return ok;
+}
+
+inline bool writePPM(const std::string& path, int w, int h, const unsigned char* rgb) {
+  FILE* f = fopen(path.c_str(), "wb");
+  if (!f) return false;
+  fprintf(f, "P6\n%d %d\n255\n", w, h);
+  bool ok = fwrite(rgb, 1, (size_t)w * h * 3, f) == (size_t)w * h * 3;
+  fclose(f);
+  return ok;
+}
+
+// DepthMapPixelHypothesis::getVisualizationColor (DepthMapPixelHypothesis.cpp:29-90) with the reference's operations, promotions and
+// order; debugDisplay is the reference's global (util/settings.cpp:35).  Inputs on which the reference's float -> uchar cast is
+// undefined behaviour are defined: a NaN idepth is white (modes 0 / 1), a NaN or negative variance (0, 0, 255) (modes 3 / 4), a NaN
+// byte value 0 (modes 2 / 5).
+inline void visualizationColor(const lsdhip_hypothesis& hyp, int debugDisplay, int lastFrameID, unsigned char c[3]) {
+  auto clampByte = [](float f) -> unsigned char { return !(f > 0) ? 0 : (f > 255 ? 255 : (unsigned char)f); };
+  c[0] = c[1] = c[2] = 255;
+  if (debugDisplay == 0 || debugDisplay == 1) {
+    const float id = debugDisplay == 0 ? hyp.idepth_smoothed : hyp.idepth;
+    if (!(id >= 0)) return;
+    // rainbow between 0 and 4
+    float r = (0 - id) * 255 / 1.0; if (r < 0) r = -r;
+    float g = (1 - id) * 255 / 1.0; if (g < 0) g = -g;
+    float b = (2 - id) * 255 / 1.0; if (b < 0) b = -b;
+    c[0] = (unsigned char)(255 - clampByte(r)); c[1] = (unsigned char)(255 - clampByte(g)); c[2] = (unsigned char)(255 - clampByte(b));
+  } else if (debugDisplay == 2) {
+    const float f = hyp.validity_counter * (255.0 / (250.0f + 5.0f));   // VALIDITY_COUNTER_MAX_VARIABLE + VALIDITY_COUNTER_MAX
+    c[0] = 0; c[1] = c[2] = clampByte(f);
+  } else if (debugDisplay == 3 || debugDisplay == 4) {
+    const float idv = debugDisplay == 3 ? hyp.idepth_var_smoothed : hyp.idepth_var;
+    float var = -0.5 * std::log10((double)idv);     // (the reference's unqualified log10 is the double overload)
+    var = var * 255 * 0.333;
+    if (var > 255) var = 255;
+    if (!(var >= 0)) { c[0] = 0; c[1] = 0; c[2] = 255; return; }
+    c[0] = (unsigned char)(255 - var); c[1] = (unsigned char)var; c[2] = 0;
+  } else if (debugDisplay == 5) {
+    const float f = (hyp.nextStereoFrameMinID - lastFrameID) * (255.0 / 100);
+    c[0] = c[2] = clampByte(f); c[1] = 0;
+  }
+}
+
+// DepthMap::debugPlotDepthMap (DepthMap.cpp:1400-1428): `image` is the keyframe's level-0 image, refID the map's
+// referenceFrameByID_offset, out uint8 [h][w][3].  Plain host code: what lsdhip_depth_debug_plot is held to, byte for byte.
+inline void plotDepthMap(const lsdhip_hypothesis* map, const float* image, int w, int h, int debugDisplay, int refID, unsigned char* out) {
+  for (int idx = 0; idx < w * h; idx++) {
+    // cv::Mat::convertTo(CV_8UC1): cvRound (to nearest even), saturated; cvtColor(GRAY2RGB)
+    const long r = std::lrint(image[idx]);
+    unsigned char* px = out + 3 * (size_t)idx;
+    px[0] = px[1] = px[2] = (unsigned char)(r < 0 ? 0 : (r > 255 ? 255 : r));
+    if (map[idx].blacklisted < -1 /* MIN_BLACKLIST */ && debugDisplay == 2) { px[0] = 0; px[1] = 0; px[2] = 255; }
+    if (!map[idx].isValid) continue;
+    visualizationColor(map[idx], debugDisplay, refID, px);
+  }
 }
 
 // V/KeyFrameDisplay.h:39-44

@@ -411,6 +411,22 @@ int lsdhip_ctx_batch_form(lsdhip_ctx* ctx, int which, int out[8], int* queueCoun
 /* currentDepthMap <-> host in the reference's 32-byte AoS layout (debug / parity / drop-in users that read it) */
 int lsdhip_depth_download(lsdhip_depthmap* dm, lsdhip_hypothesis* out_host);
 int lsdhip_depth_upload(lsdhip_depthmap* dm, lsdhip_frame* kf, const lsdhip_hypothesis* in_host, int reactivated);
+/* DepthMap::debugPlotDepthMap (DepthMap.cpp:1400-1428) with DepthMapPixelHypothesis::getVisualizationColor (DepthMapPixelHypothesis.cpp:29-90)
+ * for debugDisplay 0 .. 5 (C/util/settings.h:180; any other value paints every valid pixel white, DepthMapPixelHypothesis.cpp:89): the active keyframe's level-0 image
+ * as grey (cv::Mat::convertTo(CV_8UC1): round to nearest even, clamp) with the valid hypotheses painted over it, uint8 [h][w][3] in the byte
+ * order of the reference's cv::Vec3b.  refID of mode 5 is referenceFrameByID_offset (:1082): the id of the oldest frame of the map's last
+ * lsdhip_depth_update / _update_batch, 0 before the first.  One launch on the stream the map's calls run on (the mapping stream of a
+ * pipelined context), a copy of 3 * w * h bytes and a wait for that stream only, as lsdhip_depth_download; the map is read, never written.
+ * Equal byte for byte to plotDepthMap of lsd_slam_hip_io.hpp.  Inputs the reference leaves undefined (its byte cast of the result is
+ * undefined behaviour) are defined: a NaN idepth is white in modes 0 / 1, a NaN or negative variance (0, 0, 255) in modes 3 / 4, a NaN
+ * nextStereoFrameMinID byte 0 in mode 5.  LSDHIP_E_STATE without an active keyframe, LSDHIP_E_ARG for a null pointer. */
+int lsdhip_depth_debug_plot(lsdhip_depthmap* dm, int debugDisplay, uint8_t* out_host);
+/* DepthMap::debugPlotDepthMap (DepthMap.cpp:1400-1428), the same image into device memory (3 * w * h bytes, 4-byte aligned): queued behind the map's calls, returns at once, waits for nothing. */
+int lsdhip_depth_debug_plot_dev(lsdhip_depthmap* dm, int debugDisplay, uint8_t* out_dev);
+/* debugPlotDepthMap (DepthMap.cpp:1400-1428) of n maps of one context in ONE launch (blockIdx.y = map), each into its own device buffer as
+ * lsdhip_depth_debug_plot_dev; queued, no wait.  LSDHIP_E_ARG for null or misaligned pointers or maps of different contexts, LSDHIP_E_STATE
+ * if a map has no active keyframe (nothing is queued then). */
+int lsdhip_depth_debug_plot_batch(int n, lsdhip_depthmap** maps, int debugDisplay, uint8_t* const* out_dev);
 /* single stages for kernel-level parity: 0 observeDepth (refs/n as in update), 1 regularizeDepthMapFillHoles,
  * 2 regularizeDepthMap(false,24), 3 regularizeDepthMap(true,24), 4 propagateDepth(refs[0] = new keyframe),
  * 5 regularizeDepthMapFillHoles + regularizeDepthMap(false,24) fused in one launch (what updateKeyframe runs) */

@@ -211,7 +211,14 @@ void DepthMap::finalizeKeyFrame() {
   nFinalize++; nSetDepth++;
 }
 
-int DepthMap::debugPlotDepthMap() { return 0; }        // the debug images of the CPU implementation are not produced
+// DepthMap.cpp:1400-1428, drawn on the device from the map's planes (lsdhip_depth_debug_plot: one launch and a copy of 3 bytes per pixel);
+// the other debug images of the CPU implementation (hypothesis handling / propagation, stereo lines) are not produced
+int DepthMap::debugPlotDepthMap() {
+  if (activeKeyFrame == 0) return 1;
+  if (debugImageDepth.rows != height || debugImageDepth.cols != width || debugImageDepth.type() != CV_8UC3) debugImageDepth = cv::Mat(height, width, CV_8UC3);
+  lsd_slam_hipbind::check(lsdhip_depth_debug_plot(state_of(this).h, debugDisplay, debugImageDepth.data), "lsdhip_depth_debug_plot");
+  return 1;
+}
 void DepthMap::addTimingSample() {
   struct timeval now;
   gettimeofday(&now, NULL);

@@ -13,7 +13,7 @@ OUT = os.path.join(HERE, "liblsdhip.so")
 # kernels allowed to spill a few loop-invariant registers (long, memory-bound batch kernels where occupancy matters more;
 # the latency-critical single-job kernels must stay at zero)
 SCRATCH_OK = ()
-SOURCES = ["host_math.cpp", "frame.hip", "tracker.hip", "depthmap.hip", "sim3.hip", "cloud.hip"]
+SOURCES = ["host_math.cpp", "frame.hip", "tracker.hip", "depthmap.hip", "sim3.hip", "cloud.hip", "plot.hip"]
 # -disable-promote-alloca-to-lds: a private array the optimiser cannot split must show up as scratch (and fail the
 # guard below) instead of silently moving to LDS, where indexing it by thread costs a read of the AQL dispatch packet
 # in host memory (~20 us per launch, measured — profiles/r01_notes.md).

@@ -176,6 +176,9 @@ def _signatures():
         "lsdhip_depth_finalize": (i, [vp]),
         "lsdhip_depth_download": (i, [vp, vp]),
         "lsdhip_depth_upload": (i, [vp, vp, vp, i]),
+        "lsdhip_depth_debug_plot": (i, [vp, i, vp]),
+        "lsdhip_depth_debug_plot_dev": (i, [vp, i, vp]),
+        "lsdhip_depth_debug_plot_batch": (i, [i, pvp, i, pvp]),
         "lsdhip_depth_stage": (i, [vp, i, pvp, i]),
         "lsdhip_depth_copy_planes_dev": (i, [vp, vp, vp]),
         "lsdhip_depth_copy_rows_dev": (i, [vp, i, i, vp, i]),

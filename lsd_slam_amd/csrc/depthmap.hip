@@ -2330,6 +2330,7 @@ extern "C" int lsdhip_depth_update(lsdhip_depthmap* dm, lsdhip_frame** refs, int
   rc = map_call_end(c);
   if (rc) return rc;
   dm->msUpdate = ema(dm->msUpdate, now_ms() - t0);   // host wall time of the call (enqueue time only in async mode)
+  dm->referenceFrameByIDOffset = refs[0]->id;
   kf->numMappedOnThis++;
   kf->numMappedOnThisTotal++;
   return LSDHIP_OK;
@@ -2484,6 +2485,7 @@ extern "C" int lsdhip_depth_update_batch(int n, lsdhip_depthmap** maps, lsdhip_f
   for (int j = 0; j < n; j++) {
     lsdhip_depthmap* dm = maps[j];
     dm->msUpdate = ema(dm->msUpdate, dt / n);
+    dm->referenceFrameByIDOffset = refs[j]->id;
     dm->activeKeyFrame->numMappedOnThis++;
     dm->activeKeyFrame->numMappedOnThisTotal++;
   }

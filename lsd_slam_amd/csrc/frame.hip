@@ -659,6 +659,7 @@ extern "C" void lsdhip_ctx_destroy(lsdhip_ctx* c) {
   if (c->d_obsBatchAcc) (void)hipFree(c->d_obsBatchAcc);
   if (c->d_gtStage) (void)hipFree(c->d_gtStage);
   if (c->d_kfPoints) (void)hipFree(c->d_kfPoints);
+  if (c->d_plotStage) (void)hipFree(c->d_plotStage);
   if (c->d_flagArrive) (void)hipFree(c->d_flagArrive);
   if (c->d_gate) (void)hipFree(c->d_gate);
   if (c->ev_a) (void)hipEventDestroy(c->ev_a);

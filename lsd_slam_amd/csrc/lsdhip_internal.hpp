@@ -274,6 +274,7 @@ struct lsdhip_ctx {
   size_t arena_keep = 16;                // arenas of destroyed frames kept for reuse (grows with the batch width of lsdhip_frame_create_batch)
   float* d_gtStage = nullptr;                        // w x h floats: staging of lsdhip_frame_set_depth_gt
   uint8_t* d_kfPoints = nullptr;                     // w x h x 12 bytes: staging of lsdhip_frame_pack_keyframe_points (cloud.hip)
+  uint8_t* d_plotStage = nullptr;                    // w x h x 3 bytes: staging of lsdhip_depth_debug_plot (plot.hip)
   // kernel-argument arrays of the batched launches (several sequences per launch): pinned staging slots and their device twins,
   // reused round-robin; a slot is rewritten only after the launches that read it have completed (lsd_args_push / lsd_args_release)
   struct ArgRing {
@@ -463,6 +464,7 @@ struct lsdhip_depthmap {
   void* bases[3] = {nullptr, nullptr, nullptr};  // arena base pointers (for hipFree)
   lsdhip_frame* activeKeyFrame = nullptr;
   bool activeKeyFrameIsReactivated = false;
+  int referenceFrameByIDOffset = 0;   // id of the oldest frame of the last updateKeyframe (DepthMap.cpp:1082; 0 before the first): debugPlotDepthMap's refID
   char* h_stage = nullptr;         // pinned staging block (refs | refByID) and its device twin
   char* d_stage = nullptr;
   size_t stage_bytes = 0;

@@ -5,7 +5,7 @@
 // keyframe, and the viewer's PLY point cloud.
 //
 //   dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both]
-//                [--cloud-capacity POINTS]
+//                [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]]
 //
 // --cloud host (default): pc.ply and keyframe_<id>.msg from the host functions (three plane downloads and a host loop per keyframe).
 // --cloud device: every finished keyframe is appended to one PointCloud on the GPU behind the keyframe change (no split of the change; the
@@ -14,6 +14,9 @@
 // --cloud both: the host path writes pc.ply / keyframe_<id>.msg and the device path pc_device.ply / keyframe_<id>_device.msg, in the same
 //   run on the same keyframes: the like-for-like mode (a host run and a device run go through different keyframe-change paths, whose
 //   rescale factors differ in the last bits).
+// --depth-images DIR: after every mapping iteration the depth map's debug image (DepthMap::debugPlotDepthMap, drawn on the device: the
+//   keyframe in grey, the hypotheses in the colours of --debug-display N, the reference's debugDisplay 0 .. 5, default 0) is written to
+//   DIR/depth_<frame id>.ppm.  A file writer may wait: this is the host-output form, one launch and a copy of 3 bytes per pixel per frame.
 // --constraints 1 additionally aligns every new keyframe with the keyframe it replaces by Sim3Tracker::trackFrameSim3 (the
 // tracking-parent edge the reference's constraint search always tests, C/SlamSystem.cpp:1253-1262) and writes constraints.txt.
 #include <cstdlib>
@@ -45,11 +48,11 @@ static Sim3 sim3_mul(const Sim3& a, const Sim3& b) {
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::cerr << "usage: dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both] [--cloud-capacity POINTS]\n";
+    std::cerr << "usage: dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both] [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]]\n";
     return 2;
   }
-  int kfEvery = 0, device = 0, constraints = 0;
-  std::string cloudMode = "host";
+  int kfEvery = 0, device = 0, constraints = 0, debugDisplay = 0;
+  std::string cloudMode = "host", depthImages;
   long long cloudCapacity = 0;
   for (int i = 4; i + 1 < argc; i += 2) {
     if (!strcmp(argv[i], "--kf-every")) kfEvery = atoi(argv[i + 1]);
@@ -57,6 +60,8 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "--constraints")) constraints = atoi(argv[i + 1]);
     if (!strcmp(argv[i], "--cloud")) cloudMode = argv[i + 1];
     if (!strcmp(argv[i], "--cloud-capacity")) cloudCapacity = atoll(argv[i + 1]);
+    if (!strcmp(argv[i], "--depth-images")) depthImages = argv[i + 1];
+    if (!strcmp(argv[i], "--debug-display")) debugDisplay = atoi(argv[i + 1]);
   }
   if (cloudMode != "host" && cloudMode != "device" && cloudMode != "both") { std::cerr << "--cloud takes host, device or both\n"; return 2; }
   const bool hostCloud = cloudMode != "device", devCloud = cloudMode != "host";
@@ -107,6 +112,12 @@ int main(int argc, char** argv) {
       writeMsg(makeKeyframeMsgDevice(kf, kfToWorld, cal.K), hostCloud ? "_device" : "");
       if (!hostCloud) nKeyframes++;
     };
+    int currentFrame = 0;      // id of the frame whose step() is running
+    if (!depthImages.empty()) loop.onMappingIteration = [&](DepthMap& map) {
+      map.debugPlotDepthMap(debugDisplay);
+      const std::string path = depthImages + "/depth_" + std::to_string(currentFrame) + ".ppm";
+      if (!writePPM(path, w, h, map.debugImageDepth.data())) std::cerr << "dataset_slam: cannot write " << path << "\n";
+    };
     int good = 0, nConstraints = 0;
     std::unique_ptr<Sim3Tracker> sim3;
     std::ofstream cons;
@@ -118,6 +129,7 @@ int main(int argc, char** argv) {
     for (size_t i = 1; i < files.size(); i++) {
       if (!readPGM(files[i], w, h, img)) { std::cerr << "skipping " << files[i] << " (wrong size or unreadable)\n"; continue; }
       std::shared_ptr<Frame> parentKF = loop.keyframe;
+      currentFrame = (int)i;
       SE3 f2k = loop.step(img.data());
       if (constraints && loop.newKeyframe) {
         // new keyframe -> replaced keyframe, starting from the tracked pose with the depth rescale as scale

@@ -685,6 +685,26 @@ class DepthMap:
         hyp = np.ascontiguousarray(hyp, dtype=HYP_DTYPE)
         check(self.L.lsdhip_depth_upload(self.h_, kf.h_, hyp.ctypes.data, int(reactivated)), False)
 
+    def debugPlotDepthMap(self, debugDisplay=0, out_dev_ptr=None):
+        """DepthMap::debugPlotDepthMap (DepthMap.cpp:1400-1428) drawn on the device: uint8 [h, w, 3], the keyframe in grey with the valid
+        hypotheses in the colours of mode `debugDisplay` (the reference's global of that name).  out_dev_ptr: a device buffer of
+        3 * w * h bytes instead; the call then only queues the launch and returns None."""
+        if out_dev_ptr is not None:
+            check(self.L.lsdhip_depth_debug_plot_dev(self.h_, int(debugDisplay), C.c_void_p(out_dev_ptr)), False)
+            return None
+        out = np.zeros((self.ctx.h, self.ctx.w, 3), np.uint8)
+        check(self.L.lsdhip_depth_debug_plot(self.h_, int(debugDisplay), out.ctypes.data), False)
+        return out
+
+    @staticmethod
+    def debugPlotDepthMapBatch(maps, out_dev_ptrs, debugDisplay=0):
+        """the debug images of several maps of one context in one launch, each into its own device buffer (lsdhip_depth_debug_plot_batch);
+        queued, nothing waits"""
+        n = len(maps)
+        ma = (C.c_void_p * n)(*[m.h_ for m in maps])
+        oa = (C.c_void_p * n)(*[int(p) for p in out_dev_ptrs])
+        check(maps[0].L.lsdhip_depth_debug_plot_batch(n, ma, int(debugDisplay), oa), False)
+
     def stage(self, name, frames=()):
         frames = list(frames)
         self._keep.extend(frames)
