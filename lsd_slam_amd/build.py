@@ -50,7 +50,7 @@ def needs_build():
         return True
     t = os.path.getmtime(OUT)
     deps = [os.path.join(SRC, s) for s in SOURCES] + [os.path.join(SRC, "lsdhip_internal.hpp"), os.path.join(SRC, "pose_math.hpp"),
-                                                       os.path.join(SRC, "track_device.hpp"), os.path.join(SRC, "rcp_exact.hpp"), os.path.join(SRC, "frame_layout.hpp"),
+                                                       os.path.join(SRC, "track_device.hpp"), os.path.join(SRC, "rcp_exact.hpp"), os.path.join(SRC, "frame_layout.hpp"), os.path.join(SRC, "track_plan.hpp"),
                                                        os.path.join(HERE, "..", "include", "lsdhip.h"),
                                                        os.path.join(HERE, "..", "include", "lsd_slam_hip_cloud_constants.hpp")]
     return any(os.path.getmtime(d) > t for d in deps)

@@ -2,6 +2,8 @@
 // Frame / FramePoseStruct / SE3Tracker / DepthMap members; all per-pixel data lives in HBM as SoA planes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <atomic>
+#include <chrono>
 #include <cmath>
 #include <cstddef>
 #include <cstdint>
@@ -30,6 +32,7 @@ void lsd_set_error(const char* fmt, ...);
 #include "pose_math.hpp"  // lsdm:: pose algebra (host + device)
 
 #include "frame_layout.hpp"   // the arena of a frame, lsd_refblk_* / lsd_gradcand_* sizes (plain C++: tests/cpp/frame_layout_test.cpp)
+#include "track_plan.hpp"     // how a tracking job is run: tilings, trials, grids, launch budget and their constants (plain C++: tests/cpp/track_plan_test.cpp)
 #include "rcp_exact.hpp"   // lsd_rcp_exact: 1.0f / x bit for bit in 4 instructions (its own header: tools/rcp_exhaustive.hip checks the same code)
 
 // ---- device-visible parameter blocks --------------------------------------------------------------------
@@ -112,7 +115,6 @@ struct TrackSpec {
 };
 
 // Levenberg-Marquardt state of a tracking job, resident in HBM, advanced by k_lm_step.
-#define LSD_SPEC_MAX 6
 struct TrackState {
   lsdm::SE3fH T;             // last accepted referenceToFrame
   lsdm::SE3fH Tn;            // pose being evaluated
@@ -164,20 +166,11 @@ struct DeferredSlot { double sum, count, flag, pad; };
 // by tests/test_abi_cpu.py::test_header_prose_states_the_built_defaults.
 #define LSD_DEFAULT_ASYNC 0                 // lsdhip_ctx_set_async
 #define LSD_DEFAULT_PIPELINE 0              // lsdhip_ctx_set_pipeline
-#define LSD_SPEC_TRIALS_SMALL 6             // automatic speculation policy: trials per step on levels of up to LSD_SPEC_SMALL_PX pixels
-#define LSD_SPEC_SMALL_PX 6144
-#define LSD_SPEC_TRIALS_MID 5               // ... up to LSD_SPEC_MID_PX pixels; larger levels: one evaluation per step
-#define LSD_SPEC_MID_PX 90112
-#define LSD_SPEC_CAP_WORKGROUPS 80          // workgroups per trial on speculating levels above LSD_SPEC_CAP_ABOVE_PX pixels
-#define LSD_SPEC_CAP_ABOVE_PX 24576
+// (the tracker's speculation and batch policy: track_plan.hpp)
 #ifndef LSD_OBS_SPLIT_MIN_MAPS
 #define LSD_OBS_SPLIT_MIN_MAPS 4             // lsdhip_depth_update_batch: select + walk launches from this many maps on
 #endif
 #define LSD_OBS_WALK_WAVES 4096             // one-wave workgroups of the walk launch
-#define LSD_BATCH_THROUGHPUT_MIN_JOBS 8     // lsdhip_tracker_track_batch: throughput mode from this many jobs on
-#define LSD_BATCH_SPEC_MAX 4                // reject-chain speculation of batches in throughput mode: most trials per step (levels without a mask)
-#define LSD_BATCH_SPEC_PIXELS 500000        // ... trials per step at a level = what keeps jobs x trials x pixels of the level within this (1 M until round 5: 64-job batches lost 12 % to it)
-#define LSD_BATCH_STRIP_WORKGROUPS 768      // strips x jobs of a throughput-mode evaluation launch (3 workgroups per CU)
 struct lsdhip_frame;
 
 // Host-side state of a context (arena free list, deferred-result slot ring and its owner tables, profiling events, the
@@ -373,10 +366,10 @@ struct lsdhip_tracker {
   int levelEvaluations[LSD_LEVELS] = {};   // evaluations of the last job per pyramid level
   int block = 256;                // workgroup size of k_track_step (LSDHIP_TRACK_BLOCK)
   int grid_cap = 304;             // most workgroups one evaluation uses (LSDHIP_TRACK_CAP); larger levels grid-stride
-  int recent[4] = {0, 0, 0, 0};   // evaluating launches of the last jobs: size the launch budget of the next one
+  LaunchHistory recent;           // evaluating launches of the last jobs: size the launch budget of the next one
   int specC = 6;                  // most trials per launch (LSDHIP_SPEC; 1 = no speculation)
   int soloMinJobs = -1;           // batches of at least this many jobs walk their coarse levels in one workgroup per job (k_track_solo); 0: never; -1: build default
-  bool specAuto = true;           // trials per level from the level's size (see track_device); false after set_speculation
+  bool specAuto = true;           // trials per level from the level's size (lsd_single_plan, track_plan.hpp); false after set_speculation
   int specCaps[LSD_LEVELS] = {0, 0, 0, 0, 0};    // per-level workgroups per trial (LSDHIP_SPEC_CAPS; 0 = automatic)
   int specLevel[LSD_LEVELS] = {0, 0, 0, 0, 0};   // per-level trials (LSDHIP_SPEC_LEVELS = "l0,l1,l2,l3,l4"; 0 = automatic / specC)
   int specCap = LSD_SPEC_CAP_WORKGROUPS;              // workgroups per trial on levels of 24 K - 88 K pixels when speculating (0 = grid_cap / 2)
@@ -396,7 +389,6 @@ struct lsdhip_tracker {
   int* d_log = nullptr;      // launch log of the current job (TrackSpec::dbgLog), 4096 x 16 ints
   std::vector<int> lastLog;  // ... of the last finished job, read by lsdhip_tracker_debug_log
 #endif
-  TrackSpec spec = {};             // of the job being launched
   const lsdhip_frame* jobKf = nullptr;   // keyframe whose planes the job being run reads (trackFrame jobs), and their version at its start
   unsigned jobKfVersion = 0;
   int jobTag = 0, launchOrdinal = 0;   // progress tag of the launch chain (TrackSummary::seq)
@@ -412,7 +404,7 @@ struct lsdhip_tracker {
   TrackJob* h_bjobs = nullptr;        // pinned staging
   TrackState* d_bstate = nullptr;     // [capacity][2]
   float* d_bscratch = nullptr;        // TrackScratch arena x capacity (sums | topkey | topval | recs, each [job][parity][trial][...])
-  int batchRecent[4] = {0, 0, 0, 0};  // rounds the last batches needed: size the launch budget of the next one
+  LaunchHistory batchRecent;          // rounds the last batches needed: size the launch budget of the next one
   int batchTag = 1;                   // what `done` of a polled batch's summaries is raised to (>= 2; 1 = a batch the host synchronises for)
   TrackSummary* h_bsummary = nullptr; // pinned, device-mapped
   float* d_pts = nullptr;         // permaref point upload
@@ -554,6 +546,68 @@ struct LsdTrackJobScope {
   bool drain;
   LsdTrackJobScope(lsdhip_ctx* c_, bool waitAll) : c(c_), drain(waitAll) { if (c->pipeline && waitAll) rc = lsd_t_wait_m(c, c->mSeq); }
   ~LsdTrackJobScope() { if (c->pipeline && drain) (void)hipStreamSynchronize(c->stream); }
+};
+// ---- waiting for pinned words ----------------------------------------------------------------------------------------------------
+// The host polls pinned memory instead of sleeping in hipStreamSynchronize (whose wake-up costs more than an evaluation).  No stream
+// query in the wait but as a safety net (a faulted launch never reports): each one puts a marker packet into the queue the launches run
+// through (profiles/r03_notes.md §2b).  How each site looks up from its words — every (period + 1) spins:
+//                              period   asks the stream   idle stream   failed stream   past the deadline
+//   LSD_WAIT_SIM3   (sim3.hip)  0xFFFFF  yes               goes on       LSDHIP_E_HIP    drains; settled() has the last word, else LSDHIP_E_STATE
+//   LSD_WAIT_JOB    (one job)   0xFFFFF  yes               ends it       LSDHIP_E_HIP    drains; the caller looks at `done`
+//   LSD_WAIT_BATCH  (batch)     0xFFFF   yes               ends it       ends it         LSDHIP_E_STATE (the caller lets `done` have the last word)
+//   LSD_WAIT_RECORD (summary)   0xFFFF   no                -             -               LSDHIP_E_STATE
+// Time limits in seconds: Sim3's three (the record of a single evaluation, the flags of a launch budget, a finished job's result
+// record), a single tracking job's report, a batch's reports, the rest of a summary record once its `done` word is in.
+enum { S3_EVAL_WAIT_S = 5, S3_FLAG_WAIT_S = 10, S3_RESULT_WAIT_S = 2, LSD_JOB_WAIT_S = 5, LSD_BATCH_WAIT_S = 20, LSD_SUMMARY_WAIT_S = 2 };
+struct LsdWait {
+  unsigned period;
+  bool query, idleEnds, failedEnds, drains;
+  const char* failure;   // the error of a wait that ends with LSDHIP_E_STATE (nullptr: none such, or the caller words it)
+};
+constexpr LsdWait LSD_WAIT_JOB = {0xFFFFFu, true, true, false, true, nullptr};
+constexpr LsdWait LSD_WAIT_BATCH = {0xFFFFu, true, true, true, false, "tracking batch: no progress report from the device"};
+constexpr LsdWait LSD_WAIT_RECORD = {0xFFFFu, false, false, false, false, nullptr};
+constexpr LsdWait lsd_wait_sim3(const char* failure) { return {0xFFFFFu, true, false, false, true, failure}; }
+typedef std::chrono::steady_clock::time_point LsdDeadline;
+inline LsdDeadline lsd_deadline(int seconds) { return std::chrono::steady_clock::now() + std::chrono::seconds(seconds); }
+// Spins until settled() holds or the rule `how` ends the wait; LSDHIP_OK either way, so the caller reads its words again where a wait can
+// end unsettled.  settled: a lambda reading the pinned words through volatile (inlined: this is a job's latency path).
+template <class Pred>
+inline int lsd_spin_until(lsdhip_ctx* c, Pred settled, LsdDeadline deadline, const LsdWait& how) {
+  for (unsigned spins = 1; !settled(); spins++) {
+    if ((spins & how.period) == 0) {
+      if (how.query) {
+        const hipError_t q = hipStreamQuery(c->stream);
+        if (q == hipSuccess ? how.idleEnds : (q != hipErrorNotReady && how.failedEnds)) break;
+        if (q != hipSuccess && q != hipErrorNotReady) { lsd_set_error("hipStreamQuery failed: %s", hipGetErrorString(q)); return LSDHIP_E_HIP; }
+      }
+      if (std::chrono::steady_clock::now() > deadline) {
+        if (how.drains) HIPCHK(hipStreamSynchronize(c->stream));
+        if ((how.drains && !how.failure) || settled()) break;
+        if (how.failure) lsd_set_error("%s", how.failure);
+        return LSDHIP_E_STATE;
+      }
+    }
+    __builtin_ia32_pause();
+  }
+  std::atomic_thread_fence(std::memory_order_acquire);
+  return LSDHIP_OK;
+}
+// A pinned record of n words is whole when seed + the position-weighted sum of its words equals the check word the device stored with
+// it: whole record or nothing.  (They are separate posted writes: the words of such a record have been seen to land after the flag stored
+// behind the fence, profiles/r06_notes.md section 1.)  `late` counts the records that were not whole at the first look.
+inline int lsd_wait_record(lsdhip_ctx* c, const void* record, unsigned n, unsigned seed, const void* check, LsdDeadline deadline, const LsdWait& how,
+                           long long* late = nullptr) {
+  volatile const unsigned* w = (volatile const unsigned*)record;
+  auto whole = [&]() { unsigned chk = seed; for (unsigned i = 0; i < n; i++) chk += lsd_summary_term(i, w[i]); return *(volatile const unsigned*)check == chk; };
+  if (late && !whole()) ++*late;
+  return lsd_spin_until(c, whole, deadline, how);
+}
+// the context's mutex released while the host waits for the device — nothing in between touches context state — and retaken on every exit path
+struct LsdCtxUnlocked {
+  std::recursive_mutex& m;
+  explicit LsdCtxUnlocked(lsdhip_ctx* c) : m(c->mtx) { m.unlock(); }
+  ~LsdCtxUnlocked() { m.lock(); }
 };
 int lsd_frame_build_pyramids(lsdhip_frame* f, const uint8_t* src, hipStream_t stream);
 int lsd_frames_require_ref_blocks(lsdhip_frame** kfs, int n, hipStream_t stream);   // the published planes' reference blocks, where missing (frame.hip)

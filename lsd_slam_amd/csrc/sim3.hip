@@ -624,42 +624,6 @@ static void sim3_scratch(const lsdhip_sim3tracker* t, int slot, int parity, floa
   *topkey = t->d_topkey + at;
 }
 
-// ---- waiting for pinned words ----------------------------------------------------------------------------------------------------
-// The host polls pinned memory instead of sleeping in hipStreamSynchronize (whose wake-up costs more than an evaluation).  Time limits of
-// the three waits, in seconds: the record of a single evaluation, the flags of a launch budget, a finished job's result record
-enum { S3_EVAL_WAIT_S = 5, S3_FLAG_WAIT_S = 10, S3_RESULT_WAIT_S = 2 };
-typedef std::chrono::steady_clock::time_point Sim3Deadline;
-static Sim3Deadline sim3_deadline(int seconds) { return std::chrono::steady_clock::now() + std::chrono::seconds(seconds); }
-// Spins until settled() holds.  No stream query in the wait but as a safety net: each one puts a marker packet into the queue the
-// launches run through (profiles/r03_notes.md §2b).  Past the deadline the stream is drained and settled() has its last word.
-template <class Pred>
-static int sim3_spin_until(lsdhip_ctx* c, Pred settled, Sim3Deadline deadline, const char* failure) {
-  for (unsigned spins = 1; !settled(); spins++) {
-    if ((spins & 0xFFFFFu) == 0) {
-      hipError_t q = hipStreamQuery(c->stream);
-      if (q != hipSuccess && q != hipErrorNotReady) { lsd_set_error("hipStreamQuery failed: %s", hipGetErrorString(q)); return LSDHIP_E_HIP; }
-      if (std::chrono::steady_clock::now() > deadline) {
-        HIPCHK(hipStreamSynchronize(c->stream));
-        if (!settled()) { lsd_set_error("%s", failure); return LSDHIP_E_STATE; }
-        break;
-      }
-    }
-    __builtin_ia32_pause();
-  }
-  std::atomic_thread_fence(std::memory_order_acquire);
-  return LSDHIP_OK;
-}
-// A pinned record of n words is whole when seed + the position-weighted sum of its words equals the check word the device stored with
-// it: whole record or nothing.  (They are separate posted writes: the words of such a record have been seen to land after the flag stored
-// behind the fence, profiles/r06_notes.md section 1.)  `late` counts the records that were not whole at the first look.
-static int sim3_wait_record(lsdhip_ctx* c, const void* record, unsigned n, unsigned seed, const void* check, Sim3Deadline deadline,
-                            const char* failure, long long* late = nullptr) {
-  volatile const unsigned* w = (volatile const unsigned*)record;
-  auto whole = [&]() { unsigned chk = seed; for (unsigned i = 0; i < n; i++) chk += lsd_summary_term(i, w[i]); return *(volatile const unsigned*)check == chk; };
-  if (late && !whole()) ++*late;
-  return sim3_spin_until(c, whole, deadline, failure);
-}
-
 // one evaluation = calcSim3Buffers + calcSim3WeightsAndResidualSSE + calcSim3LGSSSE at one transformation.
 // Description of the evaluation for batch slot `slot`:
 static int sim3_build_job(lsdhip_sim3tracker* t, int slot, lsdhip_frame* kf, lsdhip_frame* frame, const Sim3H& referenceToFrame, int level,
@@ -696,11 +660,11 @@ static int sim3_run_batch(lsdhip_sim3tracker* t, Sim3Batch& batch, int nslots) {
   hipLaunchKernelGGL(k_sim3_eval, dim3(grid, nslots), dim3(S3_BLOCK), 0, c->stream, batch);
   hipLaunchKernelGGL(k_sim3_finalize, dim3(1, nslots), dim3(256), 0, c->stream, batch);
   HIPCHK(hipGetLastError());
-  const Sim3Deadline deadline = sim3_deadline(S3_EVAL_WAIT_S);
+  const LsdDeadline deadline = lsd_deadline(S3_EVAL_WAIT_S);
   for (int k = 0; k < nslots; k++) {
     if (batch.j[k].nblocks <= 0) continue;
     const float* rec = t->h_record + (size_t)k * 64;      // word 63 = seq + the weighted sum of the 63 words before it (k_sim3_finalize)
-    if (int rc = sim3_wait_record(c, rec, 63, (unsigned)seq, rec + 63, deadline, "Sim3 evaluation did not complete")) return rc;
+    if (int rc = lsd_wait_record(c, rec, 63, (unsigned)seq, rec + 63, deadline, lsd_wait_sim3("Sim3 evaluation did not complete"))) return rc;
   }
   return LSDHIP_OK;
 }
@@ -1187,14 +1151,14 @@ static int sim3_run_budgets(lsdhip_sim3tracker* t, const Sim3LM& P, const Sim3Tr
       hipLaunchKernelGGL(k_sim3_fused, dim3(grid, m), dim3(S3_BLOCK), 0, c->stream, (const Sim3Set*)t->d_sets, t->d_states, P, parity,
                          i == budget - 1 ? b : -1, b == 0 ? i : -1);
     HIPCHK(hipGetLastError());
-    const Sim3Deadline deadline = sim3_deadline(S3_FLAG_WAIT_S);
+    const LsdDeadline deadline = lsd_deadline(S3_FLAG_WAIT_S);
     bool unfinished = false;
     for (int k = 0; k < m; k++) {
       if (jobs[k].phase == Sim3Track::DONE) continue;
       volatile const int* flag = t->h_done + k;
       int v;
       auto settled = [&]() { v = *flag; return v == sim3_done_word(seq, 255) || v == sim3_done_word(seq, 254) || v == sim3_done_word(seq, b); };
-      if (int rc = sim3_spin_until(c, settled, deadline, "Sim3 tracking did not complete")) return rc;
+      if (int rc = lsd_spin_until(c, settled, deadline, lsd_wait_sim3("Sim3 tracking did not complete"))) return rc;
       if (v == sim3_done_word(seq, b)) unfinished = true;
     }
     if (!unfinished) return LSDHIP_OK;
@@ -1210,8 +1174,8 @@ static int sim3_collect_chunk(lsdhip_sim3tracker* t, Sim3Track* jobs, int m, int
     Sim3Track& J = jobs[k];
     if (J.phase == Sim3Track::DONE) continue;             // finished before any evaluation
     const int word = ((volatile const int*)t->h_done)[k];
-    if (int rc = sim3_wait_record(t->ctx, &t->h_results[k], sizeof(lsdhip_sim3_result) / 4, (unsigned)word, t->h_done + S3_MAXB + k,
-                                  sim3_deadline(S3_RESULT_WAIT_S), "Sim3 result record in pinned memory never became consistent", &t->lateRecords))
+    if (int rc = lsd_wait_record(t->ctx, &t->h_results[k], sizeof(lsdhip_sim3_result) / 4, (unsigned)word, t->h_done + S3_MAXB + k, lsd_deadline(S3_RESULT_WAIT_S),
+                                 lsd_wait_sim3("Sim3 result record in pinned memory never became consistent"), &t->lateRecords))
       return rc;
     *J.hostOut = t->h_results[k];
     J.rc = word == sim3_done_word(seq, 255) ? LSDHIP_OK : LSDHIP_DIVERGED;

@@ -986,7 +986,7 @@ __global__ __launch_bounds__(BLOCK) void k_track_step(TrackJob jobv, const Track
 // kernel's own fixed order; no speculation (a retry is one more iteration of a few microseconds, not a launch).
 // Measured (profiles/r06_notes.md section 21): the tile neither gains nor costs against gathering the taps from L2 / HBM — the iteration
 // is bound by what one CU can issue — and the launch takes about what the ten rounds it replaces took, on n CUs instead of the chip.
-#define LSD_SOLO_MAX_PX 4800
+// (LSD_SOLO_MAX_PX and the batch size it pays from, LSD_SOLO_MIN_JOBS: track_plan.hpp)
 #define LSD_SOLO_TRIPS 9          // x 512 lanes = 4608 points >= the (w - 2)(h - 2) interior of any level of at most 4800 pixels
 #define LSD_SOLO_MAX_PTS (LSD_SOLO_TRIPS * 512)
 #define LSD_SOLO_LDS_PTS 4544     // (w - 2)(h - 2) <= w h - 4 sqrt(w h) + 4 <= 4527 interior pixels of a level of at most 4800
@@ -1001,10 +1001,6 @@ constexpr int lsd_solo_max_interior() {
   return best;
 }
 static_assert(lsd_solo_max_interior() <= LSD_SOLO_LDS_PTS, "the dense interior of any level k_track_solo takes fits its LDS lists");
-// Worth it from this many jobs per batch: one workgroup per job walks its coarse levels in about the time the lock-step rounds take, on
-// n CUs instead of the chip — a gain where other work (the mapping stream of the S-sequence loop) wants the other CUs, a small loss for
-// a few jobs that have the chip to themselves (profiles/r06_notes.md section 21).
-#define LSD_SOLO_MIN_JOBS 24
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict__ jobs, TrackState* __restrict__ st2, TrackSummary* __restrict__ outs,
                                                           const int parity, const int doneWord) {
@@ -1383,13 +1379,7 @@ extern "C" int lsdhip_tracker_create(lsdhip_ctx* c, lsdhip_tracker** out) {
   if (const char* e = getenv("LSDHIP_TRACK_BLOCK")) t->block = atoi(e);
   if (const char* e = getenv("LSDHIP_TRACK_CAP")) t->grid_cap = atoi(e);
   if (t->block != 256) { lsd_set_error("LSDHIP_TRACK_BLOCK must be 256"); delete t; return LSDHIP_E_ARG; }
-  if (t->grid_cap < 8) t->grid_cap = 8;
-  t->grid_cap &= ~7;
-  {
-    // rows per column slice must fit the 20 float4 loads of the column-sum phase: 80 rows x NSLICE slices
-    const int nslice = ((t->block / 64 - 1) * 64) / RS_END;
-    if (t->grid_cap > 80 * nslice) t->grid_cap = (80 * nslice) & ~7;
-  }
+  t->grid_cap = lsd_grid_cap(t->grid_cap, t->block, RS_END);
   t->max_blocks = t->grid_cap;
   const size_t partials_bytes = scratch_layout(1, LSD_SPEC_MAX, (size_t)t->max_blocks).end * sizeof(float);
   if (const char* e = getenv("LSDHIP_SPEC")) t->specC = atoi(e);
@@ -1544,7 +1534,7 @@ extern "C" int lsdhip_tracker_set_speculation(lsdhip_tracker* t, int trials, int
   t->specAuto = false;                                        // the same number of trials at every level
   if (finestLevelWorkgroups > 0) t->specCap = finestLevelWorkgroups < 8 ? 8 : (finestLevelWorkgroups & ~7);   // multiples of 8 (one tile band per XCD), at least 8
   for (int l = 0; l < LSD_LEVELS; l++) t->specLevel[l] = 0;
-  for (int i = 0; i < 4; i++) t->recent[i] = 0;
+  t->recent = LaunchHistory{};
   return LSDHIP_OK;
 }
 extern "C" int lsdhip_tracker_set_batch_coarse_min_jobs(lsdhip_tracker* t, int minJobs) {
@@ -1582,16 +1572,6 @@ static const float MIN_GOODPERGOODBAD_PIXEL = 0.5f;
 static const float MIN_GOODPERALL_PIXEL = 0.04f;
 static const float MIN_GOODPERALL_PIXEL_ABSMIN = 0.01f;
 
-// The batch a job is described for: how many jobs share its launches, and the workgroups each of them may use at a level.  With many
-// jobs in flight the other jobs hide a job's latency, so each job gets fewer, fatter workgroups: the per-workgroup LM replay (the price
-// of the launch needing no inter-workgroup communication) shrinks accordingly.  {0, 0}: a single job on the tracker's own grid_cap.
-struct BatchShape { int jobs, cap; };
-static BatchShape batch_shape(const lsdhip_tracker* t, int n) {
-  if (n <= 1) return {0, 0};
-  const int cap = (t->grid_cap / n) & ~7;
-  return {n, cap < 16 ? 16 : cap};
-}
-
 // Developer switches of the batch path (sweeps and A/Bs; tools/gpu.sh ab sets them per process): read once, at the first batch.
 static long long env_num(const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; }
 struct BatchEnv {
@@ -1626,28 +1606,10 @@ static int fill_level(lsdhip_tracker* t, TrackJob& job, BatchShape shape, int le
     L.kf_refBlk = kf->d_refBlk[level];
     L.pts_pos = L.pts_colvar = nullptr; L.npts = -1;
   }
-  int work = npts >= 0 ? npts : L.w * L.h;
-  L.nblocks = (work + t->block - 1) / t->block;
-  if (L.nblocks >= 16) L.nblocks = (L.nblocks + 7) & ~7;   // multiples of 8: one contiguous band of tiles per XCD
-  const int cap = shape.cap > 0 ? shape.cap : t->grid_cap;
-  if (L.nblocks > cap) L.nblocks = cap;                     // larger levels grid-stride
-  if (L.nblocks < 1) L.nblocks = 1;
-  L.singlePass = (long long)L.nblocks * t->block >= work ? 1 : 0;
-  L.tilePx = 0;
-  if (shape.jobs >= LSD_BATCH_THROUGHPUT_MIN_JOBS && npts < 0 && L.kf_refBlk != nullptr) {   // (levels >= 1: level 0 has no reference blocks)
-    // throughput mode: strips of tilePx pixels, compacted in the workgroup; enough strips over all jobs to fill the chip
-    const int wgTarget = batch_env().stripWgs;
-    // strips x jobs = the chip's 768 workgroup slots (3 per CU) where the level is large enough: one full round of equal strips;
-    // a strip is a multiple of 256 pixels (the lanes take 4 consecutive pixels each)
-    long long px = (((long long)work * shape.jobs + wgTarget - 1) / wgTarget + 255) & ~255LL;
-    if (px < 1024) px = 1024;
-    if (px > 8192) px = 8192;                                  // the strip's list lives in the reduction's LDS (10545 words)
-    if ((work + px - 1) / px <= t->max_blocks) {               // (levels beyond 2.4 Mpixel keep the grid-stride form)
-      L.tilePx = (int)px;
-      L.nblocks = (int)((work + px - 1) / px);
-      L.singlePass = 0;
-    }
-  }
+  const int work = npts >= 0 ? npts : L.w * L.h;
+  // (strips only where the level has reference blocks: levels >= 1 of a keyframe)
+  const LevelTiling T = lsd_level_tiling(work, t->block, t->grid_cap, shape, npts < 0 && L.kf_refBlk != nullptr, batch_env().stripWgs, t->max_blocks);
+  L.nblocks = T.nblocks; L.singlePass = T.singlePass; L.tilePx = T.tilePx;
   L.lambdaInitial = t->lambdaInitial[level]; L.stepSizeMin = t->stepSizeMin[level]; L.convergenceEps = t->convergenceEps[level];
   L.maxIts = t->maxItsPerLvl[level];
   L.minWarped = MIN_GOODPERALL_PIXEL_ABSMIN * (c->w >> level) * (c->h >> level);
@@ -1686,6 +1648,18 @@ static void take_summary(lsdhip_tracker* t, const TrackSummary* S) {
   t->affineEstimation_a_lastIt = S->aff_a_lastIt; t->affineEstimation_b_lastIt = S->aff_b_lastIt;
   t->lastResidual = S->lastResidual;
 }
+// the summary of a job whose LM loop ran on the host (debugging path), from the tracker's members: what finish_trackframe expects
+static TrackSummary host_lm_summary(const lsdhip_tracker* t, const lsdm::SE3fH& referenceToFrame, float lastResidual) {
+  TrackSummary S = *t->h_summary;
+  S.diverged = 0;
+  S.q[0] = referenceToFrame.q.w; S.q[1] = referenceToFrame.q.x; S.q[2] = referenceToFrame.q.y; S.q[3] = referenceToFrame.q.z;
+  S.t[0] = referenceToFrame.t[0]; S.t[1] = referenceToFrame.t[1]; S.t[2] = referenceToFrame.t[2];
+  S.lastResidual = lastResidual; S.numEvaluations = t->numEvaluations; S.numWarpUpdates = t->numWarpUpdates;
+  S.pointUsage = t->pointUsage; S.goodCount = t->lastGoodCount; S.badCount = t->lastBadCount; S.meanRes = t->lastMeanRes;
+  S.aff_a = t->affineEstimation_a; S.aff_b = t->affineEstimation_b;
+  S.aff_a_lastIt = t->affineEstimation_a_lastIt; S.aff_b_lastIt = t->affineEstimation_b_lastIt;
+  return S;
+}
 // trackingWasGood of a job that ended at `level` (SE3Tracker.cpp:267-269, 475-477), from the counts the tracker holds
 static bool tracking_was_good(const lsdhip_tracker* t, int level) {
   const lsdhip_ctx* c = t->ctx;
@@ -1694,55 +1668,176 @@ static bool tracking_was_good(const lsdhip_tracker* t, int level) {
 }
 
 static TrackScratch scratch_of(lsdhip_tracker* t) { return scratch_at(t, t->d_partials, 1, LSD_SPEC_MAX, LSD_SPEC_MAX); }
-static void launch_step(lsdhip_tracker* t, const TrackJob& job, int grid, int parity, int first) {
+
+// elapsed time of the last profiled launch batch (events are read one call late so that nothing waits for them)
+static int prof_collect(lsdhip_ctx* c) {
+  if (!c->prof_pending) return LSDHIP_OK;
+  HIPCHK(hipEventSynchronize(c->ev_b));
+  float ms = 0;
+  HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
+  c->prof_ms += ms;
+  c->prof_pending = false;
+  return LSDHIP_OK;
+}
+int lsd_prof_collect(lsdhip_ctx* c) { return prof_collect(c); }
+
+// ---- developer scaffolding (LSD_DEVTOOLS builds; lsdhip_internal.hpp lists the switches): the functions that run a job call these by
+// name, the default library gets the empty stand-ins of the #else branch --------------------------------------------------------------
+#ifdef LSD_DEVTOOLS
+static int track_device(lsdhip_tracker* t, TrackJob& job, int topLevel, const lsdm::SE3fH& T0, lsdm::SE3fH* Tout);
+typedef std::chrono::steady_clock::time_point DevTime;
+static DevTime dev_now() { return std::chrono::steady_clock::now(); }
+static long long dev_ns_since(DevTime t0) { return std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); }
+static void dev_log_pointer(lsdhip_tracker* t, TrackSpec& spec) { spec.dbgLog = t->d_log; }
+// LSDHIP_TRACK_DEBUG's counters (printed at destroy): jobs, launches queued and the host time that took, budgets that ran out, host time waiting
+static void dev_job_begins(lsdhip_tracker* t) { t->dbgJobs++; }
+static void dev_launches_queued(lsdhip_tracker* t, int steps, DevTime t0) { t->dbgEnqueued += steps; t->dbgLaunchNs += dev_ns_since(t0); }
+static void dev_budget_missed(lsdhip_tracker* t) { t->dbgMisses++; }
+struct DevWaitClock {
+  lsdhip_tracker* t;
+  DevTime t0;
+  explicit DevWaitClock(lsdhip_tracker* t_) : t(t_), t0(dev_now()) {}
+  ~DevWaitClock() { t->dbgWaitNs += dev_ns_since(t0); }
+};
+// LSDHIP_DUMP_L0 (with LSDHIP_BUDGET_FIXED=1, after the first budget has drained): what the job's first launch (level `topLevel`, one
+// trial) left — it wrote parity 1, trial 0: rows | keys | tail contributions of its tiles, and the state behind them
+static int dev_dump_first_launch(lsdhip_tracker* t, const TrackJob& job, int topLevel, int guard) {
+  static const bool dumpL0 = getenv("LSDHIP_DUMP_L0") != nullptr;
+  if (!dumpL0 || guard != 0 || t->budgetFixed != 1) return LSDHIP_OK;
+  const TrackScratch sc = scratch_of(t);
+  const size_t rows = (size_t)t->max_blocks;
+  const int nb = job.lv[topLevel].nblocks;
+  t->dumpL0.assign((size_t)nb * (RS_COLS + 4 + 96) + sizeof(TrackState) / 4, 0u);
+  unsigned* d = t->dumpL0.data();
+  HIPCHK(hipMemcpy(d, sc.sums + (size_t)(1 * LSD_SPEC_MAX + 0) * RS_COLS * rows, (size_t)nb * RS_COLS * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(d + (size_t)nb * RS_COLS, sc.topkey + (size_t)(1 * LSD_SPEC_MAX + 0) * rows, (size_t)nb * 16, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(d + (size_t)nb * (RS_COLS + 4), sc.topval + (size_t)(1 * LSD_SPEC_MAX + 0) * rows * 96, (size_t)nb * 96 * 4, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(d + (size_t)nb * (RS_COLS + 4 + 96), t->d_state + 1, sizeof(TrackState), hipMemcpyDeviceToHost));
+  return LSDHIP_OK;
+}
+// LSDHIP_LAUNCH_LOG: every launch of the job has been queued; wait for the ones behind the finishing launch too, then keep the log and clear it
+static int dev_keep_launch_log(lsdhip_tracker* t) {
+  static const bool keepLog = getenv("LSDHIP_LAUNCH_LOG") != nullptr;
+  if (!keepLog) return LSDHIP_OK;
+  HIPCHK(hipStreamSynchronize(t->ctx->stream));
+  const int n = t->launchOrdinal < 4095 ? t->launchOrdinal + 1 : 4096;
+  t->lastLog.assign((size_t)n * 16, 0);
+  HIPCHK(hipMemcpy(t->lastLog.data(), t->d_log, (size_t)n * 64, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemset(t->d_log, 0, (size_t)n * 64));
+  return LSDHIP_OK;
+}
+// LSDHIP_TRACE_SUMS entries of a job.  Its inputs (LSDHIP_TRACE_INPUTS), kinds base + ..:
+static void dev_trace_inputs(lsdhip_ctx* c, const lsdhip_frame* kf, const lsdhip_frame* frame, int base) {
+  static const bool traceInputs = getenv("LSDHIP_TRACE_INPUTS") != nullptr;
+  if (!traceInputs) return;
+  for (int l = 1; l <= 4; l++) {
+    const size_t nl = (size_t)c->wl[l] * c->hl[l];
+    lsd_trace_sum(c, c->stream, base + 10 + l, frame->id, kf->d_idepth[l], nl * 4);
+    lsd_trace_sum(c, c->stream, base + 14 + l, frame->id, kf->d_idepthVar[l], nl * 4);
+    lsd_trace_sum(c, c->stream, base + 50 + l, frame->id, kf->d_image[l], nl * 4);
+    lsd_trace_sum(c, c->stream, base + 54 + l, frame->id, frame->d_grad[l], nl * 16);
+  }
+}
+// ... the pose it starts from and its keyframe (kinds 22, 23)
+static void dev_trace_job(lsdhip_ctx* c, const lsdhip_frame* kf, const lsdhip_frame* frame, const double init[7]) {
+  dev_trace_inputs(c, kf, frame, 0);
+  unsigned long long pv = 0;
+  for (int i = 0; i < 7; i++) { unsigned long long u; memcpy(&u, &init[i], 8); pv = pv * 1000003ull + u; }
+  lsd_trace_val(c, 22, frame->id, pv);
+  lsd_trace_val(c, 23, frame->id, (unsigned long long)kf->id);
+}
+// ... the workgroups launched before it (in units of a 640x480 job's grid)
+static void dev_trace_launched(lsdhip_tracker* t, int kind, const lsdhip_frame* frame) { lsd_trace_val(t->ctx, kind, frame->id, t->dbgCum / 400ull); }
+// ... and its result: the hash of the pose's seven words (kind), evaluations and last executed trial (kind + 1)
+static void dev_trace_result(lsdhip_tracker* t, int kind, const lsdhip_frame* frame) {
+  const TrackSummary* S = t->h_summary;
+  unsigned long long pv = 0;
+  for (int i = 0; i < 4; i++) { unsigned u; memcpy(&u, &S->q[i], 4); pv = pv * 1000003ull + u; }
+  for (int i = 0; i < 3; i++) { unsigned u; memcpy(&u, &S->t[i], 4); pv = pv * 1000003ull + u; }
+  lsd_trace_val(t->ctx, kind, frame->id, pv);
+  lsd_trace_val(t->ctx, kind + 1, frame->id, (unsigned long long)S->numEvaluations * 1000 + S->lastCand);
+}
+// LSDHIP_TRACK_REPLAY (pipelined contexts): the job that has just ended with `rc`, once more with the mapping stream drained — identical
+// inputs must give the identical result; the first launches' dumps (LSDHIP_DUMP_L0) are compared word by word.  Returns the replay's rc.
+static int dev_replay_check(lsdhip_tracker* t, TrackJob& job, const lsdhip_frame* kf, const lsdhip_frame* frame, const lsdm::SE3fH& T0,
+                            lsdm::SE3fH* Tout, int rc) {
+  static const bool replay = getenv("LSDHIP_TRACK_REPLAY") != nullptr;
+  lsdhip_ctx* c = t->ctx;
+  if (!replay || !c->pipeline) return rc;
+  dev_trace_result(t, 24, frame);
+  HIPCHK(hipStreamSynchronize(c->mstream));
+  HIPCHK(hipStreamSynchronize(c->stream));
+  c->mDoneSeq = c->mSeq;
+  const std::vector<unsigned> dump1 = t->dumpL0;
+  dev_trace_inputs(c, kf, frame, 100);
+  dev_trace_launched(t, 27, frame);
+  rc = track_device(t, job, LSD_TRACK_MAX_LEVEL - 1, T0, Tout);
+  if (rc != LSDHIP_OK && rc != LSDHIP_DIVERGED) return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  if (!dump1.empty() && dump1.size() == t->dumpL0.size()) {
+    const int nb = job.lv[LSD_TRACK_MAX_LEVEL - 1].nblocks;
+    int shown = 0;
+    for (size_t i = 0; i < dump1.size(); i++)
+      if (dump1[i] != t->dumpL0[i] && shown++ < 12) {
+        const size_t a = (size_t)nb * RS_COLS, b = a + (size_t)nb * 4, cst = b + (size_t)nb * 96;
+        float f1, f2; memcpy(&f1, &dump1[i], 4); memcpy(&f2, &t->dumpL0[i], 4);
+        if (i < a) fprintf(stderr, "L0DIFF frame %d: sums tile %zu column %zu: run %.9g (%08x) replay %.9g (%08x)\n", frame->id, i / RS_COLS, i % RS_COLS, f1, dump1[i], f2, t->dumpL0[i]);
+        else if (i < b) fprintf(stderr, "L0DIFF frame %d: topkey tile %zu [%zu]: run %d replay %d\n", frame->id, (i - a) / 4, (i - a) % 4, (int)dump1[i], (int)t->dumpL0[i]);
+        else if (i < cst) fprintf(stderr, "L0DIFF frame %d: topval tile %zu slot %zu entry %zu: run %.9g replay %.9g\n", frame->id, (i - b) / 96, ((i - b) % 96) / 32, (i - b) % 32, f1, f2);
+        else fprintf(stderr, "L0DIFF frame %d: state word %zu: run %08x (%.9g) replay %08x (%.9g)\n", frame->id, i - cst, dump1[i], f1, t->dumpL0[i], f2);
+      }
+    if (shown) fprintf(stderr, "L0DIFF frame %d: %d words differ after the first launch\n", frame->id, shown);
+  }
+  return rc;
+}
+#else
+struct DevTime {};
+inline DevTime dev_now() { return {}; }
+inline void dev_log_pointer(lsdhip_tracker*, TrackSpec&) {}
+inline void dev_job_begins(lsdhip_tracker*) {}
+inline void dev_launches_queued(lsdhip_tracker*, int, DevTime) {}
+inline void dev_budget_missed(lsdhip_tracker*) {}
+struct DevWaitClock { explicit DevWaitClock(lsdhip_tracker*) {} };
+inline int dev_dump_first_launch(lsdhip_tracker*, const TrackJob&, int, int) { return LSDHIP_OK; }
+inline int dev_keep_launch_log(lsdhip_tracker*) { return LSDHIP_OK; }
+inline void dev_trace_job(lsdhip_ctx*, const lsdhip_frame*, const lsdhip_frame*, const double*) {}
+inline void dev_trace_launched(lsdhip_tracker*, int, const lsdhip_frame*) {}
+inline void dev_trace_result(lsdhip_tracker*, int, const lsdhip_frame*) {}
+inline int dev_replay_check(lsdhip_tracker*, TrackJob&, const lsdhip_frame*, const lsdhip_frame*, const lsdm::SE3fH&, lsdm::SE3fH*, int rc) { return rc; }
+#endif
+
+// progress tag of the launch queued last (TrackSummary::seq): (job tag << 12) | launch ordinal; 0 for jobs nobody polls for
+static int launch_seq(const lsdhip_tracker* t) { return t->jobTag ? ((t->jobTag << 12) | (t->launchOrdinal & 0xFFF)) : 0; }
+// one k_track_step launch of a single job; `last`: the last launch of the enqueued budget
+static void launch_step(lsdhip_tracker* t, const TrackJob& job, TrackSpec spec, int grid, int parity, int first, int last) {
   lsdhip_ctx* c = t->ctx;
   LSD_CTX_LOCK(c);
   TrackScratch sc = scratch_of(t);
   t->launchOrdinal++;
-  t->spec.seq = t->jobTag ? ((t->jobTag << 12) | (t->launchOrdinal & 0xFFF)) : 0;
-#ifdef LSD_DEVTOOLS
-  t->spec.dbgLog = t->d_log;
-#endif
+  spec.seq = launch_seq(t);
+  spec.last = last;
+  dev_log_pointer(t, spec);
 #ifdef LSD_ORDER_CHECK
-  t->spec.dbgCum = t->dbgCum;
-  t->spec.dbgCounters = t->d_dbg;
+  spec.dbgCum = t->dbgCum;
+  spec.dbgCounters = t->d_dbg;
   t->dbgCum += (unsigned long long)grid;
 #endif
   hipLaunchKernelGGL((k_track_step<256, false>), dim3(grid), dim3(256), 0, c->stream, job, (const TrackJob*)nullptr, t->d_state, sc,
-                     t->d_summary, parity, first, t->spec);
+                     t->d_summary, parity, first, spec);
 }
-// launch `steps` fused k_track_step kernels (alternating parity); grid = the largest level the job can still visit.
-static int launch_steps(lsdhip_tracker* t, TrackJob& job, int steps, int* parity, int* first) {
-  int grid = 1;
-  for (int l = job.lastLevel; l <= job.topLevel; l++) if (job.lv[l].nblocks > grid) grid = job.lv[l].nblocks;
-  t->spec.specGrid = 0;
-  if (t->spec.specC > 1) {
-    // workgroup = (trial, tile) of the level being evaluated: the launch needs the most tiles x trials of any level
-    for (int l = job.lastLevel; l <= job.topLevel; l++) {
-      const int g = job.lv[l].nblocks * (t->spec.trials[l] > 1 ? t->spec.trials[l] : 1);
-      if (g > grid) grid = g;
-    }
-    t->spec.specGrid = grid;
-  }
-#ifdef LSD_DEVTOOLS
-  const auto tl0 = std::chrono::steady_clock::now();
-#endif
+// launch `steps` fused k_track_step kernels of `grid` workgroups (alternating parity)
+static int launch_steps(lsdhip_tracker* t, const TrackJob& job, const TrackSpec& spec, int grid, int steps, int* parity, int* first) {
+  const DevTime tl0 = dev_now();
   for (int i = 0; i < steps; i++) {
-    t->spec.last = (i + 1 == steps) ? 1 : 0;
-    launch_step(t, job, grid, *parity, *first);
+    launch_step(t, job, spec, grid, *parity, *first, i + 1 == steps);
     lsdhip_host_mark(20);
     *first = 0;
     *parity ^= 1;
   }
-#ifdef LSD_DEVTOOLS
-  t->dbgEnqueued += steps;
-  t->dbgLaunchNs += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - tl0).count();
-#endif
+  dev_launches_queued(t, steps, tl0);
   HIPCHK(hipGetLastError());
   return LSDHIP_OK;
 }
-
-static int prof_collect(lsdhip_ctx* c);
 struct EvalOut {       // what one evaluation leaves behind, in the reference's terms
   int warped_size;
   float retval;        // calcResidualAndBuffers return value
@@ -1782,14 +1877,13 @@ static int evaluate_pose(lsdhip_tracker* t, TrackJob& job, const lsdm::SE3fH& T,
   job.T0 = T;
   job.aff_a0 = t->affineEstimation_a; job.aff_b0 = t->affineEstimation_b;
   t->h_summary->done = 0;
-  t->spec = TrackSpec{};                              // one evaluation, one trial
   t->jobTag = 0;
+  const TrackSpec spec = TrackSpec{};                 // one evaluation, one trial
   if (int rcp = prof_collect(c)) return rcp;
   if (c->prof_on) HIPCHK(hipEventRecord(c->ev_a, c->stream));
-  t->spec.last = 0;
-  launch_step(t, job, job.lv[level].nblocks, 0, 1);   // residual evaluation
+  launch_step(t, job, spec, job.lv[level].nblocks, 0, 1, 0);   // residual evaluation
   if (c->prof_on) HIPCHK(hipEventRecord(c->ev_b, c->stream));
-  launch_step(t, job, 1, 1, 0);                       // finalises the sums (evalOnly)
+  launch_step(t, job, spec, 1, 1, 0, 0);                       // finalises the sums (evalOnly)
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   const TrackSummary* S = t->h_summary;
@@ -1878,57 +1972,37 @@ static int lm_level_host(lsdhip_tracker* t, TrackJob& job, int lvl, lsdm::SE3fH&
   return LSDHIP_OK;
 }
 
-// elapsed time of the last profiled launch batch (events are read one call late so that nothing waits for them)
-static int prof_collect(lsdhip_ctx* c) {
-  if (!c->prof_pending) return LSDHIP_OK;
-  HIPCHK(hipEventSynchronize(c->ev_b));
-  float ms = 0;
-  HIPCHK(hipEventElapsedTime(&ms, c->ev_a, c->ev_b));
-  c->prof_ms += ms;
-  c->prof_pending = false;
-  return LSDHIP_OK;
-}
-int lsd_prof_collect(lsdhip_ctx* c) { return prof_collect(c); }
-
 // A polled summary is accepted when its words add up to its `check` word: `done` has arrived, but the record's other words are separate
 // posted writes and — one job in a few thousand, measured (profiles/r06_notes.md section 1) — the ones stored last (numLaunches, lastCand,
 // levelEvals) still held the previous job's values at that moment.  Spins until the record is whole; counts what it saw.
 static int summary_wait_consistent(lsdhip_tracker* t, const int doneWord, const TrackSummary* rec = nullptr) {
   if (!rec) rec = t->h_summary;
   volatile const unsigned* w = (volatile const unsigned*)rec;
-  t->sumPolled++;
-  unsigned first[LSD_SUMMARY_CHECK_WORDS];
-  std::chrono::steady_clock::time_point t0;
-  for (unsigned spins = 0;; spins++) {
-    unsigned cur[LSD_SUMMARY_CHECK_WORDS];
-    unsigned chk = (unsigned)doneWord;
+  unsigned cur[LSD_SUMMARY_CHECK_WORDS], chk = 0, want = 0;
+  auto whole = [&]() {
+    chk = (unsigned)doneWord;
     for (unsigned i = 1; i < LSD_SUMMARY_CHECK_WORDS; i++) { cur[i] = w[i]; chk += lsd_summary_term(i, cur[i]); }
-    const unsigned want = *(volatile const unsigned*)&rec->check;
-    if (chk == want) {
-      if (spins > 0) {
-        const long long ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
-        if (ns > t->sumLateMaxNs) t->sumLateMaxNs = ns;
-        for (unsigned i = 1; i < LSD_SUMMARY_CHECK_WORDS; i++)
-          if (first[i] != cur[i]) {
-            t->sumLateWords++;
-            if (t->sumLateFirstWord < 0 || (int)i < t->sumLateFirstWord) t->sumLateFirstWord = (int)i;
-            if ((int)i > t->sumLateLastWord) t->sumLateLastWord = (int)i;
-          }
-      }
-      std::atomic_thread_fence(std::memory_order_acquire);
-      return LSDHIP_OK;
+    want = *(volatile const unsigned*)&rec->check;
+    return chk == want;
+  };
+  t->sumPolled++;
+  if (whole()) { std::atomic_thread_fence(std::memory_order_acquire); return LSDHIP_OK; }
+  t->sumLate++;
+  unsigned first[LSD_SUMMARY_CHECK_WORDS];
+  memcpy(first, cur, sizeof(first));
+  const auto t0 = std::chrono::steady_clock::now();
+  const int rc = lsd_spin_until(t->ctx, whole, t0 + std::chrono::seconds(LSD_SUMMARY_WAIT_S), LSD_WAIT_RECORD);
+  if (rc == LSDHIP_E_STATE) lsd_set_error("tracking summary in pinned memory never became consistent (check %08x, sum %08x)", want, chk);
+  if (rc) return rc;
+  const long long ns = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count();
+  if (ns > t->sumLateMaxNs) t->sumLateMaxNs = ns;
+  for (unsigned i = 1; i < LSD_SUMMARY_CHECK_WORDS; i++)
+    if (first[i] != cur[i]) {
+      t->sumLateWords++;
+      if (t->sumLateFirstWord < 0 || (int)i < t->sumLateFirstWord) t->sumLateFirstWord = (int)i;
+      if ((int)i > t->sumLateLastWord) t->sumLateLastWord = (int)i;
     }
-    if (spins == 0) {
-      t->sumLate++;
-      t0 = std::chrono::steady_clock::now();
-      memcpy(first, cur, sizeof(first));
-    }
-    if ((spins & 0xFFFFu) == 0xFFFFu && std::chrono::steady_clock::now() - t0 > std::chrono::seconds(2)) {
-      lsd_set_error("tracking summary in pinned memory never became consistent (check %08x, sum %08x)", want, chk);
-      return LSDHIP_E_STATE;
-    }
-    __builtin_ia32_pause();
-  }
+  return LSDHIP_OK;
 }
 extern "C" int lsdhip_tracker_summary_stats(const lsdhip_tracker* t, long long out[6]) {
   if (!t || !out) return LSDHIP_E_ARG;
@@ -1936,25 +2010,36 @@ extern "C" int lsdhip_tracker_summary_stats(const lsdhip_tracker* t, long long o
   return LSDHIP_OK;
 }
 
-// device-resident LM over levels topLevel..job.lastLevel; one host synchronisation per budget of launches.  The budget
-// is the previous job's launch count (evaluations + the finalising step) plus a margin, so that few steps run empty.
-// With profiling on, the whole budget is bracketed by one HIP event pair on the context's stream and charged to the
-// launches that did work.
-static int track_device(lsdhip_tracker* t, TrackJob& job, int topLevel, const lsdm::SE3fH& T0, lsdm::SE3fH* Tout) {
+// The loop every device-resident job (or batch of jobs) runs through: enqueue a budget of launches, let the caller's hook queue what the
+// device can do beside them (once), wait for the reports, and top the budget up while a job needs more.  With `sample`, a budget is
+// bracketed by one HIP event pair on the context's stream (read one call late, prof_collect).
+//   enqueue(budget) -> rc               queues `budget` launches
+//   wait(guard, &finished) -> rc        returns with every job finished, or with the stream drained and some job not
+//   topUp(guard) -> the next budget     (a job may start over here: lsdhip_tracker_track's keyframe check)
+template <class Enqueue, class Wait, class TopUp>
+static int run_budgets(lsdhip_tracker* t, bool sample, bool hook, int budget, const char* what, Enqueue enqueue, Wait wait, TopUp topUp) {
   lsdhip_ctx* c = t->ctx;
-  // (the caller — an extern "C" entry — holds the context mutex once; it is released below while the host waits)
-  job.evalOnly = 0;
-  job.topLevel = topLevel;
-  job.T0 = T0;
-  job.aff_a0 = 1.0f; job.aff_b0 = 0.0f;
-  t->spec.specC = t->specC;
-  t->spec.specGrid = 0;
-  // two sets of side planes, alternating by job: on a pipelined context the merge of job t's final mask runs on the mapping stream
-  // while job t + 1 writes the other set
+  for (int guard = 0; guard <= 200; guard++) {
+    if (sample) HIPCHK(hipEventRecord(c->ev_a, c->stream));
+    if (int rc = enqueue(budget)) return rc;
+    if (sample) { HIPCHK(hipEventRecord(c->ev_b, c->stream)); c->prof_pending = true; }
+    if (guard == 0 && hook && t->enqueueHook) t->enqueueHook(t->enqueueHookUser);
+    bool finished = false;
+    if (int rc = wait(guard, &finished)) return rc;
+    if (finished) return LSDHIP_OK;
+    if (int rc = prof_collect(c)) return rc;
+    budget = topUp(guard);
+  }
+  lsd_set_error("%s did not terminate", what);
+  return LSDHIP_E_STATE;
+}
+
+// The side planes (refPixelWasGood of trials 1 ..) the job being launched writes: two sets, alternating by job — on a pipelined context
+// the merge of job t's final mask runs on the mapping stream while job t + 1 writes the other set.
+static uint8_t* side_planes(const lsdhip_tracker* t) { return t->d_maskSide + (size_t)t->maskSet * t->maskStride * (LSD_SPEC_MAX - 1); }
+static int claim_side_planes(lsdhip_tracker* t) {
+  lsdhip_ctx* c = t->ctx;
   t->maskSet ^= 1;
-  t->spec.wasGoodSide = t->d_maskSide + (size_t)t->maskSet * t->maskStride * (LSD_SPEC_MAX - 1);
-  t->spec.maskStride = (unsigned)t->maskStride;
-  t->spec.copyMask = c->pipeline ? 0 : 1;
   if (c->pipeline && t->maskMergeSeq[t->maskSet] != 0) {
     // the merge that reads this set (noted two jobs ago) must have run before the set is overwritten (in a frame loop a mapping
     // operation has queued it long ago and the job's own frame was created behind it)
@@ -1963,134 +2048,105 @@ static int track_device(lsdhip_tracker* t, TrackJob& job, int topLevel, const ls
     if (int rcw = lsd_t_wait_m(c, t->maskMergeSeq[t->maskSet])) return rcw;
     t->maskMergeSeq[t->maskSet] = 0;
   }
-  // Trials per launch and workgroups per trial, per level.  Speculation pays where a level is latency-bound, i.e. small: the
-  // automatic policy goes by the level's pixel (or point) count — <= 6 K: 6 trials, <= 24 K: 5, <= 88 K: 5 trials on specCap (80)
-  // workgroups each (multi-pass; 4 x 104 measured 1.5 % slower), larger: one evaluation per launch on the full grid (such levels are work-bound: at
-  // 1280x1024 speculating on level 1 cost 15 % of the frame rate).  An explicit lsdhip_tracker_set_speculation / the
-  // LSDHIP_SPEC_LEVELS / _CAPS environment overrides it.
-  for (int l = 0; l < LSD_LEVELS; l++) t->spec.trials[l] = 1;
-  if (t->specC > 1) {
-    for (int l = job.lastLevel; l <= topLevel; l++) {
-      TrackLevel& L = job.lv[l];
-      const long long work = L.npts >= 0 ? L.npts : (long long)L.w * L.h;
-      int trials, cap = t->specCaps[l];
-      if (t->specLevel[l] > 0) trials = t->specLevel[l];
-      else if (!t->specAuto) trials = t->specC;
-      else trials = work <= LSD_SPEC_SMALL_PX ? LSD_SPEC_TRIALS_SMALL : (work <= LSD_SPEC_MID_PX ? LSD_SPEC_TRIALS_MID : 1);
-      if (trials > t->specC) trials = t->specC;
-      if (cap <= 0 && trials > 1 && (t->specAuto ? work > LSD_SPEC_CAP_ABOVE_PX : l == job.lastLevel)) cap = t->specCap > 0 ? t->specCap : ((t->grid_cap / 2 + 7) & ~7);
-      t->spec.trials[l] = trials;
-      if (trials > 1 && cap > 0 && L.nblocks > cap && L.tilePx == 0) {
-        L.nblocks = cap;
-        L.singlePass = (long long)L.nblocks * t->block >= work ? 1 : 0;
-      }
-    }
+  return LSDHIP_OK;
+}
+// The plan of a single job's launches (track_plan.hpp) under the tracker's speculation settings; the job's tilings become the plan's.
+static SinglePlan plan_job(const lsdhip_tracker* t, TrackJob& job) {
+  LevelWork lv[LSD_LEVELS];
+  SpecPolicy p;
+  p.specC = t->specC; p.specAuto = t->specAuto; p.specCap = t->specCap; p.grid_cap = t->grid_cap; p.block = t->block;
+  for (int l = 0; l < LSD_LEVELS; l++) {
+    const TrackLevel& L = job.lv[l];
+    lv[l] = {L.npts >= 0 ? (long long)L.npts : (long long)L.w * L.h, {L.nblocks, L.singlePass, L.tilePx}};
+    p.specLevel[l] = t->specLevel[l]; p.specCaps[l] = t->specCaps[l];
   }
-  t->h_summary->done = 0;
-  const TrackSummary* S = t->h_summary;
+  const SinglePlan P = lsd_single_plan(lv, p, job.lastLevel, job.topLevel);
+  for (int l = 0; l < LSD_LEVELS; l++) { job.lv[l].nblocks = P.tiling[l].nblocks; job.lv[l].singlePass = P.tiling[l].singlePass; }
+  return P;
+}
+// ... and the TrackSpec its launches take (launch_step adds the per-launch fields)
+static TrackSpec job_spec(const lsdhip_tracker* t, const SinglePlan& P) {
+  TrackSpec spec = TrackSpec{};
+  spec.specC = t->specC;
+  spec.specGrid = P.specGrid;
+  for (int l = 0; l < LSD_LEVELS; l++) spec.trials[l] = P.trials[l];
+  spec.wasGoodSide = side_planes(t);
+  spec.maskStride = (unsigned)t->maskStride;
+  spec.copyMask = t->ctx->pipeline ? 0 : 1;
+  return spec;
+}
+
+// device-resident LM over levels topLevel..job.lastLevel; one host synchronisation per budget of launches.  Launches of the k_track_step
+// chain a job needs = its evaluating launches + the finalising step; the budget is the most of the recent jobs plus a margin (launches
+// queued behind the finishing one leave at once, ~4 us each).  While profiling, every 8th job's budget is timed and charged to the
+// launches that did work (two event packets and a host-side event query per job cost ~5 % of a frame).
+static int track_device(lsdhip_tracker* t, TrackJob& job, int topLevel, const lsdm::SE3fH& T0, lsdm::SE3fH* Tout) {
+  lsdhip_ctx* c = t->ctx;
+  // (the caller — an extern "C" entry — holds the context mutex once; it is released below while the host waits)
+  job.evalOnly = 0;
+  job.topLevel = topLevel;
+  job.T0 = T0;
+  job.aff_a0 = 1.0f; job.aff_b0 = 0.0f;
+  if (int rc = claim_side_planes(t)) return rc;
+  const SinglePlan plan = plan_job(t, job);
+  const TrackSpec spec = job_spec(t, plan);
+  TrackSummary* S = t->h_summary;
+  volatile const int* done = &S->done;
+  S->done = 0;
   const long long myEpoch = ++c->enqEpoch;   // everything enqueued on the stream so far precedes this job
-  // Launches of the k_track_step chain a job needs = its evaluating launches + the finalising step; budget = the most of the
-  // recent jobs + 2 (launches queued behind the finishing one leave at once, ~4 us each).
-  int budget = 12;
-  if (t->recent[0] > 0) {
-    budget = 0;
-    for (int i = 0; i < 4; i++) if (t->recent[i] > budget) budget = t->recent[i];
-    budget += t->budgetExtra;
-  }
-  if (t->budgetFixed > 0) budget = t->budgetFixed;
-  // timing events on every 8th job only: two event packets and a host-side event query per job cost ~5 % of a frame
   const bool sample = c->prof_on && ((c->prof_tick++ & 7) == 0);
-#ifdef LSD_DEVTOOLS
-  t->dbgJobs++;
-#endif
+  dev_job_begins(t);
   t->jobTag = (t->jobTag % 0x7FFFF) + 1;
   t->launchOrdinal = 0;
-  t->h_summary->seq = 0;
-  t->h_summary->exhausted = 0;
-  int guard = 0;
+  S->seq = 0;
+  S->exhausted = 0;
   int parity = 0, first = 1;
   if (int rc = prof_collect(c)) return rc;
   lsdhip_host_mark(2);
-  while (true) {
-    if (sample) HIPCHK(hipEventRecord(c->ev_a, c->stream));
-    int rc = LSDHIP_OK;
-    rc = launch_steps(t, job, budget, &parity, &first);
-    if (rc) return rc;
-    if (sample) { HIPCHK(hipEventRecord(c->ev_b, c->stream)); c->prof_pending = true; }
+  auto enqueue = [&](int budget) {
+    const int rc = launch_steps(t, job, spec, plan.grid, budget, &parity, &first);
     lsdhip_host_mark(3);
-    if (guard == 0 && t->enqueueHook && job.trackFrameSemantics) t->enqueueHook(t->enqueueHookUser);
+    return rc;
+  };
+  // The finishing step writes the summary to pinned host memory and raises `done` last (system-scope fence in between): poll it instead
+  // of sleeping in hipStreamSynchronize, whose wake-up costs more than two evaluations; the budget's last launch says so if it leaves the
+  // job unfinished (`exhausted`).  Steps of the budget still queued behind the finishing one exit immediately; later work is stream-ordered.
+  auto wait = [&](int guard, bool* finished) -> int {
     lsdhip_host_mark(4);
-    // The finishing step writes the summary to pinned host memory and raises `done` last (system-scope fence in
-    // between): poll it instead of sleeping in hipStreamSynchronize, whose wake-up costs more than two evaluations.
-    // Steps of the budget still queued behind the finishing one exit immediately; later work is stream-ordered.
-#ifdef LSD_DEVTOOLS
-    const auto tw0 = std::chrono::steady_clock::now();
-    struct WaitClock { lsdhip_tracker* t; std::chrono::steady_clock::time_point t0; ~WaitClock() { t->dbgWaitNs += std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t0).count(); } } waitClock_{t, tw0};
-#endif
-    c->mtx.unlock();    // nothing below touches context state until the result is in: let the mapping thread enqueue
-    struct Relock { std::recursive_mutex& m; ~Relock() { m.lock(); } };
+    DevWaitClock waitClock_(t);
     {
-    Relock relock_{c->mtx};
-    if (t->spinWait) {
-      volatile const int* done = &S->done;
-      volatile const int* exhausted = &S->exhausted;
-      const int lastSeq = t->spec.seq;                      // tag of the last launch enqueued
-      const auto tStart = std::chrono::steady_clock::now();
-      unsigned spins = 0;
-      while (*done != t->jobTag) {
-        if (*exhausted == lastSeq) break;                   // budget consumed, job unfinished (the last launch said so)
-        if ((++spins & 0xFFFFFu) == 0) {                    // safety net only (a faulted launch never reports): every ~30 ms
-          hipError_t q = hipStreamQuery(c->stream);
-          if (q == hipSuccess) break;                       // budget consumed (done or not)
-          if (q != hipErrorNotReady) { lsd_set_error("hipStreamQuery failed: %s", hipGetErrorString(q)); return LSDHIP_E_HIP; }
-          if (std::chrono::steady_clock::now() - tStart > std::chrono::seconds(5)) { HIPCHK(hipStreamSynchronize(c->stream)); break; }
-        }
-        __builtin_ia32_pause();
+      LsdCtxUnlocked unlocked_(c);   // let the mapping thread enqueue
+      if (t->spinWait) {
+        volatile const int* exhausted = &S->exhausted;
+        const int tag = t->jobTag, lastSeq = launch_seq(t);
+        if (int rc = lsd_spin_until(c, [=]() { return *done == tag || *exhausted == lastSeq; }, lsd_deadline(LSD_JOB_WAIT_S), LSD_WAIT_JOB)) return rc;
+      } else {
+        HIPCHK(hipStreamSynchronize(c->stream));
       }
-      std::atomic_thread_fence(std::memory_order_acquire);
-    } else {
-      HIPCHK(hipStreamSynchronize(c->stream));
-    }
     }
     lsdhip_host_mark(5);
-    if (*(volatile const int*)&S->done == t->jobTag) break;
-#ifdef LSD_DEVTOOLS
-    t->dbgMisses++;
-#endif
-    HIPCHK(hipStreamSynchronize(c->stream));   // out of budget: rare
-#ifdef LSD_DEVTOOLS
-    {
-      static const bool dumpL0 = getenv("LSDHIP_DUMP_L0") != nullptr;
-      if (dumpL0 && guard == 0 && t->budgetFixed == 1) {
-        // the first launch (level `topLevel`, one trial) wrote parity 1, trial 0: rows | keys | tail contributions of its tiles
-        const TrackScratch sc = scratch_of(t);
-        const size_t rows = (size_t)t->max_blocks;
-        const int nb = job.lv[topLevel].nblocks;
-        t->dumpL0.assign((size_t)nb * (RS_COLS + 4 + 96) + sizeof(TrackState) / 4, 0u);
-        unsigned* d = t->dumpL0.data();
-        HIPCHK(hipMemcpy(d, sc.sums + (size_t)(1 * LSD_SPEC_MAX + 0) * RS_COLS * rows, (size_t)nb * RS_COLS * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(d + (size_t)nb * RS_COLS, sc.topkey + (size_t)(1 * LSD_SPEC_MAX + 0) * rows, (size_t)nb * 16, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(d + (size_t)nb * (RS_COLS + 4), sc.topval + (size_t)(1 * LSD_SPEC_MAX + 0) * rows * 96, (size_t)nb * 96 * 4, hipMemcpyDeviceToHost));
-        HIPCHK(hipMemcpy(d + (size_t)nb * (RS_COLS + 4 + 96), t->d_state + 1, sizeof(TrackState), hipMemcpyDeviceToHost));
-      }
+    if (*done != t->jobTag) {
+      dev_budget_missed(t);
+      HIPCHK(hipStreamSynchronize(c->stream));   // out of budget: rare
+      if (int rc = dev_dump_first_launch(t, job, topLevel, guard)) return rc;
     }
-#endif
-    if (*(volatile const int*)&S->done == t->jobTag) break;
-    if (int rc2 = prof_collect(c)) return rc2;
+    *finished = *done == t->jobTag;
+    return LSDHIP_OK;
+  };
+  auto topUp = [&](int guard) {
     if (t->jobKf && t->jobKf->depthVersion != t->jobKfVersion && guard < 8) {
       // While the host waited without the context lock, the mapping thread rewrote the keyframe's depth planes (setDepth): the
       // launches appended now would read the new planes in the middle of a job that started on the old ones.  The reference's
       // TrackingReference is a snapshot that cannot change under a job, so run the job again, whole, on the planes as they are now.
       t->jobKfVersion = t->jobKf->depthVersion;
-      t->h_summary->done = 0;
+      S->done = 0;
       parity = 0; first = 1;
-      budget = 12;
-      ++guard;
-      continue;
+      return 12;
     }
-    budget = t->budgetFixed > 0 ? t->budgetFixed : 6;
-    if (++guard > 200) { lsd_set_error("tracking job did not terminate"); return LSDHIP_E_STATE; }
-  }
+    return t->budgetFixed > 0 ? t->budgetFixed : 6;
+  };
+  if (int rc = run_budgets(t, sample, job.trackFrameSemantics != 0, t->recent.budget(12, t->budgetExtra, t->budgetFixed), "tracking job", enqueue, wait, topUp))
+    return rc;
   // `done` is in; the rest of the record is taken only once it adds up (summary_wait_consistent)
   if (int rcs = summary_wait_consistent(t, t->jobTag)) return rcs;
   if (sample) {
@@ -2098,21 +2154,9 @@ static int track_device(lsdhip_tracker* t, TrackJob& job, int topLevel, const ls
     c->prof_launches += S->numLaunches;
   }
   if (myEpoch > c->doneEpoch) c->doneEpoch = myEpoch;
-#ifdef LSD_DEVTOOLS
-  {
-    static const bool keepLog = getenv("LSDHIP_LAUNCH_LOG") != nullptr;
-    if (keepLog) {
-      // every launch of the job has been queued; wait for the ones behind the finishing launch too, then keep the log and clear it
-      HIPCHK(hipStreamSynchronize(c->stream));
-      const int n = t->launchOrdinal < 4095 ? t->launchOrdinal + 1 : 4096;
-      t->lastLog.assign((size_t)n * 16, 0);
-      HIPCHK(hipMemcpy(t->lastLog.data(), t->d_log, (size_t)n * 64, hipMemcpyDeviceToHost));
-      HIPCHK(hipMemset(t->d_log, 0, (size_t)n * 64));
-    }
-  }
-#endif
+  if (int rc = dev_keep_launch_log(t)) return rc;
   t->numLaunches = S->numLaunches;
-  t->recent[3] = t->recent[2]; t->recent[2] = t->recent[1]; t->recent[1] = t->recent[0]; t->recent[0] = t->numLaunches;
+  t->recent.note(t->numLaunches);
   for (int l = 0; l < LSD_LEVELS; l++) t->levelEvaluations[l] = S->levelEvals[l];
   take_summary(t, S);
   *Tout = pose_of(S);
@@ -2236,25 +2280,7 @@ extern "C" int lsdhip_tracker_track(lsdhip_tracker* t, lsdhip_frame* kf, lsdhip_
   if (rc) return rc;
   if (int rcg = lsd_gate_open(c)) return rcg;
   if (int rcd = lsd_pipe_dummy(c)) return rcd;
-#ifdef LSD_DEVTOOLS
-  static const bool traceInputs = getenv("LSDHIP_TRACE_INPUTS") != nullptr;
-  auto trace_inputs = [&](int base) {
-    for (int l = 1; l <= 4; l++) {
-      const size_t nl = (size_t)c->wl[l] * c->hl[l];
-      lsd_trace_sum(c, c->stream, base + 10 + l, frame->id, kf->d_idepth[l], nl * 4);
-      lsd_trace_sum(c, c->stream, base + 14 + l, frame->id, kf->d_idepthVar[l], nl * 4);
-      lsd_trace_sum(c, c->stream, base + 50 + l, frame->id, kf->d_image[l], nl * 4);
-      lsd_trace_sum(c, c->stream, base + 54 + l, frame->id, frame->d_grad[l], nl * 16);
-    }
-  };
-  if (traceInputs) trace_inputs(0);
-  {
-    unsigned long long pv = 0;
-    for (int i = 0; i < 7; i++) { unsigned long long u; memcpy(&u, &init[i], 8); pv = pv * 1000003ull + u; }
-    lsd_trace_val(c, 22, frame->id, pv);
-    lsd_trace_val(c, 23, frame->id, (unsigned long long)kf->id);
-  }
-#endif
+  dev_trace_job(c, kf, frame, init);
   lsdm::SE3fH referenceToFrame = lsdm::se3f_from_d(lsdm::se3d_inverse(lsdm::se3d_from7(init)));
 
   if (t->hostLM) {
@@ -2265,75 +2291,23 @@ extern "C" int lsdhip_tracker_track(lsdhip_tracker* t, lsdhip_frame* kf, lsdhip_
     t->lastResidual = last_residual;
     if (rc == LSDHIP_DIVERGED) return finish_diverged(t, out);
     if (rc) return rc;
-    // host-LM debugging path: build the summary the common epilogue expects
-    TrackSummary S = *t->h_summary;
-    S.diverged = 0;
-    S.q[0] = referenceToFrame.q.w; S.q[1] = referenceToFrame.q.x; S.q[2] = referenceToFrame.q.y; S.q[3] = referenceToFrame.q.z;
-    S.t[0] = referenceToFrame.t[0]; S.t[1] = referenceToFrame.t[1]; S.t[2] = referenceToFrame.t[2];
-    S.lastResidual = last_residual; S.numEvaluations = t->numEvaluations; S.numWarpUpdates = t->numWarpUpdates;
-    S.pointUsage = t->pointUsage; S.goodCount = t->lastGoodCount; S.badCount = t->lastBadCount; S.meanRes = t->lastMeanRes;
-    S.aff_a = t->affineEstimation_a; S.aff_b = t->affineEstimation_b;
-    S.aff_a_lastIt = t->affineEstimation_a_lastIt; S.aff_b_lastIt = t->affineEstimation_b_lastIt;
+    const TrackSummary S = host_lm_summary(t, referenceToFrame, last_residual);
     return finish_trackframe(t, &S, kf, frame, out);
   }
   t->jobKf = kf;
   t->jobKfVersion = kf->depthVersion;
-#ifdef LSD_DEVTOOLS
-  const lsdm::SE3fH referenceToFrame0 = referenceToFrame;
-  lsd_trace_val(c, 26, frame->id, t->dbgCum / 400ull);
-#endif
-  rc = track_device(t, job, LSD_TRACK_MAX_LEVEL - 1, referenceToFrame, &referenceToFrame);
-  if (rc != LSDHIP_OK && rc != LSDHIP_DIVERGED) { t->jobKf = nullptr; return rc; }
-#ifdef LSD_DEVTOOLS
-  static const bool replay = getenv("LSDHIP_TRACK_REPLAY") != nullptr;
-  if (replay && c->pipeline) {
-    // developer check: the same job once more with the mapping stream drained — identical inputs must give the identical result
-    unsigned long long pv = 0;
-    for (int i = 0; i < 4; i++) { unsigned u; memcpy(&u, &t->h_summary->q[i], 4); pv = pv * 1000003ull + u; }
-    for (int i = 0; i < 3; i++) { unsigned u; memcpy(&u, &t->h_summary->t[i], 4); pv = pv * 1000003ull + u; }
-    lsd_trace_val(c, 24, frame->id, pv);
-    lsd_trace_val(c, 25, frame->id, (unsigned long long)t->h_summary->numEvaluations * 1000 + t->h_summary->lastCand);
-    HIPCHK(hipStreamSynchronize(c->mstream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    c->mDoneSeq = c->mSeq;
-    const std::vector<unsigned> dump1 = t->dumpL0;
-    if (traceInputs) trace_inputs(100);
-    lsd_trace_val(c, 27, frame->id, t->dbgCum / 400ull);
-    referenceToFrame = referenceToFrame0;
-    rc = track_device(t, job, LSD_TRACK_MAX_LEVEL - 1, referenceToFrame, &referenceToFrame);
-    if (rc != LSDHIP_OK && rc != LSDHIP_DIVERGED) { t->jobKf = nullptr; return rc; }
-    HIPCHK(hipStreamSynchronize(c->stream));
-    if (!dump1.empty() && dump1.size() == t->dumpL0.size()) {
-      const int nb = job.lv[LSD_TRACK_MAX_LEVEL - 1].nblocks;
-      int shown = 0;
-      for (size_t i = 0; i < dump1.size(); i++)
-        if (dump1[i] != t->dumpL0[i] && shown++ < 12) {
-          const size_t a = (size_t)nb * RS_COLS, b = a + (size_t)nb * 4, cst = b + (size_t)nb * 96;
-          float f1, f2; memcpy(&f1, &dump1[i], 4); memcpy(&f2, &t->dumpL0[i], 4);
-          if (i < a) fprintf(stderr, "L0DIFF frame %d: sums tile %zu column %zu: run %.9g (%08x) replay %.9g (%08x)\n", frame->id, i / RS_COLS, i % RS_COLS, f1, dump1[i], f2, t->dumpL0[i]);
-          else if (i < b) fprintf(stderr, "L0DIFF frame %d: topkey tile %zu [%zu]: run %d replay %d\n", frame->id, (i - a) / 4, (i - a) % 4, (int)dump1[i], (int)t->dumpL0[i]);
-          else if (i < cst) fprintf(stderr, "L0DIFF frame %d: topval tile %zu slot %zu entry %zu: run %.9g replay %.9g\n", frame->id, (i - b) / 96, ((i - b) % 96) / 32, (i - b) % 32, f1, f2);
-          else fprintf(stderr, "L0DIFF frame %d: state word %zu: run %08x (%.9g) replay %08x (%.9g)\n", frame->id, i - cst, dump1[i], f1, t->dumpL0[i], f2);
-        }
-      if (shown) fprintf(stderr, "L0DIFF frame %d: %d words differ after the first launch\n", frame->id, shown);
-    }
-  }
-#endif
+  const lsdm::SE3fH T0 = referenceToFrame;
+  dev_trace_launched(t, 26, frame);
+  rc = track_device(t, job, LSD_TRACK_MAX_LEVEL - 1, T0, &referenceToFrame);
+  if (rc == LSDHIP_OK || rc == LSDHIP_DIVERGED) rc = dev_replay_check(t, job, kf, frame, T0, &referenceToFrame, rc);
   t->jobKf = nullptr;
+  if (rc != LSDHIP_OK && rc != LSDHIP_DIVERGED) return rc;
   lsdhip_host_mark(6);
-#ifdef LSD_DEVTOOLS
-  {
-    unsigned long long pv = 0;
-    for (int i = 0; i < 4; i++) { unsigned u; memcpy(&u, &t->h_summary->q[i], 4); pv = pv * 1000003ull + u; }
-    for (int i = 0; i < 3; i++) { unsigned u; memcpy(&u, &t->h_summary->t[i], 4); pv = pv * 1000003ull + u; }
-    lsd_trace_val(c, 20, frame->id, pv);
-    lsd_trace_val(c, 21, frame->id, (unsigned long long)t->h_summary->numEvaluations * 1000 + t->h_summary->lastCand);
-  }
-#endif
+  dev_trace_result(t, 20, frame);
   if (c->pipeline && rc == LSDHIP_OK && t->h_summary->lastCand > 0 && t->h_summary->level == LSD_TRACK_MIN_LEVEL) {
     // the final mask sits in a side plane: to be merged into the frame's plane on the mapping stream, ahead of whatever reads the mask
     // next — noted here, queued by the next mapping-stream operation (nothing is launched between two tracking jobs)
-    const uint8_t* side = t->spec.wasGoodSide + (size_t)(t->h_summary->lastCand - 1) * t->maskStride;
+    const uint8_t* side = side_planes(t) + (size_t)(t->h_summary->lastCand - 1) * t->maskStride;
     t->maskMergeSeq[t->maskSet] = -1;               // pending
     c->pendingMerges.push_back({frame->d_wasGood, side, &t->maskMergeSeq[t->maskSet]});
   }
@@ -2359,172 +2333,158 @@ static int batch_reserve(lsdhip_tracker* t, int n) {
   HIPCHK(hipHostMalloc((void**)&t->h_bsummary, B * sizeof(TrackSummary), hipHostMallocMapped));
   return LSDHIP_OK;
 }
-// scratch of a batch: arrays over [job][parity][trial]; cmax = trial slots per parity (1: no speculation)
-static TrackScratch batch_scratch(lsdhip_tracker* t, int cmax) {
-  return scratch_at(t, t->d_bscratch, (size_t)t->batch_capacity, LSD_BATCH_SPEC_MAX, cmax);
+// What every launch of a batch takes besides its shape: the scratch (arrays over [job][parity][trial]; cmax = trial slots per parity, 1: no
+// speculation) and the device alias of the pinned summaries.  Built once per batch.
+struct BatchLaunch { TrackScratch sc; TrackSummary* d_sum; };
+static int batch_launch_record(lsdhip_tracker* t, int cmax, BatchLaunch* out) {
+  out->sc = scratch_at(t, t->d_bscratch, (size_t)t->batch_capacity, LSD_BATCH_SPEC_MAX, cmax);
+  HIPCHK(hipHostGetDevicePointer((void**)&out->d_sum, t->h_bsummary, 0));
+  return LSDHIP_OK;
 }
-// runs the n jobs described in t->h_bjobs[0..n) to completion; summaries in t->h_bsummary
-static int batch_run(lsdhip_tracker* t, int n, bool callHook = false) {
+// one k_track_step launch over the n jobs in t->d_bjobs (job = blockIdx.y), `grid` workgroups each
+template <int MODE>
+static void launch_batch_step(lsdhip_tracker* t, const BatchLaunch& r, int grid, int n, int parity, int first, const TrackSpec& spec) {
+  hipLaunchKernelGGL((k_track_step<256, true, MODE>), dim3(grid, n), dim3(256), 0, t->ctx->stream, t->h_bjobs[0], (const TrackJob*)t->d_bjobs, t->d_bstate,
+                     r.sc, r.d_sum, parity, first, spec);
+}
+// the plan (track_plan.hpp) of the batch described in t->h_bjobs[0..n) under the tracker's settings and the developer switches
+static BatchPlan plan_batch(const lsdhip_tracker* t, int n) {
+  const BatchEnv& env = batch_env();
+  BatchPolicy p;
+  p.specC = t->specC; p.specMax = env.specMax; p.specPixels = env.specPixels; p.fused = env.fused;
+  p.spinWait = t->spinWait; p.poll = env.poll;
+  p.soloMin = t->soloMinJobs >= 0 ? t->soloMinJobs : env.soloMin;     // lsdhip_tracker_set_batch_coarse_min_jobs
+  return lsd_batch_plan(n, p, [t](int j, int l) {
+    const TrackJob& job = t->h_bjobs[j];
+    const TrackLevel& L = job.lv[l];
+    return BatchLevel{(long long)L.w * L.h, L.nblocks, L.tilePx, L.writeMask, job.lastLevel <= l && l <= job.topLevel};
+  });
+}
+// Runs the n jobs batch_open left in t->d_bjobs to completion; summaries in t->h_bsummary.  record: the rounds it took size the next
+// batch's budget and become launch_stats (not for the test hook lsdhip_tracker_evaluate_batch).
+// Fused rounds: the host polls the jobs' summaries in pinned memory (as lsdhip_tracker_track does for one job) instead of draining the
+// stream: the budget's launches behind the last job's finishing step (~3 us each, a handful per batch) then run while the host is
+// already reading the results and queueing what follows.  `done` carries the batch's tag, the record is taken once it adds up to its
+// check word; the budget's last launch reports a job it leaves unfinished (`exhausted`).
+static int batch_run(lsdhip_tracker* t, int n, bool callHook, bool record) {
   lsdhip_ctx* c = t->ctx;
   LSD_CTX_LOCK(c);
   const BatchEnv& env = batch_env();
-  int grid = 1;
-  bool split = false;
-  for (int j = 0; j < n; j++) {
-    const TrackJob& job = t->h_bjobs[j];
-    for (int l = job.lastLevel; l <= job.topLevel; l++) {
-      if (job.lv[l].nblocks > grid) grid = job.lv[l].nblocks;
-      if (job.lv[l].tilePx > 0) split = true;
-    }
-    t->h_bsummary[j].done = 0;
-  }
-  HIPCHK(hipMemcpyAsync(t->d_bjobs, t->h_bjobs, (size_t)n * sizeof(TrackJob), hipMemcpyHostToDevice, c->stream));
-  // Reject-chain speculation in throughput mode (as single jobs have it, SE3Tracker.cpp:341-447): a step evaluates the next `trials`
-  // retries of the LM loop side by side, the next step consumes them in the reference's order — same decisions, same evaluation
-  // counts, fewer dependent rounds.  Per level as many trials as keep jobs x trials x pixels of the level within LSD_BATCH_SPEC_PIXELS
-  // (a round must not cost more than the rounds it saves); one at the level that writes refPixelWasGood (no side planes in batches).
+  const BatchPlan plan = plan_batch(t, n);
   TrackSpec spec = TrackSpec{};
 #ifdef LSD_PHASE_TRACE
   spec.traceWg = env.traceWg;
 #endif
-  int lmGrid = 1;
-  int specMax = env.specMax;
-  if (t->specC < specMax) specMax = t->specC;        // lsdhip_tracker_set_speculation(t, 1, 0): one evaluation per step, batches too
-  if (env.fused == 1) specMax = 1;
-  if (split && specMax > 1) {
-    for (int l = 0; l < LSD_LEVELS; l++) spec.trials[l] = 1;
-    const TrackJob& j0 = t->h_bjobs[0];
-    for (int l = j0.lastLevel; l <= j0.topLevel; l++) {
-      bool ok = true;
-      for (int j = 0; j < n; j++) ok = ok && t->h_bjobs[j].lv[l].tilePx > 0 && !t->h_bjobs[j].lv[l].writeMask && t->h_bjobs[j].lastLevel <= l && t->h_bjobs[j].topLevel >= l;
-      if (!ok) continue;
-      long long tr = env.specPixels / ((long long)j0.lv[l].w * j0.lv[l].h * n);
-      if (tr > specMax) tr = specMax;
-      if (tr < 1) tr = 1;
-      spec.trials[l] = (int)tr;
-      if (tr > lmGrid) lmGrid = (int)tr;
-    }
-    spec.specC = lmGrid;
-    // the evaluation launch holds (trial, strip) workgroups of the level with the most of them
-    for (int j = 0; j < n; j++) {
-      const TrackJob& job = t->h_bjobs[j];
-      for (int l = job.lastLevel; l <= job.topLevel; l++) if (job.lv[l].nblocks * spec.trials[l] > grid) grid = job.lv[l].nblocks * spec.trials[l];
-    }
+  if (plan.speculates) {
+    spec.specC = plan.lmGrid;
+    for (int l = 0; l < LSD_LEVELS; l++) spec.trials[l] = plan.trials[l];
   }
-  const TrackScratch sc = batch_scratch(t, split && lmGrid > 1 ? LSD_BATCH_SPEC_MAX : 1);
-  TrackSummary* d_sum = nullptr;
-  HIPCHK(hipHostGetDevicePointer((void**)&d_sum, t->h_bsummary, 0));
+  BatchLaunch rec;
+  if (int rc = batch_launch_record(t, plan.cmax, &rec)) return rc;
   if (int rcp = prof_collect(c)) return rcp;
-  // budget of rounds: what the recent batches needed (+ the finishing step and a margin); launches behind the last job's finishing step
-  // cost ~3 us each
-  int budget = 26;
-  if (split && t->batchRecent[0] > 0) {
-    budget = 0;
-    for (int i = 0; i < 4; i++) if (t->batchRecent[i] > budget) budget = t->batchRecent[i];
-    budget += env.margin;
-  }
-  int parity = 0, first = 1, guard = 0;
-  // Fused rounds: the host polls the jobs' summaries in pinned memory (as lsdhip_tracker_track does for one job) instead of draining the
-  // stream: the budget's launches behind the last job's finishing step (~3 us each, a handful per batch) then run while the host is
-  // already reading the results and queueing what follows.  `done` carries the batch's tag, the record is taken once it adds up to its
-  // check word; the budget's last launch reports a job it leaves unfinished (`exhausted`).
-  const bool polled = split && env.fused && t->spinWait && env.poll;
-  if (polled) {
+  if (plan.polled) {
     t->batchTag = t->batchTag >= 0x3FFFFFFF ? 2 : t->batchTag + 1;
     if (t->batchTag < 2) t->batchTag = 2;
     spec.seq = t->batchTag;
     for (int j = 0; j < n; j++) t->h_bsummary[j].exhausted = 0;
   }
-  // the coarse levels of every job inside one workgroup (k_track_solo), then lock-step rounds for the rest
-  const int soloMin = t->soloMinJobs >= 0 ? t->soloMinJobs : env.soloMin;     // lsdhip_tracker_set_batch_coarse_min_jobs
-  bool soloDue = split && env.fused && soloMin > 0 && n >= soloMin;
-  if (soloDue) {
-    // (nothing to walk if no job's top level fits the tile — 1280x1024: level 4 is 80x64 = 5120 pixels —: the launch would only copy states)
-    bool any = false;
-    for (int j = 0; j < n && !any; j++) {
-      const TrackLevel& L = t->h_bjobs[j].lv[t->h_bjobs[j].topLevel];
-      any = L.tilePx > 0 && !L.writeMask && (long long)L.w * L.h <= LSD_SOLO_MAX_PX;
-    }
-    soloDue = any;
-  }
-  while (true) {
-    if (c->prof_on) HIPCHK(hipEventRecord(c->ev_a, c->stream));
+  const bool fused = plan.split && env.fused;
+  bool soloDue = plan.soloDue;
+  int parity = 0, first = 1;
+  auto enqueue = [&](int budget) -> int {
     if (soloDue) {
+      // the coarse levels of every job inside one workgroup (k_track_solo), then lock-step rounds for the rest
       soloDue = false;
-      const int dw = polled ? t->batchTag : 1;
-      hipLaunchKernelGGL(k_track_solo<512>, dim3(n), dim3(512), 0, c->stream, (const TrackJob*)t->d_bjobs, t->d_bstate, d_sum, parity, dw);
+      hipLaunchKernelGGL(k_track_solo<512>, dim3(n), dim3(512), 0, c->stream, (const TrackJob*)t->d_bjobs, t->d_bstate, rec.d_sum, parity, plan.polled ? t->batchTag : 1);
       first = 0;
       parity ^= 1;
     }
-    for (int i = 0; i < budget; i++) {
-      spec.last = (polled && i == budget - 1) ? 1 : 0;
-      if (split && env.fused) {
-        hipLaunchKernelGGL((k_track_step<256, true, TS_FUSED>), dim3(grid, n), dim3(256), 0, c->stream, t->h_bjobs[0], (const TrackJob*)t->d_bjobs,
-                           t->d_bstate, sc, d_sum, parity, first, spec);
-      } else if (split) {
-        // throughput mode: one LM workgroup per (trial, job), then a pure evaluation launch over all jobs' (trial, strip) pairs
-        hipLaunchKernelGGL((k_track_step<256, true, TS_LM>), dim3(lmGrid, n), dim3(256), 0, c->stream, t->h_bjobs[0], (const TrackJob*)t->d_bjobs,
-                           t->d_bstate, sc, d_sum, parity, first, spec);
-        hipLaunchKernelGGL((k_track_step<256, true, TS_EVAL>), dim3(grid, n), dim3(256), 0, c->stream, t->h_bjobs[0], (const TrackJob*)t->d_bjobs,
-                           t->d_bstate, sc, d_sum, 1 - parity, 0, spec);
+    for (int i = 0; i < budget; i++, first = 0, parity ^= 1) {
+      spec.last = (plan.polled && i == budget - 1) ? 1 : 0;
+      if (fused) {
+        launch_batch_step<TS_FUSED>(t, rec, plan.grid, n, parity, first, spec);
+      } else if (plan.split) {
+        // LSDHIP_BATCH_FUSED=0: one LM workgroup per (trial, job), then a pure evaluation launch over all jobs' (trial, strip) pairs
+        launch_batch_step<TS_LM>(t, rec, plan.lmGrid, n, parity, first, spec);
+        launch_batch_step<TS_EVAL>(t, rec, plan.grid, n, 1 - parity, 0, spec);
       } else {
-        hipLaunchKernelGGL((k_track_step<256, true>), dim3(grid, n), dim3(256), 0, c->stream, t->h_bjobs[0], (const TrackJob*)t->d_bjobs,
-                           t->d_bstate, sc, d_sum, parity, first, TrackSpec{});
+        launch_batch_step<TS_FUSED>(t, rec, plan.grid, n, parity, first, TrackSpec{});
       }
-      first = 0;
-      parity ^= 1;
     }
     HIPCHK(hipGetLastError());
-    if (c->prof_on) { HIPCHK(hipEventRecord(c->ev_b, c->stream)); c->prof_pending = true; }
-    // the batch's launches are queued: the place for everything the device can do beside them (lsdhip_tracker_set_enqueue_hook)
-    if (callHook && guard == 0 && t->enqueueHook) t->enqueueHook(t->enqueueHookUser);
+    return LSDHIP_OK;
+  };
+  auto wait = [&](int, bool* finished) -> int {
     bool all = true;
-    if (polled) {
-      const auto t0 = std::chrono::steady_clock::now();
+    if (plan.polled) {
+      const int tag = t->batchTag;
+      const LsdDeadline deadline = lsd_deadline(LSD_BATCH_WAIT_S);
       for (int j = 0; j < n && all; j++) {
         volatile const int* done = &t->h_bsummary[j].done;
         volatile const int* exhausted = &t->h_bsummary[j].exhausted;
-        for (unsigned spins = 0;; spins++) {
-          if (*done == t->batchTag) break;
-          if (*exhausted == t->batchTag) { all = false; break; }
-          if ((spins & 0xFFFFu) == 0xFFFFu) {
-            // the stream may have stopped on an error, or (a budget cut short by a failed launch) nobody is left to report
-            if (hipStreamQuery(c->stream) != hipErrorNotReady) { all = *done == t->batchTag; if (!all) break; }
-            if (std::chrono::steady_clock::now() - t0 > std::chrono::seconds(20)) { lsd_set_error("tracking batch: no progress report from the device"); return LSDHIP_E_STATE; }
-          }
-          __builtin_ia32_pause();
-        }
-        if (all) { if (int rcs = summary_wait_consistent(t, t->batchTag, &t->h_bsummary[j])) return rcs; }
+        if (int rc = lsd_spin_until(c, [=]() { return *done == tag || *exhausted == tag; }, deadline, LSD_WAIT_BATCH)) return rc;
+        all = *done == tag;
+        if (all) { if (int rcs = summary_wait_consistent(t, tag, &t->h_bsummary[j])) return rcs; }
       }
       if (!all) {
         HIPCHK(hipStreamSynchronize(c->stream));   // out of budget: rare
         all = true;
-        for (int j = 0; j < n; j++) { all = all && t->h_bsummary[j].done == t->batchTag; t->h_bsummary[j].exhausted = 0; }
+        for (int j = 0; j < n; j++) { all = all && t->h_bsummary[j].done == tag; t->h_bsummary[j].exhausted = 0; }
       }
     } else {
       HIPCHK(hipStreamSynchronize(c->stream));
       for (int j = 0; j < n; j++) all = all && t->h_bsummary[j].done;
     }
-    if (all) break;
-    if (int rc2 = prof_collect(c)) return rc2;
-    budget = 6;
-    if (++guard > 200) { lsd_set_error("tracking batch did not terminate"); return LSDHIP_E_STATE; }
-  }
+    *finished = all;
+    return LSDHIP_OK;
+  };
+  // budget of rounds: what the recent batches needed (+ the finishing step and a margin); launches behind the last job's finishing step
+  // cost ~3 us each
+  const int budget = plan.split ? t->batchRecent.budget(26, env.margin, 0) : 26;
+  if (int rc = run_budgets(t, c->prof_on, callHook, budget, "tracking batch", enqueue, wait, [](int) { return 6; })) return rc;
   if (c->prof_on)
     for (int j = 0; j < n; j++) { c->prof_bytes += t->h_bsummary[j].bytes; c->prof_launches += t->h_bsummary[j].numEvaluations; }
-  if (split) {
+  if (plan.split && record) {
     int rounds = 0;
     for (int j = 0; j < n; j++) if (t->h_bsummary[j].numLaunches > rounds) rounds = t->h_bsummary[j].numLaunches;
-    t->batchRecent[3] = t->batchRecent[2]; t->batchRecent[2] = t->batchRecent[1]; t->batchRecent[1] = t->batchRecent[0]; t->batchRecent[0] = rounds;
+    t->batchRecent.note(rounds);
     t->numLaunches = rounds;
   }
   return LSDHIP_OK;
 }
 
-// SE3Tracker::trackFrame for n independent (keyframe, frame) pairs in the same launches.  Each job runs the arithmetic
-// of lsdhip_tracker_track (same kernel; a batch tiles a level into fewer workgroups, which only changes summation
-// order); the point is throughput — n evaluations share one launch and its latency chain.  inits: n x 7, results: n.
-// Returns LSDHIP_OK, or LSDHIP_DIVERGED if any job diverged (see results[j].diverged).
+// The shared prologue of the batch entries.  The pairs are complete (a missing frame: LSDHIP_E_ARG; a keyframe without depth:
+// LSDHIP_E_STATE), the reference blocks that the strips of throughput mode read exist, the tracker's batch buffers hold n jobs, and
+// fill(j, job, shape) -> rc has described job j for the batch's shape; the descriptions are on their way to t->d_bjobs and no summary
+// says `done`.  keyframes: nullptr for jobs on point lists.  inputsOnly (lsdhip_tracker_track_batch; the other entries enter behind
+// everything the mapping stream holds, LsdTrackJobScope): on a pipelined context the tracking stream waits for the mapping-stream points
+// the jobs' inputs were complete at (the frames' pyramids, the keyframes' PUBLISHED depth) and for nothing queued behind them.
+struct BatchOpened { int rc; BatchShape shape; };
+template <class Fill>
+static BatchOpened batch_open(lsdhip_tracker* t, const char* entry, int n, lsdhip_frame** keyframes, lsdhip_frame** frames, bool inputsOnly, Fill fill) {
+  lsdhip_ctx* c = t->ctx;
+  LSD_CTX_LOCK(c);
+  BatchOpened o = {LSDHIP_OK, lsd_batch_shape(t->grid_cap, n)};
+  o.rc = [&]() -> int {
+    long long need = 0;
+    for (int j = 0; j < n; j++) {
+      if ((keyframes && !keyframes[j]) || !frames[j]) return LSDHIP_E_ARG;
+      if (keyframes && !keyframes[j]->hasIDepth) { lsd_set_error("%s: keyframe %d (job %d) has no depth", entry, keyframes[j]->id, j); return LSDHIP_E_STATE; }
+      need = std::max(need, frames[j]->readySeq);
+      if (keyframes) need = std::max(need, std::max(keyframes[j]->readySeq, keyframes[j]->depthSeq));
+    }
+    if (c->pipeline && inputsOnly) { if (int rcw = lsd_t_wait_m(c, need)) return rcw; }
+    if (keyframes && n >= LSD_BATCH_THROUGHPUT_MIN_JOBS) { if (int rcb = lsd_frames_require_ref_blocks(keyframes, n, c->stream)) return rcb; }   // the strips read them
+    if (int rc = batch_reserve(t, n)) return rc;
+    for (int j = 0; j < n; j++) {
+      if (int rc = fill(j, t->h_bjobs[j], o.shape)) return rc;
+      t->h_bsummary[j].done = 0;
+    }
+    HIPCHK(hipMemcpyAsync(t->d_bjobs, t->h_bjobs, (size_t)n * sizeof(TrackJob), hipMemcpyHostToDevice, c->stream));
+    return LSDHIP_OK;
+  }();
+  return o;
+}
 extern "C" void lsdhip_build_defaults(lsdhip_build_defaults_t* out) {
   if (!out) return;
   out->ctx_async = LSD_DEFAULT_ASYNC; out->ctx_pipeline = LSD_DEFAULT_PIPELINE;
@@ -2536,41 +2496,29 @@ extern "C" void lsdhip_build_defaults(lsdhip_build_defaults_t* out) {
   out->batch_coarse_min_jobs = LSD_SOLO_MIN_JOBS; out->batch_coarse_max_pixels = LSD_SOLO_MAX_PX; out->batch_coarse_max_points = LSD_SOLO_LDS_PTS;
 }
 
+// SE3Tracker::trackFrame for n independent (keyframe, frame) pairs in the same launches.  Each job runs the arithmetic
+// of lsdhip_tracker_track (same kernel; a batch tiles a level into fewer workgroups, which only changes summation
+// order); the point is throughput — n evaluations share one launch and its latency chain.  inits: n x 7, results: n.
+// Returns LSDHIP_OK, or LSDHIP_DIVERGED if any job diverged (see results[j].diverged).
 extern "C" int lsdhip_tracker_track_batch(lsdhip_tracker* t, int n, lsdhip_frame** keyframes, lsdhip_frame** frames,
                                           const double* inits, lsdhip_track_result* results) {
   if (!t || n <= 0 || !keyframes || !frames || !inits || !results) return LSDHIP_E_ARG;
   lsdhip_ctx* c = t->ctx;
   LSD_CTX_LOCK(c);
   HIPCHK(hipSetDevice(c->device));
-  for (int j = 0; j < n; j++) {
-    if (!keyframes[j] || !frames[j]) return LSDHIP_E_ARG;
-    if (!keyframes[j]->hasIDepth) { lsd_set_error("lsdhip_tracker_track_batch: keyframe %d has no depth", keyframes[j]->id); return LSDHIP_E_STATE; }
-  }
-  if (c->pipeline) {
-    // as lsdhip_tracker_track: the tracking stream waits for the mapping-stream points its inputs were complete at (the frames'
-    // pyramids, the keyframes' PUBLISHED depth) and for nothing queued behind them — the mapping iterations of OTHER sequences run
-    // beside this batch (SlamLoopBatch::setOverlapped).  When batch_run returns only the summaries are complete: the launches of its budget
-    // behind the last job's finishing step may still be queued on the tracking stream (they leave at once, see track_step_impl).
-    long long need = 0;
-    for (int j = 0; j < n; j++) {
-      need = std::max(need, std::max(frames[j]->readySeq, std::max(keyframes[j]->readySeq, keyframes[j]->depthSeq)));
-    }
-    if (int rcw = lsd_t_wait_m(c, need)) return rcw;
-  }
-  if (n >= LSD_BATCH_THROUGHPUT_MIN_JOBS) { if (int rcb = lsd_frames_require_ref_blocks(keyframes, n, c->stream)) return rcb; }   // the strips read them
-  int rc = batch_reserve(t, n);
-  if (rc) return rc;
-  const BatchShape shape = batch_shape(t, n);
-  for (int j = 0; j < n; j++) {
-    TrackJob& job = t->h_bjobs[j];
-    rc = fill_trackframe_job(t, job, shape, keyframes[j], frames[j]);
-    if (rc) return rc;
+  // (pipelined contexts, as lsdhip_tracker_track: mapping iterations of OTHER sequences run beside this batch — SlamLoopBatch::setOverlapped.
+  // When batch_run returns only the summaries are complete: the launches of its budget behind the last job's finishing step may still be
+  // queued on the tracking stream; they leave at once, see track_step_impl.)
+  const BatchOpened o = batch_open(t, "lsdhip_tracker_track_batch", n, keyframes, frames, true, [&](int j, TrackJob& job, BatchShape shape) {
+    if (int rcf = fill_trackframe_job(t, job, shape, keyframes[j], frames[j])) return rcf;
     job.evalOnly = 0;
     job.topLevel = LSD_TRACK_MAX_LEVEL - 1;
     job.T0 = lsdm::se3f_from_d(lsdm::se3d_inverse(lsdm::se3d_from7(inits + 7 * (size_t)j)));
     job.aff_a0 = 1.0f; job.aff_b0 = 0.0f;
-  }
-  rc = batch_run(t, n, true);
+    return (int)LSDHIP_OK;
+  });
+  if (o.rc) return o.rc;
+  int rc = batch_run(t, n, true, true);
   if (rc) return rc;
   int rcAll = LSDHIP_OK;
   for (int j = 0; j < n; j++) {
@@ -2597,23 +2545,16 @@ extern "C" int lsdhip_tracker_eval_throughput(lsdhip_tracker* t, int n, lsdhip_f
   if (tjob_.rc) return tjob_.rc;
   HIPCHK(hipSetDevice(c->device));
   for (int j = 0; j < n; j++) if (!keyframes[j] || !frames[j] || !keyframes[j]->hasIDepth) return LSDHIP_E_ARG;
-  if (int rcb = lsd_frames_require_ref_blocks(keyframes, n, c->stream)) return rcb;
-  int rc = batch_reserve(t, n);
-  if (rc) return rc;
-  const BatchShape shape = batch_shape(t, n);
   int grid = 1;
-  for (int j = 0; j < n; j++) {
-    TrackJob& job = t->h_bjobs[j];
-    rc = fill_eval_job(t, job, shape, keyframes[j], frames[j], level, refToFrame + 7 * (size_t)j, 1.0f, 0.0f);
-    if (rc) return rc;
+  const BatchOpened o = batch_open(t, "lsdhip_tracker_eval_throughput", n, keyframes, frames, false, [&](int j, TrackJob& job, BatchShape shape) {
+    if (int rcf = fill_eval_job(t, job, shape, keyframes[j], frames[j], level, refToFrame + 7 * (size_t)j, 1.0f, 0.0f)) return rcf;
     if (job.lv[level].nblocks > grid) grid = job.lv[level].nblocks;
-    if (job.lv[level].tilePx == 0) { lsd_set_error("lsdhip_tracker_eval_throughput: level %d is not in throughput mode", level); return LSDHIP_E_STATE; }
-    t->h_bsummary[j].done = 0;
-  }
-  HIPCHK(hipMemcpyAsync(t->d_bjobs, t->h_bjobs, (size_t)n * sizeof(TrackJob), hipMemcpyHostToDevice, c->stream));
-  const TrackScratch sc = batch_scratch(t, 1);
-  TrackSummary* d_sum = nullptr;
-  HIPCHK(hipHostGetDevicePointer((void**)&d_sum, t->h_bsummary, 0));
+    if (job.lv[level].tilePx == 0) { lsd_set_error("lsdhip_tracker_eval_throughput: level %d is not in throughput mode", level); return (int)LSDHIP_E_STATE; }
+    return (int)LSDHIP_OK;
+  });
+  if (o.rc) return o.rc;
+  BatchLaunch rec;
+  if (int rcl = batch_launch_record(t, 1, &rec)) return rcl;
   struct EventPair {      // destroyed on every exit path
     hipEvent_t a = nullptr, b = nullptr;
     ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
@@ -2621,20 +2562,12 @@ extern "C" int lsdhip_tracker_eval_throughput(lsdhip_tracker* t, int n, lsdhip_f
   HIPCHK(hipEventCreate(&evp.a));
   HIPCHK(hipEventCreate(&evp.b));
   const hipEvent_t e0 = evp.a, e1 = evp.b;
-  hipLaunchKernelGGL((k_track_step<256, true, TS_LM>), dim3(1, n), dim3(256), 0, c->stream, t->h_bjobs[0], (const TrackJob*)t->d_bjobs, t->d_bstate, sc,
-                     d_sum, 0, 1, TrackSpec{});
-  auto eval_launch = [&]() -> int {
-    hipLaunchKernelGGL((k_track_step<256, true, TS_EVAL>), dim3(grid, n), dim3(256), 0, c->stream, t->h_bjobs[0], (const TrackJob*)t->d_bjobs, t->d_bstate, sc,
-                       d_sum, 1, 0, TrackSpec{});
-    return LSDHIP_OK;
-  };
-  if (int rcw = eval_launch()) return rcw;     // warm-up
+  launch_batch_step<TS_LM>(t, rec, 1, n, 0, 1, TrackSpec{});
+  launch_batch_step<TS_EVAL>(t, rec, grid, n, 1, 0, TrackSpec{});     // warm-up
   HIPCHK(hipEventRecord(e0, c->stream));
-  for (int r = 0; r < repeats; r++)
-    if (int rce = eval_launch()) return rce;
+  for (int r = 0; r < repeats; r++) launch_batch_step<TS_EVAL>(t, rec, grid, n, 1, 0, TrackSpec{});
   HIPCHK(hipEventRecord(e1, c->stream));
-  hipLaunchKernelGGL((k_track_step<256, true, TS_LM>), dim3(1, n), dim3(256), 0, c->stream, t->h_bjobs[0], (const TrackJob*)t->d_bjobs, t->d_bstate, sc,
-                     d_sum, 1, 0, TrackSpec{});
+  launch_batch_step<TS_LM>(t, rec, 1, n, 1, 0, TrackSpec{});
   HIPCHK(hipGetLastError());
   HIPCHK(hipStreamSynchronize(c->stream));
   float ms = 0;
@@ -2683,26 +2616,11 @@ extern "C" int lsdhip_tracker_evaluate_batch(lsdhip_tracker* t, int n, lsdhip_fr
   LsdTrackJobScope tjob_(c, true);
   if (tjob_.rc) return tjob_.rc;
   HIPCHK(hipSetDevice(c->device));
-  for (int j = 0; j < n; j++) {
-    if (!keyframes[j] || !frames[j]) return LSDHIP_E_ARG;
-    if (!keyframes[j]->hasIDepth) { lsd_set_error("lsdhip_tracker_evaluate_batch: keyframe of job %d has no depth", j); return LSDHIP_E_STATE; }
-  }
-  if (n >= LSD_BATCH_THROUGHPUT_MIN_JOBS) { if (int rcb = lsd_frames_require_ref_blocks(keyframes, n, c->stream)) return rcb; }   // the strips read them
-  int rc = batch_reserve(t, n);
-  if (rc) return rc;
-  const BatchShape shape = batch_shape(t, n);
-  for (int j = 0; j < n; j++) {
-    rc = fill_eval_job(t, t->h_bjobs[j], shape, keyframes[j], frames[j], level, refToFrame + 7 * (size_t)j, affine[2 * (size_t)j], affine[2 * (size_t)j + 1]);
-    if (rc) return rc;
-  }
-  // what batch_run leaves in the tracker besides the summaries: the rounds of recent batches (the next batch's budget) and launch_stats
-  int recent[4];
-  memcpy(recent, t->batchRecent, sizeof(recent));
-  const int numLaunches = t->numLaunches;
-  rc = batch_run(t, n);
-  memcpy(t->batchRecent, recent, sizeof(recent));
-  t->numLaunches = numLaunches;
-  if (rc) return rc;
+  const BatchOpened o = batch_open(t, "lsdhip_tracker_evaluate_batch", n, keyframes, frames, false, [&](int j, TrackJob& job, BatchShape shape) {
+    return fill_eval_job(t, job, shape, keyframes[j], frames[j], level, refToFrame + 7 * (size_t)j, affine[2 * (size_t)j], affine[2 * (size_t)j + 1]);
+  });
+  if (o.rc) return o.rc;
+  if (int rc = batch_run(t, n, false, false)) return rc;
   for (int j = 0; j < n; j++) {
     const TrackSummary* S = &t->h_bsummary[j];
     if (!S->done) { lsd_set_error("lsdhip_tracker_evaluate_batch: job %d did not finish", j); return LSDHIP_E_STATE; }
@@ -2734,7 +2652,7 @@ extern "C" int lsdhip_tracker_track_permaref(lsdhip_tracker* t, const float* pos
   LsdTrackJobScope tjob_(c, true);
   if (tjob_.rc) return tjob_.rc;
   HIPCHK(hipSetDevice(c->device));
-    int rc = upload_points(t, pos, colvar, n);
+  int rc = upload_points(t, pos, colvar, n);
   if (rc) return rc;
   lsdm::SE3fH referenceToFrame = lsdm::se3f_from_d(lsdm::se3d_from7(refToFrame));
   t->affineEstimation_a = 1; t->affineEstimation_b = 0;
@@ -2771,17 +2689,15 @@ extern "C" int lsdhip_tracker_track_permaref_batch(lsdhip_tracker* t, int n, con
   for (int j = 0; j < n; j++) { if (counts[j] <= 0 || !frames[j]) return LSDHIP_E_ARG; total += counts[j]; }
   int rc = upload_points(t, pos, colvar, total);
   if (rc) return rc;
-  rc = batch_reserve(t, n);
-  if (rc) return rc;
-  const BatchShape shape = batch_shape(t, n);
   int off = 0;
-  for (int j = 0; j < n; j++) {
-    rc = fill_permaref_job(t, t->h_bjobs[j], shape, t->d_pts + (size_t)off * 3, t->d_pts + (size_t)t->pts_capacity * 3 + (size_t)off * 2, counts[j],
-                           frames[j], lsdm::se3f_from_d(lsdm::se3d_from7(refToFrame + 7 * (size_t)j)));
-    if (rc) return rc;
+  const BatchOpened o = batch_open(t, "lsdhip_tracker_track_permaref_batch", n, nullptr, frames, false, [&](int j, TrackJob& job, BatchShape shape) {
+    const int at = off;
     off += counts[j];
-  }
-  rc = batch_run(t, n);
+    return fill_permaref_job(t, job, shape, t->d_pts + (size_t)at * 3, t->d_pts + (size_t)t->pts_capacity * 3 + (size_t)at * 2, counts[j], frames[j],
+                             lsdm::se3f_from_d(lsdm::se3d_from7(refToFrame + 7 * (size_t)j)));
+  });
+  if (o.rc) return o.rc;
+  rc = batch_run(t, n, false, true);
   if (rc) return rc;
   int rcAll = LSDHIP_OK;
   for (int j = 0; j < n; j++) {

@@ -13,7 +13,12 @@ builders, so a call that is refused half-way cannot leave it behind for the next
   * lsdhip_tracker_evaluate and lsdhip_tracker_evaluate_batch with one job describe the same job (one builder): the integer fields of the record
     agree exactly, the float sums within the bound test_track_batch_eval_gpu.py holds each form to against the float64 sums (its module
     docstring; the single job and the batch of one tile a level alike, so the small-batch depth covers both), the other fields at that
-    file's tolerances."""
+    file's tolerances.
+  * a tracker created under LSDHIP_SPIN=0 (the host drains the stream instead of polling the pinned summaries: the branches of the shared
+    wait that no other test reaches) gives the results, masks and launch counts of a default tracker, bit for bit, for single jobs and for a
+    batch; its summary record is checked all the same (lsdhip_tracker_summary_stats counts it).
+  * lsdhip_tracker_evaluate_batch between two identical lsdhip_tracker_track_batch calls leaves the second call's results and
+    lsdhip_tracker_launch_stats as they were: the test hook takes no part in the budget history."""
 import ctypes as C
 
 import numpy as np
@@ -162,3 +167,61 @@ def test_a_single_evaluation_equals_the_batch_of_one(oracle, hip, scene, lvl):
     assert g.meanRes == pytest.approx(s.meanRes, rel=max(1e-3, 2 * M * EPS), abs=1e-4)
     assert g.affine_a_lastIt == pytest.approx(s.affine_a_lastIt, rel=5e-4)
     assert g.affine_b_lastIt == pytest.approx(s.affine_b_lastIt, abs=0.08)
+
+
+def spin_pair(hip, world, monkeypatch):
+    """a default tracker and one that does not poll (the environment is read when the tracker is created)"""
+    tr_a = hip.SE3Tracker(world["ctx"])
+    monkeypatch.setenv("LSDHIP_SPIN", "0")
+    tr_b = hip.SE3Tracker(world["ctx"])
+    monkeypatch.delenv("LSDHIP_SPIN")
+    return tr_a, tr_b
+
+
+def track_batch(hip, world, tr, first_id):
+    """trackFrameBatch of the 8 jobs of job_arrays (fresh frames); returns the records' bits, the masks and launch_stats"""
+    frs, _, _, T = job_arrays(hip, world, first_id)
+    inits = T.astype(np.float64)                       # (the same small offsets, taken as frameToReference)
+    _, res = tr.trackFrameBatch([world["ref"]] * JOBS, frs, inits)
+    assert not any(r.diverged for r in res)
+    return [field_bits(r) for r in res], [f.refPixelWasGoodNoCreate() for f in frs], tr.launch_stats()
+
+
+def assert_same_batch(a, b, what):
+    for j in range(JOBS):
+        for name in a[0][j]:
+            assert a[0][j][name] == b[0][j][name], "job %d: %s differs %s" % (j, name, what)
+        assert np.array_equal(a[1][j], b[1][j]), "job %d: refPixelWasGood differs %s" % (j, what)
+    assert a[2] == b[2], (what, a[2], b[2])
+
+
+def test_polling_off_changes_nothing(hip, world, monkeypatch):
+    tr_a, tr_b = spin_pair(hip, world, monkeypatch)
+    for i in (1, 2, 3):
+        fa, fb = hip.Frame(world["ctx"], 3000 + i, world["frames"][i]), hip.Frame(world["ctx"], 3000 + i, world["frames"][i])
+        tr_a.trackFrame(world["ref"], fa, IDENT7.astype(np.float64))
+        tr_b.trackFrame(world["ref"], fb, IDENT7.astype(np.float64))
+        assert not tr_a.last.diverged
+        a, b = field_bits(tr_a.last), field_bits(tr_b.last)
+        for name in a:
+            assert a[name] == b[name], "frame %d: %s differs without polling" % (i, name)
+        assert np.array_equal(fa.refPixelWasGoodNoCreate(), fb.refPixelWasGoodNoCreate()), i
+        assert tr_a.launch_stats()[0] == tr_b.launch_stats()[0] > 0, (i, tr_a.launch_stats(), tr_b.launch_stats())
+    assert_same_batch(track_batch(hip, world, tr_a, 3100), track_batch(hip, world, tr_b, 3100), "without polling")
+
+
+def test_batch_evaluation_leaves_launch_stats_alone(hip, world):
+    tr = hip.SE3Tracker(world["ctx"])
+    first = track_batch(hip, world, tr, 3200)
+    assert first[2][0] > 0
+    frs, _, _, T = job_arrays(hip, world, 3300)
+    tr.evaluateBatch([world["ref"]] * JOBS, frs, T, 2)
+    assert tr.launch_stats() == first[2]
+    assert_same_batch(first, track_batch(hip, world, tr, 3200), "after evaluateBatch")
+
+
+def test_a_summary_is_checked_with_and_without_polling(hip, world, monkeypatch):
+    for tr in spin_pair(hip, world, monkeypatch):
+        assert tr.summary_stats()[0] == 0
+        track_once(hip, world, tr, 3400)
+        assert tr.summary_stats()[0] == 1, tr.summary_stats()
