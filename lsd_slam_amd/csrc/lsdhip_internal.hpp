@@ -74,6 +74,7 @@ struct TrackLevel {
   int maxIts;
   float minWarped;           // MIN_GOODPERALL_PIXEL_ABSMIN * (width>>lvl) * (height>>lvl)
   int writeMask;             // level == SE3TRACKING_MIN_LEVEL: write frame->refPixelWasGood
+  int evalBatch;             // single jobs, dense multi-pass level: a lane evaluates its points four at a time, their loads in flight together
 };
 
 // Everything one trackFrame call needs, resident in HBM (uploaded once per call).
@@ -366,6 +367,7 @@ struct lsdhip_tracker {
   int levelEvaluations[LSD_LEVELS] = {};   // evaluations of the last job per pyramid level
   int block = 256;                // workgroup size of k_track_step (LSDHIP_TRACK_BLOCK)
   int grid_cap = 304;             // most workgroups one evaluation uses (LSDHIP_TRACK_CAP); larger levels grid-stride
+  bool evalBatch = true;          // multi-pass dense levels take their points four at a time (LSDHIP_EVAL_BATCH=0: the plain grid-stride loop)
   LaunchHistory recent;           // evaluating launches of the last jobs: size the launch budget of the next one
   int specC = 6;                  // most trials per launch (LSDHIP_SPEC; 1 = no speculation)
   int soloMinJobs = -1;           // batches of at least this many jobs walk their coarse levels in one workgroup per job (k_track_solo); 0: never; -1: build default

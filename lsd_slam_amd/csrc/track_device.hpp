@@ -233,6 +233,23 @@ __device__ __forceinline__ void eval_point(const EvalCtx& a, float px, float py,
   eval_finish(a, q, t, pz, I_ref, var, o);
 }
 
+// A reference point of a dense keyframe level in two parts, so that a caller may have the loads of several points in flight before it
+// looks at any of them (the batched evaluation loop of k_track_step): the request reads the two planes that decide whether pixel i
+// (in [0, w h)) is a reference point at all, the finish part is the test on them and makePointCloud's arithmetic.
+struct RefPlanes { float var, id; };
+__device__ __forceinline__ void fetch_request(const EvalCtx& a, int i, RefPlanes& r) {
+  r.var = a.kf_idepthVar[i];
+  r.id = a.kf_idepth[i];
+}
+__device__ __forceinline__ bool ref_pixel_inside(const EvalCtx& a, int x, int y) { return !(x < 1 || x >= a.w - 1 || y < 1 || y >= a.h - 1); }
+__device__ __forceinline__ bool fetch_finish(const EvalCtx& a, int x, int y, const RefPlanes& r, float& px, float& py, float& pz) {
+  if (r.var <= 0 || r.id == 0) return false;
+  float inv = lsd_rcp_exact(r.id);
+  px = inv * (a.fxi * x + a.cxi);
+  py = inv * (a.fyi * y + a.cyi);
+  pz = inv * 1.0f;
+  return true;
+}
 // fetch the reference point `i` (dense index into the keyframe level, or index into the explicit list)
 __device__ __forceinline__ bool fetch_point(const EvalCtx& a, int i, float& px, float& py, float& pz, float& I_ref,
                                             float& var, int& maskIdx) {
@@ -245,14 +262,11 @@ __device__ __forceinline__ bool fetch_point(const EvalCtx& a, int i, float& px, 
   }
   if (i >= a.w * a.h) return false;
   int x = i % a.w, y = i / a.w;
-  if (x < 1 || x >= a.w - 1 || y < 1 || y >= a.h - 1) return false;
-  var = a.kf_idepthVar[i];
-  float id = a.kf_idepth[i];
-  if (var <= 0 || id == 0) return false;
-  float inv = lsd_rcp_exact(id);
-  px = inv * (a.fxi * x + a.cxi);
-  py = inv * (a.fyi * y + a.cyi);
-  pz = inv * 1.0f;
+  if (!ref_pixel_inside(a, x, y)) return false;
+  RefPlanes r;
+  fetch_request(a, i, r);
+  var = r.var;
+  if (!fetch_finish(a, x, y, r, px, py, pz)) return false;
   I_ref = a.kf_image[i];
   maskIdx = i;
   return true;

@@ -819,6 +819,60 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
       }
     }
     __syncthreads();   // the list aliases s_red
+  } else if (!BATCH && job.lv[level].evalBatch != 0) {
+    // Multi-pass dense level of a single job (the host sets the flag: plan_job / fill_level): the lane's points i0, i0 + s, ... (s = nb x
+    // BLOCK) are taken four at a time.  In the plain loop below every load sits behind a branch on the one before it (the validity planes,
+    // then the keyframe colour, then the four texels behind in_image), so a lane makes 2 - 3 dependent memory round trips per point, one
+    // point after the other: at 640x480 level 1 that is four points per lane and a third of the launch's body.  Here the
+    // round trips of a group travel together: (1) the three plane loads of all four points, unconditional — a point past the end of the
+    // level reads pixel 0 and is dropped; (2) for all four: validity, the reference point, the warp, the texel loads (texel 0 where the
+    // point is not in the image); (3) in pass order what the plain loop does with a point, so every lane adds the same contributions in
+    // the same order and the partial rows, keys and mask bytes are those of the plain loop bit for bit.  (x, y) of the later points
+    // follow from the first by the uniform stride: one integer division per lane instead of one per point.
+    const int stride = nb * BLOCK;
+    const int sy = stride / a.w, sx = stride - sy * a.w;   // uniform; sx < w: one carry at most
+    int i = tile * BLOCK + tid;
+    int x = i % a.w, y = i / a.w;
+    struct Pt { int i, x, y; bool valid; RefPlanes r; float img, pz; PointWarp q; PointTexels t; };
+    while (i < work) {
+      Pt P[4];
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        Pt& p = P[k];
+        p.i = i; p.x = x; p.y = y;
+        p.valid = i < work;
+        const int li = p.valid ? i : 0;
+        fetch_request(a, li, p.r);
+        p.img = a.kf_image[li];
+        i += stride; x += sx; y += sy;
+        if (x >= a.w) { x -= a.w; y++; }
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        Pt& p = P[k];
+        float px = 0.f, py = 0.f;
+        p.pz = 1.f;
+        p.valid = p.valid && ref_pixel_inside(a, p.x, p.y) && fetch_finish(a, p.x, p.y, p.r, px, py, p.pz);
+        eval_warp(a, px, py, p.pz, p.q);
+        eval_fetch(a, p.q, p.valid && p.q.in_image, p.t);
+      }
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const Pt& p = P[k];
+        if (p.valid) {
+          acc[RS_NREF] += 1.f;
+          if (!p.q.in_image) {
+            if (wasGood) wasGood[p.i] = 0;
+          } else {
+            PointOut o;
+            eval_finish(a, p.q, p.t, p.pz, p.img, p.r.var, o);
+            if (wasGood) wasGood[p.i] = o.good ? 1 : 0;
+            top3_insert(p.x * a.h + p.y, key0, key1, key2);
+            accumulate_point(o, acc);
+          }
+        }
+      }
+    }
   } else
   for (int i = tile * BLOCK + tid; i < work; i += nb * BLOCK) {
     float px, py, pz, I_ref, var;
@@ -1378,6 +1432,7 @@ extern "C" int lsdhip_tracker_create(lsdhip_ctx* c, lsdhip_tracker** out) {
   }
   if (const char* e = getenv("LSDHIP_TRACK_BLOCK")) t->block = atoi(e);
   if (const char* e = getenv("LSDHIP_TRACK_CAP")) t->grid_cap = atoi(e);
+  if (const char* e = getenv("LSDHIP_EVAL_BATCH")) t->evalBatch = atoi(e) != 0;
   if (t->block != 256) { lsd_set_error("LSDHIP_TRACK_BLOCK must be 256"); delete t; return LSDHIP_E_ARG; }
   t->grid_cap = lsd_grid_cap(t->grid_cap, t->block, RS_END);
   t->max_blocks = t->grid_cap;
@@ -1586,6 +1641,9 @@ struct BatchEnv {
 };
 static const BatchEnv& batch_env() { static const BatchEnv env; return env; }
 
+// Does a single job's evaluation take the points of this level four at a time (k_track_step, TrackLevel::evalBatch)?  Dense keyframe
+// levels on which a lane has more than one point; decided again wherever the level's tiling changes.
+static int eval_batch_level(const lsdhip_tracker* t, const TrackLevel& L) { return t->evalBatch && L.npts < 0 && !L.singlePass && L.tilePx == 0 ? 1 : 0; }
 // one level of a job: planes, intrinsics, LM settings and its tiling for the batch `shape`.  Fails only if the level-0 planes cannot be built.
 static int fill_level(lsdhip_tracker* t, TrackJob& job, BatchShape shape, int level, lsdhip_frame* kf, lsdhip_frame* frame, const float* pts_pos,
                       const float* pts_colvar, int npts) {
@@ -1610,6 +1668,7 @@ static int fill_level(lsdhip_tracker* t, TrackJob& job, BatchShape shape, int le
   // (strips only where the level has reference blocks: levels >= 1 of a keyframe)
   const LevelTiling T = lsd_level_tiling(work, t->block, t->grid_cap, shape, npts < 0 && L.kf_refBlk != nullptr, batch_env().stripWgs, t->max_blocks);
   L.nblocks = T.nblocks; L.singlePass = T.singlePass; L.tilePx = T.tilePx;
+  L.evalBatch = eval_batch_level(t, L);
   L.lambdaInitial = t->lambdaInitial[level]; L.stepSizeMin = t->stepSizeMin[level]; L.convergenceEps = t->convergenceEps[level];
   L.maxIts = t->maxItsPerLvl[level];
   L.minWarped = MIN_GOODPERALL_PIXEL_ABSMIN * (c->w >> level) * (c->h >> level);
@@ -2061,7 +2120,10 @@ static SinglePlan plan_job(const lsdhip_tracker* t, TrackJob& job) {
     p.specLevel[l] = t->specLevel[l]; p.specCaps[l] = t->specCaps[l];
   }
   const SinglePlan P = lsd_single_plan(lv, p, job.lastLevel, job.topLevel);
-  for (int l = 0; l < LSD_LEVELS; l++) { job.lv[l].nblocks = P.tiling[l].nblocks; job.lv[l].singlePass = P.tiling[l].singlePass; }
+  for (int l = 0; l < LSD_LEVELS; l++) {
+    job.lv[l].nblocks = P.tiling[l].nblocks; job.lv[l].singlePass = P.tiling[l].singlePass;
+    job.lv[l].evalBatch = eval_batch_level(t, job.lv[l]);
+  }
   return P;
 }
 // ... and the TrackSpec its launches take (launch_step adds the per-launch fields)
