@@ -115,7 +115,7 @@ struct TrackSpec {
 #endif
 };
 
-// Levenberg-Marquardt state of a tracking job, resident in HBM, advanced by k_lm_step.
+// Levenberg-Marquardt state of a tracking job, resident in HBM, advanced by the finishing phase of k_track_step (lm_wave, track_device.hpp).
 struct TrackState {
   lsdm::SE3fH T;             // last accepted referenceToFrame
   lsdm::SE3fH Tn;            // pose being evaluated
@@ -136,8 +136,8 @@ struct TrackState {
   int numLaunches;           // k_track_step launches that did an evaluation so far
 };
 
-// What the host reads back (pinned, device-mapped): written by k_lm_step when the job finishes (or every step in
-// evalOnly mode).
+// What the host reads back (pinned, device-mapped): written by lm_wave (write_summary, track_device.hpp) in workgroup 0 of the launch
+// that finishes the job (or of every step in evalOnly mode).
 struct TrackSummary {
   int done;                  // raised last: the job's tag (TrackSpec::seq >> 12) for jobs the host polls for, 1 for jobs it synchronises the stream for
   int diverged, level, numEvaluations, numWarpUpdates, pad_[3];

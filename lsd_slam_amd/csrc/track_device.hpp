@@ -1,5 +1,6 @@
-// Device code shared by the tracking kernels (k_track_step in tracker.hip): per-point
-// arithmetic of K0-K3 in the reference's operation order, the wave-parallel Levenberg-Marquardt step, small reductions.  gfx950 only.
+// Device code shared by the tracking kernels (k_track_step and k_track_solo in tracker.hip): per-point arithmetic of K0-K3 in the
+// reference's operation order, the wave-parallel Levenberg-Marquardt step, small reductions, and the records the launches of a job leave
+// for each other (TrialRecord, the tail rows, TrackScratch).  gfx950 only.
 //
 // Reference behaviour restated:
 //   TrackingReference::makePointCloud   C/Tracking/TrackingReference.cpp:128-138
@@ -21,11 +22,11 @@ template <int CTRL, int ROW_MASK, int BANK_MASK>
 __device__ __forceinline__ int dpp_i(int v) {   // masked-off / out-of-row lanes read INT_MIN-like identity (-1)
   return __builtin_amdgcn_update_dpp(-1, v, CTRL, ROW_MASK, BANK_MASK, false);
 }
-// wave64 max of non-negative keys (identity -1); result valid in lane 63
 template <int CTRL, int ROW_MASK, int BANK_MASK>
 __device__ __forceinline__ int dpp_i0(int v) {   // masked-off / out-of-row lanes read 0 (the identity of a sum)
   return __builtin_amdgcn_update_dpp(0, v, CTRL, ROW_MASK, BANK_MASK, true);
 }
+// wave64 max of non-negative keys (identity -1); result valid in lane 63
 __device__ __forceinline__ int wave_max_to_lane63(int v) {
   int t = dpp_max_i(v, dpp_i<0x111, 0xf, 0xf>(v));
   t = dpp_max_i(t, dpp_i<0x112, 0xf, 0xf>(v));
@@ -47,28 +48,77 @@ __device__ __forceinline__ float wave_sum_to_lane63(float v) {
   return t;
 }
 
-// Workgroup-wide top-3 of non-negative unique integer keys.  Every lane contributes up to three candidates sorted
-// descending (c0 >= c1 >= c2, -1 = none).  Result in s_out[0..2] (descending, -1 = none) after the final barrier.
-__device__ __forceinline__ void block_top3(int c0, int c1, int c2, int (*s_wave)[3], int* s_out) {
-  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+// Workgroup-wide top-3 of non-negative unique integer keys, in two halves with a barrier between them.  Every lane contributes up to
+// three candidates sorted descending (c0 >= c1 >= c2, -1 = none).
+// first half, every wave: its three largest keys to s_wave[wave]
+__device__ __forceinline__ void wave_top3(int c0, int c1, int c2, int (*s_wave)[3]) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
 #pragma unroll
   for (int r = 0; r < 3; r++) {
     int m = __builtin_amdgcn_readlane(wave_max_to_lane63(c0), 63);
     if (lane == 0) s_wave[wave][r] = m;
     if (c0 == m && m >= 0) { c0 = c1; c1 = c2; c2 = -1; }
   }
-  __syncthreads();
-  if (wave == 0) {
-    const int nw = blockDim.x >> 6;
-    int v = (lane < nw * 3) ? s_wave[lane / 3][lane % 3] : -1;
+}
+// second half, one wave (nw * 3 <= 64): the three largest of the waves' keys (descending, -1 = none), uniform
+__device__ __forceinline__ void merge_top3(const int (*s_wave)[3], const int nw, int (&top)[3]) {
+  const int lane = threadIdx.x & 63;
+  int v = (lane < nw * 3) ? s_wave[lane / 3][lane % 3] : -1;
 #pragma unroll
-    for (int r = 0; r < 3; r++) {
-      int m = __builtin_amdgcn_readlane(wave_max_to_lane63(v), 63);
-      if (lane == 0) s_out[r] = m;
-      if (v == m) v = -1;
-    }
+  for (int r = 0; r < 3; r++) {
+    top[r] = __builtin_amdgcn_readlane(wave_max_to_lane63(v), 63);
+    if (v == top[r]) v = -1;
+  }
+}
+// Result in s_out[0..2] (descending, -1 = none) after the final barrier.
+__device__ __forceinline__ void block_top3(int c0, int c1, int c2, int (*s_wave)[3], int* s_out) {
+  wave_top3(c0, c1, c2, s_wave);
+  __syncthreads();
+  if (threadIdx.x < 64) {
+    int top[3];
+    merge_top3(s_wave, blockDim.x >> 6, top);
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+      if (threadIdx.x == 0) s_out[r] = top[r];
   }
   __syncthreads();
+}
+// The three largest keys a lane has seen (descending, -1 = none), each with a payload, and their extraction over the wave.
+struct Top3Payload {
+  int k0 = -1, k1 = -1, k2 = -1, e0 = 0, e1 = 0, e2 = 0;
+  __device__ __forceinline__ void insert(const int k, const int ek) {
+    const bool g0 = k > k0, g1 = k > k1, g2 = k > k2;
+    k2 = g1 ? k1 : (g2 ? k : k2); e2 = g1 ? e1 : (g2 ? ek : e2);
+    k1 = g0 ? k0 : (g1 ? k : k1); e1 = g0 ? e0 : (g1 ? ek : e1);
+    k0 = g0 ? k : k0; e0 = g0 ? ek : e0;
+  }
+  // all lanes: the largest key of the wave (-1: none left) and its owner's payload (the lowest lane that holds it); the owner drops it
+  __device__ __forceinline__ int take(int& payload) {
+    const int m = __builtin_amdgcn_readlane(wave_max_to_lane63(k0), 63);
+    const unsigned long long own = __ballot(k0 == m && m >= 0);
+    const int owner = own ? (int)__ffsll((long long)own) - 1 : 0;
+    payload = __builtin_amdgcn_readlane(e0, owner);
+    if (k0 == m && m >= 0) { k0 = k1; e0 = e1; k1 = k2; e1 = e2; k2 = -1; }
+    return m;
+  }
+};
+// inclusive scan of one count per lane over lanes 0..31 in six DPP additions (lanes 32..63 scan on their own)
+__device__ __forceinline__ int wave_scan32(const int v) {
+  int incl = v + dpp_i0<0x111, 0xf, 0xf>(v);        // row_shr:1
+  incl += dpp_i0<0x112, 0xf, 0xf>(v);                // row_shr:2
+  incl += dpp_i0<0x113, 0xf, 0xf>(v);                // row_shr:3
+  incl += dpp_i0<0x114, 0xf, 0xe>(incl);             // row_shr:4 bank_mask:0xe
+  incl += dpp_i0<0x118, 0xf, 0xc>(incl);             // row_shr:8 bank_mask:0xc
+  incl += dpp_i0<0x142, 0xa, 0xf>(incl);             // row_bcast:15 row_mask:0xa
+  return incl;
+}
+// pixel index i of a level of width w as x | y << 16 (inv_w = 1.0f / w: the quotient is off by one at most)
+__device__ __forceinline__ unsigned pixel_xy16(const int i, const int w, const float inv_w) {
+  int y = (int)((float)i * inv_w);
+  int x = i - y * w;
+  if (x < 0) { y--; x += w; }
+  if (x >= w) { y++; x -= w; }
+  return (unsigned)x | ((unsigned)y << 16);
 }
 // index of (r, c), c >= r, in the row-major upper triangle of the 6x6 normal matrix, as a constant expression (a running
 // counter keeps the accumulator array from being promoted to registers)
@@ -242,12 +292,19 @@ __device__ __forceinline__ void fetch_request(const EvalCtx& a, int i, RefPlanes
   r.id = a.kf_idepth[i];
 }
 __device__ __forceinline__ bool ref_pixel_inside(const EvalCtx& a, int x, int y) { return !(x < 1 || x >= a.w - 1 || y < 1 || y >= a.h - 1); }
+// makePointCloud's arithmetic (TrackingReference.cpp:128-138) for the valid reference pixel (x, y) with inverse depth `idepth`; the
+// x and y of a point whose 1 / idepth (= its z) a caller keeps: ref_point_xy
+__device__ __forceinline__ void ref_point_xy(const EvalCtx& a, int x, int y, float inv, float& px, float& py) {
+  px = inv * (a.fxi * x + a.cxi); py = inv * (a.fyi * y + a.cyi);
+}
+__device__ __forceinline__ void ref_point_at(const EvalCtx& a, int x, int y, float idepth, float& px, float& py, float& pz) {
+  float inv = lsd_rcp_exact(idepth);
+  ref_point_xy(a, x, y, inv, px, py);
+  pz = inv * 1.0f;
+}
 __device__ __forceinline__ bool fetch_finish(const EvalCtx& a, int x, int y, const RefPlanes& r, float& px, float& py, float& pz) {
   if (r.var <= 0 || r.id == 0) return false;
-  float inv = lsd_rcp_exact(r.id);
-  px = inv * (a.fxi * x + a.cxi);
-  py = inv * (a.fyi * y + a.cyi);
-  pz = inv * 1.0f;
+  ref_point_at(a, x, y, r.id, px, py, pz);
   return true;
 }
 // fetch the reference point `i` (dense index into the keyframe level, or index into the explicit list)
@@ -287,7 +344,7 @@ __device__ __forceinline__ int rli(int v, int l) { return __builtin_amdgcn_readl
 // 6x6 solve for the LM step, Gauss-Jordan on the augmented 6x7 system with ONE ELEMENT PER LANE (lane = 8 i + j, i < 6 rows,
 // j < 7 columns) and the pivot row / pivot column read back through LDS: six steps of (write own element, read pivot, pivot-row
 // and pivot-column entries, divide, multiply-subtract) instead of the ~460 dependent lane-exchange instructions of the
-// row-per-lane LDL^T above (3800 -> ~1300 cycles of the single wave the whole launch waits for).  No pivoting: the matrix
+// row-per-lane LDL^T it replaced (3800 -> ~1300 cycles of the single wave the whole launch waits for).  No pivoting: the matrix
 // is J^T W J with its diagonal scaled by (1 + lambda), symmetric positive SEMI-definite, and elimination without pivoting is
 // backward stable on it.  It is singular when a degree of freedom gets no constraint at all (a frame with gx = 0 everywhere
 // has a zero tx column in J): its row and column of A are exactly zero, elimination keeps them zero, and a pivot that is
@@ -470,7 +527,7 @@ __device__ __forceinline__ void stage_lm_par(const TrackJob& job, int level, LmP
 // workgroup on identical inputs (so every workgroup reaches the same decision without talking to the others).
 //   col  : this lane's column total of the evaluation's raw sums, tail-drop corrected (lane c < RS_END <-> column c)
 //   S    : the job state in LDS (read and updated in place; every lane writes the same values)
-//   tot  : LDS copy of the corrected sums (what the summary reports)
+//   sh   : LDS: the corrected sums (tot, what the summary reports; the caller has stored them) and the scratch of the 6x6 solve
 // `out` is non-null in workgroup 0 only.
 #ifdef LSD_PHASE_TRACE
 #define LM_MARK(k) do { if (trp && lane == 0) trp[k] = clock64(); } while (0)
@@ -489,10 +546,21 @@ __device__ __forceinline__ float lm_lambda_fail(float LM_lambda, int incTry, flo
   for (int i = 0; i < incTry; i++) p *= (double)lambdaFailFac;   // std::pow(lambdaFailFac, incTry)
   return (float)((double)LM_lambda * p);
 }
+// algorithmic bytes of one evaluation that visits N reference points: 20 N + [mask] 5 N + 12 min(w h, 4 N)
+__device__ __forceinline__ float eval_bytes(const float N, const LmPar& L) {
+  const float wh = (float)L.w * (float)L.h;
+  const float texels = 4.0f * N < wh ? 4.0f * N : wh;
+  return 20.0f * N + (L.writeMask ? 5.0f * N : 0.0f) + 12.0f * texels;
+}
+// squared norm of an increment, in the one association the step-size test is made with everywhere
+__device__ __forceinline__ float inc_norm2(const float* inc) {
+  const float i0 = inc[0], i1 = inc[1], i2 = inc[2], i3 = inc[3], i4 = inc[4], i5 = inc[5];
+  return (i0 * i0 + (i1 * i1 + i2 * i2)) + (i3 * i3 + (i4 * i4 + i5 * i5));
+}
 template <bool SPEC = false>
-__device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const float col, float* tot, const int lane,
+__device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const float col, LmShared& sh, const int lane,
                                         TrackSummary* out, unsigned long long* trp, const int consumed = 0, const int mycand = 0, const int doneWord = 1) {
-  float* const s_gj = tot - 48;   // LmShared::gj precedes tot
+  float* const tot = sh.tot;
   S.lastCand = consumed;
   S.ncand = 1;
   const LmPar L = par;
@@ -518,12 +586,7 @@ __device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const f
   S.aff_b_lastIt = aff_b_lastIt;
   S.numEvaluations = S.numEvaluations + 1;
   if (lane == 0) S.levelEvals[S.level] = S.levelEvals[S.level] + 1;
-  {
-    // algorithmic bytes of this evaluation: 20 N + [mask] 5 N + 12 min(w h, 4 N)
-    const float N = refNum, wh = (float)L.w * (float)L.h;
-    const float texels = 4.0f * N < wh ? 4.0f * N : wh;
-    S.bytes = S.bytes + (20.0f * N + (L.writeMask ? 5.0f * N : 0.0f) + 12.0f * texels);
-  }
+  S.bytes = S.bytes + eval_bytes(refNum, L);
   S.pending = 0;
   LM_MARK(12);
   if (L.evalOnly) { S.done = 1; if (out && lane == 0) write_summary(S, tot, out, doneWord); return false; }
@@ -562,9 +625,7 @@ __device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const f
       iteration++;
       start_iteration = true;
     } else {
-      const float i0 = S.inc[0], i1 = S.inc[1], i2 = S.inc[2], i3 = S.inc[3], i4 = S.inc[4], i5 = S.inc[5];
-      const float incdot = (i0 * i0 + (i1 * i1 + i2 * i2)) + (i3 * i3 + (i4 * i4 + i5 * i5));
-      if (!(incdot > L.stepSizeMin)) {
+      if (!(inc_norm2(S.inc) > L.stepSizeMin)) {
         iteration = maxIts;
         iteration++;
         start_iteration = true;
@@ -603,18 +664,12 @@ __device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const f
     float inc[6];
     const float damp = 1 + LM_lambda;
     LM_MARK(14);
-    gj6_solve_wave(S.A, S.b, damp, s_gj, lane, inc);
+    gj6_solve_wave(S.A, S.b, damp, sh.gj, lane, inc);
     LM_MARK(15);
     S.incTry = incTry + 1;
 #pragma unroll
     for (int i = 0; i < 6; i++) S.inc[i] = inc[i];
-    const lsdm::SE3fH Tn = se3f_mul_wave(se3f_exp_wave(inc, lane), T, lane);
-    S.Tn = Tn;
-    float R[9];
-    lsdm::quatf_to_rot(Tn.q, R);
-#pragma unroll
-    for (int i = 0; i < 9; i++) S.R[i] = R[i];
-    S.t[0] = Tn.t[0]; S.t[1] = Tn.t[1]; S.t[2] = Tn.t[2];
+    set_eval_pose(S, se3f_mul_wave(se3f_exp_wave(inc, lane), T, lane));
     S.phase = 1;
     LM_MARK(16);
     return true;
@@ -628,12 +683,7 @@ __device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const f
   } else {
     S.level = S.level - 1;
     S.phase = 0;
-    S.Tn = T;
-    float R[9];
-    lsdm::quatf_to_rot(T.q, R);
-#pragma unroll
-    for (int i = 0; i < 9; i++) S.R[i] = R[i];
-    S.t[0] = T.t[0]; S.t[1] = T.t[1]; S.t[2] = T.t[2];
+    set_eval_pose(S, T);
   }
   return false;
 }
@@ -664,16 +714,111 @@ __device__ __forceinline__ void accumulate_point(const PointOut& o, float (&acc)
   acc[RS_ERR] = __builtin_fmaf(resw, o.res, acc[RS_ERR]);
 }
 
+// What happens to a reference point the evaluation visits, whichever loop found it: the count, the refPixelWasGood byte at maskIdx (`mask` null:
+// the level writes none, or the point has no pixel), and for a point in the image its reference-order key and its sums.
+__device__ __forceinline__ void visit_point(const EvalCtx& a, const PointWarp& q, const PointTexels& t, const float pz, const float I_ref, const float var,
+                                            gbyte* mask, const int maskIdx, const int key, float (&acc)[RS_END], int& key0, int& key1, int& key2) {
+  acc[RS_NREF] += 1.f;
+  if (!q.in_image) { if (mask) mask[maskIdx] = 0; return; }
+  PointOut o;
+  eval_finish(a, q, t, pz, I_ref, var, o);
+  if (mask) mask[maskIdx] = o.good ? 1 : 0;
+  top3_insert(key, key0, key1, key2);
+  accumulate_point(o, acc);
+}
+
+// ---- the tail rows --------------------------------------------------------------------------------------------------
+// The SSE loops of the reference leave out the last M % 4 in-image points (in reference order).  Every tile (or strip) leaves up to
+// TAIL_ROWS candidates for them, one row each: the point's K2 / K3 contributions — werr | the 21 upper-triangular J J^T w | the 6 J r w |
+// r^2 w, TAIL_WORDS floats — and, in the rows a strip writes, the point's key in word TAIL_KEY (-1: none).
+enum { TAIL_WORDS = 29, TAIL_KEY = 31, TAIL_STRIDE = 32, TAIL_ROWS = 3 };
+// from one point's evaluation
+__device__ __forceinline__ void tail_row(const PointOut& o, float* row) {
+  row[0] = o.werr;
+  int k = 1;
+#pragma unroll
+  for (int rr = 0; rr < 6; rr++) {
+    const float Jw = o.J[rr] * o.w;
+#pragma unroll
+    for (int cc = rr; cc < 6; cc++) row[k++] = Jw * o.J[cc];
+  }
+  const float resw = o.res * o.w;
+#pragma unroll
+  for (int rr = 0; rr < 6; rr++) row[k++] = resw * o.J[rr];
+  row[k++] = resw * o.res;
+}
+// from the running sums of a lane that has visited one point: they are exactly its contributions (0 + x == x)
+__device__ __forceinline__ void tail_row_from_sums(const float (&acc)[RS_END], float* row) {
+  row[0] = acc[RS_WERR];
+#pragma unroll
+  for (int k = 0; k < 21; k++) row[1 + k] = acc[RS_A0 + k];
+#pragma unroll
+  for (int k = 0; k < 6; k++) row[22 + k] = acc[RS_B0 + k];
+  row[28] = acc[RS_ERR];
+}
+// the word of a tail row that column `col` of the sums loses (-1: the column has no tail): RS_WERR -> 0, RS_A0.. -> 1..21, RS_B0.. -> 22..27, RS_ERR -> 28
+__device__ __forceinline__ int tail_word(const int col) {
+  return (col == RS_WERR) ? 0 : ((col >= RS_A0 && col < RS_B0) ? 1 + col - RS_A0 : ((col >= RS_B0 && col < RS_ERR) ? 22 + col - RS_B0 : (col == RS_ERR ? 28 : -1)));
+}
+// the tail drop: column total `s` of an evaluation with M in-image points, without the M % 4 last of them (as far as `nsub` candidate
+// rows `sub` exist), largest key first
+__device__ __forceinline__ float tail_drop(float s, const int M, const int nsub, const int word, const float (*sub)[TAIL_STRIDE]) {
+  int need = M & 3;
+  if (need > nsub) need = nsub;
+  const float sub0 = sub[0][word < 0 ? 0 : word], sub1 = sub[1][word < 0 ? 0 : word], sub2 = sub[2][word < 0 ? 0 : word];
+  if (word >= 0) {
+    if (need > 0) s -= sub0;
+    if (need > 1) s -= sub1;
+    if (need > 2) s -= sub2;
+  }
+  return s;
+}
+
+// a candidate for the tail that a lane evaluates once more, alone: its key (x h + y; -1: none) and what the keyframe says about the pixel
+struct TailCandidate {
+  int key = -1, x = 0, y = 0;
+  float var = 0.f, id = 1.f, img = 0.f;
+  __device__ __forceinline__ void request(const EvalCtx& a, const int k) {
+    key = k;
+    if (k < 0) return;
+    x = k / a.h; y = k - x * a.h;
+    const int ci = __mul24(y, a.w) + x;
+    var = a.kf_idepthVar[ci]; id = a.kf_idepth[ci]; img = a.kf_image[ci];
+  }
+};
+
+// ---- the workgroup reduction's middle step --------------------------------------------------------------------------------
+// Every lane has parked its sums in its column of s_red (row k = sum k, row stride STRIDE = lanes + 1: conflict-free both ways); thread
+// (slice, k) adds a contiguous run of RRUN lanes of row k in lane order.  The loads are unconditional: the last run may spill into the
+// next row (allocated).
+template <int STRIDE, int RRUN>
+__device__ __forceinline__ float slice_sum(const float* s_red, const int k, const int slice) {
+  const float* row = s_red + k * STRIDE;
+  const int j0 = slice * RRUN;
+  float v[RRUN];
+#pragma unroll
+  for (int j = 0; j < RRUN; j++) v[j] = row[j0 + j];
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < RRUN; j++) s += (j0 + j < STRIDE - 1) ? v[j] : 0.f;
+  return s;
+}
+
+// an evaluation at the pose of a state or of a trial record
+template <class Posed>
+__device__ __forceinline__ void ctx_set_pose(EvalCtx& a, const Posed& p) {
+#pragma unroll
+  for (int i = 0; i < 9; i++) a.R[i] = p.R[i];
+#pragma unroll
+  for (int i = 0; i < 3; i++) a.t[i] = p.t[i];
+}
 __device__ __forceinline__ void make_ctx_dev(const TrackJob& jobr, const TrackState& S, int level, EvalCtx& a) {
   const TrackJob* job = &jobr;
   const TrackLevel& L = job->lv[level];
   a.kf_idepth = (gfloat*)L.kf_idepth; a.kf_idepthVar = (gfloat*)L.kf_idepthVar; a.kf_image = (gfloat*)L.kf_image; a.fr_grad = (gfloat*)L.fr_grad;
   a.pts_pos = (gfloat*)L.pts_pos; a.pts_colvar = (gfloat*)L.pts_colvar; a.npts = L.npts; a.w = L.w; a.h = L.h;
   a.fx = L.fx; a.fy = L.fy; a.cx = L.cx; a.cy = L.cy; a.fxi = L.fxi; a.fyi = L.fyi; a.cxi = L.cxi; a.cyi = L.cyi;
-#pragma unroll
-  for (int i = 0; i < 9; i++) a.R[i] = S.R[i];
-#pragma unroll
-  for (int i = 0; i < 3; i++) a.t[i] = S.t[i];
+  ctx_set_pose(a, S);
   a.aff_a = S.aff_a; a.aff_b = S.aff_b;
   a.cameraPixelNoise2 = job->cameraPixelNoise2; a.var_weight = job->var_weight; a.huber_half = job->huber_half;
 }
@@ -690,15 +835,40 @@ __device__ __forceinline__ void copy_words(void* dst, const void* src, int tid, 
 __device__ __forceinline__ int xcd_tile(int b, int nb) { return (nb & 7) == 0 ? (b & 7) * (nb >> 3) + (b >> 3) : b; }
 
 
+// What a workgroup that evaluates trial c > 0 leaves for the launch that finishes it (32 floats per slot of the scratch arena).
+struct TrialRecord {
+  float inc[6];
+  float pose[7];       // lsdm::SE3fH: q (w, x, y, z), t
+  float R[9], t[3];    // the pose as the evaluation reads it
+  float pad_[7];
+};
+static_assert(sizeof(TrialRecord) == 128 && sizeof(lsdm::SE3fH) == sizeof(float[7]), "a trial record is 32 floats; its pose is a TrackState::Tn");
+enum { TRIAL_RECORD_WORDS = offsetof(TrialRecord, pad_) / 4 };
+// word i < TRIAL_RECORD_WORDS of the record of the trial whose proposal S holds
+__device__ __forceinline__ float trial_record_word(const TrackState& S, const int i) {
+  constexpr int P = offsetof(TrialRecord, pose) / 4, R = offsetof(TrialRecord, R) / 4, T = offsetof(TrialRecord, t) / 4;
+  return i < P ? S.inc[i] : (i < R ? ((const float*)&S.Tn)[i - P] : (i < T ? S.R[i - R] : S.t[i - T]));
+}
+// S takes the record's proposal (lanes 0..8 of a wave)
+__device__ __forceinline__ void trial_record_adopt(TrackState& S, const TrialRecord& rec, const int lane) {
+  if (lane < 6) S.inc[lane] = rec.inc[lane];
+  if (lane < 7) ((float*)&S.Tn)[lane] = rec.pose[lane];
+  if (lane < 9) S.R[lane] = rec.R[lane];
+  if (lane < 3) S.t[lane] = rec.t[lane];
+}
+// trials a launch evaluates side by side at `level` (1: no speculation)
+__device__ __forceinline__ int trials_at(const TrackSpec& spec, const int level) { return (spec.specC > 1 && spec.trials[level] > 1) ? spec.trials[level] : 1; }
+
 #define RS_COLS 44   // RS_END rounded up: floats per partial-sum row
-// Scratch of a tracker in HBM, double-buffered by launch parity (a launch reads [parity], writes [1 - parity]).
+// Scratch of a tracker in HBM, double-buffered by launch parity (a launch reads [parity], writes [1 - parity]); every array is
+// [2][cmax][...]: cmax trial slots per parity (reject-chain speculation).
 struct TrackScratch {
-  float* sums;     // [2][RS_COLS][max_rows]  column-major partial sums: one row per workgroup tile
-  int4* topkey;    // [2][max_rows]           each tile's three largest reference-order keys among in-image points (x>=y>=z)
-  float* topval;   // [2][max_rows][3][32]    K2/K3 contributions of those points (single-pass levels only)
+  float* sums;     // [2][cmax][max_rows][RS_COLS]  partial sums, row-major: one row of RS_COLS floats per workgroup tile
+  int4* topkey;    // [2][cmax][max_rows]           each tile's three largest reference-order keys among in-image points (x>=y>=z)
+  float* topval;   // [2][cmax][max_rows][TAIL_ROWS][TAIL_STRIDE]  the tail rows of those points (single-pass levels and strips only)
   int max_rows;    // multiple of 4
-  int cmax;        // trial slots per parity (reject-chain speculation): sums [2][cmax][RS_COLS][max_rows], topkey / topval likewise
-  float* recs;     // [2][cmax][32]  increment / pose of the trials > 0 of a launch (null when cmax == 1)
+  int cmax;        // trial slots per parity
+  TrialRecord* recs;   // [2][cmax]  increment / pose of the trials > 0 of a launch (null when cmax == 1)
 #ifdef LSD_PHASE_TRACE
   unsigned long long* trace;   // [0] = launch counter, then 20 words per launch (developer build only, tools/phase_trace.py)
 #endif

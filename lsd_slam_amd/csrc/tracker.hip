@@ -1,12 +1,9 @@
 // SE3Tracker on the device.  gfx950 only.
 //
-// One evaluation = one launch of k_track_step on the context's stream:
-//   (1) every workgroup finishes the *previous* evaluation: fixed-order sum of the partial rows, SSE tail-drop
-//       correction, and the Levenberg-Marquardt decision of SE3Tracker::trackFrame (accept / reject, lambda schedule,
-//       6x6 LDL^T solve, SE3 exp, level change) — redundantly and identically in every workgroup, so the launch needs no
-//       atomics, fences or inter-workgroup waits and the pose never leaves HBM between evaluations;
-//   (2) fused K0 (point generation from the keyframe planes) + K1 (warp / bilinear sample / mask) + K2 (weights) + K3
-//       (normal equations) at the pose (1) produced; 41 sums reduced wave (DPP) -> workgroup (LDS) -> partials[tile].
+// One evaluation = one launch of k_track_step on the context's stream (described in front of the kernel's pieces below): every workgroup
+// finishes the *previous* evaluation — the Levenberg-Marquardt decision of SE3Tracker::trackFrame with its 6x6 Gauss-Jordan solve
+// (gj6_solve_wave) and SE3 exp, redundantly and identically, so the pose never leaves HBM between evaluations — and evaluates at the pose
+// that gives: fused K0 (point generation from the keyframe planes) + K1 (warp / bilinear sample / mask) + K2 (weights) + K3 (normal equations).
 // The host enqueues a budget of k_track_step launches back to back and synchronises once; steps launched
 // after the job has finished return immediately.  A host-driven LM loop (one evaluation per round trip) is kept behind
 // lsdhip_tracker.hostLM for debugging and as the kernel-level parity hook (lsdhip_tracker_evaluate).
@@ -20,8 +17,8 @@
 //   SE3Tracker::trackFrameOnPermaref    :162-272, checkPermaRefOverlap :121-157
 //
 // Quirks kept on purpose: the SSE loops ignore the last size%4 in-image points (in the reference's
-// x-outer point order) for K2/K3 — emulated in k_lm_step; LGS6::updateSSE counts 6 constraints per group of 4;
-// `LM_lambda <= 0.2` compares a float with a double.
+// x-outer point order) for K2/K3 — emulated by the tail drop in front of the LM step (tail_drop, track_device.hpp); LGS6::updateSSE
+// counts 6 constraints per group of 4; `LM_lambda <= 0.2` compares a float with a double.
 //
 // Data layout: keyframe planes idepth/idepthVar/image (3 x 4 B per pixel, row-major, coalesced per wave), tracked-frame
 // texels float4 (gx, gy, I, 0) so that one bilinear tap is one 16-byte load.  Algorithmic bytes per evaluation at level l
@@ -30,12 +27,32 @@
 #include <chrono>
 #include "track_device.hpp"
 
-
+// developer build LSD_PHASE_TRACE: the functions that leave timestamps take the traced workgroup's flag and record (TRACE_PARAMS / _ARGS)
 #ifdef LSD_PHASE_TRACE
 #define PHASE_MARK(k) do { if (trOn_ && threadIdx.x == 0) tr_[k] = clock64(); } while (0)
 #define LSD_TRACE_WORDS 32
+#define TRACE_PARAMS , const bool trOn_, unsigned long long* const tr_
+#define TRACE_ARGS , trOn_, tr_
+#define TRACE_PUT(rec, who, k, v) do { if (trOn_ && threadIdx.x == (who)) (rec)[k] = (unsigned long long)(v); } while (0)
+#define TRACE_LM_REC (trOn_ ? tr_ : nullptr)
+// thread 0 of the traced workgroup takes the launch's record (32 words), clears it and stamps the start; everybody else gets the buffer's base
+__device__ __forceinline__ unsigned long long* trace_open(unsigned long long* trace, const bool mine, unsigned long long** s_trp) {
+  if (!mine) return trace;
+  const unsigned long long n = trace[0];
+  trace[0] = n + 1;
+  unsigned long long* tr_ = trace + 1 + (n % 4096) * LSD_TRACE_WORDS;
+  for (int k = 0; k < LSD_TRACE_WORDS; k++) tr_[k] = 0;
+  tr_[8] = wall_clock64();
+  tr_[24] = (unsigned long long)gridDim.x; tr_[25] = (unsigned long long)gridDim.y;
+  *s_trp = tr_;
+  return tr_;
+}
 #else
 #define PHASE_MARK(k) do { } while (0)
+#define TRACE_PARAMS
+#define TRACE_ARGS
+#define TRACE_PUT(rec, who, k, v) do { } while (0)
+#define TRACE_LM_REC nullptr
 #endif
 
 #ifdef LSD_DEVTOOLS
@@ -70,6 +87,7 @@
 // MODE (batches in throughput mode split a step into two launches, so that the LM replay is paid once per job instead of
 // once per workgroup): TS_FUSED = finish + evaluate as described above; TS_LM = finish the pending evaluation and publish the
 // state (grid.x = 1); TS_EVAL = evaluate the published state (reads st2[parity], writes scratch[parity]; no state change).
+// The step is track_step_impl at the end of this part; the phases it runs, in the order it runs them, come first.
 enum { TS_FUSED = 0, TS_LM = 1, TS_EVAL = 2 };
 // the state a job's first launch starts from (SE3Tracker.cpp:280-320: the initial estimate, affine parameters of the settings, the top level)
 __device__ __forceinline__ void track_state_begin(TrackState& S, const TrackJob& job, const int tid) {
@@ -88,79 +106,646 @@ __device__ __forceinline__ void track_state_begin(TrackState& S, const TrackJob&
   if (tid < 36) S.A[tid] = 0;
   if (tid < 6) { S.b[tid] = 0; S.inc[tid] = 0; }
 }
-// one point's K2 / K3 contributions as the 29-float row the tail drop subtracts: werr | the 21 upper-triangular J J^T w | the 6 J r w | r^2 w
-__device__ __forceinline__ void tail_row(const PointOut& o, float* row) {
-  row[0] = o.werr;
-  int k = 1;
-#pragma unroll
-  for (int rr = 0; rr < 6; rr++) {
-    const float Jw = o.J[rr] * o.w;
-#pragma unroll
-    for (int cc = rr; cc < 6; cc++) row[k++] = Jw * o.J[cc];
-  }
-  const float resw = o.res * o.w;
-#pragma unroll
-  for (int rr = 0; rr < 6; rr++) row[k++] = resw * o.J[rr];
-  row[k++] = resw * o.res;
+
+// Where this launch reads and writes in the scratch arena: the bases of its job and parities (trial 0; trial c sits c slots further).
+struct StepAddr {
+  const float *sums_in, *topval_in;
+  float *sums_out, *topval_out;
+  const int4* topkey_in; int4* topkey_out;
+  const TrialRecord* recs_in;   // (no arena when cmax == 1: never dereferenced then)
+  TrialRecord* recs_out;
+  int max_rows, cmax;
+};
+template <bool BATCH, int MODE>
+__device__ __forceinline__ StepAddr step_addr(const TrackScratch& sc, const int parity) {
+  // every array is [job][parity][trial slot][...]: the slots this launch reads from and writes to, then each array's words per slot
+  const size_t rows = (size_t)sc.max_rows, cm = (size_t)sc.cmax, job0 = BATCH ? (size_t)blockIdx.y * 2 * cm : 0;
+  const size_t in = job0 + (size_t)parity * cm, out = job0 + (size_t)(MODE == TS_EVAL ? parity : 1 - parity) * cm;
+  constexpr size_t TAIL = TAIL_ROWS * TAIL_STRIDE;
+  return {sc.sums + in * RS_COLS * rows, sc.topval + in * rows * TAIL, sc.sums + out * RS_COLS * rows, sc.topval + out * rows * TAIL,
+          sc.topkey + in * rows, sc.topkey + out * rows, sc.recs + in, sc.recs + out, sc.max_rows, sc.cmax};
 }
 
+// What this workgroup does in the launch: trial `cand` and tile (or strip) `bx` of the pending level; leader = workgroup 0, which publishes
+// the state and writes the summary; leaves: nothing to do, gone before the finishing phase.
+struct StepRole { int cand, bx; bool leader, leaves; };
+template <bool BATCH, int MODE>
+__device__ __forceinline__ void step_role(StepRole& r, const TrackJob& job, const TrackSpec& spec, const TrackState& S) {
+  const int lvlPending = S.level;
+  if (MODE == TS_FUSED) {
+    // The launch is sized for the level with the most (tiles x trials).  This one either evaluates trials at S.level —
+    // workgroup = (trial, tile) of that level — or, if the pending decision ends the level, the first evaluation of
+    // S.level - 1 (workgroup = tile).  Workgroups that have no work either way leave before the finishing phase (whose loads
+    // they would only add to everybody else's).
+    const int nbl = job.lv[lvlPending].nblocks;
+    const int tr = trials_at(spec, lvlPending);
+    r.cand = (int)blockIdx.x / nbl; r.bx = (int)blockIdx.x - r.cand * nbl;
+    const bool needTrial = S.pending ? r.cand < tr : r.cand == 0;
+    const bool needNext = S.pending && lvlPending > job.lastLevel && (int)blockIdx.x < job.lv[lvlPending - 1].nblocks;
+    r.leaves = !r.leader && !needTrial && !needNext;
+  }
+  if (BATCH && MODE == TS_LM) {
+    // one workgroup per (trial, job): workgroup `cand` proposes the cand-th retry down the reject chain; those without a trial leave
+    r.cand = (int)blockIdx.x; r.bx = 0;
+    r.leaves = !r.leader && !(S.pending && r.cand < trials_at(spec, lvlPending));
+  }
+  if (BATCH && MODE == TS_EVAL) {
+    // workgroup = (trial, strip) of the job's level
+    const int nbl = job.lv[lvlPending].nblocks;
+    r.cand = (int)blockIdx.x / nbl; r.bx = (int)blockIdx.x - r.cand * nbl;
+  }
+}
+
+// Throughput-mode strips (batches): the strip's list is the concatenation of its reference blocks (k_ref_blocks, frame.hip).  The loads —
+// one block count per lane (at most 32 blocks), one word of four offsets per lane and step — depend on the level alone, not on the pose:
+// a (trial, strip) workgroup that is going to evaluate at the pending level (the usual case; a level ends three times per job) requests
+// them at the head of the finishing phase, so they travel with the previous round's partial sums instead of behind the LM step.
+constexpr int STRIP_CHMAX = 8;                   // tilePx <= 8192 (fill_level): 32 blocks, 8 steps of 4 waves
+__device__ __forceinline__ void strip_request(const TrackLevel& L, const int tile_, const int wave, const int lane, int& cntv, unsigned (&ow)[STRIP_CHMAX]) {
+  const int px = L.w * L.h;
+  const int base_ = tile_ * L.tilePx;
+  const int b0_ = base_ >> 8;
+  const int mblk_ = (min(base_ + L.tilePx, px) - base_ + 255) >> 8;
+  const gbyte* offs = (const gbyte*)L.kf_refBlk;
+  const __attribute__((address_space(1))) int* cnts = (const __attribute__((address_space(1))) int*)(offs + ((size_t)((px + 255) >> 8) << 8));
+  cntv = lane < mblk_ ? cnts[b0_ + lane] : 0;
+#pragma unroll
+  for (int c = 0; c < STRIP_CHMAX; c++) {
+    const int blk = c * 4 + wave;
+    ow[c] = blk < mblk_ ? *(const __attribute__((address_space(1))) unsigned*)(offs + ((size_t)(b0_ + blk) << 8) + (lane << 2)) : 0u;
+  }
+}
+
+// ---- the finishing phase: the tail points of the pending trials ------------------------------------------------------------
+// The last (M % 4) in-image points in reference order = the largest keys (x * h + y, or list index) over all tiles' top-3 lists left
+// behind by the residual pass — per trial, one wave per trial (two when there are more than four), the last wave first: it has no
+// column sums to add.  What a wave finds goes to the trial's tail table: sub[trial] (TAIL_ROWS rows) and nsub[trial] (how many exist).
+typedef float (*TailTable)[TAIL_ROWS][TAIL_STRIDE];
+// the three largest of a wave's keys (KROWS int4 per lane: lane's rows lane, lane + 64, ...) and where they sit (row * 3 + slot)
+template <int KROWS>
+__device__ __forceinline__ void top3_of_keys(const int4 (&kv)[KROWS], const int lane, int (&keys)[3], int (&src)[3]) {
+  Top3Payload top;
+#pragma unroll
+  for (int q = 0; q < KROWS; q++) {
+    const int e = (lane + 64 * q) * 3;
+    const int ks[3] = {kv[q].x, kv[q].y, kv[q].z};
+#pragma unroll
+    for (int rr = 0; rr < 3; rr++) top.insert(ks[rr], e + rr);
+  }
+#pragma unroll
+  for (int r = 0; r < 3; r++) keys[r] = top.take(src[r]);
+}
+// a wave takes up to two trials (ca, cb; cb < 0: one): both key loads travel together, the second merge runs while the
+// first trial's contributions travel, and on multi-pass levels the (up to 6) tail points are re-evaluated side by side
+template <int KROWS>   // rows per lane: KROWS * 64 >= nb
+__device__ __forceinline__ void tail_two(const TrackJob& job, const TrackState& S, const int level, const int nb, const StepAddr& A, const TrialRecord* s_rec,
+                                         const TailTable s_subT, int* const s_nsubT, const int ca, const int cb, const int lane) {
+  const int max_rows = A.max_rows;
+  const int cbb = cb < 0 ? ca : cb;
+  const int4* tka = A.topkey_in + (size_t)ca * max_rows;
+  const int4* tkb = A.topkey_in + (size_t)cbb * max_rows;
+  int4 kva[KROWS], kvb[KROWS];
+#pragma unroll
+  for (int q = 0; q < KROWS; q++) {
+    const int row = lane + 64 * q;
+    const int4 ka = tka[row < max_rows ? row : 0];   // unconditional, issued together
+    const int4 kb = tkb[row < max_rows ? row : 0];
+    kva[q] = row < nb ? ka : make_int4(-1, -1, -1, -1);
+    kvb[q] = row < nb ? kb : make_int4(-1, -1, -1, -1);
+  }
+  // the owners of the keys left their K2/K3 contributions next to them: single-pass levels (one point per lane) and the strips of
+  // a throughput-mode batch (the three largest keys of a strip are re-evaluated at the end of its launch)
+  const bool single = job.lv[level].singlePass != 0 || job.lv[level].tilePx > 0;
+  const int j = lane & 31, rj = lane >> 5;
+  int keysA[3], srcA[3], keysB[3], srcB[3];
+  float a0 = 0.f, a2 = 0.f, b0 = 0.f, b2 = 0.f;
+  // word j of the rows the owners of a trial's keys left next to them: rows 0 and 1 in the two half-waves, row 2 in the lower one
+  auto request = [&](const int c, const int (&keys)[3], const int (&src)[3], float& v0, float& v2) {
+    const float* tv = A.topval_in + (size_t)c * max_rows * (TAIL_ROWS * TAIL_STRIDE);
+    if (keys[rj] >= 0) v0 = tv[(size_t)src[rj] * TAIL_STRIDE + j];
+    if (rj == 0 && keys[2] >= 0) v2 = tv[(size_t)src[2] * TAIL_STRIDE + j];
+  };
+  auto deliver = [&](const int c, const int (&keys)[3], const float v0, const float v2) {
+    if (keys[rj] >= 0) s_subT[c][rj][j] = v0;
+    if (rj == 0 && keys[2] >= 0) s_subT[c][2][j] = v2;
+  };
+  top3_of_keys(kva, lane, keysA, srcA);
+  if (single && j < TAIL_WORDS) request(ca, keysA, srcA, a0, a2);
+  if (cb >= 0) {
+    top3_of_keys(kvb, lane, keysB, srcB);
+    if (single && j < TAIL_WORDS) request(cb, keysB, srcB, b0, b2);
+  }
+  if (lane == 0) {
+    s_nsubT[ca] = (keysA[0] >= 0) + (keysA[1] >= 0) + (keysA[2] >= 0);
+    if (cb >= 0) s_nsubT[cb] = (keysB[0] >= 0) + (keysB[1] >= 0) + (keysB[2] >= 0);
+  }
+  if (single) {
+    if (j < TAIL_WORDS) {
+      deliver(ca, keysA, a0, a2);
+      if (cb >= 0) deliver(cb, keysB, b0, b2);
+    }
+  } else {
+    // multi-pass level: re-evaluate the tail points at their trial's pose: lanes 0..2 trial ca, 3..5 trial cb
+    const bool second = lane >= 3;
+    const int r = second ? lane - 3 : lane;
+    const int c = second ? cb : ca;
+    int key = -1;
+    if (lane < 6 && c >= 0) key = second ? (r == 0 ? keysB[0] : (r == 1 ? keysB[1] : keysB[2])) : (r == 0 ? keysA[0] : (r == 1 ? keysA[1] : keysA[2]));
+    if (key >= 0) {
+      EvalCtx a;
+      make_ctx_dev(job, S, level, a);
+      if (c > 0) ctx_set_pose(a, s_rec[c]);
+      const int idx = (a.npts >= 0) ? key : ((key / a.h) + (key % a.h) * a.w);
+      float px, py, pz, I_ref, var;
+      int maskIdx;
+      fetch_point(a, idx, px, py, pz, I_ref, var, maskIdx);
+      PointOut o;
+      eval_point(a, px, py, pz, I_ref, var, o);
+      tail_row(o, s_subT[c][r]);
+    }
+  }
+}
+// Strips of a throughput-mode batch, at most 24 per job: a strip's launch leaves one tail row per candidate — its (up to) three
+// largest keys' K2/K3 contributions [0..28] and the key itself [31] — so ALL rows of the job travel in the same round trip as the
+// partial sums (NQ 16-byte loads per lane), the three largest keys are picked from the rows in registers, and their rows go to the
+// tail table: no second, dependent round trip (the keys first, then the owners' contributions) in front of the LM step.
+static_assert(TAIL_STRIDE == 32 && TAIL_KEY == 31, "a tail row is eight 16-byte words; the key is the last word of the eighth");
+// from the nf4 16-byte words of a job's rows (word f in v[f / 64] of lane f % 64) the three rows with the largest keys -> sub, their number -> nsub
+template <int NQ>
+__device__ __forceinline__ void tail_rows_pick(const float4 (&v)[NQ], const int nf4, float (*const sub)[TAIL_STRIDE], int* const nsubOut, const int lane) {
+  Top3Payload top;
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const int f = q * 64 + lane;
+    top.insert(((lane & 7) == 7 && f < nf4) ? __float_as_int(v[q].w) : -1, f >> 3);   // the row's key sits in its last word
+  }
+  int nsub = 0;
+#pragma unroll
+  for (int r = 0; r < 3; r++) {
+    int row;
+    const int m = top.take(row);
+    if (m >= 0) {
+      nsub++;
+      // the row's 16-byte words sit in v[row / 8] of lanes 8 (row % 8) ..: a scalar branch per q (row is uniform).  (The empty asm
+      // keeps the compiler from folding the branches into an indexed read of v[] — scratch memory; a chain of 4 (NQ - 1) selects
+      // per candidate was the first form.)
+      const int qsel = row >> 3;
+#pragma unroll
+      for (int q = 0; q < NQ; q++) {
+        if (q == qsel) {
+          float4 w4 = v[q];
+          asm volatile("" : "+v"(w4.x), "+v"(w4.y), "+v"(w4.z), "+v"(w4.w));
+          if ((lane >> 3) == (row & 7)) *(float4*)&sub[r][(lane & 7) * 4] = w4;
+        }
+      }
+    }
+  }
+  if (lane == 0) *nsubOut = nsub;
+}
+template <int NQ>   // NQ * 64 >= nb * 24 (16-byte words of the rows)
+__device__ __forceinline__ void tail_rows(const int nb, const StepAddr& A, const TailTable s_subT, int* const s_nsubT, const int ca, const int cb, const int lane) {
+  const int cbb = cb < 0 ? ca : cb;
+  const float4* ta = (const float4*)(A.topval_in + (size_t)ca * A.max_rows * (TAIL_ROWS * TAIL_STRIDE));
+  const float4* tb = (const float4*)(A.topval_in + (size_t)cbb * A.max_rows * (TAIL_ROWS * TAIL_STRIDE));
+  const int nf4 = nb * (TAIL_ROWS * TAIL_STRIDE / 4);
+  float4 va[NQ], vb[NQ];
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const int f = q * 64 + lane;
+    va[q] = ta[f < nf4 ? f : 0];   // unconditional, issued together
+    vb[q] = tb[f < nf4 ? f : 0];
+  }
+  tail_rows_pick(va, nf4, s_subT[ca], &s_nsubT[ca], lane);
+  if (cb >= 0) tail_rows_pick(vb, nf4, s_subT[cb], &s_nsubT[cb], lane);
+}
+// this wave's share of the tail work
+template <bool BATCH, int WAVES>
+__device__ __forceinline__ void gather_tails(const TrackJob& job, const TrackState& S, const int level, const int nb, const int ncandPending, const StepAddr& A,
+                                             const TrialRecord* s_rec, const TailTable s_subT, int* const s_nsubT, const int wave, const int lane) {
+  // trial c -> wave WAVES-1 - (c mod WAVES): the last wave first (it has no column sums to add)
+  const int ca = WAVES - 1 - wave;
+  const int cb = ca + WAVES < ncandPending ? ca + WAVES : -1;
+  if (ca < ncandPending) {
+    if (BATCH && job.lv[level].tilePx > 0 && nb <= 24) {
+      if (nb <= 5) tail_rows<2>(nb, A, s_subT, s_nsubT, ca, cb, lane);
+      else if (nb <= 13) tail_rows<5>(nb, A, s_subT, s_nsubT, ca, cb, lane);
+      else tail_rows<9>(nb, A, s_subT, s_nsubT, ca, cb, lane);
+    } else if (nb <= 128) tail_two<2>(job, S, level, nb, A, s_rec, s_subT, s_nsubT, ca, cb, lane);
+    else tail_two<5>(job, S, level, nb, A, s_rec, s_subT, s_nsubT, ca, cb, lane);
+  }
+}
+
+// ---- the finishing phase: column sums ---------------------------------------------------------------------------------------
+// Fixed-order column sums over the tiles' partial rows (row-major [tile][RS_COLS]: a wave's load covers whole rows, i.e.
+// contiguous memory): thread t < NSLOT * 11 takes columns 4 c4 .. 4 c4 + 3 of rows slot, slot + NSLOT, ... , for every
+// trial (the other lanes of these waves run along and store nothing: the tail work behind it is wave-wide).
+constexpr int SUM_NSLOT = 16;                                // row slots of the column sums: slot s adds rows s, s + 16, ...
+constexpr int SUM_QMAX = 20;                                 // float4 loads per thread: rows per slice <= 80
+typedef float (*SumTable)[SUM_NSLOT][RS_COLS];               // per pending trial: column sums by row slot
+// Q rows per slot, NT trials from `base` on: the loads are unconditional and issued together (trials past the last one re-read it, rows past
+// the last one re-read the slot's first row)
+template <int Q, int NT>
+__device__ __forceinline__ void colsum(const float4* p, const size_t trialStrideF4, const int nb, const int ncandPending, const int base,
+                                       const int slot, const int c4, const bool sumLane, const SumTable s_sumT) {
+  constexpr int NSLOT = SUM_NSLOT;
+  const int K = (nb + NSLOT - 1) / NSLOT;                // rows per slot
+  float4 v[NT][Q];
+#pragma unroll
+  for (int c = 0; c < NT; c++) {
+    const int pc = base + c < ncandPending ? base + c : ncandPending - 1;
+    const float4* pp = p + (size_t)pc * trialStrideF4;
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+      const int r = slot + NSLOT * q;
+      v[c][q] = pp[(size_t)(r < nb ? r : slot) * (RS_COLS / 4)];
+    }
+  }
+#pragma unroll
+  for (int c = 0; c < NT; c++) {
+    float4 a4 = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+    for (int q = 0; q < Q; q++) {
+      const bool live = q < K && slot + NSLOT * q < nb;
+      a4.x += live ? v[c][q].x : 0.f;
+      a4.y += live ? v[c][q].y : 0.f;
+      a4.z += live ? v[c][q].z : 0.f;
+      a4.w += live ? v[c][q].w : 0.f;
+    }
+    if (sumLane && base + c < ncandPending) *(float4*)&s_sumT[base + c][slot][c4 * 4] = a4;
+  }
+}
+// coarse levels (few tiles) take the short forms
+template <int TRIALS_MAX>
+__device__ __forceinline__ void column_sums(const StepAddr& A, const int nb, const int ncandPending, const int t, const SumTable s_sumT) {
+  constexpr int NSLOT = SUM_NSLOT, QMAX = SUM_QMAX;
+  const int slot_ = t / (RS_COLS / 4); const bool sumLane = slot_ < NSLOT;
+  const int slot = sumLane ? slot_ : 0, c4 = sumLane ? t - slot_ * (RS_COLS / 4) : 0;
+  const int K = (nb + NSLOT - 1) / NSLOT;                // rows per slot
+  const float4* p = (const float4*)A.sums_in + c4;
+  const size_t trialStrideF4 = (size_t)RS_COLS * A.max_rows / 4;
+  if (ncandPending == 1) {
+    if (K <= 2) colsum<2, 1>(p, trialStrideF4, nb, ncandPending, 0, slot, c4, sumLane, s_sumT);
+    else if (K <= 5) colsum<5, 1>(p, trialStrideF4, nb, ncandPending, 0, slot, c4, sumLane, s_sumT);
+    else if (K <= 10) colsum<10, 1>(p, trialStrideF4, nb, ncandPending, 0, slot, c4, sumLane, s_sumT);
+    else colsum<QMAX, 1>(p, trialStrideF4, nb, ncandPending, 0, slot, c4, sumLane, s_sumT);
+  } else if (K <= 2) colsum<2, TRIALS_MAX>(p, trialStrideF4, nb, ncandPending, 0, slot, c4, sumLane, s_sumT);
+  else if (K <= 5) colsum<5, TRIALS_MAX>(p, trialStrideF4, nb, ncandPending, 0, slot, c4, sumLane, s_sumT);
+  else if (K <= 10) { for (int base = 0; base < ncandPending; base += 3) colsum<10, 3>(p, trialStrideF4, nb, ncandPending, base, slot, c4, sumLane, s_sumT); }
+  else { for (int base = 0; base < ncandPending; base++) colsum<QMAX, 1>(p, trialStrideF4, nb, ncandPending, base, slot, c4, sumLane, s_sumT); }
+}
+// the finishing phase's tables in `buf`, per pending trial: column sums by row slot | its (up to 3) tail rows | how many of them exist
+template <int TRIALS_MAX>
+struct FinishTables {
+  enum { WORDS = TRIALS_MAX * (SUM_NSLOT * RS_COLS + TAIL_ROWS * TAIL_STRIDE + 1) };
+  SumTable sum; TailTable sub; int* nsub;
+  __device__ __forceinline__ explicit FinishTables(float* buf)
+      : sum((SumTable)buf), sub((TailTable)(buf + TRIALS_MAX * SUM_NSLOT * RS_COLS)), nsub((int*)(buf + TRIALS_MAX * (SUM_NSLOT * RS_COLS + TAIL_ROWS * TAIL_STRIDE))) {}
+};
+// total of column `col` of trial c over the row slots, in slot order
+__device__ __forceinline__ float slot_total(const SumTable s_sumT, const int c, const int col) {
+  float s = s_sumT[c][0][col];
+#pragma unroll
+  for (int k = 1; k < SUM_NSLOT; k++) s += s_sumT[c][k][col];
+  return s;
+}
+
+// ---- the finishing phase: wave 0 ------------------------------------------------------------------------------------------------
+// Which pending trial does the LM loop stop at?  Trial c stops it when it diverges (M < minWarped), is accepted
+// (error < lastErr) or is rejected with a step below stepSizeMin — each test needs only that trial's own totals and
+// increment, so lane c answers for trial c and the first "yes" wins.  The trials before it were plain rejections: they
+// leave nothing behind but lambda, incTry and the counters, which are advanced in closed form; then ONE LM step runs,
+// on the totals of the trial that stopped the loop (or of the last pending one).
+__device__ __forceinline__ int pick_trial(TrackState& S, const LmPar& par, const int level, const int ncandPending, const SumTable s_sumT, const TailTable s_subT,
+                                          const int* s_nsubT, const TrialRecord* s_rec, const int tid) {
+  if (ncandPending <= 1) return 0;
+  const int c = tid < ncandPending ? tid : 0;
+  const int Mc = (int)slot_total(s_sumT, c, RS_M);
+  const float ws = tail_drop(slot_total(s_sumT, c, RS_WERR), Mc, s_nsubT[c], tail_word(RS_WERR), s_subT[c]);
+  const float werrc = lm_werr(ws, Mc);
+  const float incdot = inc_norm2(c == 0 ? S.inc : s_rec[c].inc);
+  const bool stop = Mc < par.minWarped || werrc < S.lastErr || !(incdot > par.stepSizeMin);
+  const unsigned long long sm = __ballot(stop && tid < ncandPending);
+  const int pc = sm ? (int)__ffsll((long long)sm) - 1 : ncandPending - 1;
+  if (pc > 0) {
+    float lam = S.LM_lambda;
+    const int it0 = S.incTry;
+    for (int j = 0; j < pc; j++) lam = lm_lambda_fail(lam, it0 + j, par.lambdaFailFac);
+    // algorithmic bytes of the skipped evaluations (as in lm_wave)
+    const float skipped = eval_bytes(slot_total(s_sumT, 0, RS_NREF), par);
+    const float bytes0 = S.bytes;
+    const int ne0 = S.numEvaluations, le0 = S.levelEvals[level];
+    float bytes1 = bytes0;
+    for (int j = 0; j < pc; j++) bytes1 = bytes1 + skipped;
+    S.LM_lambda = lam;
+    S.incTry = it0 + pc;
+    S.numEvaluations = ne0 + pc;
+    if (tid == 0) S.levelEvals[level] = le0 + pc;
+    S.bytes = bytes1;
+    trial_record_adopt(S, s_rec[pc], tid);
+  }
+  return pc;
+}
+// column totals and tail-drop correction of trial pc, one column per lane (0 in the lanes past the columns)
+__device__ __forceinline__ float finish_totals(const SumTable s_sumT, const TailTable s_subT, const int* s_nsubT, const int pc, const int tid) {
+  const int M = (int)slot_total(s_sumT, pc, RS_M);
+  const float s = tid < RS_END ? slot_total(s_sumT, pc, tid) : 0.f;
+  return tail_drop(s, M, s_nsubT[pc], tail_word(tid), s_subT[pc]);
+}
+// the frame's refPixelWasGood must be what the last trial the LM loop executed wrote: trials > 0 wrote side planes
+template <int BLOCK>
+__device__ __forceinline__ void copy_side_mask(const TrackJob& job, const TrackState& S, const TrackSpec& spec, const int level, const int bx, const int nb, const int tid) {
+  const uint8_t* side = spec.wasGoodSide + (size_t)(S.lastCand - 1) * spec.maskStride;
+  EvalCtx a;
+  make_ctx_dev(job, S, level, a);
+  const int work = a.npts >= 0 ? a.npts : a.w * a.h;
+  for (int i = bx * BLOCK + tid; i < work; i += nb * BLOCK) {
+    float px, py, pz, I_ref, var;
+    int maskIdx;
+    if (fetch_point(a, i, px, py, pz, I_ref, var, maskIdx) && maskIdx >= 0) job.wasGood[maskIdx] = side[maskIdx];
+  }
+}
+
+// ---- the residual evaluation, three forms: every lane adds its points' contributions to acc[] and keeps their three largest keys ------
+// Throughput mode (batches): the workgroup owns a strip of tilePx consecutive pixels of the keyframe level.  It first
+// compacts the strip's valid reference pixels (semi-dense: ~30 %) into an LDS list — fixed order: chunk, then pixel
+// slot, then lane, so the result is run-to-run deterministic — and then evaluates the list with all lanes busy.
+// The strip's list is the concatenation of its reference blocks (k_ref_blocks, frame.hip: per 256 consecutive pixels the offsets of the
+// valid ones, compacted in pixel order, and a count): wave v takes block 4 c + v of the strip in step c, lane l its slots l, l + 64, ...;
+// every wave derives the blocks' places in the list from the counts itself (at most 32 blocks: one lane each), so nothing is exchanged
+// and the only barrier is the one in front of the evaluation.  (Until round 6 the strip streamed the level's validity planes, 8 bytes per
+// pixel, and compacted them with four ballots per 1024 pixels in every evaluation: a quarter of a level-1 round at 64 jobs.)
+// cntv / ow: the strip's block counts and offset words (strip_request).  Two barriers: the list is complete | the list is read.
+template <int BLOCK>
+__device__ __forceinline__ void eval_strip(const EvalCtx& a, const int tilePx, const int tile, const int work, const int cntv, const unsigned (&ow)[STRIP_CHMAX],
+                                           unsigned* const s_list /* (x | y << 16) */, gbyte* const wasGood, float (&acc)[RS_END], int& key0, int& key1, int& key2,
+                                           const int tid TRACE_PARAMS) {
+  const int wave = tid >> 6, lane = tid & 63;
+  const int base = tile * tilePx;
+  const int stripEnd = min(base + tilePx, work);
+  const int b0 = base >> 8;                                  // strips are multiples of 256 pixels
+  const int mblk = (stripEnd - base + 255) >> 8;             // <= 32 (tilePx <= 8192, fill_level)
+  const float inv_w = 1.0f / (float)a.w;
+  // inclusive scan of the (at most 32) block counts over lanes 0..31, the blocks' entries through v_readlane (the
+  // wave index is uniform: readfirstlane tells the compiler so)
+  const int incl = wave_scan32(cntv);
+  const int total = __builtin_amdgcn_readlane(incl, 31);
+  const int waveU = __builtin_amdgcn_readfirstlane(wave);
+  PHASE_MARK(20);
+#pragma unroll
+  for (int c = 0; c < STRIP_CHMAX; c++) {
+    const int blk = c * 4 + waveU;
+    if (blk < mblk) {
+      const int cb = __builtin_amdgcn_readlane(cntv, blk);
+      const int pb = __builtin_amdgcn_readlane(incl, blk) - cb;
+#pragma unroll
+      for (int k = 0; k < 4; k++) {
+        const int sl = lane + 64 * k;                       // (the block's bytes are slot-interleaved: k_ref_blocks)
+        if (sl < cb) s_list[pb + sl] = pixel_xy16(((b0 + blk) << 8) + (int)((ow[c] >> (8 * k)) & 255u), a.w, inv_w);
+      }
+    }
+  }
+  __syncthreads();
+  PHASE_MARK(21);
+  TRACE_PUT(tr_, 0, 23, total);
+  if (total > 0) {
+    // three-stage software pipeline over the list entries tid, tid + BLOCK, ...: (A) list entry + keyframe planes,
+    // (B) reference point, warp, texel fetch, (C) residual / weights / normal equations.  Stage A of entry r + 2 and
+    // stage B of entry r + 1 are issued before stage C of entry r, so two dependent memory round trips overlap the
+    // arithmetic.  Lanes past the end of the list run the loads on entry 0 and discard them.
+    struct StA { unsigned xy; float var, id, img; bool live; };
+    struct StB { unsigned xy; float pz, I_ref, var; PointWarp q; PointTexels t; bool live; };
+    auto stageA = [&](int p, StA& A) {
+      A.live = p < total;
+      A.xy = s_list[A.live ? p : 0];
+      const int i = __mul24((int)(A.xy >> 16), a.w) + (int)(A.xy & 0xffffu);
+      A.var = a.kf_idepthVar[i];
+      A.id = a.kf_idepth[i];
+      A.img = a.kf_image[i];
+    };
+    auto stageB = [&](const StA& A, StB& B) {
+      B.live = A.live;
+      B.xy = A.xy;
+      float px, py;
+      ref_point_at(a, (int)(A.xy & 0xffffu), (int)(A.xy >> 16), A.id, px, py, B.pz);
+      B.I_ref = A.img; B.var = A.var;
+      eval_warp(a, px, py, B.pz, B.q);
+      eval_fetch(a, B.q, B.live && B.q.in_image, B.t);
+    };
+    const int rounds = (total + BLOCK - 1) / BLOCK;
+    StA A1, A2;
+    StB B0, B1;
+    stageA(tid, A1);
+    stageB(A1, B0);
+    stageA(tid + BLOCK, A1);
+    PHASE_MARK(22);
+    auto stageC = [&](const StB& B) {
+      if (B.live) {
+        const int x_ = (int)(B.xy & 0xffffu), y_ = (int)(B.xy >> 16);
+        visit_point(a, B.q, B.t, B.pz, B.I_ref, B.var, wasGood, __mul24(y_, a.w) + x_, __mul24(x_, a.h) + y_, acc, key0, key1, key2);
+      }
+    };
+    // two rounds per trip with the roles of (A1, A2) and (B0, B1) swapped in the second half: a rotating pipeline written with
+    // struct copies costs ~30 register moves per round
+    for (int r = 0; r < rounds; r += 2) {
+      stageB(A1, B1);
+      stageA(tid + (r + 2) * BLOCK, A2);
+      stageC(B0);
+      stageB(A2, B0);
+      stageA(tid + (r + 3) * BLOCK, A1);
+      stageC(B1);                       // entry r + 1: not live past the end of the list
+    }
+  }
+  __syncthreads();   // the list aliases s_red
+}
+// Multi-pass dense level of a single job (the host sets the flag: plan_job / fill_level): the lane's points i0, i0 + s, ... (s = nb x
+// BLOCK) are taken four at a time.  In the plain loop below every load sits behind a branch on the one before it (the validity planes,
+// then the keyframe colour, then the four texels behind in_image), so a lane makes 2 - 3 dependent memory round trips per point, one
+// point after the other: at 640x480 level 1 that is four points per lane and a third of the launch's body.  Here the
+// round trips of a group travel together: (1) the three plane loads of all four points, unconditional — a point past the end of the
+// level reads pixel 0 and is dropped; (2) for all four: validity, the reference point, the warp, the texel loads (texel 0 where the
+// point is not in the image); (3) in pass order what the plain loop does with a point, so every lane adds the same contributions in
+// the same order and the partial rows, keys and mask bytes are those of the plain loop bit for bit.  (x, y) of the later points
+// follow from the first by the uniform stride: one integer division per lane instead of one per point.
+__device__ __forceinline__ void eval_groups_of_four(const EvalCtx& a, int i, const int stride, const int work, gbyte* const wasGood, float (&acc)[RS_END],
+                                                    int& key0, int& key1, int& key2) {
+  const int sy = stride / a.w, sx = stride - sy * a.w;   // uniform; sx < w: one carry at most
+  int x = i % a.w, y = i / a.w;
+  struct Pt { int i, x, y; bool valid; RefPlanes r; float img, pz; PointWarp q; PointTexels t; };
+  while (i < work) {
+    Pt P[4];
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      Pt& p = P[k];
+      p.i = i; p.x = x; p.y = y;
+      p.valid = i < work;
+      const int li = p.valid ? i : 0;
+      fetch_request(a, li, p.r);
+      p.img = a.kf_image[li];
+      i += stride; x += sx; y += sy;
+      if (x >= a.w) { x -= a.w; y++; }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      Pt& p = P[k];
+      float px = 0.f, py = 0.f;
+      p.pz = 1.f;
+      p.valid = p.valid && ref_pixel_inside(a, p.x, p.y) && fetch_finish(a, p.x, p.y, p.r, px, py, p.pz);
+      eval_warp(a, px, py, p.pz, p.q);
+      eval_fetch(a, p.q, p.valid && p.q.in_image, p.t);
+    }
+#pragma unroll
+    for (int k = 0; k < 4; k++) {
+      const Pt& p = P[k];
+      if (p.valid) visit_point(a, p.q, p.t, p.pz, p.img, p.r.var, wasGood, p.i, p.x * a.h + p.y, acc, key0, key1, key2);
+    }
+  }
+}
+// the plain loop: one point after the other (explicit point lists, single-pass levels, small batches)
+__device__ __forceinline__ void eval_plain(const EvalCtx& a, const int i0, const int stride, const int work, gbyte* const wasGood, float (&acc)[RS_END],
+                                           int& key0, int& key1, int& key2) {
+  for (int i = i0; i < work; i += stride) {
+    float px, py, pz, I_ref, var;
+    int maskIdx;
+    if (fetch_point(a, i, px, py, pz, I_ref, var, maskIdx)) {
+      PointWarp q; PointTexels t;
+      eval_warp(a, px, py, pz, q);
+      if (q.in_image) eval_fetch(a, q, true, t);
+      visit_point(a, q, t, pz, I_ref, var, maskIdx >= 0 ? wasGood : nullptr, maskIdx, a.npts >= 0 ? i : (i % a.w) * a.h + (i / a.w), acc, key0, key1, key2);
+    }
+  }
+}
+
+// ---- reduction and publish ----------------------------------------------------------------------------------------------------
+// Workgroup reduction through LDS: every lane parks its 41 accumulators in column `tid` of s_red (row stride
+// BLOCK + 1: conflict-free both ways), then thread (slice, k) adds a contiguous run of lanes of row k in lane order
+// and 41 threads add the slices — ~130 instructions per wave instead of 41 x 7 DPP steps.  The tile's row of sums, its three largest
+// keys and (single-pass levels, strips) its tail rows go to the trial's slots sums_out / topkey_out / topval_out.
+// The workgroup reduction handles the columns in NPASS batches (2 halves the LDS; measured slower — also for the throughput-mode
+// evaluation, where it would let four workgroups share a CU: profiles/r05_notes.md)
+constexpr int RED_NPASS = 1;
+constexpr int RED_CPP = (RS_END + RED_NPASS - 1) / RED_NPASS;      // columns per batch
+template <int BLOCK, bool BATCH, int MODE>
+__device__ __forceinline__ void reduce_and_store(const EvalCtx& a, const TrackLevel& L, TrackState& S, const int tile, const float (&acc)[RS_END],
+                                                 const int key0, const int key1, const int key2, float* const s_red, float (*const s_sum)[64], int (*const s_wtop)[3],
+                                                 int* const s_top, float* const sums_out, int4* const topkey_out, float* const topval_out, const int tid) {
+  constexpr int NPASS = RED_NPASS, CPP = RED_CPP;
+  constexpr int RSLICE = BLOCK / CPP;                  // slices per row
+  constexpr int RRUN = (BLOCK + RSLICE - 1) / RSLICE;  // lanes per slice
+  // Strips of a throughput-mode batch: the (up to) three in-image points of the strip with the largest reference-order keys are
+  // candidates for the job's tail (the last M % 4 in-image points, which the SSE loops of the reference leave out): three lanes evaluate
+  // them once more, alone, and leave their K2/K3 contributions in the strip's candidate rows — the launch that finishes this evaluation
+  // then needs no evaluation of its own in front of the LM step (it used to: keys, reference point, texels = three dependent round
+  // trips).  The two round trips of this evaluation run under the barriers of the reduction.
+  const bool stripRows = BATCH && L.tilePx > 0;
+  const bool candLane = tid >= BLOCK - 64 && tid < BLOCK - 61;   // lanes 0..2 of the LAST wave: wave 0 adds the slices and stores the sums meanwhile
+  TailCandidate c;
+  float cPz = 0.f;
+  PointWarp cq; PointTexels ct;
+  if (stripRows) {
+    block_top3(key0, key1, key2, s_wtop, s_top);
+    if (candLane) c.request(a, s_top[tid - (BLOCK - 64)]);
+  }
+#pragma unroll
+  for (int hp = 0; hp < NPASS; hp++) {
+    if (hp > 0) __syncthreads();
+#pragma unroll
+    for (int k = 0; k < CPP; k++)
+      if (hp * CPP + k < RS_END) s_red[k * (BLOCK + 1) + tid] = acc[hp * CPP + k];
+    __syncthreads();
+    // (S.pending = 1 / S.numLaunches++ for the state this launch publishes are set here, behind the first barrier of the reduction, and not
+    // where the evaluation begins: in a job's first launch the finishing phase is skipped, so no barrier separates a wave that is still
+    // about to test `S.pending` from wave 0 arriving there — with the write there, a wave held up by LDS traffic of another stream's
+    // workgroups on the same CU could read 1, enter the finishing phase alone and pair its barriers with the others' reduction barriers:
+    // one tile's sums came out as LDS residue.  Seen only with a second stream active, profiles/r04_notes.md.)
+    if (MODE == TS_FUSED && hp == 0 && tid == 0) { S.pending = 1; S.numLaunches = S.numLaunches + 1; }   // every wave is past its reads of S.pending
+    if (stripRows && hp == 0 && candLane && c.key >= 0) {
+      float px, py;
+      ref_point_at(a, c.x, c.y, c.id, px, py, cPz);
+      eval_warp(a, px, py, cPz, cq);
+      eval_fetch(a, cq, cq.in_image, ct);
+    }
+    {
+      const int slice = tid / CPP, k = tid - slice * CPP;
+      if (slice < RSLICE) s_sum[slice][k] = slice_sum<BLOCK + 1, RRUN>(s_red, k, slice);
+    }
+    __syncthreads();
+    if (stripRows && hp == 0 && candLane) {
+      float* row = topval_out + (size_t)(tile * TAIL_ROWS + (tid - (BLOCK - 64))) * TAIL_STRIDE;
+      if (c.key >= 0) {
+        PointOut o;
+        eval_finish(a, cq, ct, cPz, c.img, c.var, o);
+        tail_row(o, row);
+      }
+      ((int*)row)[TAIL_KEY] = c.key;
+    }
+    if (tid < CPP && hp * CPP + tid < RS_END) {
+      float s = s_sum[0][tid];
+#pragma unroll
+      for (int sl = 1; sl < RSLICE; sl++) s += s_sum[sl][tid];
+      sums_out[(size_t)tile * RS_COLS + (hp * CPP + tid)] = s;
+    }
+  }
+  if (!stripRows) block_top3(key0, key1, key2, s_wtop, s_top);
+  if (tid == 0) topkey_out[tile] = make_int4(s_top[0], s_top[1], s_top[2], -1);
+  if (L.singlePass && key0 >= 0) {
+    // one point per lane: its accumulators are exactly its K2/K3 contributions (0 + x == x)
+    const int r = key0 == s_top[0] ? 0 : (key0 == s_top[1] ? 1 : (key0 == s_top[2] ? 2 : -1));
+    if (r >= 0) tail_row_from_sums(acc, topval_out + (size_t)(tile * TAIL_ROWS + r) * TAIL_STRIDE);
+  }
+}
+
+#ifdef LSD_ORDER_CHECK
+// developer build: do all workgroups of this launch finish the previous evaluation with the same totals?
+__device__ __forceinline__ void order_check_totals(const TrackSpec& spec, const float s, const int pc, const int tid) {
+  unsigned hv = tid < RS_END ? __float_as_uint(s) * (2654435761u * (unsigned)(tid + 1)) : 0u;
+  hv += (unsigned)pc * 97u;
+  for (int off = 32; off > 0; off >>= 1) hv += __shfl_xor(hv, off);
+  if (tid == 0) {
+    const unsigned long long slot = 8 + 2 * ((spec.dbgCum / 400ull) % 8192ull);
+    __hip_atomic_fetch_min(&spec.dbgCounters[slot], (unsigned long long)hv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_fetch_max(&spec.dbgCounters[slot + 1], (unsigned long long)hv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+#endif
+
+// The job description travels in the kernel arguments, which the host has just written: the first touch of each of its
+// cache lines misses down to HBM (~1 us), and the fields of lv[level] are addressed only once the level is known, i.e. in
+// the middle of the dependent chain.  Touch every line now, together with the loads of the prologue.
+__device__ __forceinline__ void warm_job_arguments() {
+  typedef const unsigned __attribute__((address_space(4))) cuint;
+  cuint* ka = (cuint*)__builtin_amdgcn_kernarg_segment_ptr();
+  unsigned warm = 0;
+#pragma unroll
+  for (int i = 0; i < (int)(sizeof(TrackJob) / 4); i += 32) warm ^= ka[i];
+  asm volatile("" ::"s"(warm));   // the loads complete here, in the shadow of the prologue's own argument loads
+}
+
+// ---- the step ------------------------------------------------------------------------------------------------------------------
+// Every early return and every barrier of the finishing phase is in this body; the strip evaluation (eval_strip) has two barriers of its
+// own and the reduction (reduce_and_store, block_top3 inside it) has its own: all waves of a workgroup that get past the last return
+// reach each of them.
 template <int BLOCK, bool BATCH, int MODE>
 __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const TrackJob* __restrict__ jobs, TrackState* __restrict__ st2,
                                                 TrackScratch sc, TrackSummary* __restrict__ out, int parity, int first, const TrackSpec& spec) {
   const TrackJob& job = BATCH ? jobs[blockIdx.y] : jobv;
-  // The job description travels in the kernel arguments, which the host has just written: the first touch of each of its
-  // cache lines misses down to HBM (~1 us), and the fields of lv[level] are addressed only once the level is known, i.e. in
-  // the middle of the dependent chain.  Touch every line now, together with the loads of the prologue.
-  unsigned warm = 0;
-  if (!BATCH) {
-    typedef const unsigned __attribute__((address_space(4))) cuint;
-    cuint* ka = (cuint*)__builtin_amdgcn_kernarg_segment_ptr();
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(TrackJob) / 4); i += 32) warm ^= ka[i];
-    asm volatile("" ::"s"(warm));   // the loads complete here, in the shadow of the prologue's own argument loads
-  }
-  if (BATCH) {
-    const size_t j = blockIdx.y, rows = (size_t)sc.max_rows, cm = (size_t)sc.cmax;
-    st2 += 2 * j;
-    out += j;
-    sc.sums += j * 2 * cm * RS_COLS * rows;
-    sc.topkey += j * 2 * cm * rows;
-    sc.topval += j * 2 * cm * rows * 96;
-    if (sc.recs) sc.recs += j * 2 * cm * 32;
-  }
-  constexpr int WAVES = BLOCK / 64;
-  constexpr int SUMW = WAVES - 1;                    // waves that sum partials (the last one does the tail work)
-  constexpr int NSLICE = (SUMW * 64) / RS_END;       // row slices per column
-  constexpr int QMAX = 20;                           // float4 loads per thread: rows per slice <= 80
+  if (!BATCH) warm_job_arguments();
+  if (BATCH) { st2 += 2 * (size_t)blockIdx.y; out += blockIdx.y; }
+  const StepAddr A = step_addr<BATCH, MODE>(sc, parity);
+  constexpr int WAVES = BLOCK / 64, SUMW = WAVES - 1;                       // SUMW waves sum partials (the last one does the tail work)
+  constexpr int NSLICE = (SUMW * 64) / RS_END, CPP = RED_CPP, RSLICE_ = BLOCK / CPP;   // row slices per column: of the column sums, of the reduction
   __shared__ TrackState S;
   __shared__ LmShared sh;
   __shared__ LmPar s_par;
-  // the workgroup reduction handles the columns in NPASS batches (2 halves the LDS; measured slower — also for the throughput-mode
-  // evaluation, where it would let four workgroups share a CU: profiles/r05_notes.md)
-  constexpr int NPASS = 1;
-  constexpr int CPP = (RS_END + NPASS - 1) / NPASS;      // columns per batch
-  constexpr int RSLICE_ = BLOCK / CPP;
   __shared__ float s_sum[(NSLICE > RSLICE_ ? NSLICE : RSLICE_)][64];
   __shared__ __attribute__((aligned(16))) float s_red[CPP * (BLOCK + 1) + 8];
   __shared__ int s_wtop[WAVES][3];
   __shared__ int s_top[3];
-  const int tid = threadIdx.x;
-  const int wave = tid >> 6, lane = tid & 63;
-  const int max_rows = sc.max_rows;
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   // reject-chain speculation (single jobs): workgroup = (trial `cand`, tile `bx`) of the level of the pending evaluation —
-  // fixed below, once the state says which level that is
-  int cand = 0, bx = (int)blockIdx.x;
-  const bool leader = blockIdx.x == 0;
-  const int cmax = sc.cmax;
+  // fixed below (step_role), once the state says which level that is
+  StepRole role = {0, (int)blockIdx.x, blockIdx.x == 0, false};
+  const bool leader = role.leader;
   TrackState* next = st2 + (1 - parity);
-  const int outp = MODE == TS_EVAL ? parity : 1 - parity;
-  const float* sums_in0 = sc.sums + (size_t)parity * cmax * RS_COLS * max_rows;
-  float* sums_out = sc.sums + (size_t)outp * cmax * RS_COLS * max_rows;              // + the trial's slot, below
-  const int4* topkey_in0 = sc.topkey + (size_t)parity * cmax * max_rows;
-  int4* topkey_out = sc.topkey + (size_t)outp * cmax * max_rows;
-  const float* topval_in0 = sc.topval + (size_t)parity * cmax * max_rows * 96;
-  float* topval_out = sc.topval + (size_t)outp * cmax * max_rows * 96;
-  constexpr int NSLOT = 16;                                  // row slots of the column sums: slot s adds rows s, s + 16, ...
   // trials a launch can finish: single jobs up to LSD_SPEC_MAX; batches in throughput mode up to LSD_BATCH_SPEC_MAX (the LM launch has one
   // workgroup per (trial, job): each proposes its own retry, as the trial groups of a single job's launch do); small batches one
   constexpr int TRIALS_MAX = BATCH ? (MODE == TS_EVAL ? 1 : LSD_BATCH_SPEC_MAX) : LSD_SPEC_MAX;
@@ -168,25 +753,14 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
   // The finishing phase's per-trial tables live in the reduction buffer s_red: neither the strip list nor the reduction is live before the
   // barrier that ends the LM step, and nothing of these tables is read after it — so a launch that can finish four (batches) or six
   // (single jobs) trials needs no more LDS than one that finishes one (three workgroups per CU stay three).
-  static_assert(TRIALS_MAX * (NSLOT * RS_COLS + 96 + 1) <= CPP * (BLOCK + 1) + 8, "the finishing phase's tables must fit the reduction buffer");
-  float (*const s_sumT)[NSLOT][RS_COLS] = (float (*)[NSLOT][RS_COLS])s_red;                        // per pending trial: column sums by row slot
-  float (*const s_subT)[3][32] = (float (*)[3][32])(s_red + TRIALS_MAX * NSLOT * RS_COLS);          // ... K2/K3 contributions of its (up to 3) tail points
-  int* const s_nsubT = (int*)(s_red + TRIALS_MAX * (NSLOT * RS_COLS + 96));
-  __shared__ float s_rec[TRIALS_MAX][32];                   // ... increment [0..5], pose [6..12], R [13..21], t [22..24] (trials > 0)
+  static_assert(FinishTables<TRIALS_MAX>::WORDS <= CPP * (BLOCK + 1) + 8, "the finishing phase's tables must fit the reduction buffer");
+  const FinishTables<TRIALS_MAX> ft(s_red);
+  __shared__ TrialRecord s_rec[TRIALS_MAX];                 // per pending trial > 0: its increment and pose
 #ifdef LSD_PHASE_TRACE
   __shared__ unsigned long long* s_trp;
-  unsigned long long* tr_ = sc.trace;
   // the traced workgroup: workgroup 0 (batches: workgroup LSDHIP_TRACE_WG of job 0; tools/phase_trace_batch.py)
   const bool trOn_ = sc.trace != nullptr && (int)blockIdx.x == (BATCH ? spec.traceWg : 0) && (!BATCH || blockIdx.y == 0);
-  if (trOn_ && tid == 0) {
-    unsigned long long n = sc.trace[0];
-    sc.trace[0] = n + 1;
-    tr_ = sc.trace + 1 + (n % 4096) * LSD_TRACE_WORDS;
-    for (int k = 0; k < LSD_TRACE_WORDS; k++) tr_[k] = 0;
-    tr_[8] = wall_clock64();
-    tr_[24] = (unsigned long long)gridDim.x; tr_[25] = (unsigned long long)gridDim.y;
-    s_trp = tr_;
-  }
+  unsigned long long* const tr_ = trace_open(sc.trace, trOn_ && tid == 0, &s_trp);
 #endif
   PHASE_MARK(0);
   if (!BATCH && MODE == TS_FUSED && !first && !leader && st2[parity].done) return;   // launches queued behind the finishing one
@@ -195,13 +769,12 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
     track_state_begin(S, job, tid);
   } else {
     copy_words<sizeof(TrackState) / 4>(&S, st2 + parity, tid, BLOCK);
-    if (SPEC_LM && cmax > 1 && tid < 32 * TRIALS_MAX) (&s_rec[0][0])[tid] = sc.recs[(size_t)parity * cmax * 32 + (tid < 32 * cmax ? tid : 0)];
+    if (SPEC_LM && A.cmax > 1 && tid < (int)(sizeof(s_rec) / 4)) ((float*)s_rec)[tid] = ((const float*)A.recs_in)[tid < (int)(sizeof(TrialRecord) / 4) * A.cmax ? tid : 0];
   }
   __syncthreads();
   PHASE_MARK(1);
 #ifdef LSD_DEVTOOLS
   const int lvlIn_ = S.level, numLaunchesIn_ = S.numLaunches, pendingIn_ = S.pending, ncandIn_ = S.ncand;
-  int pcLog_ = -1;
 #endif
   // A finished job's launches leave here.  The host may have read the summary and gone on already (polled jobs and batches do not drain
   // the stream), so two things must stay true: (a) every workgroup of a launch queued behind the finishing one returns at this point,
@@ -217,61 +790,17 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
   // what the finishing launch raises `done` to: the job's tag where the host polls pinned memory for it (single jobs), 1 where it synchronises
   // (batches whose host polls: spec.seq is the batch's tag itself)
   const int doneWord = (MODE == TS_FUSED && spec.seq != 0) ? (BATCH ? spec.seq : (spec.seq >> 12)) : 1;
-  if (MODE == TS_FUSED) {
-    // The launch is sized for the level with the most (tiles x trials).  This one either evaluates trials at S.level —
-    // workgroup = (trial, tile) of that level — or, if the pending decision ends the level, the first evaluation of
-    // S.level - 1 (workgroup = tile).  Workgroups that have no work either way leave before the finishing phase (whose loads
-    // they would only add to everybody else's).
-    const int nbl = job.lv[lvlPending].nblocks;
-    const int tr = (spec.specC > 1 && spec.trials[lvlPending] > 1) ? spec.trials[lvlPending] : 1;
-    cand = (int)blockIdx.x / nbl;
-    bx = (int)blockIdx.x - cand * nbl;
-    const bool needTrial = S.pending ? cand < tr : cand == 0;
-    const bool needNext = S.pending && lvlPending > job.lastLevel && (int)blockIdx.x < job.lv[lvlPending - 1].nblocks;
-    if (!leader && !needTrial && !needNext) return;
-  }
+  step_role<BATCH, MODE>(role, job, spec, S);
+  if (role.leaves) return;
+  int cand = role.cand, bx = role.bx;
 
-  if (BATCH && MODE == TS_LM) {
-    // one workgroup per (trial, job): workgroup `cand` proposes the cand-th retry down the reject chain; those without a trial leave
-    cand = (int)blockIdx.x;
-    bx = 0;
-    const int tr = (spec.specC > 1 && spec.trials[lvlPending] > 1) ? spec.trials[lvlPending] : 1;
-    if (!leader && !(S.pending && cand < tr)) return;
-  }
-  if (BATCH && MODE == TS_EVAL) {
-    // workgroup = (trial, strip) of the job's level
-    const int nbl = job.lv[lvlPending].nblocks;
-    cand = (int)blockIdx.x / nbl;
-    bx = (int)blockIdx.x - cand * nbl;
-  }
-
-  // Throughput-mode strips (batches): the strip's list is the concatenation of its reference blocks (k_ref_blocks, frame.hip).  The loads —
-  // one block count per lane (at most 32 blocks), one word of four offsets per lane and step — depend on the level alone, not on the pose:
-  // a (trial, strip) workgroup that is going to evaluate at the pending level (the usual case; a level ends three times per job) requests
-  // them at the head of the finishing phase, so they travel with the previous round's partial sums instead of behind the LM step.
-  constexpr int CHMAX = 8;                       // tilePx <= 8192 (fill_level): 32 blocks, 8 steps of 4 waves
+  // the strip's list, requested ahead of time where this workgroup is going to evaluate at the pending level (strip_request)
   int cntv = 0;
-  unsigned ow[CHMAX];
-  auto strip_request = [&](const int lvl, const int tile_) {
-    const TrackLevel& L = job.lv[lvl];
-    const int px = L.w * L.h;
-    const int base_ = tile_ * L.tilePx;
-    const int b0_ = base_ >> 8;
-    const int mblk_ = (min(base_ + L.tilePx, px) - base_ + 255) >> 8;
-    const gbyte* offs = (const gbyte*)L.kf_refBlk;
-    const __attribute__((address_space(1))) int* cnts = (const __attribute__((address_space(1))) int*)(offs + ((size_t)((px + 255) >> 8) << 8));
-    cntv = lane < mblk_ ? cnts[b0_ + lane] : 0;
-#pragma unroll
-    for (int c = 0; c < CHMAX; c++) {
-      const int blk = c * 4 + wave;
-      ow[c] = blk < mblk_ ? *(const __attribute__((address_space(1))) unsigned*)(offs + ((size_t)(b0_ + blk) << 8) + (lane << 2)) : 0u;
-    }
-  };
+  unsigned ow[STRIP_CHMAX];
   bool havePre = false;
   if (BATCH && MODE == TS_FUSED && S.pending && job.lv[lvlPending].tilePx > 0) {
-    const int tr = (spec.specC > 1 && spec.trials[lvlPending] > 1) ? spec.trials[lvlPending] : 1;
-    havePre = cand < tr;
-    if (havePre) strip_request(lvlPending, xcd_tile(bx, job.lv[lvlPending].nblocks));
+    havePre = cand < trials_at(spec, lvlPending);
+    if (havePre) strip_request(job.lv[lvlPending], xcd_tile(bx, job.lv[lvlPending].nblocks), wave, lane, cntv, ow);
   }
 
   if (MODE != TS_EVAL && S.pending) {
@@ -282,392 +811,42 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
     const int ncandPending = S.ncand < 1 ? 1 : (S.ncand > TRIALS_MAX ? TRIALS_MAX : S.ncand);
     const int level = S.level;
     const int nb = job.lv[level].nblocks;
-    const size_t trialStrideF4 = (size_t)RS_COLS * max_rows / 4;
-      // the last (M % 4) in-image points in reference order = the largest keys (x * h + y, or list index) over all
-      // tiles' top-3 lists left behind by the residual pass — per trial, one wave per trial (two when there are more than
-      // four), the last wave first: it has no column sums to add
-      // a wave takes up to two trials (ca, cb; cb < 0: one): both key loads travel together, the second merge runs while the
-      // first trial's contributions travel, and on multi-pass levels the (up to 6) tail points are re-evaluated side by side
-      auto tail_two = [&](const int ca, const int cb, auto krn) {
-        constexpr int KROWS = decltype(krn)::value;   // rows per lane: KROWS * 64 >= nb
-        const int cbb = cb < 0 ? ca : cb;
-        const int4* tka = topkey_in0 + (size_t)ca * max_rows;
-        const int4* tkb = topkey_in0 + (size_t)cbb * max_rows;
-        int4 kva[KROWS], kvb[KROWS];
-#pragma unroll
-        for (int q = 0; q < KROWS; q++) {
-          const int row = lane + 64 * q;
-          const int4 ka = tka[row < max_rows ? row : 0];   // unconditional, issued together
-          const int4 kb = tkb[row < max_rows ? row : 0];
-          kva[q] = row < nb ? ka : make_int4(-1, -1, -1, -1);
-          kvb[q] = row < nb ? kb : make_int4(-1, -1, -1, -1);
-        }
-        auto merge = [&](const int4 (&kv)[KROWS], int (&keys)[3], int (&src)[3]) {
-          int k0 = -1, k1 = -1, k2 = -1, e0 = 0, e1 = 0, e2 = 0;
-#pragma unroll
-          for (int q = 0; q < KROWS; q++) {
-            const int e = (lane + 64 * q) * 3;
-            const int ks[3] = {kv[q].x, kv[q].y, kv[q].z};
-#pragma unroll
-            for (int rr = 0; rr < 3; rr++) {
-              const int k = ks[rr], ek = e + rr;
-              const bool g0 = k > k0, g1 = k > k1, g2 = k > k2;
-              k2 = g1 ? k1 : (g2 ? k : k2); e2 = g1 ? e1 : (g2 ? ek : e2);
-              k1 = g0 ? k0 : (g1 ? k : k1); e1 = g0 ? e0 : (g1 ? ek : e1);
-              k0 = g0 ? k : k0; e0 = g0 ? ek : e0;
-            }
-          }
-#pragma unroll
-          for (int r = 0; r < 3; r++) {
-            const int m = __builtin_amdgcn_readlane(wave_max_to_lane63(k0), 63);
-            const unsigned long long own = __ballot(k0 == m && m >= 0);
-            const int owner = own ? (int)__ffsll((long long)own) - 1 : 0;
-            keys[r] = m;
-            src[r] = __builtin_amdgcn_readlane(e0, owner);
-            if (k0 == m && m >= 0) { k0 = k1; e0 = e1; k1 = k2; e1 = e2; k2 = -1; }
-          }
-        };
-        // the owners of the keys left their K2/K3 contributions next to them: single-pass levels (one point per lane) and the strips of
-        // a throughput-mode batch (the three largest keys of a strip are re-evaluated at the end of its launch)
-        const bool single = job.lv[level].singlePass != 0 || job.lv[level].tilePx > 0;
-        const int j = lane & 31, rj = lane >> 5;
-        int keysA[3], srcA[3], keysB[3], srcB[3];
-        float a0 = 0.f, a2 = 0.f, b0 = 0.f, b2 = 0.f;
-        merge(kva, keysA, srcA);
-        if (single && j < 29) {
-          // the owners left their K2/K3 contributions next to the keys
-          const float* tv = topval_in0 + (size_t)ca * max_rows * 96;
-          if (keysA[rj] >= 0) a0 = tv[(size_t)srcA[rj] * 32 + j];
-          if (rj == 0 && keysA[2] >= 0) a2 = tv[(size_t)srcA[2] * 32 + j];
-        }
-        if (cb >= 0) {
-          merge(kvb, keysB, srcB);
-          if (single && j < 29) {
-            const float* tv = topval_in0 + (size_t)cb * max_rows * 96;
-            if (keysB[rj] >= 0) b0 = tv[(size_t)srcB[rj] * 32 + j];
-            if (rj == 0 && keysB[2] >= 0) b2 = tv[(size_t)srcB[2] * 32 + j];
-          }
-        }
-        if (lane == 0) {
-          s_nsubT[ca] = (keysA[0] >= 0) + (keysA[1] >= 0) + (keysA[2] >= 0);
-          if (cb >= 0) s_nsubT[cb] = (keysB[0] >= 0) + (keysB[1] >= 0) + (keysB[2] >= 0);
-        }
-        if (single) {
-          if (j < 29) {
-            if (keysA[rj] >= 0) s_subT[ca][rj][j] = a0;
-            if (rj == 0 && keysA[2] >= 0) s_subT[ca][2][j] = a2;
-            if (cb >= 0) {
-              if (keysB[rj] >= 0) s_subT[cb][rj][j] = b0;
-              if (rj == 0 && keysB[2] >= 0) s_subT[cb][2][j] = b2;
-            }
-          }
-        } else {
-          // multi-pass level: re-evaluate the tail points at their trial's pose: lanes 0..2 trial ca, 3..5 trial cb
-          const bool second = lane >= 3;
-          const int r = second ? lane - 3 : lane;
-          const int c = second ? cb : ca;
-          int key = -1;
-          if (lane < 6 && c >= 0) key = second ? (r == 0 ? keysB[0] : (r == 1 ? keysB[1] : keysB[2])) : (r == 0 ? keysA[0] : (r == 1 ? keysA[1] : keysA[2]));
-          if (key >= 0) {
-            EvalCtx a;
-            make_ctx_dev(job, S, level, a);
-            if (c > 0) {
-              const float* rec = s_rec[c];
-#pragma unroll
-              for (int i = 0; i < 9; i++) a.R[i] = rec[13 + i];
-#pragma unroll
-              for (int i = 0; i < 3; i++) a.t[i] = rec[22 + i];
-            }
-            const int idx = (a.npts >= 0) ? key : ((key / a.h) + (key % a.h) * a.w);
-            float px, py, pz, I_ref, var;
-            int maskIdx;
-            fetch_point(a, idx, px, py, pz, I_ref, var, maskIdx);
-            PointOut o;
-            eval_point(a, px, py, pz, I_ref, var, o);
-            float* sub = s_subT[c][r];
-            sub[0] = o.werr;
-            int k = 1;
-#pragma unroll
-            for (int rr = 0; rr < 6; rr++) {
-              float Jw = o.J[rr] * o.w;
-#pragma unroll
-              for (int cc = rr; cc < 6; cc++) sub[k++] = Jw * o.J[cc];
-            }
-            float resw = o.res * o.w;
-#pragma unroll
-            for (int rr = 0; rr < 6; rr++) sub[k++] = resw * o.J[rr];
-            sub[k++] = resw * o.res;
-          }
-        }
-      };
-      // Strips of a throughput-mode batch, at most 24 per job: a strip's launch leaves one 32-float row per candidate — its (up to) three
-      // largest keys' K2/K3 contributions [0..28] and the key itself [31] — so ALL rows of the job travel in the same round trip as the
-      // partial sums (NQ 16-byte loads per lane), the three largest keys are picked from the rows in registers, and their rows go to the
-      // tail table: no second, dependent round trip (the keys first, then the owners' contributions) in front of the LM step.
-      auto tail_rows = [&](const int ca, const int cb, auto nqn) {
-        constexpr int NQ = decltype(nqn)::value;   // NQ * 64 >= nb * 24 (16-byte words of the rows)
-        const int cbb = cb < 0 ? ca : cb;
-        const float4* ta = (const float4*)(topval_in0 + (size_t)ca * max_rows * 96);
-        const float4* tb = (const float4*)(topval_in0 + (size_t)cbb * max_rows * 96);
-        const int nf4 = nb * 24;
-        float4 va[NQ], vb[NQ];
-#pragma unroll
-        for (int q = 0; q < NQ; q++) {
-          const int f = q * 64 + lane;
-          va[q] = ta[f < nf4 ? f : 0];   // unconditional, issued together
-          vb[q] = tb[f < nf4 ? f : 0];
-        }
-        auto pick = [&](const float4 (&v)[NQ], const int c) {
-          int k0 = -1, k1 = -1, k2 = -1, e0 = 0, e1 = 0, e2 = 0;
-#pragma unroll
-          for (int q = 0; q < NQ; q++) {
-            const int f = q * 64 + lane;
-            const int k = ((lane & 7) == 7 && f < nf4) ? __float_as_int(v[q].w) : -1, ek = f >> 3;   // the row's key sits in its last word
-            const bool g0 = k > k0, g1 = k > k1, g2 = k > k2;
-            k2 = g1 ? k1 : (g2 ? k : k2); e2 = g1 ? e1 : (g2 ? ek : e2);
-            k1 = g0 ? k0 : (g1 ? k : k1); e1 = g0 ? e0 : (g1 ? ek : e1);
-            k0 = g0 ? k : k0; e0 = g0 ? ek : e0;
-          }
-          int nsub = 0;
-#pragma unroll
-          for (int r = 0; r < 3; r++) {
-            const int m = __builtin_amdgcn_readlane(wave_max_to_lane63(k0), 63);
-            const unsigned long long own = __ballot(k0 == m && m >= 0);
-            const int owner = own ? (int)__ffsll((long long)own) - 1 : 0;
-            const int row = __builtin_amdgcn_readlane(e0, owner);
-            if (k0 == m && m >= 0) { k0 = k1; e0 = e1; k1 = k2; e1 = e2; k2 = -1; }
-            if (m >= 0) {
-              nsub++;
-              // the row's 16-byte words sit in v[row / 8] of lanes 8 (row % 8) ..: a scalar branch per q (row is uniform).  (The empty asm
-              // keeps the compiler from folding the branches into an indexed read of v[] — scratch memory; a chain of 4 (NQ - 1) selects
-              // per candidate was the first form.)
-              const int qsel = row >> 3;
-#pragma unroll
-              for (int q = 0; q < NQ; q++) {
-                if (q == qsel) {
-                  float4 w4 = v[q];
-                  asm volatile("" : "+v"(w4.x), "+v"(w4.y), "+v"(w4.z), "+v"(w4.w));
-                  if ((lane >> 3) == (row & 7)) *(float4*)&s_subT[c][r][(lane & 7) * 4] = w4;
-                }
-              }
-            }
-          }
-          if (lane == 0) s_nsubT[c] = nsub;
-        };
-        pick(va, ca);
-        if (cb >= 0) pick(vb, cb);
-      };
-    // this wave's share of the tail work, run between the issue of the column-sum loads and their additions
-    auto wave_tail = [&]() {
-      // trial c -> wave WAVES-1 - (c mod WAVES): the last wave first (it has no column sums to add)
-      const int ca = WAVES - 1 - wave;
-      const int cb = ca + WAVES < ncandPending ? ca + WAVES : -1;
-      if (ca < ncandPending) {
-        if (BATCH && job.lv[level].tilePx > 0 && nb <= 24) {
-          if (nb <= 5) tail_rows(ca, cb, std::integral_constant<int, 2>());
-          else if (nb <= 13) tail_rows(ca, cb, std::integral_constant<int, 5>());
-          else tail_rows(ca, cb, std::integral_constant<int, 9>());
-        } else if (nb <= 128) tail_two(ca, cb, std::integral_constant<int, 2>());
-        else tail_two(ca, cb, std::integral_constant<int, 5>());
-      }
-    };
-    if (tid == SUMW * 64 - 1) stage_lm_par(job, level, s_par, (spec.specC > 1 && spec.trials[level] > 1) ? spec.trials[level] : 1);
+    if (tid == SUMW * 64 - 1) stage_lm_par(job, level, s_par, trials_at(spec, level));
     if (wave < SUMW) {
-      // fixed-order column sums over the tiles' partial rows (row-major [tile][RS_COLS]: a wave's load covers whole rows, i.e.
-      // contiguous memory): thread t < NSLOT * 11 takes columns 4 c4 .. 4 c4 + 3 of rows slot, slot + NSLOT, ... , for every
-      // trial (the other lanes of these waves run along and store nothing: the tail work in the middle is wave-wide)
-      const int t = tid;
-      const int slot_ = t / (RS_COLS / 4);
-      const bool sumLane = slot_ < NSLOT;
-      const int slot = sumLane ? slot_ : 0, c4 = sumLane ? t - slot_ * (RS_COLS / 4) : 0;
-      {
-        const int K = (nb + NSLOT - 1) / NSLOT;                // rows per slot
-        const float4* p = (const float4*)sums_in0 + c4;
-        const size_t trialStrideF4 = (size_t)RS_COLS * max_rows / 4;
-        // the loads are unconditional and issued together (trials past the last one re-read it, rows past the last one re-read
-        // the slot's first row); coarse levels (few tiles) take the short forms
-        auto colsum = [&](auto qn, auto ntn, const int base) {
-          constexpr int Q = decltype(qn)::value, NT = decltype(ntn)::value;
-          float4 v[NT][Q];
-#pragma unroll
-          for (int c = 0; c < NT; c++) {
-            const int pc = base + c < ncandPending ? base + c : ncandPending - 1;
-            const float4* pp = p + (size_t)pc * trialStrideF4;
-#pragma unroll
-            for (int q = 0; q < Q; q++) {
-              const int r = slot + NSLOT * q;
-              v[c][q] = pp[(size_t)(r < nb ? r : slot) * (RS_COLS / 4)];
-            }
-          }
-#pragma unroll
-          for (int c = 0; c < NT; c++) {
-            float4 a4 = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-            for (int q = 0; q < Q; q++) {
-              const bool live = q < K && slot + NSLOT * q < nb;
-              a4.x += live ? v[c][q].x : 0.f;
-              a4.y += live ? v[c][q].y : 0.f;
-              a4.z += live ? v[c][q].z : 0.f;
-              a4.w += live ? v[c][q].w : 0.f;
-            }
-            if (sumLane && base + c < ncandPending) *(float4*)&s_sumT[base + c][slot][c4 * 4] = a4;
-          }
-        };
-        typedef std::integral_constant<int, 1> I1;
-        typedef std::integral_constant<int, 3> I3;
-        typedef std::integral_constant<int, TRIALS_MAX> IM;
-        if (ncandPending == 1) {
-          if (K <= 2) colsum(std::integral_constant<int, 2>(), I1(), 0);
-          else if (K <= 5) colsum(std::integral_constant<int, 5>(), I1(), 0);
-          else if (K <= 10) colsum(std::integral_constant<int, 10>(), I1(), 0);
-          else colsum(std::integral_constant<int, QMAX>(), I1(), 0);
-        } else if (K <= 2) colsum(std::integral_constant<int, 2>(), IM(), 0);
-        else if (K <= 5) colsum(std::integral_constant<int, 5>(), IM(), 0);
-        else if (K <= 10) { for (int base = 0; base < ncandPending; base += 3) colsum(std::integral_constant<int, 10>(), I3(), base); }
-        else { for (int base = 0; base < ncandPending; base++) colsum(std::integral_constant<int, QMAX>(), I1(), base); }
-#ifdef LSD_PHASE_TRACE
-        if (trOn_ && tid == 0) tr_[17] = clock64();
-#endif
-      }
+      column_sums<TRIALS_MAX>(A, nb, ncandPending, tid, ft.sum);
+      TRACE_PUT(tr_, 0, 17, clock64());
     }
-    wave_tail();
-#ifdef LSD_PHASE_TRACE
-    if (trOn_ && tid == SUMW * 64) s_trp[18] = clock64();
-#endif
+    gather_tails<BATCH, WAVES>(job, S, level, nb, ncandPending, A, s_rec, ft.sub, ft.nsub, wave, lane);
+    TRACE_PUT(s_trp, SUMW * 64, 18, clock64());
     __syncthreads();
     PHASE_MARK(2);
     if (wave == 0) {
-      // Which pending trial does the LM loop stop at?  Trial c stops it when it diverges (M < minWarped), is accepted
-      // (error < lastErr) or is rejected with a step below stepSizeMin — each test needs only that trial's own totals and
-      // increment, so lane c answers for trial c and the first "yes" wins.  The trials before it were plain rejections: they
-      // leave nothing behind but lambda, incTry and the counters, which are advanced in closed form; then ONE LM step runs,
-      // on the totals of the trial that stopped the loop (or of the last pending one).
-      int pc = 0;
-      if (ncandPending > 1) {
-        const int c = tid < ncandPending ? tid : 0;
-        float Mf = s_sumT[c][0][RS_M], ws = s_sumT[c][0][RS_WERR];
-#pragma unroll
-        for (int k = 1; k < NSLOT; k++) { Mf += s_sumT[c][k][RS_M]; ws += s_sumT[c][k][RS_WERR]; }
-        const int Mc = (int)Mf;
-        int needc = Mc & 3;
-        if (needc > s_nsubT[c]) needc = s_nsubT[c];
-        if (needc > 0) ws -= s_subT[c][0][0];
-        if (needc > 1) ws -= s_subT[c][1][0];
-        if (needc > 2) ws -= s_subT[c][2][0];
-        const float werrc = lm_werr(ws, Mc);
-        const float* ic = c == 0 ? S.inc : s_rec[c];
-        const float i0 = ic[0], i1 = ic[1], i2 = ic[2], i3 = ic[3], i4 = ic[4], i5 = ic[5];
-        const float incdot = (i0 * i0 + (i1 * i1 + i2 * i2)) + (i3 * i3 + (i4 * i4 + i5 * i5));
-        const bool stop = Mc < s_par.minWarped || werrc < S.lastErr || !(incdot > s_par.stepSizeMin);
-        const unsigned long long sm = __ballot(stop && tid < ncandPending);
-        pc = sm ? (int)__ffsll((long long)sm) - 1 : ncandPending - 1;
-        if (pc > 0) {
-          float lam = S.LM_lambda;
-          const int it0 = S.incTry;
-          for (int j = 0; j < pc; j++) lam = lm_lambda_fail(lam, it0 + j, s_par.lambdaFailFac);
-          // algorithmic bytes of the skipped evaluations (as in lm_wave)
-          float skipped;
-          {
-            float NR = s_sumT[0][0][RS_NREF];
-#pragma unroll
-            for (int k = 1; k < NSLOT; k++) NR += s_sumT[0][k][RS_NREF];
-            const float wh = (float)s_par.w * (float)s_par.h;
-            const float texels = 4.0f * NR < wh ? 4.0f * NR : wh;
-            skipped = 20.0f * NR + (s_par.writeMask ? 5.0f * NR : 0.0f) + 12.0f * texels;
-          }
-          const float* rec = s_rec[pc];
-          const float bytes0 = S.bytes;
-          const int ne0 = S.numEvaluations, le0 = S.levelEvals[level];
-          float bytes1 = bytes0;
-          for (int j = 0; j < pc; j++) bytes1 = bytes1 + skipped;
-          S.LM_lambda = lam;
-          S.incTry = it0 + pc;
-          S.numEvaluations = ne0 + pc;
-          if (tid == 0) S.levelEvals[level] = le0 + pc;
-          S.bytes = bytes1;
-          if (tid < 6) S.inc[tid] = rec[tid];
-          if (tid < 7) ((float*)&S.Tn)[tid] = rec[6 + tid];
-          if (tid < 9) S.R[tid] = rec[13 + tid];
-          if (tid < 3) S.t[tid] = rec[22 + tid];
-        }
-      }
-      {
-        // column totals and tail-drop correction, one column per lane; then the LM decision in the same wave
-        float Mf = s_sumT[pc][0][RS_M];
-#pragma unroll
-        for (int k = 1; k < NSLOT; k++) Mf += s_sumT[pc][k][RS_M];
-        float s = 0.f;
-        if (tid < RS_END) {
-          s = s_sumT[pc][0][tid];
-#pragma unroll
-          for (int k = 1; k < NSLOT; k++) s += s_sumT[pc][k][tid];
-        }
-        const int M = (int)Mf;
-        int need = M & 3;
-        if (need > s_nsubT[pc]) need = s_nsubT[pc];
-        // RS_WERR -> 0, RS_A0.. -> 1..21, RS_B0.. -> 22..27, RS_ERR -> 28
-        const int subIdx = (tid == RS_WERR) ? 0 : ((tid >= RS_A0 && tid < RS_B0) ? 1 + tid - RS_A0 : ((tid >= RS_B0 && tid < RS_ERR) ? 22 + tid - RS_B0 : (tid == RS_ERR ? 28 : -1)));
-        const float sub0 = s_subT[pc][0][subIdx < 0 ? 0 : subIdx], sub1 = s_subT[pc][1][subIdx < 0 ? 0 : subIdx], sub2 = s_subT[pc][2][subIdx < 0 ? 0 : subIdx];
-        if (subIdx >= 0) {
-          if (need > 0) s -= sub0;
-          if (need > 1) s -= sub1;
-          if (need > 2) s -= sub2;
-        }
-        if (tid < RS_NUM) sh.tot[tid] = s;
+      const int pc = pick_trial(S, s_par, level, ncandPending, ft.sum, ft.sub, ft.nsub, s_rec, tid);
+      // column totals and tail-drop correction, one column per lane; then the LM decision in the same wave
+      const float s = finish_totals(ft.sum, ft.sub, ft.nsub, pc, tid);
+      if (tid < RS_NUM) sh.tot[tid] = s;
 #ifdef LSD_ORDER_CHECK
-        if (!BATCH && spec.dbgCounters) {
-          // do all workgroups of this launch finish the previous evaluation with the same totals?
-          unsigned hv = tid < RS_END ? __float_as_uint(s) * (2654435761u * (unsigned)(tid + 1)) : 0u;
-          hv += (unsigned)pc * 97u;
-          for (int off = 32; off > 0; off >>= 1) hv += __shfl_xor(hv, off);
-          if (tid == 0) {
-            const unsigned long long slot = 8 + 2 * ((spec.dbgCum / 400ull) % 8192ull);
-            __hip_atomic_fetch_min(&spec.dbgCounters[slot], (unsigned long long)hv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_fetch_max(&spec.dbgCounters[slot + 1], (unsigned long long)hv, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-          }
-        }
+      if (!BATCH && spec.dbgCounters) order_check_totals(spec, s, pc, tid);
 #endif
-        PHASE_MARK(3);
-#ifdef LSD_PHASE_TRACE
-        if (trOn_ && tid == 0) { tr_[19] = (unsigned long long)ncandPending; tr_[7] = (unsigned long long)pc; }
-        lm_wave<SPEC_LM>(s_par, S, s, sh.tot, tid, leader ? out : nullptr, trOn_ ? tr_ : nullptr, pc, cand, doneWord);
-#else
-        lm_wave<SPEC_LM>(s_par, S, s, sh.tot, tid, leader ? out : nullptr, nullptr, pc, cand, doneWord);
-#endif
-      }
+      PHASE_MARK(3);
+      TRACE_PUT(tr_, 0, 19, ncandPending); TRACE_PUT(tr_, 0, 7, pc);
+      lm_wave<SPEC_LM>(s_par, S, s, sh, tid, leader ? out : nullptr, TRACE_LM_REC, pc, cand, doneWord);
     }
     __syncthreads();
     PHASE_MARK(4);
     if (S.done) {
-      // the frame's refPixelWasGood must be what the last trial the LM loop executed wrote: trials > 0 wrote side planes
-      if (!BATCH && MODE == TS_FUSED && S.lastCand > 0 && spec.copyMask != 0 && job.lv[level].writeMask && cand == 0 && bx < nb) {
-        const uint8_t* side = spec.wasGoodSide + (size_t)(S.lastCand - 1) * spec.maskStride;
-        EvalCtx a;
-        make_ctx_dev(job, S, level, a);
-        const int work = a.npts >= 0 ? a.npts : a.w * a.h;
-        for (int i = bx * BLOCK + tid; i < work; i += nb * BLOCK) {
-          float px, py, pz, I_ref, var;
-          int maskIdx;
-          if (fetch_point(a, i, px, py, pz, I_ref, var, maskIdx) && maskIdx >= 0) job.wasGood[maskIdx] = side[maskIdx];
-        }
-      }
+      if (!BATCH && MODE == TS_FUSED && S.lastCand > 0 && spec.copyMask != 0 && job.lv[level].writeMask && cand == 0 && bx < nb)
+        copy_side_mask<BLOCK>(job, S, spec, level, bx, nb, tid);
       if (leader) copy_words<sizeof(TrackState) / 4>(next, &S, tid, BLOCK);
       LAUNCH_LOG(2, pendingIn_, ncandIn_, S.lastCand);
       return;
     }
     // a workgroup that evaluates trial c > 0 leaves that trial's increment and pose for the launch that finishes it
-    if (cand > 0 && bx == 0 && S.phase == 1 && cand < S.ncand && tid < 25) {
-      float v;
-      if (tid < 6) v = S.inc[tid];
-      else if (tid < 13) v = ((const float*)&S.Tn)[tid - 6];
-      else if (tid < 22) v = S.R[tid - 13];
-      else v = S.t[tid - 22];
-      sc.recs[((size_t)outp * cmax + cand) * 32 + tid] = v;
-    }
+    if (cand > 0 && bx == 0 && S.phase == 1 && cand < S.ncand && tid < TRIAL_RECORD_WORDS) ((float*)&A.recs_out[cand])[tid] = trial_record_word(S, tid);
   }
 
   if (MODE == TS_LM) {
-    __syncthreads();              // (every wave has tested S.pending before it changes: see the note at the residual evaluation below)
+    __syncthreads();              // (every wave has tested S.pending before it changes: see the note in reduce_and_store)
     if (tid == 0) { S.pending = 1; S.numLaunches = S.numLaunches + 1; }   // (numLaunches of a batch job: its rounds)
     __syncthreads();
     if (leader) copy_words<sizeof(TrackState) / 4>(next, &S, tid, BLOCK);
@@ -676,327 +855,41 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
 
   // ---- residual evaluation at S.level / S.R, S.t ------------------------------------------------------------------
   const int level = S.level;
-  // (S.pending = 1 / S.numLaunches++ for the state this launch publishes are set further down, behind the first barrier of the
-  // reduction: in a job's first launch the finishing phase above is skipped, so no barrier separates a wave that is still about to test
-  // `S.pending` from wave 0 arriving here — with the write here, a wave held up by LDS traffic of another stream's workgroups on
-  // the same CU could read 1, enter the finishing phase alone and pair its barriers with the others' reduction barriers: one
-  // tile's sums came out as LDS residue.  Seen only with a second stream active, profiles/r04_notes.md.)
-  const int nb = job.lv[level].nblocks;
+  const TrackLevel& L = job.lv[level];
+  const int nb = L.nblocks;
   if (MODE == TS_FUSED && level != lvlPending) { cand = 0; bx = (int)blockIdx.x; }   // first evaluation of the next level
   if (bx >= nb || cand >= S.ncand) return;   // workgroup 0 always has work: it publishes the state at the end
-  sums_out += (size_t)cand * RS_COLS * max_rows;
-  topkey_out += (size_t)cand * max_rows;
-  topval_out += (size_t)cand * max_rows * 96;
   const int tile = xcd_tile(bx, nb);
   EvalCtx a;
   make_ctx_dev(job, S, level, a);   // (fetched beside the finishing phase for the pending level: measured, +-0 — the scalar loads are not what the step behind the LM waits for)
-  if (BATCH && MODE == TS_EVAL && cand > 0) {
-    // a retry further down the reject chain: its pose is in the record the LM workgroup that proposed it left
-    const float* rec = sc.recs + ((size_t)parity * cmax + cand) * 32;
-#pragma unroll
-    for (int i = 0; i < 9; i++) a.R[i] = rec[13 + i];
-#pragma unroll
-    for (int i = 0; i < 3; i++) a.t[i] = rec[22 + i];
-  }
-  gbyte* wasGood = (gbyte*)(job.lv[level].writeMask ? (cand == 0 ? job.wasGood : spec.wasGoodSide + (size_t)(cand - 1) * spec.maskStride) : nullptr);
+  // a retry further down the reject chain: its pose is in the record the LM workgroup that proposed it left
+  if (BATCH && MODE == TS_EVAL && cand > 0) ctx_set_pose(a, A.recs_in[cand]);
+  gbyte* wasGood = (gbyte*)(L.writeMask ? (cand == 0 ? job.wasGood : spec.wasGoodSide + (size_t)(cand - 1) * spec.maskStride) : nullptr);
   const int work = a.npts >= 0 ? a.npts : a.w * a.h;
   float acc[RS_END];
 #pragma unroll
   for (int k = 0; k < RS_END; k++) acc[k] = 0.f;
   int key0 = -1, key1 = -1, key2 = -1;   // reference-order keys of this lane's in-image points (descending)
-
-  if (BATCH && job.lv[level].tilePx > 0) {
-    // Throughput mode (batches): the workgroup owns a strip of tilePx consecutive pixels of the keyframe level.  It first
-    // compacts the strip's valid reference pixels (semi-dense: ~30 %) into an LDS list — fixed order: chunk, then pixel
-    // slot, then lane, so the result is run-to-run deterministic — and then evaluates the list with all lanes busy.
-    unsigned* s_list = (unsigned*)s_red;   // (x | y << 16); s_red is not live before the reduction
-    // The strip's list is the concatenation of its reference blocks (k_ref_blocks, frame.hip: per 256 consecutive pixels the offsets of the
-    // valid ones, compacted in pixel order, and a count): wave v takes block 4 c + v of the strip in step c, lane l its slots l, l + 64, ...;
-    // every wave derives the blocks' places in the list from the counts itself (at most 32 blocks: one lane each), so nothing is exchanged
-    // and the only barrier is the one in front of the evaluation.  (Until round 6 the strip streamed the level's validity planes, 8 bytes per
-    // pixel, and compacted them with four ballots per 1024 pixels in every evaluation: a quarter of a level-1 round at 64 jobs.)
-    const int tilePx = job.lv[level].tilePx;
-    const int base = tile * tilePx;
-    const int stripEnd = min(base + tilePx, work);
-    const int b0 = base >> 8;                                  // strips are multiples of 256 pixels
-    const int mblk = (stripEnd - base + 255) >> 8;             // <= 32 (tilePx <= 8192, fill_level)
-    const float inv_w = 1.0f / (float)a.w;
-    if (!(havePre && level == lvlPending)) strip_request(level, tile);   // (else: requested next to the state, at the head of the finishing phase)
-    // inclusive scan of the (at most 32) block counts over lanes 0..31 in six DPP additions, the blocks' entries through v_readlane (the
-    // wave index is uniform: readfirstlane tells the compiler so)
-    int incl = cntv + dpp_i0<0x111, 0xf, 0xf>(cntv);      // row_shr:1
-    incl += dpp_i0<0x112, 0xf, 0xf>(cntv);                // row_shr:2
-    incl += dpp_i0<0x113, 0xf, 0xf>(cntv);                // row_shr:3
-    incl += dpp_i0<0x114, 0xf, 0xe>(incl);                // row_shr:4 bank_mask:0xe
-    incl += dpp_i0<0x118, 0xf, 0xc>(incl);                // row_shr:8 bank_mask:0xc
-    incl += dpp_i0<0x142, 0xa, 0xf>(incl);                // row_bcast:15 row_mask:0xa
-    const int total = __builtin_amdgcn_readlane(incl, 31);
-    const int waveU = __builtin_amdgcn_readfirstlane(wave);
-    PHASE_MARK(20);
-#pragma unroll
-    for (int c = 0; c < CHMAX; c++) {
-      const int blk = c * 4 + waveU;
-      if (blk < mblk) {
-        const int cb = __builtin_amdgcn_readlane(cntv, blk);
-        const int pb = __builtin_amdgcn_readlane(incl, blk) - cb;
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const int sl = lane + 64 * k;                       // (the block's bytes are slot-interleaved: k_ref_blocks)
-          if (sl < cb) {
-            const int i = ((b0 + blk) << 8) + (int)((ow[c] >> (8 * k)) & 255u);
-            int y = (int)((float)i * inv_w);
-            int x = i - y * a.w;
-            if (x < 0) { y--; x += a.w; }
-            if (x >= a.w) { y++; x -= a.w; }
-            s_list[pb + sl] = (unsigned)x | ((unsigned)y << 16);
-          }
-        }
-      }
-    }
-    __syncthreads();
-    PHASE_MARK(21);
-#ifdef LSD_PHASE_TRACE
-    if (trOn_ && tid == 0) tr_[23] = (unsigned long long)total;
-#endif
-    if (total > 0) {
-      // three-stage software pipeline over the list entries tid, tid + BLOCK, ...: (A) list entry + keyframe planes,
-      // (B) reference point, warp, texel fetch, (C) residual / weights / normal equations.  Stage A of entry r + 2 and
-      // stage B of entry r + 1 are issued before stage C of entry r, so two dependent memory round trips overlap the
-      // arithmetic.  Lanes past the end of the list run the loads on entry 0 and discard them.
-      struct StA { unsigned xy; float var, id, img; bool live; };
-      struct StB { unsigned xy; float pz, I_ref, var; PointWarp q; PointTexels t; bool live; };
-      auto stageA = [&](int p, StA& A) {
-        A.live = p < total;
-        A.xy = s_list[A.live ? p : 0];
-        const int i = __mul24((int)(A.xy >> 16), a.w) + (int)(A.xy & 0xffffu);
-        A.var = a.kf_idepthVar[i];
-        A.id = a.kf_idepth[i];
-        A.img = a.kf_image[i];
-      };
-      auto stageB = [&](const StA& A, StB& B) {
-        B.live = A.live;
-        B.xy = A.xy;
-        const int bx_ = (int)(A.xy & 0xffffu), by_ = (int)(A.xy >> 16);
-        const float inv = lsd_rcp_exact(A.id);
-        const float px = inv * (a.fxi * bx_ + a.cxi), py = inv * (a.fyi * by_ + a.cyi);
-        B.pz = inv * 1.0f;
-        B.I_ref = A.img; B.var = A.var;
-        eval_warp(a, px, py, B.pz, B.q);
-        eval_fetch(a, B.q, B.live && B.q.in_image, B.t);
-      };
-      const int rounds = (total + BLOCK - 1) / BLOCK;
-      StA A1, A2;
-      StB B0, B1;
-      stageA(tid, A1);
-      stageB(A1, B0);
-      stageA(tid + BLOCK, A1);
-      PHASE_MARK(22);
-      auto stageC = [&](const StB& B) {
-        if (B.live) {
-          const int x_ = (int)(B.xy & 0xffffu), y_ = (int)(B.xy >> 16);
-          const int i = __mul24(y_, a.w) + x_;
-          acc[RS_NREF] += 1.f;
-          if (!B.q.in_image) {
-            if (wasGood) wasGood[i] = 0;
-          } else {
-            PointOut o;
-            eval_finish(a, B.q, B.t, B.pz, B.I_ref, B.var, o);
-            if (wasGood) wasGood[i] = o.good ? 1 : 0;
-            top3_insert(__mul24(x_, a.h) + y_, key0, key1, key2);
-            accumulate_point(o, acc);
-          }
-        }
-      };
-      // two rounds per trip with the roles of (A1, A2) and (B0, B1) swapped in the second half: a rotating pipeline written with
-      // struct copies costs ~30 register moves per round
-      for (int r = 0; r < rounds; r += 2) {
-        stageB(A1, B1);
-        stageA(tid + (r + 2) * BLOCK, A2);
-        stageC(B0);
-        stageB(A2, B0);
-        stageA(tid + (r + 3) * BLOCK, A1);
-        stageC(B1);                       // entry r + 1: not live past the end of the list
-      }
-    }
-    __syncthreads();   // the list aliases s_red
-  } else if (!BATCH && job.lv[level].evalBatch != 0) {
-    // Multi-pass dense level of a single job (the host sets the flag: plan_job / fill_level): the lane's points i0, i0 + s, ... (s = nb x
-    // BLOCK) are taken four at a time.  In the plain loop below every load sits behind a branch on the one before it (the validity planes,
-    // then the keyframe colour, then the four texels behind in_image), so a lane makes 2 - 3 dependent memory round trips per point, one
-    // point after the other: at 640x480 level 1 that is four points per lane and a third of the launch's body.  Here the
-    // round trips of a group travel together: (1) the three plane loads of all four points, unconditional — a point past the end of the
-    // level reads pixel 0 and is dropped; (2) for all four: validity, the reference point, the warp, the texel loads (texel 0 where the
-    // point is not in the image); (3) in pass order what the plain loop does with a point, so every lane adds the same contributions in
-    // the same order and the partial rows, keys and mask bytes are those of the plain loop bit for bit.  (x, y) of the later points
-    // follow from the first by the uniform stride: one integer division per lane instead of one per point.
-    const int stride = nb * BLOCK;
-    const int sy = stride / a.w, sx = stride - sy * a.w;   // uniform; sx < w: one carry at most
-    int i = tile * BLOCK + tid;
-    int x = i % a.w, y = i / a.w;
-    struct Pt { int i, x, y; bool valid; RefPlanes r; float img, pz; PointWarp q; PointTexels t; };
-    while (i < work) {
-      Pt P[4];
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        Pt& p = P[k];
-        p.i = i; p.x = x; p.y = y;
-        p.valid = i < work;
-        const int li = p.valid ? i : 0;
-        fetch_request(a, li, p.r);
-        p.img = a.kf_image[li];
-        i += stride; x += sx; y += sy;
-        if (x >= a.w) { x -= a.w; y++; }
-      }
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        Pt& p = P[k];
-        float px = 0.f, py = 0.f;
-        p.pz = 1.f;
-        p.valid = p.valid && ref_pixel_inside(a, p.x, p.y) && fetch_finish(a, p.x, p.y, p.r, px, py, p.pz);
-        eval_warp(a, px, py, p.pz, p.q);
-        eval_fetch(a, p.q, p.valid && p.q.in_image, p.t);
-      }
-#pragma unroll
-      for (int k = 0; k < 4; k++) {
-        const Pt& p = P[k];
-        if (p.valid) {
-          acc[RS_NREF] += 1.f;
-          if (!p.q.in_image) {
-            if (wasGood) wasGood[p.i] = 0;
-          } else {
-            PointOut o;
-            eval_finish(a, p.q, p.t, p.pz, p.img, p.r.var, o);
-            if (wasGood) wasGood[p.i] = o.good ? 1 : 0;
-            top3_insert(p.x * a.h + p.y, key0, key1, key2);
-            accumulate_point(o, acc);
-          }
-        }
-      }
-    }
-  } else
-  for (int i = tile * BLOCK + tid; i < work; i += nb * BLOCK) {
-    float px, py, pz, I_ref, var;
-    int maskIdx;
-    if (fetch_point(a, i, px, py, pz, I_ref, var, maskIdx)) {
-      acc[RS_NREF] += 1.f;
-      PointOut o;
-      eval_point(a, px, py, pz, I_ref, var, o);
-      if (!o.in_image) {
-        if (wasGood && maskIdx >= 0) wasGood[maskIdx] = 0;
-      } else {
-        if (wasGood && maskIdx >= 0) wasGood[maskIdx] = o.good ? 1 : 0;
-        top3_insert(a.npts >= 0 ? i : (i % a.w) * a.h + (i / a.w), key0, key1, key2);
-        accumulate_point(o, acc);
-      }
-    }
+  if (BATCH && L.tilePx > 0) {
+    if (!(havePre && level == lvlPending)) strip_request(L, tile, wave, lane, cntv, ow);   // (else: requested next to the state, at the head of the finishing phase)
+    eval_strip<BLOCK>(a, L.tilePx, tile, work, cntv, ow, (unsigned*)s_red /* not live before the reduction */, wasGood, acc, key0, key1, key2, tid TRACE_ARGS);
+  } else if (!BATCH && L.evalBatch != 0) {
+    eval_groups_of_four(a, tile * BLOCK + tid, nb * BLOCK, work, wasGood, acc, key0, key1, key2);
+  } else {
+    eval_plain(a, tile * BLOCK + tid, nb * BLOCK, work, wasGood, acc, key0, key1, key2);
   }
-
   PHASE_MARK(5);
-#ifdef LSD_PHASE_TRACE
-  if (trOn_ && tid == 0) { tr_[10] = (unsigned long long)level; tr_[11] = (unsigned long long)nb; tr_[26] = (unsigned long long)lvlPending; }
-#endif
-  // workgroup reduction through LDS: every lane parks its 41 accumulators in column `tid` of s_red (row stride
-  // BLOCK + 1: conflict-free both ways), then thread (slice, k) adds a contiguous run of lanes of row k in lane order
-  // and 41 threads add the slices — ~130 instructions per wave instead of 41 x 7 DPP steps
-  constexpr int RSLICE = BLOCK / CPP;                  // slices per row
-  constexpr int RRUN = (BLOCK + RSLICE - 1) / RSLICE;  // lanes per slice
-  // Strips of a throughput-mode batch: the (up to) three in-image points of the strip with the largest reference-order keys are
-  // candidates for the job's tail (the last M % 4 in-image points, which the SSE loops of the reference leave out): three lanes evaluate
-  // them once more, alone, and leave their K2/K3 contributions in the strip's candidate rows — the launch that finishes this evaluation
-  // then needs no evaluation of its own in front of the LM step (it used to: keys, reference point, texels = three dependent round
-  // trips).  The two round trips of this evaluation run under the barriers of the reduction.
-  const bool stripRows = BATCH && job.lv[level].tilePx > 0;
-  const bool candLane = tid >= BLOCK - 64 && tid < BLOCK - 61;   // lanes 0..2 of the LAST wave: wave 0 adds the slices and stores the sums meanwhile
-  int cKey = -1, cX = 0, cY = 0;
-  float cVar = 0.f, cId = 1.f, cImg = 0.f, cPz = 0.f;
-  PointWarp cq;
-  PointTexels ct;
-  if (stripRows) {
-    block_top3(key0, key1, key2, s_wtop, s_top);
-    if (candLane) {
-      cKey = s_top[tid - (BLOCK - 64)];
-      if (cKey >= 0) {
-        cX = cKey / a.h;
-        cY = cKey - cX * a.h;
-        const int ci = __mul24(cY, a.w) + cX;
-        cVar = a.kf_idepthVar[ci];
-        cId = a.kf_idepth[ci];
-        cImg = a.kf_image[ci];
-      }
-    }
-  }
-#pragma unroll
-  for (int hp = 0; hp < NPASS; hp++) {
-    if (hp > 0) __syncthreads();
-#pragma unroll
-    for (int k = 0; k < CPP; k++)
-      if (hp * CPP + k < RS_END) s_red[k * (BLOCK + 1) + tid] = acc[hp * CPP + k];
-    __syncthreads();
-    if (MODE == TS_FUSED && hp == 0 && tid == 0) { S.pending = 1; S.numLaunches = S.numLaunches + 1; }   // every wave is past its reads of S.pending
-    if (stripRows && hp == 0 && candLane && cKey >= 0) {
-      const float inv = lsd_rcp_exact(cId);                // (fetch_point's arithmetic)
-      const float px = inv * (a.fxi * cX + a.cxi), py = inv * (a.fyi * cY + a.cyi);
-      cPz = inv * 1.0f;
-      eval_warp(a, px, py, cPz, cq);
-      eval_fetch(a, cq, cq.in_image, ct);
-    }
-    {
-      const int slice = tid / CPP, k = tid - slice * CPP;
-      if (slice < RSLICE) {
-        const float* row = s_red + k * (BLOCK + 1);
-        const int j0 = slice * RRUN;
-        float v[RRUN];
-#pragma unroll
-        for (int j = 0; j < RRUN; j++) v[j] = row[j0 + j];   // unconditional: the run may spill 2 words into the next row (allocated)
-        float s = 0.f;
-#pragma unroll
-        for (int j = 0; j < RRUN; j++) s += (j0 + j < BLOCK) ? v[j] : 0.f;
-        s_sum[slice][k] = s;
-      }
-    }
-    __syncthreads();
-    if (stripRows && hp == 0 && candLane) {
-      float* row = topval_out + (size_t)(tile * 3 + (tid - (BLOCK - 64))) * 32;
-      if (cKey >= 0) {
-        PointOut o;
-        eval_finish(a, cq, ct, cPz, cImg, cVar, o);
-        tail_row(o, row);
-      }
-      ((int*)row)[31] = cKey;
-    }
-    if (tid < CPP && hp * CPP + tid < RS_END) {
-      float s = s_sum[0][tid];
-#pragma unroll
-      for (int sl = 1; sl < RSLICE; sl++) s += s_sum[sl][tid];
-      sums_out[(size_t)tile * RS_COLS + (hp * CPP + tid)] = s;
-    }
-  }
-  if (!stripRows) block_top3(key0, key1, key2, s_wtop, s_top);
-  if (tid == 0) topkey_out[tile] = make_int4(s_top[0], s_top[1], s_top[2], -1);
-  if (job.lv[level].singlePass && key0 >= 0) {
-    // one point per lane: its accumulators are exactly its K2/K3 contributions (0 + x == x)
-    const int r = key0 == s_top[0] ? 0 : (key0 == s_top[1] ? 1 : (key0 == s_top[2] ? 2 : -1));
-    if (r >= 0) {
-      float* dst = topval_out + (size_t)(tile * 3 + r) * 32;
-      dst[0] = acc[RS_WERR];
-#pragma unroll
-      for (int k = 0; k < 21; k++) dst[1 + k] = acc[RS_A0 + k];
-#pragma unroll
-      for (int k = 0; k < 6; k++) dst[22 + k] = acc[RS_B0 + k];
-      dst[28] = acc[RS_ERR];
-    }
-  }
-  if (MODE == TS_FUSED && leader) copy_words<sizeof(TrackState) / 4>(next, &S, tid, BLOCK);   // S.pending was set before the barriers above
+  TRACE_PUT(tr_, 0, 10, level); TRACE_PUT(tr_, 0, 11, nb); TRACE_PUT(tr_, 0, 26, lvlPending);
+  reduce_and_store<BLOCK, BATCH, MODE>(a, L, S, tile, acc, key0, key1, key2, s_red, s_sum, s_wtop, s_top, A.sums_out + (size_t)cand * RS_COLS * A.max_rows,
+                                       A.topkey_out + (size_t)cand * A.max_rows, A.topval_out + (size_t)cand * A.max_rows * (TAIL_ROWS * TAIL_STRIDE), tid);
+  if (MODE == TS_FUSED && leader) copy_words<sizeof(TrackState) / 4>(next, &S, tid, BLOCK);   // S.pending was set behind the reduction's first barrier
   // the budget's last launch ends with the job unfinished: tell the host (pinned memory), which polls this next to `done` and
   // appends launches — the stream order makes them follow; no hipStreamQuery in the wait loop (each one puts a marker packet into
   // the queue the chain runs through: ~3 us per frame)
- 
   if (MODE == TS_FUSED && leader && tid == 0 && spec.last != 0) out->exhausted = spec.seq;
   LAUNCH_LOG(3, pendingIn_, ncandIn_, S.lastCand);
   PHASE_MARK(6);
-#ifdef LSD_PHASE_TRACE
-  if (trOn_ && tid == 0) tr_[9] = wall_clock64();
-#endif
+  TRACE_PUT(tr_, 0, 9, wall_clock64());
 }
 
 template <int BLOCK, bool BATCH, int MODE = TS_FUSED>
@@ -1055,6 +948,15 @@ constexpr int lsd_solo_max_interior() {
   return best;
 }
 static_assert(lsd_solo_max_interior() <= LSD_SOLO_LDS_PTS, "the dense interior of any level k_track_solo takes fits its LDS lists");
+// the four taps of getInterpolatedElement43 (C/util/globalFuncs.h:63-77) out of the tile; `fetch` = false reads texel 0 instead
+__device__ __forceinline__ void solo_taps(const v4f* s_tex, const int w, const PointWarp& q, const bool fetch, PointTexels& t) {
+  const int ix = fetch ? (int)q.u_new : 0;
+  const int iy = fetch ? (int)q.v_new : 0;
+  const v4f* bp = s_tex + (ix + __mul24(iy, w));
+  const v4f v00 = bp[0], v10 = bp[1], v01 = bp[w], v11 = bp[w + 1];
+  t.t00 = Texel3{v00.x, v00.y, v00.z}; t.t10 = Texel3{v10.x, v10.y, v10.z};
+  t.t01 = Texel3{v01.x, v01.y, v01.z}; t.t11 = Texel3{v11.x, v11.y, v11.z};
+}
 template <int BLOCK>
 __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict__ jobs, TrackState* __restrict__ st2, TrackSummary* __restrict__ outs,
                                                           const int parity, const int doneWord) {
@@ -1074,7 +976,7 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
   __shared__ LmPar s_par;
   __shared__ __attribute__((aligned(16))) float s_red[CPP * (HALF + 1) + RRUN];
   __shared__ float s_sum[RSLICE][64];
-  __shared__ float s_sub[3][32];
+  __shared__ float s_sub[TAIL_ROWS][TAIL_STRIDE];
   __shared__ int s_wtop[WAVES][3];
   __shared__ v4f s_tex[LSD_SOLO_MAX_PX];
   __shared__ float s_var[LSD_SOLO_LDS_PTS], s_img[LSD_SOLO_LDS_PTS];     // the points' variances and colours, list order (the registers hold the rest of a point)
@@ -1086,15 +988,6 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
   // this lane's reference points of the level (trip r: point tid + r BLOCK of the list)
   unsigned pXY[TRIPS];
   float pZ[TRIPS];
-  // the four taps of getInterpolatedElement43 (C/util/globalFuncs.h:63-77) out of the tile; `fetch` = false reads texel 0 instead
-  auto taps = [&](const PointWarp& q, const bool fetch, PointTexels& t) {
-    const int ix = fetch ? (int)q.u_new : 0;
-    const int iy = fetch ? (int)q.v_new : 0;
-    const v4f* bp = s_tex + (ix + __mul24(iy, a.w));
-    const v4f v00 = bp[0], v10 = bp[1], v01 = bp[a.w], v11 = bp[a.w + 1];
-    t.t00 = Texel3{v00.x, v00.y, v00.z}; t.t10 = Texel3{v10.x, v10.y, v10.z};
-    t.t01 = Texel3{v01.x, v01.y, v01.z}; t.t11 = Texel3{v11.x, v11.y, v11.z};
-  };
   for (int guard = 0; guard < 4096; guard++) {
     const int level = S.level;
     // the same two invariants as at track_step_impl's early-out: once the job is done this workgroup touches no frame or keyframe memory
@@ -1110,12 +1003,7 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
       const gbyte* offs = (const gbyte*)L.kf_refBlk;
       const __attribute__((address_space(1))) int* cnts = (const __attribute__((address_space(1))) int*)(offs + ((size_t)mblk << 8));
       const int cntv = lane < mblk ? cnts[lane] : 0;
-      int incl = cntv + dpp_i0<0x111, 0xf, 0xf>(cntv);
-      incl += dpp_i0<0x112, 0xf, 0xf>(cntv);
-      incl += dpp_i0<0x113, 0xf, 0xf>(cntv);
-      incl += dpp_i0<0x114, 0xf, 0xe>(incl);
-      incl += dpp_i0<0x118, 0xf, 0xc>(incl);
-      incl += dpp_i0<0x142, 0xa, 0xf>(incl);
+      const int incl = wave_scan32(cntv);
       total = __builtin_amdgcn_readlane(incl, 31);
       if (total > LSD_SOLO_LDS_PTS) break;                  // (every wave computes the same total) cannot happen below 4800 pixels; strips if it does
       // the tile: the level's texel plane, 16 bytes per lane and step
@@ -1134,14 +1022,7 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
 #pragma unroll
         for (int k = 0; k < 4; k++) {
           const int sl = lane + 64 * k;
-          if (sl < cb) {
-            const int i = (blk << 8) + (int)((ow >> (8 * k)) & 255u);
-            int y = (int)((float)i * inv_w);
-            int x = i - y * a.w;
-            if (x < 0) { y--; x += a.w; }
-            if (x >= a.w) { y++; x -= a.w; }
-            s_list[pb + sl] = (unsigned)x | ((unsigned)y << 16);
-          }
+          if (sl < cb) s_list[pb + sl] = pixel_xy16((blk << 8) + (int)((ow >> (8 * k)) & 255u), a.w, inv_w);
         }
       }
       __syncthreads();
@@ -1162,17 +1043,14 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
         for (int r = 0; r < TRIPS; r++) {
           const int p = tid + r * BLOCK;
           if (p < total) { s_var[p] = var[r]; s_img[p] = img[r]; }
-          pZ[r] = (p < total) ? lsd_rcp_exact(id[r]) * 1.0f : 1.0f;
+          pZ[r] = (p < total) ? lsd_rcp_exact(id[r]) * 1.0f : 1.0f;      // ref_point_at's z; x and y per iteration (ref_point_xy)
         }
       }
       listLevel = level;
       __syncthreads();                                      // the list's words become the reduction buffer again
     } else {
       // the pose under evaluation (the LM step of the previous iteration left it in S)
-#pragma unroll
-      for (int i = 0; i < 9; i++) a.R[i] = S.R[i];
-#pragma unroll
-      for (int i = 0; i < 3; i++) a.t[i] = S.t[i];
+      ctx_set_pose(a, S);
       a.aff_a = S.aff_a; a.aff_b = S.aff_b;
     }
     // (the pose is the same in every lane: scalar registers — the lane's points and the 41 running sums want the vector ones)
@@ -1188,43 +1066,25 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
     int key0 = -1, key1 = -1, key2 = -1;
     {
       const int rounds = (total + BLOCK - 1) / BLOCK;
-      struct StT { PointWarp q; PointTexels t; };
-      StT T0;
-      auto stageB = [&](const int r, StT& T) {
-        const bool live = tid + r * BLOCK < total;
-        const int bx_ = (int)(pXY[r] & 0xffffu), by_ = (int)(pXY[r] >> 16);
-        const float px = pZ[r] * (a.fxi * bx_ + a.cxi), py = pZ[r] * (a.fyi * by_ + a.cyi);
-        eval_warp(a, px, py, pZ[r], T.q);
-        taps(T.q, live && T.q.in_image, T.t);
-      };
-      auto stageC = [&](const int r, const StT& T) {
-        if (tid + r * BLOCK < total) {
-          acc[RS_NREF] += 1.f;
-          if (T.q.in_image) {
-            PointOut o;
-            eval_finish(a, T.q, T.t, pZ[r], s_img[tid + r * BLOCK], s_var[tid + r * BLOCK], o);
-            top3_insert(__mul24((int)(pXY[r] & 0xffffu), a.h) + (int)(pXY[r] >> 16), key0, key1, key2);   // reference order (x h + y, TrackingReference.cpp:128-138)
-            accumulate_point(o, acc);
-          }
-        }
-      };
 #pragma unroll
       for (int r = 0; r < TRIPS; r++) {
         // (uniform branch: every lane sees the same `rounds`.  Requesting the taps of trip r + 1 before trip r is finished — two points in
         // flight — pushed the kernel over its 256 registers; the LDS round trip hides behind the SIMD's other wave)
-        if (r < rounds) { stageB(r, T0); stageC(r, T0); }
+        if (r < rounds) {
+          const bool live = tid + r * BLOCK < total;
+          const int x_ = (int)(pXY[r] & 0xffffu), y_ = (int)(pXY[r] >> 16);
+          float px, py;
+          ref_point_xy(a, x_, y_, pZ[r], px, py);
+          PointWarp q; PointTexels t;
+          eval_warp(a, px, py, pZ[r], q);
+          solo_taps(s_tex, a.w, q, live && q.in_image, t);
+          // (no mask at these levels; the key: reference order, x h + y, TrackingReference.cpp:128-138)
+          if (live) visit_point(a, q, t, pZ[r], s_img[tid + r * BLOCK], s_var[tid + r * BLOCK], nullptr, 0, __mul24(x_, a.h) + y_, acc, key0, key1, key2);
+        }
       }
     }
     // each wave's three largest keys; the upper half parks its sums
-    {
-      int c0 = key0, c1 = key1, c2 = key2;
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        const int m = __builtin_amdgcn_readlane(wave_max_to_lane63(c0), 63);
-        if (lane == 0) s_wtop[wave][r] = m;
-        if (c0 == m && m >= 0) { c0 = c1; c1 = c2; c2 = -1; }
-      }
-    }
+    wave_top3(key0, key1, key2, s_wtop);
     if (tid >= HALF) {
 #pragma unroll
       for (int k = 0; k < CPP; k++) s_red[k * (HALF + 1) + tid - HALF] = acc[k];
@@ -1232,25 +1092,11 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
     __syncthreads();
     // wave 0: the level's three largest keys = the candidates for the tail (the last M % 4 in-image points in reference order); lanes
     // 0..2 evaluate them once more — their reference pixel travels under the next two barriers, the taps come out of the tile
-    int cKey = -1, cX = 0, cY = 0;
-    float cVar = 0.f, cId = 1.f, cImg = 0.f;
+    TailCandidate c;
     if (wave == 0) {
-      int v = lane < WAVES * 3 ? s_wtop[lane / 3][lane - 3 * (lane / 3)] : -1;
       int top[3];
-#pragma unroll
-      for (int r = 0; r < 3; r++) {
-        top[r] = __builtin_amdgcn_readlane(wave_max_to_lane63(v), 63);
-        if (v == top[r]) v = -1;
-      }
-      cKey = lane == 0 ? top[0] : (lane == 1 ? top[1] : (lane == 2 ? top[2] : -1));
-      if (cKey >= 0) {
-        cX = cKey / a.h;
-        cY = cKey - cX * a.h;
-        const int ci = __mul24(cY, a.w) + cX;
-        cVar = a.kf_idepthVar[ci];
-        cId = a.kf_idepth[ci];
-        cImg = a.kf_image[ci];
-      }
+      merge_top3(s_wtop, WAVES, top);
+      c.request(a, lane == 0 ? top[0] : (lane == 1 ? top[1] : (lane == 2 ? top[2] : -1)));
     }
     if (tid < HALF) {
 #pragma unroll
@@ -1259,14 +1105,7 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
     __syncthreads();
     {
       const int slice = tid / CPP, k = tid - slice * CPP;
-      if (slice < RSLICE) {
-        const float* row = s_red + k * (HALF + 1);
-        const int j0 = slice * RRUN;
-        float sacc = 0.f;
-#pragma unroll
-        for (int j = 0; j < RRUN; j++) { const float v = row[j0 + j]; sacc += (j0 + j < HALF) ? v : 0.f; }
-        s_sum[slice][k] = sacc;
-      }
+      if (slice < RSLICE) s_sum[slice][k] = slice_sum<HALF + 1, RRUN>(s_red, k, slice);
     }
     __syncthreads();
     if (wave == 0) {
@@ -1276,35 +1115,24 @@ __global__ __launch_bounds__(BLOCK) void k_track_solo(const TrackJob* __restrict
 #pragma unroll
         for (int sl = 1; sl < RSLICE; sl++) sv += s_sum[sl][lane];
       }
-      if (cKey >= 0) {
-        const float inv = lsd_rcp_exact(cId);                // (fetch_point's arithmetic)
-        const float px = inv * (a.fxi * cX + a.cxi), py = inv * (a.fyi * cY + a.cyi);
-        const float cPz = inv * 1.0f;
-        PointWarp cq;
-        PointTexels ct;
+      if (c.key >= 0) {
+        float px, py, cPz;
+        ref_point_at(a, c.x, c.y, c.id, px, py, cPz);
+        PointWarp cq; PointTexels ct;
         eval_warp(a, px, py, cPz, cq);
-        taps(cq, cq.in_image, ct);
+        solo_taps(s_tex, a.w, cq, cq.in_image, ct);
         PointOut o;
-        eval_finish(a, cq, ct, cPz, cImg, cVar, o);
-        float* row = s_sub[lane];
-        tail_row(o, row);
+        eval_finish(a, cq, ct, cPz, c.img, c.var, o);
+        tail_row(o, s_sub[lane]);
       }
       __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
       __builtin_amdgcn_wave_barrier();
       __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
       const int M = (int)rl(sv, RS_M);
-      const int nsub = (__builtin_amdgcn_readlane(cKey, 0) >= 0) + (__builtin_amdgcn_readlane(cKey, 1) >= 0) + (__builtin_amdgcn_readlane(cKey, 2) >= 0);
-      int need = M & 3;
-      if (need > nsub) need = nsub;
-      // RS_WERR -> 0, RS_A0.. -> 1..21, RS_B0.. -> 22..27, RS_ERR -> 28
-      const int subIdx = (lane == RS_WERR) ? 0 : ((lane >= RS_A0 && lane < RS_B0) ? 1 + lane - RS_A0 : ((lane >= RS_B0 && lane < RS_ERR) ? 22 + lane - RS_B0 : (lane == RS_ERR ? 28 : -1)));
-      if (subIdx >= 0) {
-        if (need > 0) sv -= s_sub[0][subIdx];
-        if (need > 1) sv -= s_sub[1][subIdx];
-        if (need > 2) sv -= s_sub[2][subIdx];
-      }
+      const int nsub = (__builtin_amdgcn_readlane(c.key, 0) >= 0) + (__builtin_amdgcn_readlane(c.key, 1) >= 0) + (__builtin_amdgcn_readlane(c.key, 2) >= 0);
+      sv = tail_drop(sv, M, nsub, tail_word(lane), s_sub);
       if (lane < RS_NUM) sh.tot[lane] = sv;
-      lm_wave<false>(s_par, S, sv, sh.tot, lane, out, nullptr, 0, 0, doneWord);
+      lm_wave<false>(s_par, S, sv, sh, lane, out, nullptr, 0, 0, doneWord);
     }
     __syncthreads();
   }
@@ -1409,7 +1237,7 @@ static TrackScratch scratch_at(const lsdhip_tracker* t, float* base, size_t jobs
   sc.sums = base;
   sc.topkey = (int4*)(base + lay.topkey);
   sc.topval = base + lay.topval;
-  sc.recs = cmax > 1 ? base + lay.recs : nullptr;
+  sc.recs = cmax > 1 ? (TrialRecord*)(base + lay.recs) : nullptr;
   sc.max_rows = t->max_blocks;
   sc.cmax = cmax;
 #ifdef LSD_PHASE_TRACE

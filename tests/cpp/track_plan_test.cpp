@@ -122,6 +122,27 @@ int main() {
     CHECK(!P1.speculates && P1.lmGrid == 1 && P1.cmax == 1 && P1.grid == 75, "one trial per step: lmGrid %d, cmax %d, grid %d", P1.lmGrid, P1.cmax, P1.grid);
   }
 
+  // ---- the shapes of tests/test_dispatch_arms_gpu.py: the arms of k_track_step's finishing phase they are chosen for
+  {  // a 352x240 job: 88 tiles at level 1 (81..160: the column sums take ten rows per slot), and lsdhip_tracker_set_speculation(t, 5, 88) keeps them
+    LevelWork lv[L];
+    dense_levels(352, 240, BatchShape{0, 0}, lv);
+    SpecPolicy p = policy(5, false);
+    p.specCap = 88;
+    const SinglePlan P5 = lsd_single_plan(lv, p, 1, 4), P1 = lsd_single_plan(lv, policy(1, false), 1, 4);
+    CHECK(lv[1].tiling.nblocks == 88 && P5.tiling[1].nblocks == 88 && P1.tiling[1].nblocks == 88, "352x240 level 1: %d / %d / %d tiles", lv[1].tiling.nblocks, P5.tiling[1].nblocks, P1.tiling[1].nblocks);
+    CHECK(P5.trials[1] == 5 && P1.trials[1] == 1 && P5.grid == 440, "352x240 level 1: %d and %d trials, grid %d", P5.trials[1], P1.trials[1], P5.grid);
+  }
+  {  // 8 jobs at 352x288: 25 / 7 / 2 / 1 strips per job at levels 1..4 (6..13: the middle form of the tail rows), four trials below level 1
+    LevelWork lv[L];
+    dense_levels(352, 288, lsd_batch_shape(CAP, 8), lv);
+    auto level = [&](int, int l) { return BatchLevel{lv[l].work, lv[l].tiling.nblocks, lv[l].tiling.tilePx, l == 1, l >= 1 && l <= 4}; };
+    const BatchPolicy p = {LSD_SPEC_MAX, LSD_BATCH_SPEC_MAX, LSD_BATCH_SPEC_PIXELS, 2, true, true, LSD_SOLO_MIN_JOBS};
+    const BatchPlan P = lsd_batch_plan(8, p, level);
+    CHECK(lv[1].tiling.nblocks == 25 && lv[2].tiling.nblocks == 7 && lv[3].tiling.nblocks == 2 && lv[4].tiling.nblocks == 1 && lv[2].tiling.tilePx == 1024,
+          "352x288, 8 jobs: %d %d %d %d strips", lv[1].tiling.nblocks, lv[2].tiling.nblocks, lv[3].tiling.nblocks, lv[4].tiling.nblocks);
+    CHECK(P.trials[1] == 1 && P.trials[2] == 4 && !P.soloDue, "352x288, 8 jobs: trials %d %d", P.trials[1], P.trials[2]);
+  }
+
   // ---- launch budget
   {
     LaunchHistory h;
