@@ -362,14 +362,17 @@ def test_update_batch_1280x1024(oracle, hip):
 # ---------------------------------------------------------------------------------------------------------------
 # changeKeyframeBatch
 # ---------------------------------------------------------------------------------------------------------------
-def change_round(oracle, hip, ctx, twins, nk, what, masks, change_py, zoom_out=()):
-    """finalizeKeyFrame + createKeyFrame(frame nk of each sequence) of every twin.  Oracle per map: A = finalize, then propagate,
+def change_round(oracle, hip, ctx, twins, nk, what, masks, change_py, zoom_out=(), poses=None):
+    """finalizeKeyFrame + createKeyFrame(frame nk of each sequence; a list: frame nk[j] for map j) of every twin.  poses[j], where given,
+    is map j's Sim3 new keyframe -> old keyframe instead of the sequence's own.  Oracle per map: A = finalize, then propagate,
     regularize_occ, fillholes, regularize -> the pre-rescale map; B = finalize + create_keyframe from the same start -> its own factor and
     pose.  Afterwards the twins stand on the new keyframes with the map the device must hold (pre-rescale map times the device's factor)."""
     n = len(twins)
+    nks = [int(nk)] * n if np.isscalar(nk) else [int(v) for v in nk]
+    poses = list(poses) if poses is not None else [None] * n
     start = [t.dm.get() for t in twins]
     back = np.concatenate([oracle.se3_exp(np.array([0.0, 0.0, -3.5, 0.0, 0.0, 0.0])), [1.0]])   # camera 3.5 depth units behind: image shrinks ~2.7x
-    inputs = [frame_inputs(oracle, t, nk, masks[j], 977 * nk + j, pose=back if j in zoom_out else None) for j, t in enumerate(twins)]
+    inputs = [frame_inputs(oracle, t, nks[j], masks[j], 977 * nks[j] + j, pose=back if j in zoom_out else poses[j]) for j, t in enumerate(twins)]
 
     def one(j):
         t, r = twins[j], {}
@@ -383,9 +386,10 @@ def change_round(oracle, hip, ctx, twins, nk, what, masks, change_py, zoom_out=(
         dmR = oracle.DepthMap(t.w, t.h, t.K, params=t.op, threads=1)
         dmR.set_from_existing(kfA)
         r["react"] = dmR.get()
-        nkA, nkB = oracle_frame(oracle, t, nk, inputs[j], kfA), oracle_frame(oracle, t, nk, inputs[j], kfB)
+        nkA, nkB = oracle_frame(oracle, t, nks[j], inputs[j], kfA), oracle_frame(oracle, t, nks[j], inputs[j], kfB)
         dmA.stage("propagate", [nkA])
-        r["n_src"], r["n_dst"] = int((r["fin"]["isValid"] > 0).sum()), int((dmA.get()["isValid"] > 0).sum())
+        r["prop"] = dmA.get()
+        r["n_src"], r["n_dst"] = int((r["fin"]["isValid"] > 0).sum()), int((r["prop"]["isValid"] > 0).sum())
         r["pre"] = oracle_prerescale_after_propagate(dmA)
         r["s_o"] = dmB.create_keyframe(nkB)
         r["pose_o"] = nkB.pose()
@@ -398,7 +402,7 @@ def change_round(oracle, hip, ctx, twins, nk, what, masks, change_py, zoom_out=(
     scales = None
     if ctx is not None:
         olds = [t.dev["kf"] for t in twins]
-        nkgs = [device_frame(hip, ctx, t, nk, inputs[j], t.dev["kf"]) for j, t in enumerate(twins)]
+        nkgs = [device_frame(hip, ctx, t, nks[j], inputs[j], t.dev["kf"]) for j, t in enumerate(twins)]
         scales = hip.DepthMap.changeKeyframeBatch([t.dev["dm"] for t in twins], nkgs)
         assert_form(ctx, "change", {"n": n} if change_py is None else {"n": n, "py": change_py}, what)
     for j, t in enumerate(twins):
@@ -414,7 +418,7 @@ def change_round(oracle, hip, ctx, twins, nk, what, masks, change_py, zoom_out=(
                 assert_bit_equal(olds[j].idepthVar(lvl), r["old"].plane("idepthVar", lvl), tag + " old keyframe idepthVar L%d" % lvl)
             assert_mean_idepth(olds[j].stats(), r["old"].plane("idepth", 0), r["old"].plane("idepthVar", 0), tag + " old keyframe")
             want = assert_created_keyframe_exact(oracle, tag, pre, scales[j], r["s_o"], t.dev["dm"].currentDepthMap(), nkgs[j], r["pose_o"], t.K,
-                                                 t.frames[nk])
+                                                 t.frames[nks[j]])
             t.dev["kf"] = nkgs[j]
             t.dev.setdefault("old", []).append(olds[j])
         else:
@@ -425,8 +429,8 @@ def change_round(oracle, hip, ctx, twins, nk, what, masks, change_py, zoom_out=(
         nxt = pre.copy()
         for k in FLOAT_PLANES:
             nxt[k] = want[k]
-        t.base, t.react = nk, False
-        t.kf = oracle.Frame(nk, t.frames[nk], t.K)
+        t.base, t.react = nks[j], False
+        t.kf = oracle.Frame(nks[j], t.frames[nks[j]], t.K)
         t.dm = fresh_map(oracle, t, t.kf, nxt)
     return res
 
