@@ -226,6 +226,7 @@ class Frame {
   std::vector<float> permaRef_posData;       // 3 floats per point
   std::vector<float> permaRef_colorAndVarData;  // 2 floats per point
   int permaRefNumPts = 0;
+  int idxInKeyframes = -1;   // Frame.h:203: position in the keyframe graph = the frame's slot in a KeyFrameBank (set by KeyFrameBank::put)
 
  private:
   std::vector<float> plane(int what, int level, int channels) const {
@@ -439,6 +440,8 @@ class SE3Tracker {
   int numLaunches = 0;                         // evaluating launches of the last job (< numEvaluations: retries share launches)
   void setSpeculation(int trials, int finestLevelWorkgroups = 0) { check(lsdhip_tracker_set_speculation(h_, trials, finestLevelWorkgroups), "lsdhip_tracker_set_speculation"); }
   void setBatchCoarseMinJobs(int minJobs) { check(lsdhip_tracker_set_batch_coarse_min_jobs(h_, minJobs), "lsdhip_tracker_set_batch_coarse_min_jobs"); }
+  lsdhip_tracker* handle() const { return h_; }
+  const std::shared_ptr<Context>& context() const { return ctx_; }
 
  private:
   void pushSettings() {   // the public `settings` member is plain data in the reference: hand it over before every job
@@ -471,6 +474,106 @@ class SE3Tracker {
   std::exception_ptr hookError_;
   std::shared_ptr<Context> ctx_;
   lsdhip_tracker* h_ = nullptr;
+};
+
+// The permanent references of all keyframes on the device (lsdhip.h: lsdhip_kfbank_*): Frame::setPermaRef (DataStructures/Frame.cpp:149-174)
+// per keyframe, in one allocation made at construction, plus what TrackableKeyFrameSearch reads of a keyframe on the host (frame id,
+// meanIdepth, getScaledCamToWorld()).  The host-cloud members (Frame::setPermaRef, SE3Tracker::checkPermaRefOverlap /
+// trackFrameOnPermaref) stay as the yardstick.
+class KeyFrameBank {
+ public:
+  struct Info { int frameId, numPoints; float meanIdepth; Sim3 camToWorld; };
+  KeyFrameBank(std::shared_ptr<Context> ctx, int maxKeyframes) : ctx_(std::move(ctx)) {
+    check(lsdhip_kfbank_create(ctx_->handle(), maxKeyframes, &h_), "lsdhip_kfbank_create");
+  }
+  KeyFrameBank(const KeyFrameBank&) = delete;
+  KeyFrameBank& operator=(const KeyFrameBank&) = delete;
+  ~KeyFrameBank() { lsdhip_kfbank_destroy(h_); }
+  // Frame::setPermaRef on the device, behind the Frame::setDepth of finalizeKeyFrame; returns the slot = kf.idxInKeyframes
+  // (SlamSystem.cpp:408-412).  A keyframe the bank holds (a re-activated one that is finalised again) has its cloud replaced.
+  int put(Frame& kf) {
+    int slot = -1;
+    check(lsdhip_kfbank_put(h_, kf.handle(), &slot), "lsdhip_kfbank_put");
+    kf.idxInKeyframes = slot;
+    return slot;
+  }
+  int put(Frame& kf, const Sim3& camToWorld, float meanIdepth = -1.0f) {
+    const int slot = put(kf);
+    setMeta(slot, camToWorld, meanIdepth);
+    return slot;
+  }
+  // getScaledCamToWorld() / meanIdepth as the search reads them (TrackableKeyFrameSearch.cpp:76-91); meanIdepth < 0 keeps the recorded one
+  void setMeta(int slot, const Sim3& camToWorld, float meanIdepth = -1.0f) {
+    const double p[8] = {camToWorld.q[0], camToWorld.q[1], camToWorld.q[2], camToWorld.q[3], camToWorld.t[0], camToWorld.t[1], camToWorld.t[2], camToWorld.s};
+    check(lsdhip_kfbank_set_meta(h_, slot, p, meanIdepth), "lsdhip_kfbank_set_meta");
+  }
+  int size() const { return check(lsdhip_kfbank_size(h_), "lsdhip_kfbank_size"); }
+  Info info(int slot) const {
+    Info o;
+    double p[8];
+    check(lsdhip_kfbank_info(h_, slot, &o.frameId, &o.numPoints, &o.meanIdepth, p), "lsdhip_kfbank_info");
+    for (int i = 0; i < 4; i++) o.camToWorld.q[i] = p[i];
+    for (int i = 0; i < 3; i++) o.camToWorld.t[i] = p[4 + i];
+    o.camToWorld.s = p[7];
+    return o;
+  }
+  // the slot's cloud as Frame::permaRef_posData / permaRef_colorAndVarData hold it; returns the point count
+  int download(int slot, std::vector<float>* posData, std::vector<float>* colorAndVarData) const {
+    const int n = info(slot).numPoints;
+    std::vector<float> pos((size_t)n * 3 + 1), cv((size_t)n * 2 + 1);
+    check(lsdhip_kfbank_download(h_, slot, pos.data(), cv.data()), "lsdhip_kfbank_download");
+    if (posData) posData->assign(pos.begin(), pos.begin() + (size_t)n * 3);
+    if (colorAndVarData) colorAndVarData->assign(cv.begin(), cv.begin() + (size_t)n * 2);
+    return n;
+  }
+  lsdhip_kfbank* handle() const { return h_; }
+  const std::shared_ptr<Context>& context() const { return ctx_; }
+
+ private:
+  std::shared_ptr<Context> ctx_;
+  lsdhip_kfbank* h_ = nullptr;
+};
+
+// GlobalMapping/TrackableKeyFrameSearch.h:58-101, the re-position search: findRePositionCandidate (TrackableKeyFrameSearch.cpp:103-172)
+// over a KeyFrameBank in two launches and two host waits (lsdhip_tracker_find_reposition_candidate).  The graph's part — which
+// keyframes exist, where they are — is the bank's metadata; the frame's getScaledCamToWorld() and tracking parent are arguments.
+class TrackableKeyFrameSearch {
+ public:
+  // (bank, w, h, K) in the place of the reference's (graph, w, h, K) (TrackableKeyFrameSearch.cpp:32-46); the tracker made from
+  // (w, h, K) has to live on the bank's context
+  TrackableKeyFrameSearch(KeyFrameBank* bank, int w, int h, const Mat3f& K) : bank_(bank), tracker_(new SE3Tracker(w, h, K)) {
+    if (!bank || tracker_->context() != bank->context())
+      throw Error(LSDHIP_E_ARG, "TrackableKeyFrameSearch: (w, h, K) name another context than the bank's");
+  }
+  // returns the slot of the keyframe to re-activate, -1 if none (a new keyframe is to be made); `last` holds what was decided
+  int findRePositionCandidate(Frame* frame, const Sim3& frameCamToWorld, int trackingParentId, float maxScore = 1.0f) {
+    const double p[8] = {frameCamToWorld.q[0], frameCamToWorld.q[1], frameCamToWorld.q[2], frameCamToWorld.q[3],
+                         frameCamToWorld.t[0], frameCamToWorld.t[1], frameCamToWorld.t[2], frameCamToWorld.s};
+    check(lsdhip_tracker_set_relocalization_th(tracker_->handle(), relocalizationTH), "lsdhip_tracker_set_relocalization_th");
+    check(lsdhip_tracker_find_reposition_candidate(tracker_->handle(), bank_->handle(), frame->handle(), p, trackingParentId, maxScore, &last),
+          "lsdhip_tracker_find_reposition_candidate");
+    return last.slot;
+  }
+  // one record per banked keyframe of the last search (what printRelocalizationInfo prints, and the branch each keyframe took)
+  std::vector<lsdhip_reposition_record> records() const {
+    int n = 0;
+    check(lsdhip_tracker_reposition_records(tracker_->handle(), 0, nullptr, &n), "lsdhip_tracker_reposition_records");
+    std::vector<lsdhip_reposition_record> r((size_t)n);
+    if (n > 0) check(lsdhip_tracker_reposition_records(tracker_->handle(), n, r.data(), &n), "lsdhip_tracker_reposition_records");
+    return r;
+  }
+  // TrackableKeyFrameSearch.h:75-79 with the context's KFDistWeight / KFUsageWeight
+  float getRefFrameScore(float distanceSquared, float usage) const {
+    const lsdhip_params& p = bank_->context()->params;
+    return distanceSquared * p.KFDistWeight * p.KFDistWeight + (1 - usage) * (1 - usage) * p.KFUsageWeight * p.KFUsageWeight;
+  }
+  float relocalizationTH = 0.7f;   // util/settings.cpp:101
+  lsdhip_reposition_result last = {};
+  SE3Tracker& tracker() { return *tracker_; }
+
+ private:
+  KeyFrameBank* bank_;
+  std::unique_ptr<SE3Tracker> tracker_;
 };
 
 // Tracking/Sim3Tracker.h:71-187

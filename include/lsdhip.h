@@ -53,6 +53,8 @@ typedef struct lsdhip_params {
   int allowNegativeIdepths;      /* 1  */
   int useSubpixelStereo;         /* 1  */
   int useAffineLightningEstimation; /* 1 (ROS cfg default 0, cfg/LSDParams.cfg:27) */
+  float KFDistWeight;            /* 4  (C/util/settings.cpp:77): lsdhip_tracker_find_reposition_candidate */
+  float KFUsageWeight;           /* 3  (C/util/settings.cpp:78) */
 } lsdhip_params;
 void lsdhip_default_params(lsdhip_params* p);
 /* The execution defaults this header states in prose, as built into the library (no GPU needed): tests/test_abi_cpu.py compares the
@@ -308,6 +310,93 @@ int lsdhip_tracker_track_permaref_batch(lsdhip_tracker* t, int n, const float* p
                                         lsdhip_track_result* results);
 int lsdhip_tracker_check_overlap(lsdhip_tracker* t, const float* pos3_host, int n, const double referenceToFrame[7],
                                  float* usage_out);
+
+/* ---- keyframe bank: the permanent references of all keyframes on the device ------------------ */
+/* What Frame::setPermaRef (C/DataStructures/Frame.cpp:149-174) keeps per keyframe in host vectors — the level-QUICK_KF_CHECK_LVL
+ * (C/util/settings.h:104) point cloud as pos[3] + colorAndVar[2] — kept in device memory for every keyframe of the graph, so that
+ * TrackableKeyFrameSearch::findRePositionCandidate (C/GlobalMapping/TrackableKeyFrameSearch.cpp:103-172) tests all candidates in two
+ * launches without uploading a cloud.  One device allocation at creation: max_keyframes slots of (w4 - 2) * (h4 - 2) points (w4 x h4 =
+ * level 4, the most TrackingReference::makePointCloud can take, C/Tracking/TrackingReference.cpp:112-131); nothing is allocated afterwards.
+ * Beside each cloud the bank keeps, on the host, the frame id, the point count, the frame's meanIdepth and its world pose
+ * (Frame::getScaledCamToWorld as the search reads it, TrackableKeyFrameSearch.cpp:76-91).  Banks are destroyed before their context. */
+typedef struct lsdhip_kfbank lsdhip_kfbank;
+int lsdhip_kfbank_create(lsdhip_ctx* ctx, int max_keyframes, lsdhip_kfbank** out);
+void lsdhip_kfbank_destroy(lsdhip_kfbank* bank);   /* waits for the context's streams */
+/* Frame::setPermaRef (Frame.cpp:149-174) on the device: the keyframe's level-4 cloud, in the x-outer / y-inner order of
+ * TrackingReference::makePointCloud (TrackingReference.cpp:96-147), written into the keyframe's slot by ONE launch of one workgroup
+ * (per-column counts, a scan inside the workgroup, the write; no atomics, no scratch buffer), queued on the stream the DepthMap calls
+ * run on, i.e. behind the Frame::setDepth of finalizeKeyFrame (DepthMap.cpp:1363-1395), whose planes it reads.  The cloud equals what
+ * lsdhip_ref_pointcloud(keyframe, 4, ...) returns at the same point bit for bit.  A frame id the bank has not seen takes the next free
+ * slot — the slot index is the keyframe's idxInKeyframes (C/SlamSystem.cpp:408-412) — and a frame id it holds has its
+ * slot's cloud replaced (finishCurrentKeyframe runs again on a re-activated keyframe, C/SlamSystem.cpp:395-426); the world pose of a
+ * new slot is the identity until lsdhip_kfbank_set_meta.  The call WAITS for the 4-byte point count (and, on an asynchronous context,
+ * for the frame's deferred meanIdepth, as lsdhip_frame_stats does): the searches size their launches by it on the host.
+ * LSDHIP_E_CAPACITY (nothing changed) when all slots are taken, LSDHIP_E_STATE for a frame without depth. */
+int lsdhip_kfbank_put(lsdhip_kfbank* bank, lsdhip_frame* keyframe, int* slot_out);
+/* Host-side metadata only: the keyframe's getScaledCamToWorld() and meanIdepth as findEuclideanOverlapFrames reads them at search time
+ * (TrackableKeyFrameSearch.cpp:76-91); poses change after graph optimisation, so the caller refreshes them.  meanIdepth < 0 keeps the
+ * recorded one. */
+int lsdhip_kfbank_set_meta(lsdhip_kfbank* bank, int slot, const double camToWorld_sim3[8], float meanIdepth);
+int lsdhip_kfbank_size(lsdhip_kfbank* bank);        /* slots in use (graph->keyframesAll.size(), TrackableKeyFrameSearch.cpp:74) */
+/* any output may be NULL */
+int lsdhip_kfbank_info(lsdhip_kfbank* bank, int slot, int* frameId, int* numPoints, float* meanIdepth, double camToWorld_sim3[8]);
+/* test hook and the host yardstick's input: the slot's cloud (Frame::permaRef_posData / permaRef_colorAndVarData, Frame.cpp:160-173)
+ * copied to the host; returns the point count.  Waits for the context's streams. */
+int lsdhip_kfbank_download(lsdhip_kfbank* bank, int slot, float* pos3_host, float* colorAndVar2_host);
+/* SE3Tracker::checkPermaRefOverlap (SE3Tracker.cpp:121-157) for n (slots[j], refToFrame[7 j ..]) pairs in ONE launch (one workgroup per
+ * pair, clouds of any sizes) and one wait; pairs and poses go up in one copy.  Each pair is summed as lsdhip_tracker_check_overlap sums
+ * it: usage_out[j] equals that call on the downloaded cloud bit for bit.  A slot may appear several times.  LSDHIP_E_ARG for a slot that
+ * is not in use or holds no point. */
+int lsdhip_tracker_check_overlap_bank(lsdhip_tracker* t, lsdhip_kfbank* bank, int n, const int* slots, const double* refToFrame,
+                                      float* usage_out);
+/* SE3Tracker::trackFrameOnPermaref (SE3Tracker.cpp:162-272) for n banked references (slots[j] against frames[j] from refToFrame[7 j ..])
+ * in the launches of lsdhip_tracker_track_permaref_batch (n = 1: in those of lsdhip_tracker_track_permaref, the single job's chain), the
+ * jobs reading their points where they lie in the bank: only the job records are uploaded.  results[j] equals
+ * lsdhip_tracker_track_permaref_batch on the downloaded clouds bit for bit. */
+int lsdhip_tracker_track_permaref_bank(lsdhip_tracker* t, lsdhip_kfbank* bank, int n, const int* slots, lsdhip_frame** frames,
+                                       const double* refToFrame, lsdhip_track_result* results);
+/* What TrackableKeyFrameSearch::findRePositionCandidate decided (TrackableKeyFrameSearch.cpp:103-172). */
+typedef struct lsdhip_reposition_result {
+  int slot, frameId;                        /* bestFrame: its slot and frame id, -1 / -1 if none (:156-171) */
+  int numPotential, numChecked, numTracked; /* potentialReferenceFrames.size(), checkPermaRefOverlap calls (:126), checkedSecondary (:141) */
+  int overlapLaunches, trackingBatches;     /* launches of the overlap kernel / tracking batches this search ran (0 or 1 each) */
+  float bestScore, bestDist, bestUsage, bestPoseDiscrepancy;   /* :145-151 (bestScore = maxScore, the others 0, if none) */
+  double refToFrame[7], refToFrame_tracked[7];                 /* bestRefToFrame, bestRefToFrame_tracked (:148-149) */
+} lsdhip_reposition_result;
+/* One record per banked keyframe of the last search, in slot order (the order of graph->keyframesAll, :74). */
+#define LSDHIP_REPO_FAR 0        /* dNorm2 > distanceTH (TrackableKeyFrameSearch.cpp:83) */
+#define LSDHIP_REPO_ANGLE 1      /* dirDotProd < cosAngleTH (:87) */
+#define LSDHIP_REPO_PARENT 2     /* the frame's tracking parent (:118-119) */
+#define LSDHIP_REPO_INIT_PHASE 3 /* idxInKeyframes < INITIALIZATION_PHASE_COUNT (:121-122) */
+#define LSDHIP_REPO_EMPTY 4      /* the slot holds no point (its usage would be 0 / 0: never below maxScore) */
+#define LSDHIP_REPO_SCORE 5      /* overlap checked, score >= maxScore (:133) */
+#define LSDHIP_REPO_REJECTED 6   /* tracked, the acceptance test failed (:143) */
+#define LSDHIP_REPO_TAKEN 7      /* tracked and accepted at its turn (:145-151; a later candidate may replace it) */
+typedef struct lsdhip_reposition_record {
+  int slot, frameId, stage;
+  float dist2, angle;                        /* TrackableKFStruct::dist / angle (:92-93) */
+  float usage, score;                        /* tracker->pointUsage after checkPermaRefOverlap, getRefFrameScore (:131) */
+  float usageTracked;                        /* tracker->pointUsage after trackFrameOnPermaref (:138, :151) */
+  float newScore, goodVal, poseDiscrepancy;  /* :138-140 */
+  int trackingWasGood, diverged;
+  double refToFrame[7], refToFrame_tracked[7];
+} lsdhip_reposition_record;
+/* TrackableKeyFrameSearch::findRePositionCandidate(frame, maxScore) (TrackableKeyFrameSearch.cpp:103-172) over the bank, for a frame
+ * whose getScaledCamToWorld() is frameCamToWorld_sim3 and whose tracking parent has frame id trackingParentId:
+ *   1. findEuclideanOverlapFrames(frame, maxScore / KFDistWeight^2, 0.75) (:56-98) on the host, in double like the reference;
+ *   2. the skips (:118-122);
+ *   3. checkPermaRefOverlap of all survivors in one launch (lsdhip_tracker_check_overlap_bank), one wait;
+ *   4. trackFrameOnPermaref of those with getRefFrameScore(dist, usage) < maxScore (TrackableKeyFrameSearch.h:75-79) in one batch
+ *      (lsdhip_tracker_track_permaref_bank), one wait — the host stands between the two because the score decides which jobs exist;
+ *   5. the selection loop (:131-152) replayed on the host in candidate order, with its own arithmetic: the acceptance test reads
+ *      newScore < bestScore, what it stores is bestScore = score.
+ * KFDistWeight / KFUsageWeight are the context's params; relocalizationTH (C/util/settings.cpp:101) is the tracker's
+ * (lsdhip_tracker_set_relocalization_th).  fowX / fowY as the constructor forms them (:37-38) from the context's level-0 intrinsics. */
+int lsdhip_tracker_find_reposition_candidate(lsdhip_tracker* t, lsdhip_kfbank* bank, lsdhip_frame* frame, const double frameCamToWorld_sim3[8],
+                                             int trackingParentId, float maxScore, lsdhip_reposition_result* result);
+/* the records of the tracker's last search: *n = records it made (= bank size then); the first min(*n, max) are copied out */
+int lsdhip_tracker_reposition_records(lsdhip_tracker* t, int max, lsdhip_reposition_record* records, int* n);
+int lsdhip_tracker_set_relocalization_th(lsdhip_tracker* t, float relocalizationTH);   /* C/util/settings.cpp:101: 0.7 */
 
 /* ---- Sim3Tracker ----------------------------------------------------------------- */
 /* Sim3 as double[8] = (qw,qx,qy,qz,tx,ty,tz,scale): p' = scale * R(q) p + t.

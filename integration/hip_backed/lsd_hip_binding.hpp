@@ -53,6 +53,7 @@ inline lsdhip_ctx* context_for(int w, int h, const Eigen::Matrix3f& K) {
   p.minUseGrad = lsd_slam::minUseGrad; p.cameraPixelNoise2 = lsd_slam::cameraPixelNoise2; p.depthSmoothingFactor = lsd_slam::depthSmoothingFactor;
   p.allowNegativeIdepths = lsd_slam::allowNegativeIdepths; p.useSubpixelStereo = lsd_slam::useSubpixelStereo;
   p.useAffineLightningEstimation = lsd_slam::useAffineLightningEstimation;
+  p.KFDistWeight = lsd_slam::KFDistWeight; p.KFUsageWeight = lsd_slam::KFUsageWeight;
   const float K4[4] = {K(0, 0), K(1, 1), K(0, 2), K(1, 2)};
   lsdhip_ctx* c = nullptr;
   check(lsdhip_ctx_create(0, w, h, K4, &p, &c), "lsdhip_ctx_create");

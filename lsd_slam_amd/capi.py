@@ -28,7 +28,7 @@ class BuildDefaults(C.Structure):
 class Params(C.Structure):
     _fields_ = [("minUseGrad", C.c_float), ("cameraPixelNoise2", C.c_float), ("depthSmoothingFactor", C.c_float),
                 ("allowNegativeIdepths", C.c_int), ("useSubpixelStereo", C.c_int),
-                ("useAffineLightningEstimation", C.c_int)]
+                ("useAffineLightningEstimation", C.c_int), ("KFDistWeight", C.c_float), ("KFUsageWeight", C.c_float)]
 
 
 class TrackerSettings(C.Structure):
@@ -44,6 +44,25 @@ class TrackResult(C.Structure):
                 ("lastBadCount", C.c_float), ("lastMeanRes", C.c_float), ("lastResidual", C.c_float),
                 ("affineEstimation_a", C.c_float), ("affineEstimation_b", C.c_float), ("diverged", C.c_int),
                 ("trackingWasGood", C.c_int), ("numEvaluations", C.c_int), ("numWarpUpdates", C.c_int)]
+
+
+class RepositionResult(C.Structure):
+    """lsdhip_reposition_result: what findRePositionCandidate decided (C/GlobalMapping/TrackableKeyFrameSearch.cpp:103-172)"""
+    _fields_ = [("slot", C.c_int), ("frameId", C.c_int), ("numPotential", C.c_int), ("numChecked", C.c_int), ("numTracked", C.c_int),
+                ("overlapLaunches", C.c_int), ("trackingBatches", C.c_int), ("bestScore", C.c_float), ("bestDist", C.c_float),
+                ("bestUsage", C.c_float), ("bestPoseDiscrepancy", C.c_float), ("refToFrame", C.c_double * 7),
+                ("refToFrame_tracked", C.c_double * 7)]
+
+
+class RepositionRecord(C.Structure):
+    """lsdhip_reposition_record: one banked keyframe's way through the last search"""
+    _fields_ = [("slot", C.c_int), ("frameId", C.c_int), ("stage", C.c_int), ("dist2", C.c_float), ("angle", C.c_float),
+                ("usage", C.c_float), ("score", C.c_float), ("usageTracked", C.c_float), ("newScore", C.c_float), ("goodVal", C.c_float),
+                ("poseDiscrepancy", C.c_float), ("trackingWasGood", C.c_int), ("diverged", C.c_int), ("refToFrame", C.c_double * 7),
+                ("refToFrame_tracked", C.c_double * 7)]
+
+
+REPO_STAGES = ("far", "angle", "parent", "init_phase", "empty", "score", "rejected", "taken")   # LSDHIP_REPO_*
 
 
 class ResidualRecord(C.Structure):
@@ -147,6 +166,18 @@ def _signatures():
         "lsdhip_tracker_track_permaref": (i, [vp, vp, vp, i, vp, vp, C.POINTER(TrackResult)]),
         "lsdhip_tracker_track_permaref_batch": (i, [vp, i, vp, vp, vp, pvp, vp, C.POINTER(TrackResult)]),
         "lsdhip_tracker_check_overlap": (i, [vp, vp, i, vp, C.POINTER(C.c_float)]),
+        "lsdhip_kfbank_create": (i, [vp, i, pvp]),
+        "lsdhip_kfbank_destroy": (None, [vp]),
+        "lsdhip_kfbank_put": (i, [vp, vp, C.POINTER(C.c_int)]),
+        "lsdhip_kfbank_set_meta": (i, [vp, i, vp, f]),
+        "lsdhip_kfbank_size": (i, [vp]),
+        "lsdhip_kfbank_info": (i, [vp, i, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_float), vp]),
+        "lsdhip_kfbank_download": (i, [vp, i, vp, vp]),
+        "lsdhip_tracker_check_overlap_bank": (i, [vp, vp, i, vp, vp, vp]),
+        "lsdhip_tracker_track_permaref_bank": (i, [vp, vp, i, vp, pvp, vp, C.POINTER(TrackResult)]),
+        "lsdhip_tracker_find_reposition_candidate": (i, [vp, vp, vp, vp, i, f, C.POINTER(RepositionResult)]),
+        "lsdhip_tracker_reposition_records": (i, [vp, i, C.POINTER(RepositionRecord), C.POINTER(C.c_int)]),
+        "lsdhip_tracker_set_relocalization_th": (i, [vp, f]),
         "lsdhip_sim3tracker_create": (i, [vp, pvp]),
         "lsdhip_sim3tracker_destroy": (None, [vp]),
         "lsdhip_sim3tracker_set_max_its": (i, [vp, vp]),

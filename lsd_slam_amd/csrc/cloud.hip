@@ -11,6 +11,7 @@
 //   k_cloud_write  back-projection of the kept pixels to their slots: row-major pixel order within a keyframe, keyframes in call order
 // No atomics, no arrival order anywhere: the output is identical from run to run.
 #include "lsdhip_internal.hpp"
+#include "block_scan.hpp"   // lsd_block_excl_scan: the ordered compaction's scan inside a workgroup
 #include "../../include/lsd_slam_hip_cloud_constants.hpp"   // cloudConstants: the per-keyframe constants, the one expression set both paths use
 
 #define LSD_CLOUD_CHUNK 1024
@@ -50,28 +51,6 @@ struct lsdhip_cloud {
 };
 
 // ---- device ---------------------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ int cloud_wave_incl_scan(int v, int lane) {
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-// exclusive scan of one value per lane over the 256-lane workgroup (pixel order = lane order); *total = the workgroup's sum
-__device__ __forceinline__ int cloud_block_excl_scan(int v, int* total, int* lds) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int inc = cloud_wave_incl_scan(v, lane);
-  if (lane == 63) lds[wv] = inc;
-  __syncthreads();
-  int before = 0, tot = 0;
-#pragma unroll
-  for (int k = 0; k < 4; k++) { const int s = lds[k]; if (k < wv) before += s; tot += s; }
-  __syncthreads();
-  *total = tot;
-  return before + inc - v;
-}
-
 // flushPC's filters (V/KeyFrameDisplay.cpp:286-318) for the 4 pixels of a lane
 __global__ __launch_bounds__(256) void k_cloud_count(const CloudJob* __restrict__ jobs, int w, int h, float scaledTH, float absTH, int minNearSupport) {
   __shared__ int lds[4];
@@ -132,7 +111,7 @@ __global__ __launch_bounds__(256) void k_cloud_count(const CloudJob* __restrict_
   }
   J.mask[blockIdx.x * 256 + threadIdx.x] = (uint8_t)keep;
   int total;
-  (void)cloud_block_excl_scan(__popc(keep), &total, lds);
+  (void)lsd_block_excl_scan(__popc(keep), &total, lds);
   if (threadIdx.x == 0) J.chunkCount[blockIdx.x] = total;
 }
 
@@ -146,7 +125,7 @@ __global__ __launch_bounds__(256) void k_cloud_scan(const CloudJob* __restrict__
     const int c = c0 + (int)threadIdx.x;
     const int v = c < nchunks ? J.chunkCount[c] : 0;
     int tot;
-    const int ex = cloud_block_excl_scan(v, &tot, lds);
+    const int ex = lsd_block_excl_scan(v, &tot, lds);
     if (c < nchunks) J.chunkOff[c] = first + (long long)(carry + ex);
     carry += tot;
   }
@@ -173,7 +152,7 @@ __global__ __launch_bounds__(256) void k_cloud_write(const CloudJob* __restrict_
   if (chunkFirst >= J.capacity) return;
   const unsigned keep = J.mask[blockIdx.x * 256 + threadIdx.x];
   int total;
-  const int ex = cloud_block_excl_scan(__popc(keep), &total, lds);
+  const int ex = lsd_block_excl_scan(__popc(keep), &total, lds);
   if (!keep) return;
   const int i0 = blockIdx.x * LSD_CLOUD_CHUNK + threadIdx.x * 4;
   const int y = i0 / w, x0 = i0 - y * w;

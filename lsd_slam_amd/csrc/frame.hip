@@ -553,6 +553,8 @@ extern "C" void lsdhip_default_params(lsdhip_params* p) {
   p->allowNegativeIdepths = 1;
   p->useSubpixelStereo = 1;
   p->useAffineLightningEstimation = 1;
+  p->KFDistWeight = 4;
+  p->KFUsageWeight = 3;
 }
 
 extern "C" int lsdhip_ctx_create(int device, int w, int h, const float K[4], const lsdhip_params* params, lsdhip_ctx** out) {

@@ -411,6 +411,25 @@ struct lsdhip_tracker {
   TrackSummary* h_bsummary = nullptr; // pinned, device-mapped
   float* d_pts = nullptr;         // permaref point upload
   int pts_capacity = 0;
+  float relocalizationTH = 0.7f;  // C/util/settings.cpp:101 (lsdhip_tracker_set_relocalization_th)
+  float* h_overlapSums = nullptr;   // pinned, device-mapped: the sums of lsdhip_tracker_check_overlap_bank's pairs
+  int overlapSumsCapacity = 0;
+  std::vector<lsdhip_reposition_record> repoRecords;   // per-keyframe records of the last lsdhip_tracker_find_reposition_candidate
+};
+
+// The permanent references of all keyframes (Frame::setPermaRef, C/DataStructures/Frame.cpp:149-174) in one device allocation
+// (kfbank.hip): slot s holds `capacity` points, pos[3] then colorAndVar[2], the layout fill_permaref_job reads; the metadata the
+// search reads on the host (TrackableKeyFrameSearch.cpp:76-91) beside it.
+struct lsdhip_kfbank {
+  lsdhip_ctx* ctx = nullptr;
+  int maxSlots = 0, capacity = 0;   // points per slot: (w4 - 2) * (h4 - 2)
+  size_t slotFloats = 0;            // floats from one slot to the next (a multiple of 64: slots start on 256-byte boundaries)
+  float* d_base = nullptr;
+  int* d_count = nullptr;           // one int per slot, behind the clouds in the same allocation
+  struct Slot { int frameId; int numPoints; float meanIdepth; double camToWorld[8]; };
+  std::vector<Slot> slots;          // reserved to maxSlots at creation
+  float* pos(int slot) const { return d_base + (size_t)slot * slotFloats; }
+  float* colvar(int slot) const { return pos(slot) + (size_t)capacity * 3; }
 };
 
 // SoA hypothesis planes in HBM (29 B/px + one spare validity plane for snapshot semantics)

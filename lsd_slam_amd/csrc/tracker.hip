@@ -26,6 +26,7 @@
 #include <atomic>
 #include <chrono>
 #include "track_device.hpp"
+#include "reposition_plan.hpp"   // the host stages of findRePositionCandidate (plain C++: tests/cpp/reposition_plan_test.cpp)
 
 // developer build LSD_PHASE_TRACE: the functions that leave timestamps take the traced workgroup's flag and record (TRACE_PARAMS / _ARGS)
 #ifdef LSD_PHASE_TRACE
@@ -1167,18 +1168,20 @@ int lsd_flush_merges(lsdhip_ctx* c) {
   return LSDHIP_OK;
 }
 
-// checkPermaRefOverlap (SE3Tracker.cpp:121-157): usage only, explicit point list
-__global__ __launch_bounds__(256) void k_overlap(const float* __restrict__ pos, int n, EvalCtx a, float* __restrict__ out) {
-  __shared__ float s_w[4];
+// checkPermaRefOverlap (SE3Tracker.cpp:121-157): usage only, explicit point list.  One 256-lane workgroup sums one cloud: lane-strided
+// accumulation, wave sums, the four wave totals in order; lane 0 returns the sum.  k_overlap and k_overlap_bank share it, so a candidate
+// is summed in the same order whichever launch it rides in.
+__device__ __forceinline__ float overlap_block_sum(const float* __restrict__ pos, int n, const float* R, const float* t, float fx, float fy, float cx,
+                                                   float cy, int w, int h, float* s_w) {
   float acc = 0.f;
   for (int i = threadIdx.x; i < n; i += 256) {
     float px = pos[3 * i], py = pos[3 * i + 1], pz = pos[3 * i + 2];
-    float Wx = ((a.R[0] * px + a.R[1] * py) + a.R[2] * pz) + a.t[0];
-    float Wy = ((a.R[3] * px + a.R[4] * py) + a.R[5] * pz) + a.t[1];
-    float Wz = ((a.R[6] * px + a.R[7] * py) + a.R[8] * pz) + a.t[2];
-    float u_new = (Wx / Wz) * a.fx + a.cx;
-    float v_new = (Wy / Wz) * a.fy + a.cy;
-    if (u_new > 0 && v_new > 0 && u_new < a.w - 1 && v_new < a.h - 1) {
+    float Wx = ((R[0] * px + R[1] * py) + R[2] * pz) + t[0];
+    float Wy = ((R[3] * px + R[4] * py) + R[5] * pz) + t[1];
+    float Wz = ((R[6] * px + R[7] * py) + R[8] * pz) + t[2];
+    float u_new = (Wx / Wz) * fx + cx;
+    float v_new = (Wy / Wz) * fy + cy;
+    if (u_new > 0 && v_new > 0 && u_new < w - 1 && v_new < h - 1) {
       float depthChange = pz / Wz;
       acc += depthChange < 1 ? depthChange : 1;
     }
@@ -1186,7 +1189,26 @@ __global__ __launch_bounds__(256) void k_overlap(const float* __restrict__ pos, 
   float s = wave_sum_to_lane63(acc);
   if ((threadIdx.x & 63) == 63) s_w[threadIdx.x >> 6] = s;
   __syncthreads();
-  if (threadIdx.x == 0) out[0] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+  return ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+__global__ __launch_bounds__(256) void k_overlap(const float* __restrict__ pos, int n, EvalCtx a, float* __restrict__ out) {
+  __shared__ float s_w[4];
+  const float sum = overlap_block_sum(pos, n, a.R, a.t, a.fx, a.fy, a.cx, a.cy, a.w, a.h, s_w);
+  if (threadIdx.x == 0) out[0] = sum;
+}
+// checkPermaRefOverlap for the (slot, pose) pairs of a keyframe bank (lsdhip_tracker_check_overlap_bank): workgroup = pair
+struct OverlapJob { LSD_G const float* pos; int n; float R[9], t[3]; };
+__global__ __launch_bounds__(256) void k_overlap_bank(const OverlapJob* __restrict__ jobs, float fx, float fy, float cx, float cy, int w, int h,
+                                                      float* __restrict__ out) {
+  __shared__ float s_w[4];
+  const OverlapJob& J = jobs[blockIdx.x];
+  float R[9], t[3];
+#pragma unroll
+  for (int i = 0; i < 9; i++) R[i] = J.R[i];
+#pragma unroll
+  for (int i = 0; i < 3; i++) t[i] = J.t[i];
+  const float sum = overlap_block_sum((const float*)J.pos, J.n, R, t, fx, fy, cx, cy, w, h, s_w);
+  if (threadIdx.x == 0) out[blockIdx.x] = sum;
 }
 
 // Test hook (lsdhip_devtest_se3f_lm_step): the proposal of lm_wave on given normal equations, one 64-lane workgroup per case.  A / b
@@ -1330,6 +1352,7 @@ extern "C" void lsdhip_tracker_destroy(lsdhip_tracker* t) {
 #endif
   (void)hipSetDevice(t->ctx->device);
   (void)hipStreamSynchronize(t->ctx->stream);
+  if (t->h_overlapSums) (void)hipHostFree(t->h_overlapSums);
 #ifdef LSD_ORDER_CHECK
   {
     std::vector<unsigned long long> h(8 + 2 * 8192, 0);
@@ -2534,23 +2557,17 @@ static int upload_points(lsdhip_tracker* t, const float* pos, const float* colva
   return LSDHIP_OK;
 }
 
-extern "C" int lsdhip_tracker_track_permaref(lsdhip_tracker* t, const float* pos, const float* colvar, int n, lsdhip_frame* frame,
-                                             const double refToFrame[7], lsdhip_track_result* out) {
-  if (!t || !pos || !colvar || n <= 0 || !frame || !refToFrame || !out) return LSDHIP_E_ARG;
-  lsdhip_ctx* c = t->ctx;
-  LSD_CTX_LOCK(c);
-  LsdTrackJobScope tjob_(c, true);
-  if (tjob_.rc) return tjob_.rc;
-  HIPCHK(hipSetDevice(c->device));
-  int rc = upload_points(t, pos, colvar, n);
-  if (rc) return rc;
+// trackFrameOnPermaref as a single job (the launch-per-step chain with its speculation and the polled summary) on a cloud that is
+// already on the device: the upload of lsdhip_tracker_track_permaref, or a slot of a keyframe bank
+static int permaref_single_run(lsdhip_tracker* t, const float* d_pos, const float* d_colvar, int n, lsdhip_frame* frame, const double refToFrame[7],
+                               lsdhip_track_result* out) {
   lsdm::SE3fH referenceToFrame = lsdm::se3f_from_d(lsdm::se3d_from7(refToFrame));
   t->affineEstimation_a = 1; t->affineEstimation_b = 0;
   t->diverged = false; t->trackingWasGood = true;
   t->numEvaluations = 0; t->numWarpUpdates = 0;
   const int L = LSD_QUICK_KF_CHECK_LVL;
   TrackJob job;
-  rc = fill_permaref_job(t, job, BatchShape{}, t->d_pts, t->d_pts + (size_t)t->pts_capacity * 3, n, frame, referenceToFrame);
+  int rc = fill_permaref_job(t, job, BatchShape{}, d_pos, d_colvar, n, frame, referenceToFrame);
   if (rc) return rc;
   if (t->hostLM) {
     float lastErr = 0;
@@ -2561,6 +2578,19 @@ extern "C" int lsdhip_tracker_track_permaref(lsdhip_tracker* t, const float* pos
   }
   if (rc != LSDHIP_OK && rc != LSDHIP_DIVERGED) return rc;
   return finish_permaref(t, rc == LSDHIP_DIVERGED, referenceToFrame, out);
+}
+
+extern "C" int lsdhip_tracker_track_permaref(lsdhip_tracker* t, const float* pos, const float* colvar, int n, lsdhip_frame* frame,
+                                             const double refToFrame[7], lsdhip_track_result* out) {
+  if (!t || !pos || !colvar || n <= 0 || !frame || !refToFrame || !out) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = t->ctx;
+  LSD_CTX_LOCK(c);
+  LsdTrackJobScope tjob_(c, true);
+  if (tjob_.rc) return tjob_.rc;
+  HIPCHK(hipSetDevice(c->device));
+  int rc = upload_points(t, pos, colvar, n);
+  if (rc) return rc;
+  return permaref_single_run(t, t->d_pts, t->d_pts + (size_t)t->pts_capacity * 3, n, frame, refToFrame, out);
 }
 
 // SE3Tracker::trackFrameOnPermaref (SE3Tracker.cpp:162-272) for n permanent references against frames[j] in the same
@@ -2620,6 +2650,157 @@ extern "C" int lsdhip_tracker_check_overlap(lsdhip_tracker* t, const float* pos,
   HIPCHK(hipStreamSynchronize(c->stream));
   t->pointUsage = t->h_summary->sums[0] / (float)n;
   *usage_out = t->pointUsage;
+  return LSDHIP_OK;
+}
+
+// ---- the keyframe bank (kfbank.hip): checkPermaRefOverlap / trackFrameOnPermaref over clouds that stay on the device ------------------
+static int bank_slots_ok(const char* entry, const lsdhip_tracker* t, const lsdhip_kfbank* b, int n, const int* slots) {
+  if (b->ctx != t->ctx) { lsd_set_error("%s: the bank belongs to another context", entry); return LSDHIP_E_ARG; }
+  for (int j = 0; j < n; j++) {
+    if (slots[j] < 0 || slots[j] >= (int)b->slots.size()) { lsd_set_error("%s: pair %d: slot %d is not in use", entry, j, slots[j]); return LSDHIP_E_ARG; }
+    if (b->slots[(size_t)slots[j]].numPoints <= 0) { lsd_set_error("%s: pair %d: slot %d holds no point", entry, j, slots[j]); return LSDHIP_E_ARG; }
+  }
+  return LSDHIP_OK;
+}
+// one launch and one wait for n (slot, pose) pairs; the pairs' records go up in one copy (the context's argument ring).  The caller holds the context lock and a LsdTrackJobScope.
+static int overlap_bank_run(lsdhip_tracker* t, lsdhip_kfbank* b, int n, const int* slots, const double* refToFrame, float* usage_out) {
+  lsdhip_ctx* c = t->ctx;
+  const int L = LSD_QUICK_KF_CHECK_LVL;
+  // the sums land in pinned host memory the kernel writes through its device alias (as k_overlap writes the tracker's summary): no copy
+  if (n > t->overlapSumsCapacity) {
+    HIPCHK(hipStreamSynchronize(c->stream));
+    if (t->h_overlapSums) { (void)hipHostFree(t->h_overlapSums); t->h_overlapSums = nullptr; t->overlapSumsCapacity = 0; }
+    const int cap = n < 256 ? 256 : n * 2;
+    HIPCHK(hipHostMalloc((void**)&t->h_overlapSums, sizeof(float) * (size_t)cap, hipHostMallocMapped));
+    t->overlapSumsCapacity = cap;
+  }
+  float* d_out = nullptr;
+  HIPCHK(hipHostGetDevicePointer((void**)&d_out, t->h_overlapSums, 0));
+  void* host = nullptr;
+  void* dev = nullptr;
+  if (int rc = lsd_args_begin(c, sizeof(OverlapJob) * (size_t)n, &host, &dev)) return rc;
+  OverlapJob* jobs = (OverlapJob*)host;
+  for (int j = 0; j < n; j++) {
+    const lsdm::SE3fH T = lsdm::se3f_from_d(lsdm::se3d_from7(refToFrame + 7 * (size_t)j));
+    OverlapJob& J = jobs[j];
+    J.pos = lsd_g((const float*)b->pos(slots[j]));
+    J.n = b->slots[(size_t)slots[j]].numPoints;
+    lsdm::quatf_to_rot(T.q, J.R);
+    J.t[0] = T.t[0]; J.t[1] = T.t[1]; J.t[2] = T.t[2];
+  }
+  if (int rc = lsd_args_commit(c, c->stream)) return rc;
+  const LevelIntr& in = c->intr[L];
+  hipLaunchKernelGGL(k_overlap_bank, dim3(n), dim3(256), 0, c->stream, (const OverlapJob*)dev, in.fx, in.fy, in.cx, in.cy, c->wl[L], c->hl[L], d_out);
+  HIPCHK(hipGetLastError());
+  if (int rc = lsd_args_release(c, dev, c->stream)) return rc;
+  HIPCHK(hipStreamSynchronize(c->stream));
+  for (int j = 0; j < n; j++) usage_out[j] = t->h_overlapSums[j] / (float)b->slots[(size_t)slots[j]].numPoints;
+  t->pointUsage = usage_out[n - 1];
+  return LSDHIP_OK;
+}
+// lsdhip_tracker_track_permaref_batch with the jobs' point pointers aimed into the bank: nothing but the job records is uploaded
+static int permaref_bank_run(lsdhip_tracker* t, lsdhip_kfbank* b, int n, const int* slots, lsdhip_frame** frames, const double* refToFrame,
+                             lsdhip_track_result* results) {
+  // one candidate has the chip to itself: the single job's chain (speculation, polled summary) is the shorter way to the same result
+  if (n == 1) return permaref_single_run(t, b->pos(slots[0]), b->colvar(slots[0]), b->slots[(size_t)slots[0]].numPoints, frames[0], refToFrame, &results[0]);
+  const BatchOpened o = batch_open(t, "lsdhip_tracker_track_permaref_bank", n, nullptr, frames, false, [&](int j, TrackJob& job, BatchShape shape) {
+    return fill_permaref_job(t, job, shape, b->pos(slots[j]), b->colvar(slots[j]), b->slots[(size_t)slots[j]].numPoints, frames[j],
+                             lsdm::se3f_from_d(lsdm::se3d_from7(refToFrame + 7 * (size_t)j)));
+  });
+  if (o.rc) return o.rc;
+  if (int rc = batch_run(t, n, false, true)) return rc;
+  int rcAll = LSDHIP_OK;
+  for (int j = 0; j < n; j++) {
+    const TrackSummary* S = &t->h_bsummary[j];
+    take_summary(t, S);
+    if (finish_permaref(t, S->diverged != 0, pose_of(S), &results[j]) == LSDHIP_DIVERGED) rcAll = LSDHIP_DIVERGED;
+  }
+  return rcAll;
+}
+
+extern "C" int lsdhip_tracker_check_overlap_bank(lsdhip_tracker* t, lsdhip_kfbank* b, int n, const int* slots, const double* refToFrame, float* usage_out) {
+  if (!t || !b || n <= 0 || !slots || !refToFrame || !usage_out) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = t->ctx;
+  LSD_CTX_LOCK(c);
+  if (int rc = bank_slots_ok("lsdhip_tracker_check_overlap_bank", t, b, n, slots)) return rc;
+  LsdTrackJobScope tjob_(c, true);
+  if (tjob_.rc) return tjob_.rc;
+  HIPCHK(hipSetDevice(c->device));
+  return overlap_bank_run(t, b, n, slots, refToFrame, usage_out);
+}
+
+extern "C" int lsdhip_tracker_track_permaref_bank(lsdhip_tracker* t, lsdhip_kfbank* b, int n, const int* slots, lsdhip_frame** frames,
+                                                  const double* refToFrame, lsdhip_track_result* results) {
+  if (!t || !b || n <= 0 || !slots || !frames || !refToFrame || !results) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = t->ctx;
+  LSD_CTX_LOCK(c);
+  if (int rc = bank_slots_ok("lsdhip_tracker_track_permaref_bank", t, b, n, slots)) return rc;
+  for (int j = 0; j < n; j++) if (!frames[j] || frames[j]->ctx != c) return LSDHIP_E_ARG;
+  LsdTrackJobScope tjob_(c, true);
+  if (tjob_.rc) return tjob_.rc;
+  HIPCHK(hipSetDevice(c->device));
+  return permaref_bank_run(t, b, n, slots, frames, refToFrame, results);
+}
+
+// TrackableKeyFrameSearch::findRePositionCandidate (TrackableKeyFrameSearch.cpp:103-172): the host stages are reposition_plan.hpp's, the
+// two launches stand between them.  Two host waits per search: the score of stage 3's usages decides which tracking jobs exist.
+extern "C" int lsdhip_tracker_find_reposition_candidate(lsdhip_tracker* t, lsdhip_kfbank* b, lsdhip_frame* frame, const double frameCamToWorld[8],
+                                                        int trackingParentId, float maxScore, lsdhip_reposition_result* res) {
+  if (!t || !b || !frame || !frameCamToWorld || !res || b->ctx != t->ctx || frame->ctx != t->ctx) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = t->ctx;
+  LSD_CTX_LOCK(c);
+  LsdTrackJobScope tjob_(c, true);
+  if (tjob_.rc) return tjob_.rc;
+  HIPCHK(hipSetDevice(c->device));
+  std::vector<lsdrp::Keyframe> kfs(b->slots.size());
+  for (size_t i = 0; i < kfs.size(); i++) {
+    const lsdhip_kfbank::Slot& s = b->slots[i];
+    kfs[i] = lsdrp::Keyframe{s.frameId, s.numPoints, s.meanIdepth, lsdrp::sim3_from8(s.camToWorld)};
+  }
+  const lsdrp::Weights W = {c->params.KFDistWeight, c->params.KFUsageWeight, t->relocalizationTH};
+  float fowX, fowY;
+  lsdrp::field_of_view(c->w, c->h, c->intr[0].fx, c->intr[0].fy, &fowX, &fowY);
+  std::vector<lsdhip_reposition_record>& recs = t->repoRecords;
+  memset(res, 0, sizeof(*res));
+  res->numPotential = lsdrp::prefilter(kfs, lsdrp::sim3_from8(frameCamToWorld), trackingParentId, maxScore, fowX, fowY, W, &recs);
+  // stage 3: one overlap launch for all survivors
+  std::vector<int> slots, idx;
+  std::vector<double> poses;
+  for (size_t i = 0; i < recs.size(); i++)
+    if (recs[i].stage == LSDHIP_REPO_SCORE) { idx.push_back((int)i); slots.push_back(recs[i].slot); poses.insert(poses.end(), recs[i].refToFrame, recs[i].refToFrame + 7); }
+  res->numChecked = (int)idx.size();
+  std::vector<int> tracked;
+  if (!idx.empty()) {
+    std::vector<float> usage(idx.size());
+    if (int rc = overlap_bank_run(t, b, (int)idx.size(), slots.data(), poses.data(), usage.data())) return rc;
+    res->overlapLaunches = 1;
+    for (size_t k = 0; k < idx.size(); k++)
+      if (lsdrp::wants_tracking(recs[(size_t)idx[k]], usage[k], maxScore, W)) tracked.push_back(idx[k]);
+  }
+  // stage 4: one tracking batch for those below maxScore
+  std::vector<lsdhip_track_result> out(tracked.size());
+  if (!tracked.empty()) {
+    slots.clear(); poses.clear();
+    std::vector<lsdhip_frame*> frames(tracked.size(), frame);
+    for (int i : tracked) { slots.push_back(recs[(size_t)i].slot); poses.insert(poses.end(), recs[(size_t)i].refToFrame, recs[(size_t)i].refToFrame + 7); }
+    const int rc = permaref_bank_run(t, b, (int)tracked.size(), slots.data(), frames.data(), poses.data(), out.data());
+    if (rc != LSDHIP_OK && rc != LSDHIP_DIVERGED) return rc;
+    res->trackingBatches = 1;
+  }
+  lsdrp::select(recs, kfs, tracked, out.data(), maxScore, W, res);
+  return LSDHIP_OK;
+}
+extern "C" int lsdhip_tracker_reposition_records(lsdhip_tracker* t, int max, lsdhip_reposition_record* records, int* n) {
+  if (!t || max < 0 || !n || (max > 0 && !records)) return LSDHIP_E_ARG;
+  LSD_CTX_LOCK(t->ctx);
+  *n = (int)t->repoRecords.size();
+  for (int i = 0; i < *n && i < max; i++) records[i] = t->repoRecords[(size_t)i];
+  return LSDHIP_OK;
+}
+extern "C" int lsdhip_tracker_set_relocalization_th(lsdhip_tracker* t, float th) {
+  if (!t) return LSDHIP_E_ARG;
+  LSD_CTX_LOCK(t->ctx);
+  t->relocalizationTH = th;
   return LSDHIP_OK;
 }
 

@@ -112,6 +112,7 @@ class Context:
 
 class Frame:
     """Device-resident frame: pyramids are built on the GPU at construction."""
+    idxInKeyframes = -1     # Frame::idxInKeyframes (C/DataStructures/Frame.h:203): the frame's slot once KeyFrameBank.put has taken it
 
     def __init__(self, ctx, id_, image=None, device_ptr=None):
         self.ctx = ctx
@@ -549,6 +550,119 @@ class SE3Tracker:
         check(self.L.lsdhip_tracker_check_overlap(self.h_, pos.ctypes.data, len(pos), T.ctypes.data, C.byref(u)), False)
         self.pointUsage = u.value
         return u.value
+
+    def checkPermaRefOverlapBank(self, bank, slots, referenceToFrames):
+        """checkPermaRefOverlap for (slot, pose) pairs of a KeyFrameBank in one launch -> usages float32 [n]"""
+        n = len(slots)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        T = np.ascontiguousarray(referenceToFrames, np.float64).reshape(n, 7)
+        u = np.zeros(n, np.float32)
+        check(self.L.lsdhip_tracker_check_overlap_bank(self.h_, bank.h_, n, sl.ctypes.data, T.ctypes.data, u.ctypes.data), False)
+        return u
+
+    def trackFrameOnPermarefBank(self, bank, slots, frames, referenceToFrames):
+        """trackFrameOnPermarefBatch with the clouds read where they lie in the bank; returns (poses, records)"""
+        n = len(slots)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        frs = (C.c_void_p * n)(*[f.h_ for f in frames])
+        T = np.ascontiguousarray(referenceToFrames, np.float64).reshape(n, 7)
+        res = (capi.TrackResult * n)()
+        check(self.L.lsdhip_tracker_track_permaref_bank(self.h_, bank.h_, n, sl.ctypes.data, frs, T.ctypes.data, res))
+        return np.array([list(r.frameToReference) for r in res]), list(res)
+
+
+class KeyFrameBank:
+    """The permanent references of all keyframes on the device (lsdhip_kfbank_*): Frame::setPermaRef (C/DataStructures/Frame.cpp:149-174)
+    per keyframe plus the metadata TrackableKeyFrameSearch reads (frame id, meanIdepth, world pose as Sim3 (qw,qx,qy,qz,tx,ty,tz,scale))."""
+
+    def __init__(self, ctx, max_keyframes):
+        self.ctx = ctx
+        self.L = ctx.L
+        h_ = C.c_void_p()
+        check(self.L.lsdhip_kfbank_create(ctx.h_, int(max_keyframes), C.byref(h_)), False)
+        self.h_ = h_
+
+    def __del__(self):
+        self.close()
+
+    def close(self):
+        if getattr(self, "h_", None) and getattr(self.ctx, "h_", None):
+            self.L.lsdhip_kfbank_destroy(self.h_)
+        self.h_ = None
+
+    def put(self, frame, camToWorld=None, meanIdepth=-1.0):
+        """Frame::setPermaRef on the device; returns the slot (= frame.idxInKeyframes).  camToWorld / meanIdepth: setMeta right away."""
+        slot = C.c_int(-1)
+        check(self.L.lsdhip_kfbank_put(self.h_, frame.h_, C.byref(slot)), False)
+        frame.idxInKeyframes = slot.value
+        if camToWorld is not None:
+            self.setMeta(slot.value, camToWorld, meanIdepth)
+        return slot.value
+
+    def setMeta(self, slot, camToWorld, meanIdepth=-1.0):
+        p = np.ascontiguousarray(camToWorld, dtype=np.float64)
+        assert p.shape == (8,)
+        check(self.L.lsdhip_kfbank_set_meta(self.h_, int(slot), p.ctypes.data, float(meanIdepth)), False)
+
+    def size(self):
+        return check(self.L.lsdhip_kfbank_size(self.h_))
+
+    def info(self, slot):
+        fid, n, mi, pose = C.c_int(), C.c_int(), C.c_float(), np.zeros(8, np.float64)
+        check(self.L.lsdhip_kfbank_info(self.h_, int(slot), C.byref(fid), C.byref(n), C.byref(mi), pose.ctypes.data), False)
+        return {"frameId": fid.value, "numPoints": n.value, "meanIdepth": mi.value, "camToWorld": pose}
+
+    def download(self, slot):
+        """(pos n x 3, colorAndVar n x 2) of the slot's cloud"""
+        cap = max((self.ctx.w >> 4) - 2, 1) * max((self.ctx.h >> 4) - 2, 1)
+        pos, cv = np.zeros((cap, 3), np.float32), np.zeros((cap, 2), np.float32)
+        n = check(self.L.lsdhip_kfbank_download(self.h_, int(slot), pos.ctypes.data, cv.ctypes.data))
+        return pos[:n].copy(), cv[:n].copy()
+
+
+class TrackableKeyFrameSearch:
+    """TrackableKeyFrameSearch::findRePositionCandidate (C/GlobalMapping/TrackableKeyFrameSearch.cpp:103-172) over a KeyFrameBank: the
+    prefilter and the selection on the host, the overlap check of all candidates in one launch, the tracking of those that pass in one
+    batch (lsdhip_tracker_find_reposition_candidate)."""
+
+    def __init__(self, ctx, bank, tracker=None):
+        self.ctx, self.bank = ctx, bank
+        self.tracker = tracker or SE3Tracker(ctx)
+        self._relocalizationTH = 0.7
+        self.last = None
+
+    @property
+    def relocalizationTH(self):
+        return self._relocalizationTH
+
+    @relocalizationTH.setter
+    def relocalizationTH(self, v):
+        check(self.ctx.L.lsdhip_tracker_set_relocalization_th(self.tracker.h_, float(v)), False)
+        self._relocalizationTH = float(v)
+
+    def getRefFrameScore(self, distanceSquared, usage):
+        """TrackableKeyFrameSearch.h:75-79, in single precision"""
+        f = np.float32
+        wd, wu = f(self.ctx.params.KFDistWeight), f(self.ctx.params.KFUsageWeight)
+        return float(f(distanceSquared) * wd * wd + (f(1) - f(usage)) * (f(1) - f(usage)) * wu * wu)
+
+    def findRePositionCandidate(self, frame, frameCamToWorld, trackingParentId=-1, maxScore=1.0):
+        """-> slot of the keyframe to re-activate, or None.  frameCamToWorld: the frame's getScaledCamToWorld() as Sim3[8]; trackingParentId:
+        frame id of its tracking parent.  self.last holds the result record, records() the per-keyframe ones."""
+        p = np.ascontiguousarray(frameCamToWorld, dtype=np.float64)
+        assert p.shape == (8,)
+        r = capi.RepositionResult()
+        check(self.ctx.L.lsdhip_tracker_find_reposition_candidate(self.tracker.h_, self.bank.h_, frame.h_, p.ctypes.data, int(trackingParentId),
+                                                                  float(maxScore), C.byref(r)), False)
+        self.last = r
+        return r.slot if r.slot >= 0 else None
+
+    def records(self):
+        n = C.c_int()
+        check(self.ctx.L.lsdhip_tracker_reposition_records(self.tracker.h_, 0, None, C.byref(n)), False)
+        recs = (capi.RepositionRecord * max(n.value, 1))()
+        check(self.ctx.L.lsdhip_tracker_reposition_records(self.tracker.h_, n.value, recs, C.byref(n)), False)
+        return list(recs)[:n.value]
 
 
 class Sim3Tracker:
