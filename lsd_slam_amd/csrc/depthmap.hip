@@ -20,6 +20,7 @@
 #include <chrono>
 #include <cstdlib>
 #include "lsdhip_internal.hpp"
+#include "block_scan.hpp"   // lsd_wave_sum, lsd_block_tree_sum, lsd_block_butterfly_sum
 
 // ---- constants, C/util/settings.h:34-35, :50-174 ------------------------------------------------------------------
 #define DIVISION_EPS 1e-10f
@@ -62,7 +63,8 @@
 #define OBS_MARK(k) do { } while (0)
 #define OBS_VAL(k, v) do { } while (0)
 #endif
-// per-pixel arithmetic is host+device so that tests/ can shadow-execute it on a CPU when chasing a parity bit
+// per-pixel arithmetic compiles for the host as well: a developer chasing a parity bit can call it from a scratch program on a CPU
+// (nothing in the library or in tests/ does)
 #define LSD_HD __host__ __device__ __forceinline__
 #define LSD_HD_NOINLINE __host__ __device__
 
@@ -81,6 +83,20 @@ LSD_HD float interp1(const float* __restrict__ mat, float x, float y, int width)
   float dxdy = dx * dy;
   const float* bp = mat + ix + iy * width;
   return dxdy * bp[1 + width] + (dy - dxdy) * bp[width] + (dx - dxdy) * bp[1] + (1 - dx - dy + dxdy) * bp[0];
+}
+
+// A hypothesis that has just come into being (observeDepthCreate, fill holes, propagateDepth, setFromExistingKF): not blacklisted, no
+// reference-frame hint, nothing smoothed yet.  The isValid byte is the caller's (K5 and K6 write the other plane of a ping-pong).
+// blacklisted: the fused tile alone passes -1, where K6 drops the hypothesis that K5 created in the same launch.
+__device__ __forceinline__ void store_fresh_hypothesis(const HypPlanes& m, const int idx, const float idepth, const float var, const int validity,
+                                                       const int blacklisted = 0) {
+  m.blacklisted[idx] = blacklisted;
+  m.nextID[idx] = 0;
+  m.validity[idx] = validity;
+  m.idepth[idx] = idepth;
+  m.var[idx] = var;
+  m.idepth_s[idx] = -1;
+  m.var_s[idx] = -1;
 }
 
 struct ObserveArgs {
@@ -451,11 +467,36 @@ LSD_HD bool make_and_check_epl(const ObserveArgs& a, const StereoRef& rf, int x,
 }
 
 // observeDepthRow body for one pixel (DepthMap.cpp:117-143), in two halves:
-//   observe_front: everything up to and including makeAndCheckEPL — the cheap rejections every pixel goes through; returns
-//                  true for the ~1 % of pixels that go on to the epipolar search, with the reference frame and EPL direction;
-//   observe_back : doLineStereo and observeDepthCreate / observeDepthUpdate's bookkeeping for such a pixel.
-// k_observe runs both in the same lane.  (A select kernel queueing the survivors + a walk kernel over the dense queue, and a form that
-// loads all samples of short walks up front, were built and measured in round 2: 37-52 us and 28 us against 21 us — removed.)
+//   front: everything up to and including makeAndCheckEPL — the cheap rejections every pixel goes through; passes the pixels that go on to
+//          the epipolar search (their share is given with each kernel below), with the reference frame and the EPL direction.
+//          Its tests, in the reference's order, are the three predicates below; observe_front (one pixel per lane) and
+//          observe_front4 (four, their loads staged) differ in how they load, not in what they test;
+//   observe_back: doLineStereo and observeDepthCreate / observeDepthUpdate's bookkeeping for such a pixel.
+// k_observe runs both in the same lane: for ONE map the select + walk form further down (k_observe_select_batch + k_observe_walk_batch) and a
+// form that loads all samples of short walks up front were measured in round 2 and lost, 37-52 us and 28 us against 21 us.
+// (1) :121-131: a pixel below the gradient threshold loses its hypothesis (the front half's one store); it and a blacklisted pixel search nothing
+LSD_HD bool obs_cheap_pass(const ObserveArgs& a, const int idx, const bool hasHypothesis, const float maxGrad, const int blacklisted) {
+  if (hasHypothesis && maxGrad < a.minUseGrad) { a.m.valid[idx] = 0; return false; }
+  return !(maxGrad < a.minUseGrad || blacklisted < MIN_BLACKLIST);
+}
+// (2) the reference frame a pixel searches (observeDepthCreate :243, observeDepthUpdate :311-320); false: nextStereoFrameMinID lies beyond the newest
+template <bool ONE>
+LSD_HD bool obs_pick_ref(const ObserveArgs& a, const bool hasHypothesis, const float nextID, int& refIdx) {
+  refIdx = a.reactivated ? a.nRefs - 1 : 0;
+  if (hasHypothesis && !a.reactivated) {
+    const int rel = (int)nextID - a.byIDOffset;
+    if (rel >= a.nByID) return false;
+    refIdx = (ONE || rel < 0) ? 0 : a.refByID[rel];
+  }
+  return true;
+}
+// (3) the tracking mask of the reference frame (observeDepthCreate :246-252 / observeDepthUpdate :323-329), then makeAndCheckEPL
+LSD_HD bool obs_uses_mask(const StereoRef& rf) { return rf.parentIsKF && rf.wasGood != nullptr; }
+LSD_HD bool obs_mask_epl(const ObserveArgs& a, const StereoRef& rf, const int x, const int y, const uint8_t wasGoodHere, const float kR, const float kL,
+                         const float kD, const float kU, float* pepx, float* pepy) {
+  if (!wasGoodHere) return false;
+  return make_and_check_epl(a, rf, x, y, kR, kL, kD, kU, pepx, pepy);
+}
 template <bool ONE>
 LSD_HD bool observe_front(const ObserveArgs& a, const int x, const int y, int& refIdxOut, float& epxOut, float& epyOut) {
   if (x < 3 || x >= a.w - 3 || y < 3 || y >= a.h - 3) return false;
@@ -467,25 +508,13 @@ LSD_HD bool observe_front(const ObserveArgs& a, const int x, const int y, int& r
   const float maxGrad = a.kfMaxGrad[idx];
   const int blacklisted0 = a.m.blacklisted[idx];
   const float nextID = a.m.nextID[idx];
-  if (hasHypothesis && maxGrad < a.minUseGrad) { a.m.valid[idx] = 0; return false; }
-  if (maxGrad < a.minUseGrad || blacklisted0 < MIN_BLACKLIST) return false;
-
+  if (!obs_cheap_pass(a, idx, hasHypothesis, maxGrad, blacklisted0)) return false;
   int refIdx = 0;
-  if (!hasHypothesis) {
-    refIdx = a.reactivated ? a.nRefs - 1 : 0;
-  } else if (!a.reactivated) {
-    int rel = (int)nextID - a.byIDOffset;
-    if (rel >= a.nByID) return false;
-    refIdx = (ONE || rel < 0) ? 0 : a.refByID[rel];
-  } else {
-    refIdx = a.nRefs - 1;
-  }
+  if (!obs_pick_ref<ONE>(a, hasHypothesis, nextID, refIdx)) return false;
   const StereoRef& rf = ONE ? a.one : a.refs[refIdx];
-  const bool useMask = rf.parentIsKF && rf.wasGood != nullptr;
-  const uint8_t wasGoodHere = useMask ? rf.wasGood[(x >> 1) + (a.w >> 1) * (y >> 1)] : (uint8_t)1;
+  const uint8_t wasGoodHere = obs_uses_mask(rf) ? rf.wasGood[(x >> 1) + (a.w >> 1) * (y >> 1)] : (uint8_t)1;
   const float kR = a.kfImage[idx + 1], kL = a.kfImage[idx - 1], kD = a.kfImage[idx + a.w], kU = a.kfImage[idx - a.w];
-  if (!wasGoodHere) return false;       // observeDepthCreate :246-252 / observeDepthUpdate :323-329
-  if (!make_and_check_epl(a, rf, x, y, kR, kL, kD, kU, &epxOut, &epyOut)) return false;
+  if (!obs_mask_epl(a, rf, x, y, wasGoodHere, kR, kL, kD, kU, &epxOut, &epyOut)) return false;
   refIdxOut = refIdx;
   return true;
 }
@@ -525,15 +554,8 @@ LSD_HD void observe_back_store(const ObserveArgs& a, const StereoRef& rf, const 
   if (!P.hasHypothesis) {
     if (error == -3 || error == -2) a.m.blacklisted[idx] = blacklisted0 - 1;
     if (error < 0 || result_var > MAX_VAR) return;
-    result_idepth = unzero(result_idepth);
     a.m.valid[idx] = 1;
-    a.m.blacklisted[idx] = 0;
-    a.m.nextID[idx] = 0;
-    a.m.validity[idx] = VALIDITY_COUNTER_INITIAL_OBSERVE;
-    a.m.idepth[idx] = result_idepth;
-    a.m.var[idx] = result_var;
-    a.m.idepth_s[idx] = -1;
-    a.m.var_s[idx] = -1;
+    store_fresh_hypothesis(a.m, idx, unzero(result_idepth), result_var, VALIDITY_COUNTER_INITIAL_OBSERVE);
     return;
   }
   float diff = result_idepth - idepth_smoothed;
@@ -602,9 +624,7 @@ LSD_HD int observe_pixel(const ObserveArgs& a, const int x, const int y) {
 __device__ __forceinline__ void observe_count(const ObserveArgs& a, const int steps) {
   if (a.counters == nullptr) return;
   const unsigned long long act = __popcll(__ballot(steps >= 0));
-  int s = steps > 0 ? steps : 0;
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+  const int s = lsd_wave_sum(steps > 0 ? steps : 0);
   if ((threadIdx.x & 63) == 0) {
     const size_t wv = ((size_t)blockIdx.x + (size_t)blockIdx.y * gridDim.x) * (blockDim.x >> 6) + (threadIdx.x >> 6);
     a.counters[2 * wv] = act;
@@ -612,24 +632,18 @@ __device__ __forceinline__ void observe_count(const ObserveArgs& a, const int st
   }
 }
 __global__ __launch_bounds__(256) void k_obs_count_sum(const unsigned long long* __restrict__ counters, int nwaves, unsigned long long* __restrict__ acc) {
-  __shared__ unsigned long long s_a[256], s_b[256];
   unsigned long long a0 = 0, b0 = 0;
   for (int i = threadIdx.x; i < nwaves; i += 256) { a0 += counters[2 * i]; b0 += counters[2 * i + 1]; }
-  s_a[threadIdx.x] = a0; s_b[threadIdx.x] = b0;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if ((int)threadIdx.x < off) { s_a[threadIdx.x] += s_a[threadIdx.x + off]; s_b[threadIdx.x] += s_b[threadIdx.x + off]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { acc[0] += s_a[0]; acc[1] += s_b[0]; acc[2] += 1; }
+  lsd_block_tree_sum(a0, b0);
+  if (threadIdx.x == 0) { acc[0] += a0; acc[1] += b0; acc[2] += 1; }
 }
 
-// K4: observeDepthRow over the whole map, one pixel per lane.
-// K4: observeDepthRow over the whole map, one pixel per lane.  (Compacting the ~20 % of pixels that reach the epipolar
-// search into dense waves, and batching the loads of four walk steps, were both measured and gave nothing: the kernel
+// K4: observeDepthRow over the whole map, one pixel per lane.  (Compacting the candidate pixels, about 20 % of the map in
+// profiles/r01_notes.md's run, into dense waves, and batching the loads of four walk steps, were both measured and gave nothing: the kernel
 // is bound by chains of dependent first-touch loads, not by issue slots — profiles/r01_notes.md.)
 // ROWS = rows of the 32-pixel-wide tile a workgroup owns (workgroup size 32 * ROWS).  The kernel has no barriers and no LDS,
-// so the workgroup is only a scheduling unit: small workgroups free their wave slots as soon as their own lanes are done.
+// so the workgroup is only a scheduling unit: small workgroups free their wave slots as soon as their own lanes are done
+// (ROWS = 2, 64-thread workgroups, measured best: +2.5 % Mpixel/s over 256; the developer build with per-stage timestamps takes 8).
 template <bool ONE, int ROWS>
 __global__ __launch_bounds__(32 * ROWS) void k_observe(ObserveArgs a) {
   const int x = blockIdx.x * 32 + (threadIdx.x & 31);
@@ -711,7 +725,8 @@ __device__ __forceinline__ void prop_candidate(const PropArgs& a, const int x, c
 
 // The same for many maps in TWO launches (lsdhip_depth_update_batch from LSD_OBS_SPLIT_MIN_MAPS maps on).  In k_observe_batch a wave
 // that holds a single searching pixel walks the whole dependent chain of doLineStereo at 126 registers per lane with one lane busy, and
-// three waves in four hold one (2-7 % of the pixels search).  With enough maps in a launch to fill the chip that is what bounds it, not
+// three waves in four hold one (2-7 % of the pixels search in the 32-sequence loop: profiles/r05_notes.md section 2).  With enough maps in a
+// launch to fill the chip that is what bounds it, not
 // the planes it reads.  So: k_observe_select_batch runs observe_front — the cheap rejections, a streaming pass at few registers — over
 // every pixel (four per lane, their loads in flight together) and appends the survivors of a 64x16 tile, compacted, to their map's queue
 // (one atomic per tile); k_observe_walk_batch
@@ -724,14 +739,15 @@ __device__ __forceinline__ void prop_candidate(const PropArgs& a, const int x, c
 // four are requested before the first is looked at, likewise the second batch (mask byte, four keyframe-image taps) of the survivors —
 // the pass is a chain of two dependent memory round trips per pixel, and a lane that keeps eight of them in flight needs a quarter of
 // the residency rounds (the one-pixel form ran at 1.7 TB/s: 0.84 of its wave cycles waiting, profiles/r05_notes.md).
-// Same tests in the same order as observe_front (incl. its one store: a hypothesis on a pixel below the gradient threshold is dropped).
+// The tests are observe_front's: the same three predicates in the same order (incl. the one store of the first).
 // CAND: the four pixels come from the keyframe's gradient candidates (k_observe_select_cand_batch): the border and gradient tests are
-// already answered (and no hypothesis sits below the threshold: lsdhip_depthmap::lowGradHypPossible), maxGradients is not read.
+// already answered (and no hypothesis sits below the threshold: lsdhip_depthmap::lowGradHypPossible), maxGradients is not read: the
+// first predicate is handed the threshold itself, which passes its gradient test.
 template <bool CAND>
 __device__ __forceinline__ void observe_front4(const ObserveArgs& a, const int (&xs)[4], const int (&ys)[4], const bool (&in)[4], bool (&hit)[4],
                                                float (&epx)[4], float (&epy)[4]) {
   const StereoRef& rf = a.one;
-  const bool useMask = rf.parentIsKF && rf.wasGood != nullptr;
+  const bool useMask = obs_uses_mask(rf);
   bool hyp[4];
   int idx[4], bl[4];
   float mg[4], nid[4];
@@ -753,14 +769,8 @@ __device__ __forceinline__ void observe_front4(const ObserveArgs& a, const int (
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     hyp[k] = val[k] != 0;
-    bool pass = in[k];
-    if (!CAND && pass && hyp[k] && mg[k] < a.minUseGrad) { a.m.valid[idx[k]] = 0; pass = false; }
-    if (pass && ((!CAND && mg[k] < a.minUseGrad) || bl[k] < MIN_BLACKLIST)) pass = false;
-    if (pass && hyp[k] && !a.reactivated) {
-      const int rel = (int)nid[k] - a.byIDOffset;
-      if (rel >= a.nByID) pass = false;
-    }
-    hit[k] = pass;
+    int refIdx;      // (one reference: a.one whatever the index)
+    hit[k] = in[k] && obs_cheap_pass(a, idx[k], hyp[k], mg[k], bl[k]) && obs_pick_ref<true>(a, hyp[k], nid[k], refIdx);
   }
   uint8_t good[4];
   float kR[4], kL[4], kD[4], kU[4];
@@ -782,10 +792,7 @@ __device__ __forceinline__ void observe_front4(const ObserveArgs& a, const int (
 #pragma unroll
   for (int k = 0; k < 4; k++) {
     epx[k] = 0; epy[k] = 0;
-    if (hit[k]) {
-      if (!good[k]) hit[k] = false;
-      else hit[k] = make_and_check_epl(a, rf, xs[k], ys[k], kR[k], kL[k], kD[k], kU[k], &epx[k], &epy[k]);
-    }
+    if (hit[k]) hit[k] = obs_mask_epl(a, rf, xs[k], ys[k], good[k], kR[k], kL[k], kD[k], kU[k], &epx[k], &epy[k]);
   }
 }
 // the survivors of a workgroup's pixels, compacted, go to their map's queue (one atomic per workgroup and call)
@@ -900,8 +907,7 @@ __global__ __launch_bounds__(64) void k_observe_walk_batch(const ObserveArgs* __
   }
   __syncthreads();
   if (acc != nullptr && blockIdx.x == 0) {     // sampled launch (profiling): its searches
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) total += __shfl_xor(total, off);
+    total = lsd_wave_sum(total);
     if (lane == 0) { atomicAdd(&acc[0], (unsigned long long)total); atomicAdd(&acc[65], 1ull); }
   }
   for (int ck = (int)blockIdx.x; ck < TC; ck += (int)gridDim.x) {
@@ -917,8 +923,7 @@ __global__ __launch_bounds__(64) void k_observe_walk_batch(const ObserveArgs* __
       [[clang::always_inline]] steps = observe_back<true>(a, __float_as_int(q.x), 0, q.y, q.z);   // (as a call the function is compiled without the kernel's register budget)
     }
     if (acc != nullptr) {                         // ... and walk steps
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) steps += __shfl_xor(steps, off);
+      steps = lsd_wave_sum(steps);
       if (lane == 0) atomicAdd(&acc[1 + (ck & 63)], (unsigned long long)steps);
     }
   }
@@ -936,7 +941,47 @@ struct RegArgs {
   int tileRows;             // > 0: the launch's grid may hold more tile rows than this part has (several parts per launch): the rest leave
 };
 
-// K5: regularizeDepthMapFillHolesRow (DepthMap.cpp:656-703); 5x5 validity sum replaces the integral image.
+// K5 for one pixel that holds no hypothesis, lies in K5's range of the image and reaches the gradient threshold
+// (regularizeDepthMapFillHolesRow, DepthMap.cpp:656-703; the 5x5 sum of validity counters replaces the integral image).  NB is the pre-K5
+// snapshot of the pixel's 5x5 neighbourhood: counter(dx, dy) = the validity counter of a valid neighbour (never negative), negative for
+// an invalid one; valid(dx, dy); hyp(dx, dy, idepth, var) = a valid neighbour's pair.  True: a hypothesis is created with inverse depth idepthObs,
+// variance VAR_RANDOM_INIT_INITIAL and validity counter 0.  The pixel's blacklisted counter is read only where the sum leaves it to decide.
+template <typename NB>
+__device__ __forceinline__ bool fill_hole_pixel(const NB& nb, LSD_G const int32_t* blacklistedAt, float& idepthObs) {
+  int val = 0;
+#pragma unroll NB::UNROLL
+  for (int dy = -2; dy <= 2; dy++)
+#pragma unroll NB::UNROLL
+    for (int dx = -2; dx <= 2; dx++) {
+      const int pk0 = nb.counter(dx, dy);
+      val += pk0 > 0 ? pk0 : 0;
+    }
+  if (!(val > VAL_SUM_MIN_FOR_UNBLACKLIST || (val > VAL_SUM_MIN_FOR_CREATE && *blacklistedAt >= MIN_BLACKLIST))) return false;
+  float sumIdepthObs = 0, sumIVarObs = 0;
+#pragma unroll NB::UNROLL
+  for (int dy = -2; dy <= 2; dy++)
+#pragma unroll NB::UNROLL
+    for (int dx = -2; dx <= 2; dx++)
+      if (nb.valid(dx, dy)) {
+        float id, sv;
+        nb.hyp(dx, dy, id, sv);
+        sumIdepthObs += id / sv;
+        sumIVarObs += lsd_rcp_exact(sv);
+      }
+  idepthObs = unzero(sumIdepthObs / sumIVarObs);
+  return true;
+}
+struct PlaneNeighbours {     // the neighbourhood read from the planes
+  // the 5x5 loops stay loops: unrolled, the 25 validity bytes are kept in registers from the first sum to the second and k_fill_holes
+  // needs 58 registers instead of 27 (profiles/r13_depth_device_phases.md)
+  static constexpr int UNROLL = 1;
+  const RegArgs& a;
+  int idx;
+  __device__ __forceinline__ int counter(int dx, int dy) const { const int j = idx + dx + dy * a.w; return a.validIn[j] ? a.m.validity[j] : -1; }
+  __device__ __forceinline__ bool valid(int dx, int dy) const { return a.validIn[idx + dx + dy * a.w] != 0; }
+  __device__ __forceinline__ void hyp(int dx, int dy, float& id, float& var) const { const int j = idx + dx + dy * a.w; id = a.m.idepth[j]; var = a.m.var[j]; }
+};
+// K5 as a launch of its own (the per-stage test hook, lsdhip_depth_stage)
 __global__ __launch_bounds__(256) void k_fill_holes(RegArgs a) {
   const int x = blockIdx.x * 32 + (threadIdx.x & 31);
   const int y = blockIdx.y * 8 + (threadIdx.x >> 5);
@@ -944,142 +989,97 @@ __global__ __launch_bounds__(256) void k_fill_holes(RegArgs a) {
   const int idx = x + y * a.w;
   const uint8_t wasValid = a.validIn[idx];
   uint8_t nowValid = wasValid;
-  if (x >= 3 && x < a.w - 2 && y >= 3 && y < a.h - 2 && !wasValid && !(a.kfMaxGrad[idx] < a.minUseGrad)) {
-    int val = 0;
-    for (int yy = y - 2; yy <= y + 2; yy++)
-      for (int xx = x - 2; xx <= x + 2; xx++) {
-        int j = xx + yy * a.w;
-        if (a.validIn[j]) val += a.m.validity[j];
-      }
-    if ((a.m.blacklisted[idx] >= MIN_BLACKLIST && val > VAL_SUM_MIN_FOR_CREATE) || val > VAL_SUM_MIN_FOR_UNBLACKLIST) {
-      float sumIdepthObs = 0, sumIVarObs = 0;
-      for (int yy = y - 2; yy <= y + 2; yy++)
-        for (int xx = x - 2; xx <= x + 2; xx++) {
-          int j = xx + yy * a.w;
-          if (!a.validIn[j]) continue;
-          float sv = a.m.var[j];
-          sumIdepthObs += a.m.idepth[j] / sv;
-          sumIVarObs += 1.0f / sv;
-        }
-      float idepthObs = sumIdepthObs / sumIVarObs;
-      idepthObs = unzero(idepthObs);
-      nowValid = 1;
-      a.m.blacklisted[idx] = 0;
-      a.m.nextID[idx] = 0;
-      a.m.validity[idx] = 0;
-      a.m.idepth[idx] = idepthObs;
-      a.m.var[idx] = VAR_RANDOM_INIT_INITIAL;
-      a.m.idepth_s[idx] = -1;
-      a.m.var_s[idx] = -1;
-    }
+  float idepthObs;
+  if (x >= 3 && x < a.w - 2 && y >= 3 && y < a.h - 2 && !wasValid && !(a.kfMaxGrad[idx] < a.minUseGrad) &&
+      fill_hole_pixel(PlaneNeighbours{a, idx}, a.m.blacklisted + idx, idepthObs)) {
+    nowValid = 1;
+    store_fresh_hypothesis(a.m, idx, idepthObs, VAR_RANDOM_INIT_INITIAL, 0);
   }
   a.validOut[idx] = nowValid;
 }
 
-// K6: regularizeDepthMapRow<removeOcclusions> (DepthMap.cpp:758-848)
-template <bool removeOcclusions>
-__global__ __launch_bounds__(256) void k_regularize(RegArgs a) {
-  const int x = blockIdx.x * 32 + (threadIdx.x & 31);
-  const int y = blockIdx.y * 8 + (threadIdx.x >> 5);
-  if (x >= a.w || y >= a.h) return;
-  const int idx = x + y * a.w;
-  const uint8_t wasValid = a.validIn[idx];
-  uint8_t nowValid = wasValid;
-  if (x >= 2 && x < a.w - 2 && y >= 2 && y < a.h - 2 && wasValid) {
-    const float c_id = a.m.idepth[idx];
-    const float c_var = a.m.var[idx];
-    float sum = 0, val_sum = 0, sumIvar = 0;
-    int numOccluding = 0, numNotOccluding = 0;
-    for (int dx = -2; dx <= 2; dx++)
-      for (int dy = -2; dy <= 2; dy++) {
-        int j = idx + dx + dy * a.w;
-        if (!a.validIn[j]) continue;
-        float s_id = a.m.idepth[j];
-        float s_var = a.m.var[j];
-        float diff = s_id - c_id;
-        if (DIFF_FAC_SMOOTHING * diff * diff > s_var + c_var) {
-          if (removeOcclusions) { if (s_id > c_id) numOccluding++; }
-          continue;
-        }
-        val_sum += a.m.validity[j];
-        if (removeOcclusions) numNotOccluding++;
-        float distFac = (float)(dx * dx + dy * dy) * a.regDistVar;
-        float ivar = lsd_rcp_exact(s_var + distFac);
-        sum += s_id * ivar;
-        sumIvar += ivar;
-      }
-    if (val_sum < a.validityTH) {
-      nowValid = 0;
-      a.m.blacklisted[idx] = a.m.blacklisted[idx] - 1;
-    } else if (removeOcclusions && numOccluding > numNotOccluding) {
-      nowValid = 0;
-    } else {
-      sum = sum / sumIvar;
-      sum = unzero(sum);
-      a.m.idepth_s[idx] = sum;
-      a.m.var_s[idx] = lsd_rcp_exact(sumIvar);
-    }
-  }
-  a.validOut[idx] = nowValid;
-}
-
-// K5 + K6 (+ K8) fused over one LDS tile: regularizeDepthMapFillHoles -> regularizeDepthMap<removeOcclusions> ->
-// Frame::setDepth, in one launch.  A workgroup owns 32x8 pixels; K6 on them needs the post-K5 map on a 2-pixel halo, and
-// K5 on that 36x12 region needs the pre-K5 snapshot on a 4-pixel halo, so the tile is 40x16 (36x12 without K5).  The
-// halo's K5 results are recomputed locally (identical arithmetic => identical values in every workgroup that needs
-// them) and only the owner writes them to HBM.  Every neighbour access is an LDS read issued in a fully unrolled batch;
-// the per-pixel arithmetic and its order are those of k_fill_holes / k_regularize above (and of the reference).
-//   id0 / var0 / partials: outputs of K8 (SET only): level-0 idepth planes of the keyframe and per-workgroup (sum, count).
-// KF (keyframe change, lsdhip_depth_change_keyframe_batch): the pass is finalizeKeyFrame's, and the owner of a pixel goes on with what
-//   the reference does next with that pixel's finalised hypothesis — Frame::takeReActivationData (kx->react*) and phase A of
-//   propagateDepth into the new keyframe (prop_candidate on kx->prop) — while the values are in its registers.
-// SUMV: per-workgroup (sum of idepth_smoothed, count) over the valid pixels after the pass -> partials (createKeyFrame's rescale sums).
+// K5 + K6 (+ K8) fused over one LDS tile: regularizeDepthMapFillHoles -> regularizeDepthMap<removeOcclusions>
+// (regularizeDepthMapRow, DepthMap.cpp:758-848) -> Frame::setDepth, in one launch.  A workgroup owns 32x8 pixels; K6 on them needs the
+// post-K5 map on a 2-pixel halo, and K5 on that 36x12 region needs the pre-K5 snapshot on a 4-pixel halo, so the tile is 40x16 (36x12
+// without K5).  The halo's K5 results are recomputed locally (identical arithmetic => identical values in every workgroup that needs
+// them) and only the owner writes them to HBM.  Every neighbour access is an LDS read issued in a fully unrolled batch; the per-pixel
+// arithmetic and its order are the reference's.
+//
+// What a launch does besides is its pass type, named for the place in DepthMap.cpp that the launch stands for:
+//   FillHoles         K5 runs before K6;
+//   RemoveOcclusions  regularizeDepthMap's template argument;
+//   SetDepth          K8: Frame::setDepth on the owned pixels -> the keyframe's level-0 planes (id0, var0) and per-workgroup (sum, count);
+//   KeyframeChange    the owner of a pixel goes on with what the reference does next with that pixel's finalised hypothesis —
+//                     Frame::takeReActivationData (KfExtra::react*) and phase A of propagateDepth into the new keyframe (prop_candidate
+//                     on KfExtra::prop) — while the values are in its registers;
+//   SumValid          per-workgroup (sum of idepth_smoothed, count) over the valid pixels after the pass (createKeyFrame's rescale sums).
+struct PassBase { static constexpr bool FillHoles = false, RemoveOcclusions = false, SetDepth = false, KeyframeChange = false, SumValid = false; };
+struct PassRegOnly : PassBase {};                                               // regularizeDepthMap(false, th) alone (lsdhip_depth_stage)
+struct PassRegOcc : PassBase { static constexpr bool RemoveOcclusions = true; };   // regularizeDepthMap(true, th): createKeyFrame :1263
+struct PassUpdate : PassBase { static constexpr bool FillHoles = true; };          // updateKeyframe :1135-1143: fill holes + regularizeDepthMap(false, th)
+struct PassUpdateSetDepth : PassUpdate { static constexpr bool SetDepth = true; }; // ... + Frame::setDepth where the keyframe is due for it (:1150-1153)
+struct PassKfFinalize : PassUpdateSetDepth { static constexpr bool KeyframeChange = true; };   // finalizeKeyFrame :1363-1395, then the step into createKeyFrame
+struct PassKfFillSums : PassUpdate { static constexpr bool SumValid = true; };     // createKeyFrame :1270-1294
 struct KfExtra {
   LSD_G float* reactId;        // old keyframe's re-activation planes
   LSD_G float* reactVar;
   LSD_G uint8_t* reactVal;
   PropArgs prop;         // (src unused)
 };
+// one map's (or one part's) record of a pass
+struct RegItem {
+  RegArgs a;
+  LSD_G float* id0;          // SetDepth; batched updates: null = this map's keyframe is not due for Frame::setDepth (depthHasBeenUpdatedFlag still set)
+  LSD_G float* var0;
+  LSD_G double* partials;    // SetDepth / SumValid: (sum, count) per workgroup
+};
+struct KfItem : RegItem { KfExtra x; };      // KeyframeChange
+static_assert(sizeof(KfItem) == sizeof(RegItem) + sizeof(KfExtra), "argument records: a KfItem is a RegItem followed by its KfExtra");
+
+// Per tile entry ONE 16-byte word (idepth, idepth_var, (float)pk) with pk = validity_counter of a valid pixel (never negative), -1 for an
+// invalid one: a neighbour costs K6 one LDS round trip (round 4: two dependent ones — the validity word, then, behind the branch on
+// it, the hypothesis; rounds 1-3: four arrays).  pk0 is the pre-K5 snapshot of pk that K5 reads.
+typedef float reg_entry __attribute__((ext_vector_type(4)));
+typedef float reg_entry3 __attribute__((ext_vector_type(3)));   // (what K6 reads of an entry: a 12-byte load leaves no dead register behind)
+struct TileLds { int* pk0; uint8_t* created; reg_entry* e; };
 // PY: pixels per lane = units of 8 map rows a workgroup owns (owned tile 32 x 8 PY).  The taller tile loads (32 + 2 HALO) x (8 PY + 2 HALO)
 // entries for 256 PY owned pixels — 2.5x (PY = 1), 1.88x (2), 1.56x (4) with K5 — and recomputes K5 on 1.69x / 1.41x / 1.27x of them; the
 // per-pixel arithmetic does not know the tile it runs in, so every shape gives the same planes bit for bit (profiles/r06_notes.md section 5).
-template <bool FILL, bool OCC, bool SET, bool KF, bool SUMV, int PY>
-__device__ __forceinline__ void reg_fused_tile(const RegArgs& a, float* __restrict__ id0, float* __restrict__ var0,
-                                               double* __restrict__ partials, const KfExtra* __restrict__ kx = nullptr) {
-  constexpr int HALO = FILL ? 4 : 2;
-  constexpr int OH = 8 * PY;
-  constexpr int TW = 32 + 2 * HALO, TH = OH + 2 * HALO, TN = TW * TH;
-  // Per tile entry ONE 16-byte word (idepth, idepth_var, (float)pk) with pk = validity_counter of a valid pixel (never negative), -1 for an
-  // invalid one: a neighbour costs K6 one LDS round trip (round 4: two dependent ones — the validity word, then, behind the branch on
-  // it, the hypothesis; rounds 1-3: four arrays).  s_pk0 is the pre-K5 snapshot of pk that K5 reads.
-  __shared__ int s_pk0[TN];
-  __shared__ uint8_t s_created[TN];
-  typedef float rege __attribute__((ext_vector_type(4)));
-  typedef float rege3 __attribute__((ext_vector_type(3)));   // (what K6 reads of an entry: a 12-byte load leaves no dead register behind)
-  __shared__ rege s_e[TN];
-  __shared__ double s_sum[4];
-  __shared__ int s_cnt[4];
-  const int tid = threadIdx.x;
-  // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2, and every tile re-reads a 4-pixel halo of its
-  // neighbours: give XCD x the contiguous tile range [x nt/8, (x+1) nt/8) (whole bands of tile rows), so that a halo line is
-  // fetched into one L2 instead of into the L2s of up to four XCDs.
-  const int nt = gridDim.x * gridDim.y;
-  const int lin = blockIdx.x + blockIdx.y * gridDim.x;
-  const int tIdx = (nt & 7) == 0 ? (lin & 7) * (nt >> 3) + (lin >> 3) : lin;
-  // tile rows are counted in units of 8 map rows (the C ABI's unit, lsdhip_depth_stage_rows): this workgroup owns PY of them
-  const int unit0 = (tIdx / (int)gridDim.x) * PY;
-  if (a.tileRows > 0 && unit0 >= a.tileRows) return;
-  const int tbx = tIdx % gridDim.x;
-  const int x0 = tbx * 32 - HALO, y0 = (unit0 + a.tileRow0) * 8 - HALO;
-  const int ownedRows = a.tileRows > 0 ? (a.tileRows - unit0 < PY ? (a.tileRows - unit0) * 8 : OH) : OH;   // a part may end inside the tile
-  const int w = a.w, h = a.h;
-
-  // ---- tile load (unconditional, clamped addresses; out-of-image entries are invalid) ----
+template <bool FILL, int PY>
+struct RegTile {
+  static constexpr bool FILLS = FILL;
+  static constexpr int HALO = FILL ? 4 : 2;
+  static constexpr int OH = 8 * PY;
+  static constexpr int TW = 32 + 2 * HALO, TH = OH + 2 * HALO, TN = TW * TH;
+  static constexpr int FW = TW - 4, FH = TH - 4, FN = FW * FH;     // K5's region: the tile without its outer two pixels
+  static constexpr int MG = FILL ? (FN + 255) / 256 : 1;           // pixels of that region per lane
+  int tIdx, x0, y0, ownedRows;
+  // false: the workgroup lies outside the part of the map this launch covers
+  __device__ __forceinline__ bool place(const RegArgs& a) {
+    // Workgroups are dealt round-robin to the 8 XCDs, each with its own L2, and every tile re-reads a 4-pixel halo of its
+    // neighbours: give XCD x the contiguous tile range [x nt/8, (x+1) nt/8) (whole bands of tile rows), so that a halo line is
+    // fetched into one L2 instead of into the L2s of up to four XCDs.
+    const int nt = gridDim.x * gridDim.y;
+    const int lin = blockIdx.x + blockIdx.y * gridDim.x;
+    tIdx = (nt & 7) == 0 ? (lin & 7) * (nt >> 3) + (lin >> 3) : lin;
+    // tile rows are counted in units of 8 map rows (the C ABI's unit, lsdhip_depth_stage_rows): this workgroup owns PY of them
+    const int unit0 = (tIdx / (int)gridDim.x) * PY;
+    if (a.tileRows > 0 && unit0 >= a.tileRows) return false;
+    const int tbx = tIdx % gridDim.x;
+    x0 = tbx * 32 - HALO; y0 = (unit0 + a.tileRow0) * 8 - HALO;
+    ownedRows = a.tileRows > 0 ? (a.tileRows - unit0 < PY ? (a.tileRows - unit0) * 8 : OH) : OH;   // a part may end inside the tile
+    return true;
+  }
+};
+// tile load (unconditional, clamped addresses; out-of-image entries are invalid)
+template <class T>
+__device__ __forceinline__ void tile_load(const RegArgs& a, const T& t, const TileLds& s, float (&mg)[T::MG]) {
+  const int tid = threadIdx.x, w = a.w, h = a.h;
 #pragma unroll
-  for (int it = 0; it < (TN + 255) / 256; it++) {
+  for (int it = 0; it < (T::TN + 255) / 256; it++) {
     const int e = tid + it * 256;
-    if (e < TN) {
-      const int gx = x0 + e % TW, gy = y0 + e / TW;
+    if (e < T::TN) {
+      const int gx = t.x0 + e % T::TW, gy = t.y0 + e / T::TW;
       const bool inb = gx >= 0 && gx < w && gy >= 0 && gy < h;
       const int g = inb ? gx + gy * w : 0;
       const uint8_t v = a.validIn[g];
@@ -1087,270 +1087,244 @@ __device__ __forceinline__ void reg_fused_tile(const RegArgs& a, float* __restri
       const float id = a.m.idepth[g];
       const float var = a.m.var[g];
       const int pk = (inb && v) ? vc : -1;
-      s_pk0[e] = pk;
-      s_created[e] = 0;
-      s_e[e] = rege{id, var, (float)pk, 0.f};             // (the counter as a float: K6 adds it to a float sum once per neighbour)
+      s.pk0[e] = pk;
+      s.created[e] = 0;
+      s.e[e] = reg_entry{id, var, (float)pk, 0.f};             // (the counter as a float: K6 adds it to a float sum once per neighbour)
     }
   }
   // K5's gradient test reads the keyframe's maxGradients at the pixels of its region: issued with the tile loads (one memory round
   // trip for the workgroup instead of two; the lines are needed by nearly every wave of a semi-dense map anyway)
-  constexpr int FW_ = TW - 4, FN_ = FW_ * (TH - 4);
-  float mg[FILL ? (FN_ + 255) / 256 : 1];
-  if (FILL) {
+  if (T::FILLS) {
 #pragma unroll
-    for (int it = 0; it < (FN_ + 255) / 256; it++) {
+    for (int it = 0; it < (T::FN + 255) / 256; it++) {
       const int f = tid + it * 256;
-      const int x = x0 + 2 + f % FW_, y = y0 + 2 + f / FW_;
-      const bool inb = f < FN_ && x >= 0 && x < w && y >= 0 && y < h;
+      const int x = t.x0 + 2 + f % T::FW, y = t.y0 + 2 + f / T::FW;
+      const bool inb = f < T::FN && x >= 0 && x < w && y >= 0 && y < h;
       mg[it] = a.kfMaxGrad[inb ? x + y * w : 0];
     }
   }
-  __syncthreads();
-
-  if (FILL) {
-    // ---- K5 on the inner (TW-4) x (TH-4) region ----
-    constexpr int FW = TW - 4, FH = TH - 4, FN = FW * FH;
+}
+template <int TW>
+struct TileNeighbours {      // K5's neighbourhood read from the tile, every read of a sum issued in one batch
+  static constexpr int UNROLL = 5;
+  const TileLds& s;
+  int e;
+  __device__ __forceinline__ int counter(int dx, int dy) const { return s.pk0[e + dx + dy * TW]; }
+  __device__ __forceinline__ bool valid(int dx, int dy) const { return s.pk0[e + dx + dy * TW] >= 0; }
+  __device__ __forceinline__ void hyp(int dx, int dy, float& id, float& var) const { const reg_entry iv = s.e[e + dx + dy * TW]; id = iv.x; var = iv.y; }
+};
+// K5 on the inner (TW-4) x (TH-4) region
+template <class T>
+__device__ __forceinline__ void tile_fill_holes(const RegArgs& a, const T& t, const TileLds& s, const float (&mg)[T::MG]) {
+  const int tid = threadIdx.x, w = a.w, h = a.h;
 #pragma unroll
-    for (int it = 0; it < (FN + 255) / 256; it++) {
-      const int f = tid + it * 256;
-      if (f < FN) {
-        const int lx = 2 + f % FW, ly = 2 + f / FW;
-        const int e = lx + ly * TW;
-        const int x = x0 + lx, y = y0 + ly;
-        if (x >= 3 && x < w - 2 && y >= 3 && y < h - 2 && s_pk0[e] < 0) {
-          const int idx = x + y * w;
-          if (!(mg[it] < a.minUseGrad)) {
-            int val = 0;
-#pragma unroll
-            for (int dy = -2; dy <= 2; dy++)
-#pragma unroll
-              for (int dx = -2; dx <= 2; dx++) {
-                const int j = e + dx + dy * TW;
-                const int pk0 = s_pk0[j];
-                val += pk0 > 0 ? pk0 : 0;
-              }
-            if (val > VAL_SUM_MIN_FOR_UNBLACKLIST || (val > VAL_SUM_MIN_FOR_CREATE && a.m.blacklisted[idx] >= MIN_BLACKLIST)) {
-              float sumIdepthObs = 0, sumIVarObs = 0;
-#pragma unroll
-              for (int dy = -2; dy <= 2; dy++)
-#pragma unroll
-                for (int dx = -2; dx <= 2; dx++) {
-                  const int j = e + dx + dy * TW;
-                  if (s_pk0[j] >= 0) {
-                    const rege iv = s_e[j];
-                    const float sv = iv.y;
-                    sumIdepthObs += iv.x / sv;
-                    sumIVarObs += lsd_rcp_exact(sv);
-                  }
-                }
-              float idepthObs = sumIdepthObs / sumIVarObs;
-              idepthObs = unzero(idepthObs);
-              s_created[e] = 1;
-              // nobody reads these entries during K5 (their snapshot validity is 0)
-              s_e[e] = rege{idepthObs, VAR_RANDOM_INIT_INITIAL, 0.f, 0.f};
-            }
-          }
-        }
+  for (int it = 0; it < (T::FN + 255) / 256; it++) {
+    const int f = tid + it * 256;
+    if (f < T::FN) {
+      const int lx = 2 + f % T::FW, ly = 2 + f / T::FW;
+      const int e = lx + ly * T::TW;
+      const int x = t.x0 + lx, y = t.y0 + ly;
+      float idepthObs;
+      if (x >= 3 && x < w - 2 && y >= 3 && y < h - 2 && s.pk0[e] < 0 && !(mg[it] < a.minUseGrad) &&
+          fill_hole_pixel(TileNeighbours<T::TW>{s, e}, a.m.blacklisted + (x + y * w), idepthObs)) {
+        s.created[e] = 1;
+        // nobody reads these entries during K5 (their snapshot validity is 0)
+        s.e[e] = reg_entry{idepthObs, VAR_RANDOM_INIT_INITIAL, 0.f, 0.f};
       }
     }
+  }
+}
+// the six distance terms (dx^2 + dy^2) * regDistVar of the 5x5 window and the reciprocal's class mask, once, in scalar registers: as
+// literals inside the loop each costs a move (+ a multiply) per neighbour in a loop of ~17 vector instructions per neighbour
+struct RegDist { float df0, df1, df2, df4, df5, df8; int nmask; };
+__device__ __forceinline__ RegDist reg_dist_terms(const float regDistVar) {
+  auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+  return RegDist{uni(0.0f * regDistVar), uni(1.0f * regDistVar), uni(2.0f * regDistVar), uni(4.0f * regDistVar), uni(5.0f * regDistVar),
+                 uni(8.0f * regDistVar), lsd_rcp_mask()};
+}
+struct K6Outcome {       // what K6 decides for one pixel
+  bool nowValid, smoothed, blacklistDec;      // smoothed: (ids, vars) is the pixel's new smoothed pair
+  float ids, vars;
+};
+// what the owner of a pixel stores after K5 and K6.  blFinal / return value: the pixel's blacklisted counter after the pass, where this
+// lane came to know it
+__device__ __forceinline__ bool store_outcome(const RegArgs& a, const int idx, const reg_entry c_e, const bool created, const K6Outcome& o, int& blFinal) {
+  bool blKnown = false;
+  a.validOut[idx] = o.nowValid;
+  if (created) {
+    blFinal = o.blacklistDec ? -1 : 0; blKnown = true;
+    store_fresh_hypothesis(a.m, idx, c_e.x, c_e.y, 0, blFinal);     // (the smoothed pair's -1 gives way to the store below where K6 smoothed)
+  } else if (o.blacklistDec) {
+    const int b0 = a.m.blacklisted[idx];
+    a.m.blacklisted[idx] = b0 - 1;
+    blFinal = b0 - 1; blKnown = true;
+  }
+  if (o.smoothed) { a.m.idepth_s[idx] = o.ids; a.m.var_s[idx] = o.vars; }
+  return blKnown;
+}
+// Frame::takeReActivationData for one pixel (Frame.cpp:107-145): a valid pixel's hypothesis, else whether it is blacklisted
+__device__ __forceinline__ void take_react_pixel(float* id, float* var, uint8_t* val, const int i, const bool valid, const float idepth, const float v,
+                                                 const int validity, const int blacklisted) {
+  if (valid) { id[i] = idepth; var[i] = v; val[i] = (uint8_t)validity; }
+  else var[i] = blacklisted < MIN_BLACKLIST ? -2.f : -1.f;
+}
+// Frame::setDepth for one pixel (Frame.cpp:199-243); true: the pixel counts in the keyframe's (sum, count) of inverse depths
+__device__ __forceinline__ bool set_depth_pixel(float* id0, float* var0, const int i, const bool valid, const float ids, const float vars) {
+  if (valid && (double)ids >= -0.05) {
+    id0[i] = ids;
+    var0[i] = vars;
+    return true;
+  }
+  id0[i] = -1.f;
+  var0[i] = -1.f;
+  return false;
+}
+
+template <class Pass, int PY>
+__device__ __forceinline__ void reg_fused_tile(const RegItem& it, const KfExtra* __restrict__ kx = nullptr) {
+  constexpr bool FILL = Pass::FillHoles, SUMS = Pass::SetDepth || Pass::SumValid;
+  typedef RegTile<FILL, PY> T;
+  __shared__ int s_pk0[T::TN];
+  __shared__ uint8_t s_created[T::TN];
+  __shared__ reg_entry s_e[T::TN];
+  const TileLds s{s_pk0, s_created, s_e};
+  const RegArgs& a = it.a;
+  const int tid = threadIdx.x, w = a.w, h = a.h;
+  T t;
+  if (!t.place(a)) return;
+  float mg[T::MG];
+  tile_load<T>(a, t, s, mg);
+  __syncthreads();
+  if (FILL) {
+    tile_fill_holes<T>(a, t, s, mg);
     __syncthreads();
   }
-
-  // ---- K6 on the owned 32 x (8 PY) pixels: lane (tid & 31, tid >> 5) takes rows tid >> 5, + 8, ... ----
-  // the six distance terms (dx^2 + dy^2) * regDistVar of the 5x5 window and the reciprocal's class mask, once, in scalar registers: as
-  // literals inside the loop each costs a move (+ a multiply) per neighbour in a loop of ~17 vector instructions per neighbour
-  auto uni = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
-  const float df0 = uni(0.0f * a.regDistVar), df1 = uni(1.0f * a.regDistVar), df2 = uni(2.0f * a.regDistVar), df4 = uni(4.0f * a.regDistVar),
-              df5 = uni(5.0f * a.regDistVar), df8 = uni(8.0f * a.regDistVar);
-  const int nmask = lsd_rcp_mask();
-  double accS = 0;          // (sum, count) of this lane's pixels: createKeyFrame's rescale sums (SUMV) or Frame::setDepth's statistics (SET)
+  // K6 on the owned 32 x (8 PY) pixels: lane (tid & 31, tid >> 5) takes rows tid >> 5, + 8, ...
+  const RegDist d = reg_dist_terms(a.regDistVar);
+  double accS = 0;          // (sum, count) of this lane's pixels: createKeyFrame's rescale sums (SumValid) or Frame::setDepth's statistics (SetDepth)
   int accC = 0;
 #pragma unroll
   for (int p = 0; p < PY; p++) {
-  const int lx = HALO + (tid & 31), ly = HALO + (tid >> 5) + 8 * p;
-  const int e = lx + ly * TW;
-  const int x = x0 + lx, y = y0 + ly;
-  const bool inImage = x < w && y < h && ly - HALO < ownedRows;
-  const int idx = inImage ? x + y * w : 0;
-  const bool created = FILL && s_created[e] != 0;
-  const rege c_e = s_e[e];
-  const int c_pk = (int)c_e.z;
-  const uint8_t wasValid = c_pk >= 0 ? 1 : 0;
-  uint8_t nowValid = wasValid;
-  bool smoothed = false, blacklistDec = false;
-  float out_ids = 0.f, out_vars = 0.f;
-  // (the 25-neighbour loop on compacted centres — ballots, a list in LDS, the outcome handed back to the pixel's owner — measured the
-  // same as this form at 30 % and at 50 % valid pixels: profiles/r05_notes.md section 5)
-  const bool doK6 = inImage && x >= 2 && x < w - 2 && y >= 2 && y < h - 2 && wasValid;
-  if (doK6) {
-    const float c_id = c_e.x;
-    const float c_var = c_e.y;
-    float sum = 0, val_sum = 0, sumIvar = 0;
-    int numOccluding = 0, numNotOccluding = 0;
-    // (the branches stay: on semi-dense maps whole waves skip most neighbours — the predicated form of this loop, every neighbour's
-    // arithmetic for every valid centre, ran the 32-map pass in 214 us against 166, profiles/r05_notes.md section 5.)
-    // The next neighbour's entry is requested before the current one is worked on (volatile: the read stays where it is written instead
-    // of sinking below the branches to its first use), so an LDS round trip overlaps the arithmetic instead of preceding it.
-    auto entry = [&](int k) { const int dx = k / 5 - 2, dy = k % 5 - 2; return *(const volatile __attribute__((address_space(3))) rege3*)&s_e[e + dx + dy * TW]; };
-    rege3 ej = entry(0);
+    const int lx = T::HALO + (tid & 31), ly = T::HALO + (tid >> 5) + 8 * p;
+    const int e = lx + ly * T::TW;
+    const int x = t.x0 + lx, y = t.y0 + ly;
+    const bool inImage = x < w && y < h && ly - T::HALO < t.ownedRows;
+    const int idx = inImage ? x + y * w : 0;
+    const bool created = FILL && s_created[e] != 0;
+    const reg_entry c_e = s_e[e];
+    const int c_pk = (int)c_e.z;
+    const bool wasValid = c_pk >= 0;
+    K6Outcome o{wasValid, false, false, 0.f, 0.f};
+    // K6 for a valid pixel with its whole window inside the image (regularizeDepthMapRow, DepthMap.cpp:758-848) -> o.  The block stands
+    // here and not in a function of its own: as one (outcome returned, filled in place, or five reference arguments) it cost every tile two
+    // registers, profiles/r13_depth_device_phases.md.
+    // (the 25-neighbour loop on compacted centres — ballots, a list in LDS, the outcome handed back to the pixel's owner — measured the
+    // same as this form at 30 % and at 50 % valid pixels: profiles/r05_notes.md section 5)
+    if (inImage && x >= 2 && x < w - 2 && y >= 2 && y < h - 2 && wasValid) {
+      const float c_id = c_e.x;
+      const float c_var = c_e.y;
+      float sum = 0, val_sum = 0, sumIvar = 0;
+      int numOccluding = 0, numNotOccluding = 0;
+      // (the branches stay: on semi-dense maps whole waves skip most neighbours — the predicated form of this loop, every neighbour's
+      // arithmetic for every valid centre, ran the 32-map pass in 214 us against 166, profiles/r05_notes.md section 5.)
+      // The next neighbour's entry is requested before the current one is worked on (volatile: the read stays where it is written instead
+      // of sinking below the branches to its first use), so an LDS round trip overlaps the arithmetic instead of preceding it.
+      auto entry = [&](int k) { const int dx = k / 5 - 2, dy = k % 5 - 2; return *(const volatile __attribute__((address_space(3))) reg_entry3*)&s_e[e + dx + dy * T::TW]; };
+      reg_entry3 ej = entry(0);
 #pragma unroll
-    for (int k = 0; k < 25; k++) {
-      const int dx = k / 5 - 2, dy = k % 5 - 2;     // dx outer, dy inner: the reference's order of the sums
-      const rege3 en = entry(k < 24 ? k + 1 : 24);
-      const float vcj = ej.z;                       // validity counter (small integer, exact) or -1
-      const float s_idj = ej.x;
-      const float s_varj = ej.y;
-      ej = en;
-      if (vcj < 0) continue;
-      const float diff = s_idj - c_id;
-      if (DIFF_FAC_SMOOTHING * diff * diff > s_varj + c_var) {
-        if (OCC) { if (s_idj > c_id) numOccluding++; }
-        continue;
+      for (int k = 0; k < 25; k++) {
+        const int dx = k / 5 - 2, dy = k % 5 - 2;     // dx outer, dy inner: the reference's order of the sums
+        const reg_entry3 en = entry(k < 24 ? k + 1 : 24);
+        const float vcj = ej.z;                       // validity counter (small integer, exact) or -1
+        const float s_idj = ej.x;
+        const float s_varj = ej.y;
+        ej = en;
+        if (vcj < 0) continue;
+        const float diff = s_idj - c_id;
+        if (DIFF_FAC_SMOOTHING * diff * diff > s_varj + c_var) {
+          if (Pass::RemoveOcclusions) { if (s_idj > c_id) numOccluding++; }
+          continue;
+        }
+        val_sum += vcj;
+        if (Pass::RemoveOcclusions) numNotOccluding++;
+        const int d2 = dx * dx + dy * dy;             // (float)(d2) * regDistVar, as the reference forms it
+        const float distFac = d2 == 0 ? d.df0 : (d2 == 1 ? d.df1 : (d2 == 2 ? d.df2 : (d2 == 4 ? d.df4 : (d2 == 5 ? d.df5 : d.df8))));
+        const float ivar = lsd_rcp_exact(s_varj + distFac, d.nmask);
+        sum += s_idj * ivar;
+        sumIvar += ivar;
       }
-      val_sum += vcj;
-      if (OCC) numNotOccluding++;
-      const int d2 = dx * dx + dy * dy;             // (float)(d2) * regDistVar, as the reference forms it
-      const float distFac = d2 == 0 ? df0 : (d2 == 1 ? df1 : (d2 == 2 ? df2 : (d2 == 4 ? df4 : (d2 == 5 ? df5 : df8))));
-      const float ivar = lsd_rcp_exact(s_varj + distFac, nmask);
-      sum += s_idj * ivar;
-      sumIvar += ivar;
-    }
-    if (val_sum < a.validityTH) {
-      nowValid = 0;
-      blacklistDec = true;
-    } else if (OCC && numOccluding > numNotOccluding) {
-      nowValid = 0;
-    } else {
-      sum = sum / sumIvar;
-      out_ids = unzero(sum);
-      out_vars = lsd_rcp_exact(sumIvar);
-      smoothed = true;
-    }
-  }
-  int blFinal = 0;           // the pixel's blacklisted counter after the pass, where this lane came to know it
-  bool blKnown = false;
-  if (inImage) {
-    a.validOut[idx] = nowValid;
-    if (created) {
-      a.m.nextID[idx] = 0;
-      a.m.validity[idx] = 0;
-      a.m.idepth[idx] = c_e.x;
-      a.m.var[idx] = c_e.y;
-      a.m.blacklisted[idx] = blacklistDec ? -1 : 0;
-      blFinal = blacklistDec ? -1 : 0; blKnown = true;
-      if (!smoothed) { a.m.idepth_s[idx] = -1; a.m.var_s[idx] = -1; }
-    } else if (blacklistDec) {
-      const int b0 = a.m.blacklisted[idx];
-      a.m.blacklisted[idx] = b0 - 1;
-      blFinal = b0 - 1; blKnown = true;
-    }
-    if (smoothed) { a.m.idepth_s[idx] = out_ids; a.m.var_s[idx] = out_vars; }
-  }
-  // the pixel's smoothed pair after the pass (SET / SUMV / KF)
-  float ids = -1.f, vars = -1.f;
-  if ((SET || SUMV || KF) && inImage) {
-    if (smoothed) { ids = out_ids; vars = out_vars; }
-    else if (created || !nowValid) { ids = -1.f; vars = -1.f; }    // (not valid: the value is not looked at)
-    else { ids = a.m.idepth_s[idx]; vars = a.m.var_s[idx]; }      // valid, not smoothed: the 2-pixel border only
-  }
-  if (KF && inImage) {
-    // Frame::takeReActivationData (Frame.cpp:107-145) of the keyframe being finalised, then this hypothesis' step into the new keyframe
-    if (nowValid) {
-      kx->reactId[idx] = c_e.x;
-      kx->reactVar[idx] = c_e.y;
-      kx->reactVal[idx] = (uint8_t)c_pk;
-      prop_candidate(kx->prop, x, y, idx, ids, c_e.y, c_pk);
-    } else {
-      const int bl = blKnown ? blFinal : a.m.blacklisted[idx];
-      kx->reactVar[idx] = bl < MIN_BLACKLIST ? -2.f : -1.f;
-    }
-  }
-  if (SUMV) {
-    // createKeyFrame's rescale sums (DepthMap.cpp:1286-1294): idepth_smoothed over the valid pixels
-    if (inImage && nowValid) { accS += ids; accC += 1; }
-  }
-  if (SET) {
-    // ---- K8: Frame::setDepth on the owned pixel ----
-    if (inImage) {
-      if (nowValid && (double)ids >= -0.05) {
-        id0[idx] = ids;
-        var0[idx] = vars;
-        accS += ids;
-        accC += 1;
+      if (val_sum < a.validityTH) {
+        o.nowValid = false;
+        o.blacklistDec = true;
+      } else if (Pass::RemoveOcclusions && numOccluding > numNotOccluding) {
+        o.nowValid = false;
       } else {
-        id0[idx] = -1.f;
-        var0[idx] = -1.f;
+        sum = sum / sumIvar;
+        o.ids = unzero(sum);
+        o.vars = lsd_rcp_exact(sumIvar);
+        o.smoothed = true;
+      }
+    }
+    if (!inImage) continue;
+    int blFinal = 0;
+    const bool blKnown = store_outcome(a, idx, c_e, created, o, blFinal);
+    // the pixel's smoothed pair after the pass
+    float ids = -1.f, vars = -1.f;
+    if (SUMS || Pass::KeyframeChange) {
+      if (o.smoothed) { ids = o.ids; vars = o.vars; }
+      else if (created || !o.nowValid) { ids = -1.f; vars = -1.f; }    // (not valid: the value is not looked at)
+      else { ids = a.m.idepth_s[idx]; vars = a.m.var_s[idx]; }         // valid, not smoothed: the 2-pixel border only
+    }
+    // createKeyFrame's rescale sums (DepthMap.cpp:1286-1294): idepth_smoothed over the valid pixels
+    if (Pass::SumValid && o.nowValid) { accS += ids; accC += 1; }
+    // K8
+    if (Pass::SetDepth && set_depth_pixel(it.id0, it.var0, idx, o.nowValid, ids, vars)) { accS += ids; accC += 1; }
+    if (Pass::KeyframeChange) {
+      // the keyframe being finalised hands the pixel to its re-activation planes, then the hypothesis steps into the new keyframe
+      if (o.nowValid) {
+        take_react_pixel(kx->reactId, kx->reactVar, kx->reactVal, idx, true, c_e.x, c_e.y, c_pk, 0);
+        prop_candidate(kx->prop, x, y, idx, ids, c_e.y, c_pk);
+      } else {
+        take_react_pixel(kx->reactId, kx->reactVar, kx->reactVal, idx, false, 0.f, 0.f, 0, blKnown ? blFinal : a.m.blacklisted[idx]);
       }
     }
   }
-  }   // pixels of this lane
-  if (SUMV || SET) {
-    // (sum, count) of the workgroup: butterfly inside each wave, then four partials through LDS.  The sum of at most 256 PY floats
-    // of one sign and a dynamic range below 2^20 is exact in double, so its value does not depend on the order.
-    double s = accS;
-    int c = accC;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-      s += __shfl_xor(s, off);
-      c += __shfl_xor(c, off);
-    }
-    if ((tid & 63) == 0) { s_sum[tid >> 6] = s; s_cnt[tid >> 6] = c; }
-    __syncthreads();
-    if (tid == 0) {
-      const int b = tIdx;
-      partials[2 * b] = ((s_sum[0] + s_sum[1]) + s_sum[2]) + s_sum[3];
-      partials[2 * b + 1] = (double)(((s_cnt[0] + s_cnt[1]) + s_cnt[2]) + s_cnt[3]);
-    }
+  if (SUMS) {
+    // The sum of at most 256 PY floats of one sign and a dynamic range below 2^20 is exact in double, so its value does not depend on
+    // the order: the butterfly order serves.
+    lsd_block_butterfly_sum(accS, accC);
+    if (tid == 0) { it.partials[2 * t.tIdx] = accS; it.partials[2 * t.tIdx + 1] = (double)accC; }
   }
 }
-template <bool FILL, bool OCC, bool SET, int PY>
-__global__ __launch_bounds__(256) void k_reg_fused(RegArgs a, float* __restrict__ id0, float* __restrict__ var0,
-                                                    double* __restrict__ partials) {
-  reg_fused_tile<FILL, OCC, SET, false, false, PY>(a, id0, var0, partials);
+template <class Pass, int PY>
+__global__ __launch_bounds__(256) void k_reg_fused(RegItem it) {
+  reg_fused_tile<Pass, PY>(it);
 }
-// the update-time pass (fill holes + regularise [+ setDepth]) over the maps of several sequences, blockIdx.z = map
-struct RegBatchItem {
-  RegArgs a;
-  LSD_G float* id0;          // null: this map's keyframe is not due for Frame::setDepth (depthHasBeenUpdatedFlag still set)
-  LSD_G float* var0;
-  LSD_G double* partials;
-};
-template <bool SET, int PY>
-__global__ __launch_bounds__(256) void k_reg_fused_batch(const RegBatchItem* __restrict__ items) {
-  const RegBatchItem& it = items[blockIdx.z];
-  if (SET) {
-    if (it.id0 == nullptr) return;
-    reg_fused_tile<true, false, true, false, false, PY>(it.a, it.id0, it.var0, it.partials);
-  } else {
-    if (it.id0 != nullptr) return;
-    reg_fused_tile<true, false, false, false, false, PY>(it.a, nullptr, nullptr, nullptr);
-  }
+// the update-time pass (PassUpdate or PassUpdateSetDepth) over the maps of several sequences, blockIdx.z = map: each launch takes the maps
+// whose keyframe is / is not due for Frame::setDepth
+template <class Pass, int PY>
+__global__ __launch_bounds__(256) void k_reg_fused_batch(const RegItem* __restrict__ items) {
+  const RegItem& it = items[blockIdx.z];
+  if ((it.id0 != nullptr) != Pass::SetDepth) return;
+  reg_fused_tile<Pass, PY>(it);
 }
 
 // ---- keyframe change of n maps in shared launches (lsdhip_depth_change_keyframe_batch), blockIdx.z = map -------------------------------
-//   k_kf_finalize_prop     finalizeKeyFrame's pass (fill holes + regularise + Frame::setDepth of the old keyframe) + takeReActivationData
-//                          + phase A of propagateDepth, per owner pixel
-//   k_prop_resolve_batch   phase B into the new map
-//   k_kf_reg<false, true>  regularizeDepthMap(true, ...)        (createKeyFrame, DepthMap.cpp:1271)
-//   k_kf_reg<true, false>  fill holes + regularizeDepthMap(false, ...) + the rescale sums per tile   (:1278-1294)
-//   k_kf_rescale_setdepth  mean inverse depth to one (:1296-1304) + Frame::setDepth of the new keyframe
-//   k_idepth_pyramid_batch both keyframes' pyramids and their (sum, count) records
-struct KfItem {
-  RegArgs a;
-  LSD_G float* id0;
-  LSD_G float* var0;
-  LSD_G double* partials;
-  KfExtra x;
-};
+//   k_kf_finalize_prop        PassKfFinalize: finalizeKeyFrame's pass (fill holes + regularise + Frame::setDepth of the old keyframe) +
+//                             takeReActivationData + phase A of propagateDepth, per owner pixel
+//   k_prop_resolve_batch      phase B into the new map
+//   k_kf_reg<PassRegOcc>      regularizeDepthMap(true, ...)        (createKeyFrame, DepthMap.cpp:1271)
+//   k_kf_reg<PassKfFillSums>  fill holes + regularizeDepthMap(false, ...) + the rescale sums per tile   (:1278-1294)
+//   k_kf_rescale_setdepth     mean inverse depth to one (:1296-1304) + Frame::setDepth of the new keyframe
+//   k_idepth_pyramid_batch    both keyframes' pyramids and their (sum, count) records
 template <int PY>
 __global__ __launch_bounds__(256) void k_kf_finalize_prop(const KfItem* __restrict__ items) {
   const KfItem& it = items[blockIdx.z];
-  reg_fused_tile<true, false, true, true, false, PY>(it.a, it.id0, it.var0, it.partials, &it.x);
+  reg_fused_tile<PassKfFinalize, PY>(it, &it.x);
 }
-template <bool FILL, bool OCC, int PY>
-__global__ __launch_bounds__(256) void k_kf_reg(const RegBatchItem* __restrict__ items) {
-  const RegBatchItem& it = items[blockIdx.z];
-  reg_fused_tile<FILL, OCC, false, false, FILL, PY>(it.a, nullptr, nullptr, it.partials, nullptr);   // (the rescale sums ride on the second pass)
+template <class Pass, int PY>
+__global__ __launch_bounds__(256) void k_kf_reg(const RegItem* __restrict__ items) {
+  reg_fused_tile<Pass, PY>(items[blockIdx.z]);
 }
 struct RescaleItem {
   HypPlanes m;
@@ -1363,172 +1337,102 @@ struct RescaleItem {
   LSD_G double* statPartials;        // (sum, count) per workgroup of this launch
   int n;
 };
-// The developer switches of this file, read once per process (as BatchEnv in tracker.hip)
-struct DepthEnv {
-  int regPy = getenv("LSDHIP_REG_PY") ? atoi(getenv("LSDHIP_REG_PY")) : 0;     // A/B: 1 or 2 forces the regulariser's tile height
-  // map rows per k_observe workgroup: 8, 4, else 2 — 64-thread workgroups measured best (+2.5 % Mpixel/s over 256)
-  int obsRows = [] { const char* e = getenv("LSDHIP_OBS_ROWS"); const int r = e ? atoi(e) : 2; return (r == 8 || r == 4) ? r : 2; }();
-  bool obsSplit = !(getenv("LSDHIP_OBS_SPLIT") && getenv("LSDHIP_OBS_SPLIT")[0] == '0');   // 0: batched updates never take select + walk (A/B of round 5)
-  bool obsCand = !(getenv("LSDHIP_OBS_CAND") && getenv("LSDHIP_OBS_CAND")[0] == '0');      // 0: the select pass always scans every pixel (A/B of round 6)
-  int walkWaves = getenv("LSDHIP_OBS_WALK_WAVES") ? atoi(getenv("LSDHIP_OBS_WALK_WAVES")) : LSD_OBS_WALK_WAVES;   // sweep of the walk launch's size
-  bool eventsAll = getenv("LSDHIP_DEPTH_EVENTS_ALL") != nullptr;   // every mapping call is bracketed by events: A/B of the sampling itself
-};
-static const DepthEnv& depth_env() { static const DepthEnv env; return env; }
 // Tile height of a regulariser launch: workgroups that own 32 x 16 pixels (PY = 2) move a quarter less through LDS per owned pixel and
 // recompute a sixth less of K5 than 32 x 8 ones — where the launch has enough of them to fill the chip (several maps, large frames:
 // -19 % for the 32-map pass, -6 % at 3840x2160); one 640x480 map is 1200 short workgroups or 600 long ones on 256 CUs, and the short ones
 // win there (keyframe change 0.085 against 0.097 ms).  32 x 32 (PY = 4, 33.6 KB of LDS) lost everywhere.  profiles/r06_notes.md section 5.
-static inline int lsd_reg_py(long long workgroups_at_py1) {
-  const int forced = depth_env().regPy;
-  if (forced == 1 || forced == 2) return forced;
-  return workgroups_at_py1 >= 2048 ? 2 : 1;
-}
+// (The tests that are there for the PY = 2 arms of single-map and row-part launches take the smallest shapes that reach this threshold —
+// 1024x512: tests/test_gpu_parity.py, tests/test_bands_gpu.py — and assert 2048 workgroups themselves: they move with it.)
+static inline int lsd_reg_py(long long workgroups_at_py1) { return workgroups_at_py1 >= 2048 ? 2 : 1; }
 // grid rows of a regulariser launch over `units` tile rows of 8 map rows each
 static inline int lsd_reg_grid_rows(int units, int py) { return (units + py - 1) / py; }
 #define LSD_REG_DISPATCH(py, ...) do { if ((py) == 2) { constexpr int PYV = 2; __VA_ARGS__; } else { constexpr int PYV = 1; __VA_ARGS__; } } while (0)
 #define LSD_RESCALE_PX 2048    // pixels per workgroup of k_kf_rescale_setdepth
+// createKeyFrame's rescale (DepthMap.cpp:1286-1304): the factor numIdepth / sumIdepth with both cast to float first, and a valid pixel's
+// four fields under it; (ids, vars) = the rescaled smoothed pair
+__device__ __forceinline__ float rescale_factor(const double sumIdepth, const double numIdepth) { return (float)numIdepth / (float)sumIdepth; }
+__device__ __forceinline__ void rescale_pixel(const HypPlanes& m, const int i, const float rescaleFactor, float& ids, float& vars) {
+  const float rescaleFactor2 = rescaleFactor * rescaleFactor;
+  m.idepth[i] *= rescaleFactor;
+  ids = m.idepth_s[i] * rescaleFactor;
+  m.idepth_s[i] = ids;
+  m.var[i] *= rescaleFactor2;
+  vars = m.var_s[i] * rescaleFactor2;
+  m.var_s[i] = vars;
+}
 __global__ __launch_bounds__(256) void k_kf_rescale_setdepth(const RescaleItem* __restrict__ items) {
   const RescaleItem& it = items[blockIdx.y];
-  __shared__ double s_a[256], s_b[256];
   const int tid = threadIdx.x;
   // every workgroup adds the tiles' partials in the same fixed order: the same factor everywhere, no second launch, no atomics
-  double sa = 0, sb = 0;
-  for (int i = tid; i < it.nSumPartials; i += 256) { sa += it.sumPartials[2 * i]; sb += it.sumPartials[2 * i + 1]; }
-  s_a[tid] = sa; s_b[tid] = sb;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) { s_a[tid] += s_a[tid + off]; s_b[tid] += s_b[tid + off]; }
-    __syncthreads();
-  }
-  const double sumD = s_a[0], cntD = s_b[0];
+  double sumD = 0, cntD = 0;
+  for (int i = tid; i < it.nSumPartials; i += 256) { sumD += it.sumPartials[2 * i]; cntD += it.sumPartials[2 * i + 1]; }
+  lsd_block_tree_sum(sumD, cntD);
   __syncthreads();
   if (blockIdx.x == 0 && tid == 0) {
     it.slot[0] = sumD; it.slot[1] = cntD; it.slot[2] = (double)it.flags[0];
     it.flags[0] = 0; it.flags[1] = 0;
   }
-  // rescaleFactor = numIdepth / sumIdepth with both cast to float first (DepthMap.cpp:1286-1294)
-  const float rescaleFactor = (float)cntD / (float)sumD;
-  const float rescaleFactor2 = rescaleFactor * rescaleFactor;
-  double s = 0;
-  int c = 0;
+  const float rescaleFactor = rescale_factor(sumD, cntD);
+  double s = 0, c = 0;
 #pragma unroll
   for (int k = 0; k < LSD_RESCALE_PX / 256; k++) {
     const int i = blockIdx.x * LSD_RESCALE_PX + k * 256 + tid;
     if (i < it.n) {
       float ids = -1.f, vars = -1.f;
       const bool valid = it.m.valid[i] != 0;
-      if (valid) {
-        it.m.idepth[i] *= rescaleFactor;
-        ids = it.m.idepth_s[i] * rescaleFactor;
-        it.m.idepth_s[i] = ids;
-        it.m.var[i] *= rescaleFactor2;
-        vars = it.m.var_s[i] * rescaleFactor2;
-        it.m.var_s[i] = vars;
-      }
-      // Frame::setDepth (Frame.cpp:199-243)
-      if (valid && (double)ids >= -0.05) {
-        it.id0[i] = ids;
-        it.var0[i] = vars;
-        s += ids;
-        c += 1;
-      } else {
-        it.id0[i] = -1.f;
-        it.var0[i] = -1.f;
-      }
+      if (valid) rescale_pixel(it.m, i, rescaleFactor, ids, vars);
+      if (set_depth_pixel(it.id0, it.var0, i, valid, ids, vars)) { s += ids; c += 1; }
     }
   }
-  s_a[tid] = s; s_b[tid] = (double)c;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (tid < off) { s_a[tid] += s_a[tid + off]; s_b[tid] += s_b[tid + off]; }
-    __syncthreads();
-  }
-  if (tid == 0) { it.statPartials[2 * blockIdx.x] = s_a[0]; it.statPartials[2 * blockIdx.x + 1] = s_b[0]; }
+  lsd_block_tree_sum(s, c);
+  if (tid == 0) { it.statPartials[2 * blockIdx.x] = s; it.statPartials[2 * blockIdx.x + 1] = c; }
 }
 
 // parts of the fused fill-holes + regularise pass of several maps in one launch (row-band decomposition: the windows of one process),
 // blockIdx.z = part
 template <int PY>
-__global__ __launch_bounds__(256) void k_reg_rows_batch(const RegBatchItem* __restrict__ items) {
-  const RegBatchItem& it = items[blockIdx.z];
-  reg_fused_tile<true, false, false, false, false, PY>(it.a, nullptr, nullptr, nullptr);
+__global__ __launch_bounds__(256) void k_reg_rows_batch(const RegItem* __restrict__ items) {
+  reg_fused_tile<PassUpdate, PY>(items[blockIdx.z]);
 }
 
-// K8: Frame::setDepth (Frame.cpp:199-243) + per-workgroup (sum, count) partials for meanIdepth / numPoints
+// K8: Frame::setDepth + per-workgroup (sum, count) partials for meanIdepth / numPoints
 __global__ __launch_bounds__(256) void k_set_depth(HypPlanes m, float* __restrict__ id0, float* __restrict__ var0, int n, double* __restrict__ partials) {
-  __shared__ double s_sum[256];
-  __shared__ int s_cnt[256];
   const int i = blockIdx.x * 256 + threadIdx.x;
   double s = 0;
   int c = 0;
   if (i < n) {
-    float ids = m.idepth_s[i];
-    if (m.valid[i] && (double)ids >= -0.05) {
-      id0[i] = ids;
-      var0[i] = m.var_s[i];
-      s = ids;
-      c = 1;
-    } else {
-      id0[i] = -1.f;
-      var0[i] = -1.f;
-    }
+    const float ids = m.idepth_s[i];
+    if (set_depth_pixel(id0, var0, i, m.valid[i] != 0, ids, m.var_s[i])) { s = ids; c = 1; }
   }
-  s_sum[threadIdx.x] = s;
-  s_cnt[threadIdx.x] = c;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) { s_sum[threadIdx.x] += s_sum[threadIdx.x + off]; s_cnt[threadIdx.x] += s_cnt[threadIdx.x + off]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { partials[2 * blockIdx.x] = s_sum[0]; partials[2 * blockIdx.x + 1] = (double)s_cnt[0]; }
+  lsd_block_tree_sum(s, c);
+  if (threadIdx.x == 0) { partials[2 * blockIdx.x] = s; partials[2 * blockIdx.x + 1] = (double)c; }
 }
 // sum of idepth_smoothed over valid pixels (createKeyFrame rescale, DepthMap.cpp:1286-1294)
 __global__ __launch_bounds__(256) void k_sum_valid_idepth(HypPlanes m, int n, double* __restrict__ partials) {
-  __shared__ double s_sum[256];
-  __shared__ int s_cnt[256];
   const int i = blockIdx.x * 256 + threadIdx.x;
   double s = 0;
   int c = 0;
   if (i < n && m.valid[i]) { s = m.idepth_s[i]; c = 1; }
-  s_sum[threadIdx.x] = s;
-  s_cnt[threadIdx.x] = c;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) { s_sum[threadIdx.x] += s_sum[threadIdx.x + off]; s_cnt[threadIdx.x] += s_cnt[threadIdx.x + off]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { partials[2 * blockIdx.x] = s_sum[0]; partials[2 * blockIdx.x + 1] = (double)s_cnt[0]; }
+  lsd_block_tree_sum(s, c);
+  if (threadIdx.x == 0) { partials[2 * blockIdx.x] = s; partials[2 * blockIdx.x + 1] = (double)c; }
 }
 // out = pinned DeferredSlot (sum, count, flag); dev_out = the same pair in HBM for a kernel that follows (k_rescale)
 __global__ __launch_bounds__(256) void k_reduce_pairs(const double* __restrict__ partials, int nblocks, double* __restrict__ out,
                                                        double* __restrict__ dev_out, const int* __restrict__ flag) {
-  __shared__ double s_a[256], s_b[256];
   double a = 0, b = 0;
   for (int i = threadIdx.x; i < nblocks; i += 256) { a += partials[2 * i]; b += partials[2 * i + 1]; }
-  s_a[threadIdx.x] = a;
-  s_b[threadIdx.x] = b;
-  __syncthreads();
-  for (int off = 128; off > 0; off >>= 1) {
-    if (threadIdx.x < off) { s_a[threadIdx.x] += s_a[threadIdx.x + off]; s_b[threadIdx.x] += s_b[threadIdx.x + off]; }
-    __syncthreads();
-  }
+  lsd_block_tree_sum(a, b);
   if (threadIdx.x == 0) {
-    out[0] = s_a[0]; out[1] = s_b[0]; out[2] = flag ? (double)flag[0] : 0.0;
-    if (dev_out) { dev_out[0] = s_a[0]; dev_out[1] = s_b[0]; }
+    out[0] = a; out[1] = b; out[2] = flag ? (double)flag[0] : 0.0;
+    if (dev_out) { dev_out[0] = a; dev_out[1] = b; }
   }
 }
-// rescale (DepthMap.cpp:1296-1304)
 __global__ __launch_bounds__(256) void k_rescale(HypPlanes m, int n, const double* __restrict__ sumCount) {
-  // rescaleFactor = numIdepth / sumIdepth with both cast to float first (DepthMap.cpp:1286-1294)
-  const float sumIdepth = (float)sumCount[0], numIdepth = (float)sumCount[1];
-  const float rescaleFactor = numIdepth / sumIdepth;
-  const float rescaleFactor2 = rescaleFactor * rescaleFactor;
+  const float rescaleFactor = rescale_factor(sumCount[0], sumCount[1]);
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n || !m.valid[i]) return;
-  m.idepth[i] *= rescaleFactor;
-  m.idepth_s[i] *= rescaleFactor;
-  m.var[i] *= rescaleFactor2;
-  m.var_s[i] *= rescaleFactor2;
+  float ids, vars;
+  rescale_pixel(m, i, rescaleFactor, ids, vars);
 }
 
 // phase A: every valid source hypothesis computes its target pixel and candidate, and registers in the target's slot list
@@ -1599,15 +1503,8 @@ __device__ __forceinline__ void prop_resolve_pixel(const PropArgs& a, const int 
     }
   }
   a.dst.valid[i] = tValid ? 1 : 0;
-  a.dst.blacklisted[i] = 0;
-  if (tValid) {
-    a.dst.nextID[i] = 0;
-    a.dst.validity[i] = t_validity;
-    a.dst.idepth[i] = t_idepth;
-    a.dst.var[i] = t_var;
-    a.dst.idepth_s[i] = -1;
-    a.dst.var_s[i] = -1;
-  }
+  if (tValid) store_fresh_hypothesis(a.dst, i, t_idepth, t_var, t_validity);
+  else a.dst.blacklisted[i] = 0;
   // clean at rest: the next propagation into this scratch starts without clears
   if (cnt != 0) a.slotCount[i] = 0;
   if (cnt > PROP_SLOT_CAP) a.ovfHead[i] = -1;      // (a chain exists only where the slots overflowed)
@@ -1641,9 +1538,8 @@ __global__ __launch_bounds__(256) void k_init_gt(HypPlanes m, const float* __res
 __global__ __launch_bounds__(256) void k_take_react(HypPlanes m, float* __restrict__ id, float* __restrict__ var, uint8_t* __restrict__ val, int n) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
-  if (m.valid[i]) { id[i] = m.idepth[i]; var[i] = m.var[i]; val[i] = (uint8_t)m.validity[i]; }
-  else if (m.blacklisted[i] < MIN_BLACKLIST) var[i] = -2;
-  else var[i] = -1;
+  const bool valid = m.valid[i] != 0;
+  take_react_pixel(id, var, val, i, valid, valid ? m.idepth[i] : 0.f, valid ? m.var[i] : 0.f, valid ? m.validity[i] : 0, valid ? 0 : m.blacklisted[i]);
 }
 // setFromExistingKF (DepthMap.cpp:937-959)
 __global__ __launch_bounds__(256) void k_from_react(HypPlanes m, const float* __restrict__ id, const float* __restrict__ var, const uint8_t* __restrict__ val, int n) {
@@ -1651,8 +1547,8 @@ __global__ __launch_bounds__(256) void k_from_react(HypPlanes m, const float* __
   if (i >= n) return;
   float v = var[i];
   if (v > 0) {
-    m.valid[i] = 1; m.blacklisted[i] = 0; m.nextID[i] = 0; m.validity[i] = val[i];
-    m.idepth[i] = id[i]; m.var[i] = v; m.idepth_s[i] = -1; m.var_s[i] = -1;
+    m.valid[i] = 1;
+    store_fresh_hypothesis(m, i, id[i], v, val[i]);
   } else {
     m.valid[i] = 0;
     m.blacklisted[i] = (v == -2) ? MIN_BLACKLIST - 1 : 0;
@@ -1842,8 +1738,8 @@ static RegArgs reg_args(lsdhip_depthmap* dm, int validityTH) {
 static void swap_valid(lsdhip_depthmap* dm) { uint8_t* v = (uint8_t*)dm->cur.valid; dm->cur.valid = lsd_g(dm->d_validSnap); dm->d_validSnap = v; }
 // One map's record of a batched regulariser pass on the planes as they stand (it reads cur.valid and writes the spare plane: the caller
 // swaps them, as fill_regularize does).  setDepthOf: the keyframe whose level-0 planes the pass also writes (Frame::setDepth), or null.
-static RegBatchItem reg_item(lsdhip_depthmap* dm, lsdhip_frame* setDepthOf, double* partials) {
-  RegBatchItem r;
+static RegItem reg_item(lsdhip_depthmap* dm, lsdhip_frame* setDepthOf, double* partials) {
+  RegItem r;
   memset((void*)&r, 0, sizeof(r));
   r.a = reg_args(dm, VAL_SUM_MIN_FOR_KEEP);
   r.id0 = lsd_g(setDepthOf ? lsd_depth_w(setDepthOf)[0] : nullptr);
@@ -1867,8 +1763,8 @@ static int regularize(lsdhip_depthmap* dm, bool removeOcclusions, int validityTH
   RegArgs a = reg_args(dm, validityTH);
   const RegGrid g = reg_grid(c, tile_rows(c), 1);
   LSD_REG_DISPATCH(g.py,
-    if (removeOcclusions) hipLaunchKernelGGL((k_reg_fused<false, true, false, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr);
-    else hipLaunchKernelGGL((k_reg_fused<false, false, false, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr));
+    if (removeOcclusions) hipLaunchKernelGGL((k_reg_fused<PassRegOcc, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), RegItem{a, nullptr, nullptr, nullptr});
+    else hipLaunchKernelGGL((k_reg_fused<PassRegOnly, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), RegItem{a, nullptr, nullptr, nullptr}));
   HIPCHK(hipGetLastError());
   swap_valid(dm);
   return LSDHIP_OK;
@@ -1882,9 +1778,10 @@ static int fill_regularize(lsdhip_depthmap* dm, int validityTH, bool setDepth) {
   const RegGrid g = reg_grid(c, tile_rows(c), 1);
   LSD_REG_DISPATCH(g.py,
     if (setDepth)
-      hipLaunchKernelGGL((k_reg_fused<true, false, true, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, lsd_depth_w(kf)[0], lsd_depthvar_w(kf)[0], dm->d_red + 16);
+      hipLaunchKernelGGL((k_reg_fused<PassUpdateSetDepth, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c),
+                         RegItem{a, lsd_g(lsd_depth_w(kf)[0]), lsd_g(lsd_depthvar_w(kf)[0]), lsd_g(dm->d_red + 16)});
     else
-      hipLaunchKernelGGL((k_reg_fused<true, false, false, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr));
+      hipLaunchKernelGGL((k_reg_fused<PassUpdate, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), RegItem{a, nullptr, nullptr, nullptr}));
   HIPCHK(hipGetLastError());
   swap_valid(dm);
   if (setDepth) return set_depth_finish(dm, g.tiles());
@@ -1912,7 +1809,7 @@ static int fill_regularize_rows(lsdhip_depthmap* dm, int validityTH, int tileRow
     a.tileRow0 = tileRow0;
     a.tileRows = nTileRows;
     const RegGrid g = reg_grid(c, nTileRows, 1);
-    LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL((k_reg_fused<true, false, false, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), a, nullptr, nullptr, nullptr));
+    LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL((k_reg_fused<PassUpdate, PYV>), g.grid, dim3(256), 0, lsd_map_stream(c), RegItem{a, nullptr, nullptr, nullptr}));
     HIPCHK(hipGetLastError());
   }
   if (last) swap_valid(dm);
@@ -2056,7 +1953,7 @@ static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n, bool countWo
 #ifdef LSD_PHASE_TRACE
     constexpr int rows = 8;   // the trace buffer is laid out for 32x8 tiles
 #else
-    const int rows = depth_env().obsRows;
+    constexpr int rows = 2;
 #endif
     const dim3 grid((c->w + 31) / 32, (c->h + rows - 1) / rows);
     const int nwaves = (int)(grid.x * grid.y) * (rows * 32 / 64);
@@ -2071,16 +1968,8 @@ static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n, bool countWo
       }
       if (dm->obsCounterWaves == nwaves) a.counters = lsd_g(dm->d_obsCounters);
     }
-    if (rows == 8) {
-      if (n == 1) hipLaunchKernelGGL((k_observe<true, 8>), grid, dim3(256), 0, lsd_map_stream(c), a);
-      else hipLaunchKernelGGL((k_observe<false, 8>), grid, dim3(256), 0, lsd_map_stream(c), a);
-    } else if (rows == 4) {
-      if (n == 1) hipLaunchKernelGGL((k_observe<true, 4>), grid, dim3(128), 0, lsd_map_stream(c), a);
-      else hipLaunchKernelGGL((k_observe<false, 4>), grid, dim3(128), 0, lsd_map_stream(c), a);
-    } else {
-      if (n == 1) hipLaunchKernelGGL((k_observe<true, 2>), grid, dim3(64), 0, lsd_map_stream(c), a);
-      else hipLaunchKernelGGL((k_observe<false, 2>), grid, dim3(64), 0, lsd_map_stream(c), a);
-    }
+    if (n == 1) hipLaunchKernelGGL((k_observe<true, rows>), grid, dim3(32 * rows), 0, lsd_map_stream(c), a);
+    else hipLaunchKernelGGL((k_observe<false, rows>), grid, dim3(32 * rows), 0, lsd_map_stream(c), a);
     dm->lowGradHypPossible = false;   // (the pass drops a hypothesis on a pixel below the gradient threshold: observe_front)
   }
   if (a.counters) hipLaunchKernelGGL(k_obs_count_sum, dim3(1), dim3(256), 0, lsd_map_stream(c), (const unsigned long long*)dm->d_obsCounters, dm->obsCounterWaves, dm->d_obsAcc);
@@ -2187,7 +2076,7 @@ static void timing_collect(lsdhip_depthmap* dm, bool all) {
 constexpr int EV_SKIP = -1000;
 static int timing_begin(lsdhip_depthmap* dm, int kind) {
   if (kind < 3) {
-    const unsigned period = depth_env().eventsAll ? 1u : (kind == 0 ? 7u : 2u);
+    const unsigned period = kind == 0 ? 7u : 2u;
     if ((dm->ev_tick[kind]++ % period) != 0) return EV_SKIP;
   }
   const int i = dm->ev_next;
@@ -2347,14 +2236,14 @@ struct PyramidJobs {
   int launch() { return lsd_frame_build_idepth_pyramid_batch(frames.data(), (int)frames.size(), parts.data(), 0, outs.data(), nParts.data()); }
 };
 
-// The argument record of a batched update, sub-records on 256-byte boundaries: ObserveArgs x n | RegBatchItem x n | int x n (the search
+// The argument record of a batched update, sub-records on 256-byte boundaries: ObserveArgs x n | RegItem x n | int x n (the search
 // queues' fill counts).  One layout for the pinned host copy and its device twin: the views take either base.
 struct UpdateRecord {
   size_t regOff, qcountOff, bytes;
   explicit UpdateRecord(int n)
-      : regOff(up256(sizeof(ObserveArgs) * (size_t)n)), qcountOff(regOff + up256(sizeof(RegBatchItem) * (size_t)n)), bytes(qcountOff + sizeof(int) * (size_t)n) {}
+      : regOff(up256(sizeof(ObserveArgs) * (size_t)n)), qcountOff(regOff + up256(sizeof(RegItem) * (size_t)n)), bytes(qcountOff + sizeof(int) * (size_t)n) {}
   ObserveArgs* obs(void* base) const { return (ObserveArgs*)base; }
-  RegBatchItem* reg(void* base) const { return (RegBatchItem*)((uint8_t*)base + regOff); }
+  RegItem* reg(void* base) const { return (RegItem*)((uint8_t*)base + regOff); }
   int* qcount(void* base) const { return (int*)((uint8_t*)base + qcountOff); }
 };
 
@@ -2406,12 +2295,12 @@ static int update_batch_observe(lsdhip_ctx* c, int n, const ObserveArgs* dobs, c
   return lsd_bprof_end(c, bp, ms, (double)n * c->w * c->h);
 }
 // the regulariser pass: the maps whose keyframe is due for Frame::setDepth in one launch, the others in its twin
-static int update_batch_regularize(lsdhip_ctx* c, int n, const RegBatchItem* dreg, const RegGrid& g, int nSet, hipStream_t ms) {
+static int update_batch_regularize(lsdhip_ctx* c, int n, const RegItem* dreg, const RegGrid& g, int nSet, hipStream_t ms) {
   const int bp = lsd_bprof_begin(c, 2, ms);
   if (bp < -1) return bp;
   LSD_REG_DISPATCH(g.py,
-    if (nSet > 0) hipLaunchKernelGGL((k_reg_fused_batch<true, PYV>), g.grid, dim3(256), 0, ms, dreg);
-    if (nSet < n) hipLaunchKernelGGL((k_reg_fused_batch<false, PYV>), g.grid, dim3(256), 0, ms, dreg));
+    if (nSet > 0) hipLaunchKernelGGL((k_reg_fused_batch<PassUpdateSetDepth, PYV>), g.grid, dim3(256), 0, ms, dreg);
+    if (nSet < n) hipLaunchKernelGGL((k_reg_fused_batch<PassUpdate, PYV>), g.grid, dim3(256), 0, ms, dreg));
   if (int rc = lsd_bprof_end(c, bp, ms, (double)n * c->w * c->h)) return rc;
   HIPCHK(hipGetLastError());
   return LSDHIP_OK;
@@ -2451,11 +2340,10 @@ extern "C" int lsdhip_depth_update_batch(int n, lsdhip_depthmap** maps, lsdhip_f
   double t0 = now_ms();
   if (int rcb = lsd_m_begin(c)) return rcb;
   const hipStream_t ms = lsd_map_stream(c);
-  const DepthEnv& env = depth_env();
   lsdhip_ctx::BatchForm form;     // what this call runs: becomes c->batchForm[0] once everything is queued
   form.n = n;
-  form.split = env.obsSplit && n >= LSD_OBS_SPLIT_MIN_MAPS && n <= LSD_OBS_WALK_MAX_MAPS;
-  form.walkWorkgroups = form.split ? env.walkWaves : 0;
+  form.split = n >= LSD_OBS_SPLIT_MIN_MAPS && n <= LSD_OBS_WALK_MAX_MAPS;
+  form.walkWorkgroups = form.split ? LSD_OBS_WALK_WAVES : 0;
   if (form.split)
     for (int j = 0; j < n; j++)
       if (!maps[j]->d_obsQueue) HIPCHK(hipMalloc((void**)&maps[j]->d_obsQueue, (size_t)c->w * c->h * sizeof(float4)));
@@ -2464,7 +2352,7 @@ extern "C" int lsdhip_depth_update_batch(int n, lsdhip_depthmap** maps, lsdhip_f
   if (int rc = lsd_args_begin(c, L.bytes, &host, &dev)) return rc;
   form.qcountDev = L.qcount(dev); form.argsSerial = c->args.serial; form.argsGen = c->args.gen;   // (the record's place in the ring: lsdhip_ctx_batch_form)
   std::vector<int> due;
-  bool candidates = env.obsCand;
+  bool candidates = true;
   update_batch_items(n, maps, refs, L, host, dev, form.split, due, &candidates);
   form.nSet = (int)due.size();
   form.candidates = form.split && candidates;
@@ -2577,16 +2465,16 @@ struct ChangeTxn {
     if (timing) (void)timing_end(maps[0], ev);     // (keeps the event pair of the timing sample balanced)
   }
 };
-// The argument record of a keyframe change, sub-records on 256-byte boundaries: KfItem x n | RegBatchItem x n (the pass that removes
-// occlusions) | RegBatchItem x n (fill holes + regularise) | RescaleItem x n.  One layout for the pinned host copy and its device twin.
+// The argument record of a keyframe change, sub-records on 256-byte boundaries: KfItem x n | RegItem x n (the pass that removes
+// occlusions) | RegItem x n (fill holes + regularise) | RescaleItem x n.  One layout for the pinned host copy and its device twin.
 struct ChangeRecord {
   size_t occOff, fillOff, resOff, bytes;
   explicit ChangeRecord(int n)
-      : occOff(up256(sizeof(KfItem) * (size_t)n)), fillOff(occOff + up256(sizeof(RegBatchItem) * (size_t)n)),
-        resOff(fillOff + up256(sizeof(RegBatchItem) * (size_t)n)), bytes(resOff + up256(sizeof(RescaleItem) * (size_t)n)) {}
+      : occOff(up256(sizeof(KfItem) * (size_t)n)), fillOff(occOff + up256(sizeof(RegItem) * (size_t)n)),
+        resOff(fillOff + up256(sizeof(RegItem) * (size_t)n)), bytes(resOff + up256(sizeof(RescaleItem) * (size_t)n)) {}
   KfItem* kf(void* base) const { return (KfItem*)base; }
-  RegBatchItem* occ(void* base) const { return (RegBatchItem*)((uint8_t*)base + occOff); }
-  RegBatchItem* fill(void* base) const { return (RegBatchItem*)((uint8_t*)base + fillOff); }
+  RegItem* occ(void* base) const { return (RegItem*)((uint8_t*)base + occOff); }
+  RegItem* fill(void* base) const { return (RegItem*)((uint8_t*)base + fillOff); }
   RescaleItem* res(void* base) const { return (RescaleItem*)((uint8_t*)base + resOff); }
 };
 
@@ -2655,9 +2543,9 @@ static int change_launch(lsdhip_ctx* c, int n, const ChangeRecord& L, void* dev,
   const KfItem* dkf = L.kf(dev);
   LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL(k_kf_finalize_prop<PYV>, g.grid, dim3(256), 0, ms, dkf));
   hipLaunchKernelGGL(k_prop_resolve_batch, dim3(px_blocks(c), n), dim3(256), 0, ms, dkf);
-  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL((k_kf_reg<false, true, PYV>), g.grid, dim3(256), 0, ms, (const RegBatchItem*)L.occ(dev)));
-  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL((k_kf_reg<true, false, PYV>), g.grid, dim3(256), 0, ms, (const RegBatchItem*)L.fill(dev)));
-  hipLaunchKernelGGL(k_kf_rescale_setdepth, dim3(nwg5, n), dim3(256), 0, ms, (const RescaleItem*)L.res(dev));
+  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL((k_kf_reg<PassRegOcc, PYV>), g.grid, dim3(256), 0, ms, L.occ(dev)));
+  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL((k_kf_reg<PassKfFillSums, PYV>), g.grid, dim3(256), 0, ms, L.fill(dev)));
+  hipLaunchKernelGGL(k_kf_rescale_setdepth, dim3(nwg5, n), dim3(256), 0, ms, L.res(dev));
   HIPCHK(hipGetLastError());
   return LSDHIP_OK;
 }
@@ -2907,9 +2795,9 @@ extern "C" int lsdhip_depth_stage_rows_batch(lsdhip_ctx* c, int n, lsdhip_depthm
   }
   void* host = nullptr;
   void* dev = nullptr;
-  int rc = lsd_args_begin(c, sizeof(RegBatchItem) * (size_t)n, &host, &dev);
+  int rc = lsd_args_begin(c, sizeof(RegItem) * (size_t)n, &host, &dev);
   if (rc) return rc;
-  RegBatchItem* items = (RegBatchItem*)host;
+  RegItem* items = (RegItem*)host;
   for (int k = 0; k < n; k++) {
     items[k] = reg_item(maps[k], nullptr, nullptr);
     items[k].a.tileRow0 = tile_row0[k];
@@ -2919,7 +2807,7 @@ extern "C" int lsdhip_depth_stage_rows_batch(lsdhip_ctx* c, int n, lsdhip_depthm
   rc = lsd_args_commit(c, ms);
   if (rc) return rc;
   const RegGrid g = reg_grid(c, maxRows, n, rowsInAll);
-  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL(k_reg_rows_batch<PYV>, g.grid, dim3(256), 0, ms, (const RegBatchItem*)dev));
+  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL(k_reg_rows_batch<PYV>, g.grid, dim3(256), 0, ms, (const RegItem*)dev));
   HIPCHK(hipGetLastError());
   rc = lsd_args_release(c, dev, ms);
   if (rc) return rc;

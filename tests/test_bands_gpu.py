@@ -137,3 +137,27 @@ def test_native_band_loop_two_processes_over_ipc(tmp_path, bands, overlap):
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     res = json.load(open(out))
     assert res["ok"] and res["flag_waits_failed"] == [0, 0] and res["valid"] > 10000, res
+
+
+def test_native_band_loop_one_launch_of_32x16_tiles_1024x512():
+    """1024x512 in two bands with the exchange after the pass (set_overlap(False)): the parts of a pass go into ONE k_reg_rows_batch launch,
+    and 32 tile columns x at least 64 tile rows in all = 2048 workgroups of 32x8 pixels is where lsd_reg_py takes the 32x16 tile
+    (k_reg_rows_batch<2>; every other shape of this file stays below it).  Bit-exact against the full-frame pass."""
+    from lsd_slam_amd.bands import NativeBandRegularizer
+    w, H, world, passes = 1024, 512, 2, 2
+    assert ((w + 31) // 32) * (H // 8) >= 2048
+    hyp, maxgrad = synth_s3(w, H)
+    full = HipBandEngine(w, H)
+    full.load(hyp, maxgrad)
+    for _ in range(passes):
+        full.run_pass()
+    ref = full.get()
+    assert int((ref["isValid"] > 0).sum()) > 50_000
+    nb = NativeBandRegularizer(w, H, world, list(range(world)))
+    nb.set_overlap(False)
+    nb.load(hyp, maxgrad)
+    nb.run(passes)
+    for r, rows in nb.owned_rows().items():
+        y0, y1 = nb.plan.owned[r]
+        _rows_equal(rows, ref[y0:y1], "1024x512 band %d of %d" % (r, world))
+    nb.close()

@@ -495,3 +495,33 @@ def test_batch_form_query_reports_unavailable_counts(oracle, hip):
     ctx.synchronize()
     ctx.set_async(False)
     assert got["n"] == n and got["split"] and got["queued"] == -1 and got["chunks"] == -1 and got["queueCounts"] is None, got
+
+
+def test_observe_work_of_one_update_counts_what_the_split_call_queues(oracle, hip):
+    """176x144, a synchronous context under lsdhip_prof_enable: one lsdhip_depth_update with one reference frame is sampled, so k_observe<true, 2>
+    counts its searches and walk steps per wave (observe_count) and k_obs_count_sum adds them up behind it — the path that only the benchmark
+    reads.  The search count is held to the queue count of a map in the same state that a 4-map select + walk call updates with the same
+    frame: both count the pixels that pass the front half's tests."""
+    from lsd_slam_amd import capi
+    w, h, n = 176, 144, 4
+    twins = build_twins(oracle, w, h, n)
+    ctx = hip.Context(w, h, twins[0].K)
+    upload_twins(hip, ctx, twins)
+    t = twins[0]
+    inputs = [frame_inputs(oracle, tj, 3, True, 31 * 3 + j) for j, tj in enumerate(twins)]
+    kf1 = hip.Frame(ctx, 0, t.frames[0])
+    kf1.setDepthFromGroundTruth(t.depth0)
+    dm1 = hip.DepthMap(ctx)
+    dm1.setCurrentDepthMap(kf1, t.hyp0, reactivated=t.react)
+    ctx.prof_enable(True)
+    dm1.updateKeyframe([device_frame(hip, ctx, t, 3, inputs[0], kf1)])
+    ctx.prof_enable(False)
+    work = np.zeros(3, np.float64)
+    capi.check(dm1.L.lsdhip_depth_observe_work(dm1.h_, work.ctypes.data))
+    fgs = [device_frame(hip, ctx, tj, 3, inputs[j], tj.dev["kf"]) for j, tj in enumerate(twins)]
+    hip.DepthMap.updateKeyframeBatch([tj.dev["dm"] for tj in twins], fgs)
+    got = assert_form(ctx, "update", dict(SPLIT_ALL, n=n), "observe work")
+    print("observe work: launches %d, searches %d, walk steps %d; queue counts %r" % (work[0], work[1], work[2], got["queueCounts"][:n]))
+    assert work[0] == 1, work
+    assert got["queueCounts"][0] > 0 and work[1] == got["queueCounts"][0], (work, got)
+    assert work[2] > 0, work

@@ -512,6 +512,33 @@ def test_depth_stages_bit_exact(oracle, hip, w, h, params):
     assert_hyp_equal(dmg.currentDepthMap(), dmo.get(), "observeDepth (2nd)")
 
 
+def test_single_map_regulariser_passes_on_32x16_tiles_1024x512(oracle, hip):
+    """1024x512 = 32 x 64 = 2048 workgroups of 32x8 pixels: the smallest single map whose regulariser launches take the 32x16 tile
+    (lsd_reg_py: PY = 2 from 2048 workgroups on).  regularizeDepthMap(false) and (true) as launches of their own
+    (k_reg_fused<PassRegOnly, 2>, <PassRegOcc, 2>), then two updateKeyframe calls: the first finds the keyframe due for Frame::setDepth
+    (k_reg_fused<PassUpdateSetDepth, 2>), the second does not (k_reg_fused<PassUpdate, 2>)."""
+    w, h = 1024, 512
+    assert ((w + 31) // 32) * ((h + 7) // 8) == 2048
+    frames, depth0, K, gt, ctx = make_pair(oracle, hip, w, h, 3)
+    kfo, kfg, dmo, dmg = _noisy_map(oracle, hip, ctx, frames, depth0, K, w, h, op=oracle_params(oracle))
+    dmo.stage("regularize")
+    dmg.stage("regularize")
+    assert_hyp_equal(dmg.currentDepthMap(), dmo.get(), "regularize<false>, PY = 2")
+    dmo.stage("regularize_occ")
+    dmg.stage("regularize_occ")
+    assert_hyp_equal(dmg.currentDepthMap(), dmo.get(), "regularize<true>, PY = 2")
+    kfo.set_counters(7, 3, 3, 0)
+    kfg.setCounters(7, 3, 3, 0)
+    fos, fgs = _ref_frames(oracle, hip, ctx, frames, K, gt, kfo, kfg, [1, 2])
+    for i, what in enumerate(("updateKeyframe with Frame::setDepth, PY = 2", "updateKeyframe, PY = 2")):
+        assert kfg.stats()["depthHasBeenUpdatedFlag"] == i
+        dmo.update([fos[i]])
+        dmg.updateKeyframe([fgs[i]])
+        assert_hyp_equal(dmg.currentDepthMap(), dmo.get(), what)
+        for lvl in range(5):
+            assert_bit_equal(kfg.idepth(lvl), kfo.plane("idepth", lvl), what + " keyframe idepth L%d" % lvl)
+
+
 def test_observe_reactivated_and_no_masks(oracle, hip):
     w, h = 320, 240
     frames, depth0, K, gt, ctx = make_pair(oracle, hip, w, h, 8)
