@@ -30,6 +30,7 @@
 #ifndef LSD_SLAM_HIP_HPP
 #define LSD_SLAM_HIP_HPP
 
+#include <array>
 #include <chrono>
 #include <cmath>
 #include <cstdint>
@@ -47,6 +48,7 @@
 #include <vector>
 
 #include "lsdhip.h"
+#include "lsd_slam_hip_pose.hpp"
 
 namespace lsd_slam_hip {
 
@@ -690,6 +692,18 @@ class DepthMap {
     check(lsdhip_depth_change_keyframe_batch((int)ms.size(), ms.data(), fs.data(), nullptr), "lsdhip_depth_change_keyframe_batch");
   }
   void changeKeyframe(Frame* new_keyframe) { changeKeyframeBatch({this}, {new_keyframe}); timings(); }
+  // finalizeKeyFrame() + setFromExistingKF(oldKeyframes[j]) of several sequences' maps (one context) in three shared launches and
+  // without a host wait on a pipelined context (lsdhip_depth_reactivate_keyframe_batch): the keyframe change when
+  // findRePositionCandidate found a banked keyframe (SlamSystem.cpp:507-540)
+  static void reactivateKeyframeBatch(const std::vector<DepthMap*>& maps, const std::vector<Frame*>& oldKeyframes) {
+    if (maps.empty()) return;
+    std::vector<lsdhip_depthmap*> ms;
+    std::vector<lsdhip_frame*> fs;
+    for (DepthMap* m : maps) ms.push_back(m->h_);
+    for (Frame* f : oldKeyframes) fs.push_back(f->handle());
+    check(lsdhip_depth_reactivate_keyframe_batch((int)ms.size(), ms.data(), fs.data()), "lsdhip_depth_reactivate_keyframe_batch");
+  }
+  void reactivateKeyframe(Frame* old_keyframe) { reactivateKeyframeBatch({this}, {old_keyframe}); timings(); }
   // GPU time (ms, summed) and call counts of updateKeyframe [0] / createKeyFrame [1] / finalizeKeyFrame [2]; synchronises
   void gpuTimes(double ms[3], long long calls[3]) { check(lsdhip_depth_gpu_times(h_, ms, calls), "lsdhip_depth_gpu_times"); }
   void finalizeKeyFrame() { check(lsdhip_depth_finalize(h_), "lsdhip_depth_finalize"); timings(); }
@@ -877,7 +891,17 @@ class SlamLoop {
         // the mapper promoted pendingKF_ (createNewCurrentKeyframe) while this frame was being tracked on the old keyframe: the next
         // frame is tracked on the new one, from se3FromSim3(newKeyframe^-1 * thisFrame) (SlamSystem.cpp:907-920)
         double p[7];
-        check(lsdhip_frame_relative_pose(pendingKF_->handle(), frame->handle(), p), "lsdhip_frame_relative_pose");
+        if (pendingIsReactivated_) {
+          // a banked keyframe came back: it is neither this frame's tracking parent nor its parent's child, so the estimate is the
+          // general product over the host's world poses, this frame's being camToWorld(its keyframe) * sim3(frameToKeyframe, 1)
+          double f2k[8], frameToWorld[8];
+          est.to7(f2k); f2k[7] = 1;
+          lsd_slam::pose::sim3_mul(worldPose(*trackKF_).data(), f2k, frameToWorld);
+          lsd_slam::pose::relative_se3(worldPose(*pendingKF_).data(), frameToWorld, p);
+          pendingIsReactivated_ = false;
+        } else {
+          check(lsdhip_frame_relative_pose(pendingKF_->handle(), frame->handle(), p), "lsdhip_frame_relative_pose");
+        }
         lastFrameToKF_ = SE3::from7(p);
         trackKF_ = pendingKF_;
         pendingKF_.reset();
@@ -909,9 +933,18 @@ class SlamLoop {
       // minVal = 0.2 * 0.7 (SURVEY.md §8(d) driver notes)
       const float mi = keyframe->meanIdepth();
       const float d0 = (float)est.t[0] * mi, d1 = (float)est.t[1] * mi, d2 = (float)est.t[2] * mi;
-      createNewKeyFrame = keyframeScore(d0 * d0 + d1 * d1 + d2 * d2, tracker.pointUsage) > 0.2f * 0.7f;
+      float minVal = 0.2f * 0.7f;
+      if (reactivateKeyframes) {
+        // with the keyframes kept, keyframesAll.size() is the bank's size (SlamSystem.cpp:1001-1003)
+        const int size = bank_->size();
+        minVal = std::fmin(0.2f + size * 0.8f / 5 /* INITIALIZATION_PHASE_COUNT */, 1.0f);
+        if (size < 5) minVal = (float)(minVal * 0.7);
+      }
+      createNewKeyFrame = keyframeScore(d0 * d0 + d1 * d1 + d2 * d2, tracker.pointUsage) > minVal;
     }
-    if (createNewKeyFrame) {
+    if (createNewKeyFrame && reactivateKeyframes) {
+      changeKeyframeWithReactivation(frame, est);
+    } else if (createNewKeyFrame) {
       numKeyframesFinished_++;
       mappedOnKF_ = 0;
       if (onKeyframeFinished || !sharedKeyframeChange) {
@@ -961,7 +994,132 @@ class SlamLoop {
   bool keepKeyframes = false;                        // keep every keyframe alive in keyframeLog (validation: rescale factors)
   std::vector<std::shared_ptr<Frame>> keyframeLog;
 
+  // ---- re-activation of banked keyframes: the SLAMEnabled branches of SlamSystem::finishCurrentKeyframe (SlamSystem.cpp:395-426) and
+  // SlamSystem::changeKeyframe(false, true, 1.0f) (:507-540).  Off by default: a loop that never calls enableReactivation runs none of it.
+  bool reactivateKeyframes = false;
+  // one record per keyframe change of a loop with re-activation on: the frame that triggered it, the keyframe finished and the keyframe
+  // that follows (the frame itself, or the banked keyframe found), and what the search looked at (lsdhip_reposition_result)
+  struct KeyframeChange { int frameId, previousKfId, newKfId; bool reactivated; int numPotential, numChecked, numTracked; };
+  std::vector<KeyframeChange> keyframeChanges;
+  long numReactivations = 0;                         // changes that went back to a banked keyframe
+  long numUnbanked = 0;                              // finished keyframes the full bank could not take: never re-activated
+  // Keeps every finished keyframe in a KeyFrameBank of maxKeyframes slots and, at every keyframe change, first looks for a banked
+  // keyframe to go back to (TrackableKeyFrameSearch::findRePositionCandidate).  Call before the first step().
+  void enableReactivation(int maxKeyframes) {
+    if (frameId_ != 0) throw Error(LSDHIP_E_STATE, "SlamLoop::enableReactivation: switch before the first frame");
+    if (maxKeyframes <= 0) throw Error(LSDHIP_E_ARG, "SlamLoop::enableReactivation: a bank of at least one keyframe");
+    bank_.reset(new KeyFrameBank(Context::get(w_, h_, K_), maxKeyframes));
+    search_.reset(new TrackableKeyFrameSearch(bank_.get(), w_, h_, K_));
+    bankedBySlot_.assign((size_t)maxKeyframes, nullptr);
+    std::array<double, 8> I;
+    lsd_slam::pose::sim3_identity(I.data());
+    worldPoses_[keyframe->id()] = I;                 // the first keyframe is the world frame
+    reactivateKeyframes = true;
+  }
+  const KeyFrameBank* keyframeBank() const { return bank_.get(); }
+  const TrackableKeyFrameSearch* keyframeSearch() const { return search_.get(); }
+  // camToWorld of a keyframe of this loop (8 doubles, lsd_slam_hip_pose.hpp), in double on the host as the reference keeps it
+  const std::array<double, 8>& worldPose(const Frame& kf) const {
+    auto it = worldPoses_.find(kf.id());
+    if (it == worldPoses_.end()) throw Error(LSDHIP_E_STATE, "SlamLoop::worldPose: not a keyframe of this loop");
+    return it->second;
+  }
+
  private:
+  // finishCurrentKeyframe's SLAMEnabled part (SlamSystem.cpp:402-422) for the keyframe that has just been finalised: its permanent
+  // reference into the bank, queued behind the launches that wrote its planes; a keyframe the bank holds has its slot replaced
+  void bankFinishedKeyframe(const std::shared_ptr<Frame>& kf) {
+    const bool firstTime = kf->idxInKeyframes < 0;
+    int slot = -1;
+    const int rc = lsdhip_kfbank_put(bank_->handle(), kf->handle(), &slot);
+    if (rc == LSDHIP_E_CAPACITY) {
+      numUnbanked++;
+      numKeyframesFinished_++;       // (never banked, so never finished twice)
+      return;
+    }
+    check(rc, "lsdhip_kfbank_put");
+    kf->idxInKeyframes = slot;
+    const std::array<double, 8>& p = worldPose(*kf);
+    Sim3 camToWorld;
+    for (int i = 0; i < 4; i++) camToWorld.q[i] = p[i];
+    for (int i = 0; i < 3; i++) camToWorld.t[i] = p[4 + i];
+    camToWorld.s = p[7];
+    bank_->setMeta(slot, camToWorld, kf->meanIdepth());
+    bankedBySlot_[(size_t)slot] = kf;
+    if (firstTime) numKeyframesFinished_++;          // keyframesAll grows for idxInKeyframes < 0 only (SlamSystem.cpp:408-412)
+  }
+  // SlamSystem::doMappingIteration's keyframe change with doKFReActivation (SlamSystem.cpp:783-791): finishCurrentKeyframe, then
+  // changeKeyframe(false, true, 1.0f) — a banked keyframe comes back (loadNewCurrentKeyframe, :491-505) or `frame` is promoted
+  void changeKeyframeWithReactivation(const std::shared_ptr<Frame>& frame, const SE3& est) {
+    // the candidate's getScaledCamToWorld(): camToWorld(current keyframe) * sim3(frameToKeyframe, 1)
+    double f2k[8], cw[8];
+    est.to7(f2k); f2k[7] = 1;
+    lsd_slam::pose::sim3_mul(worldPose(*keyframe).data(), f2k, cw);
+    Sim3 candidateCamToWorld;
+    for (int i = 0; i < 4; i++) candidateCamToWorld.q[i] = cw[i];
+    for (int i = 0; i < 3; i++) candidateCamToWorld.t[i] = cw[4 + i];
+    candidateCamToWorld.s = cw[7];
+    // The reference searches after finishCurrentKeyframe.  The search reads the bank entries of EARLIER keyframes only — the current
+    // keyframe is the candidate's tracking parent and is skipped (TrackableKeyFrameSearch.cpp:118) — so it may run before the current
+    // keyframe is finalised and banked, and finalizeKeyFrame can then share its launches with the change that the search decides.
+    const int slot = search_->findRePositionCandidate(frame.get(), candidateCamToWorld, keyframe->id(), 1.0f);
+    const std::shared_ptr<Frame> found = slot >= 0 ? bankedBySlot_[(size_t)slot] : nullptr;
+    if (slot >= 0 && !found) throw Error(LSDHIP_E_STATE, "SlamLoop: the search returned a slot this loop did not fill");
+    const std::shared_ptr<Frame> finished = keyframe;
+    mappedOnKF_ = 0;
+    if (onKeyframeFinished || !sharedKeyframeChange) {
+      map.finalizeKeyFrame();
+      if (onKeyframeFinished) onKeyframeFinished(*finished, map);
+      if (found) map.setFromExistingKF(found.get());
+      else map.createKeyFrame(frame.get());
+    } else if (found) {
+      map.reactivateKeyframe(found.get());
+    } else {
+      map.changeKeyframe(frame.get());
+    }
+    // (the put reads the planes the finalise pass and the pyramid launch wrote: queued behind them)
+    bankFinishedKeyframe(finished);
+    if (onKeyframeFinishedAsync) onKeyframeFinishedAsync(*finished);
+    const lsdhip_reposition_result& r = search_->last;
+    keyframeChanges.push_back(KeyframeChange{frame->id(), finished->id(), found ? found->id() : frame->id(), found != nullptr,
+                                             r.numPotential, r.numChecked, r.numTracked});
+    double nextEstimate[7] = {1, 0, 0, 0, 0, 0, 0};
+    if (found) {
+      numReactivations++;
+      keyframe = found;
+      keyframe->clearDepthHasBeenUpdatedFlag();      // loadNewCurrentKeyframe (SlamSystem.cpp:503)
+      // the next frame starts from se3FromSim3(camToWorld(keyframe)^-1 * camToWorld(lastTrackedFrame)) (SlamSystem.cpp:922-925)
+      lsd_slam::pose::relative_se3(worldPose(*keyframe).data(), cw, nextEstimate);
+    } else {
+      // camToWorld(new keyframe) = camToWorld(parent) * thisToParent_raw, the scale createKeyFrame gave it included (waits for it once)
+      double raw[8];
+      check(lsdhip_frame_get_pose(frame->handle(), raw), "lsdhip_frame_get_pose");
+      std::array<double, 8> w;
+      lsd_slam::pose::sim3_mul(worldPose(*finished).data(), raw, w.data());
+      worldPoses_[frame->id()] = w;
+      keyframe = frame;
+      if (keepKeyframes) keyframeLog.push_back(frame);
+    }
+    liveQueue_.clear();
+    if (pipelined_) {
+      pendingKF_ = keyframe;         // the tracker keeps the old keyframe for one more frame
+      pendingIsReactivated_ = found != nullptr;
+    } else {
+      trackKF_ = keyframe;
+      reference.importFrame(keyframe.get());
+      keyframe->clearDepthHasBeenUpdatedFlag();
+      lastFrameToKF_ = SE3::from7(nextEstimate);
+    }
+    sinceKF_ = 0;
+    newKeyframe = true;
+    if (onMappingIteration) onMappingIteration(map);
+  }
+  std::unique_ptr<KeyFrameBank> bank_;
+  std::unique_ptr<TrackableKeyFrameSearch> search_;
+  std::vector<std::shared_ptr<Frame>> bankedBySlot_;           // every banked keyframe stays alive: its re-activation planes, level-0 image
+                                                               // and maxGradients are needed when it comes back
+  std::map<int, std::array<double, 8>> worldPoses_;            // camToWorld per keyframe id
+  bool pendingIsReactivated_ = false;                          // pipelined: pendingKF_ is a banked keyframe that came back
   // DepthMap::updateKeyframe for one tracked frame (SlamSystem::updateKeyframe, SlamSystem.cpp:542-614)
   void runUpdate(const std::shared_ptr<Frame>& frame) {
     // blockUntilMapped = true: the unmapped queue holds exactly this frame (SlamSystem.cpp:559-571, :1030-1039).

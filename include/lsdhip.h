@@ -149,7 +149,10 @@ int lsdhip_frame_id(lsdhip_frame* f);
  * 6 (level 0; not a member of the reference's Frame) the gradient candidates the batched DepthMap update walks: per 1024 consecutive
  *   pixels the in-group offsets (uint16, pixel order) of the pixels inside the 3-pixel border with maxGradients >= minUseGrad — the two
  *   tests of DepthMap::observeDepthRow that depend on the keyframe alone (DepthMap.cpp:111-131) — then one uint16 count per group;
- *   out_host holds ceil(pixels / 1024) * 1025 * 2 bytes */
+ *   out_host holds ceil(pixels / 1024) * 1025 * 2 bytes
+ * 7, 8, 9 (level 0) what Frame::takeReActivationData kept (Frame.cpp:107-145): idepth_reAct (floats), idepthVar_reAct (floats; > 0: the
+ *   pixel held a hypothesis, -2: it was blacklisted, -1: neither) and validity_reAct (one byte per pixel); the first and the last are
+ *   defined where idepthVar_reAct > 0.  LSDHIP_E_STATE for a frame that was never finalised. */
 int lsdhip_frame_download(lsdhip_frame* f, int what, int level, float* out_host);
 /* Frame::setDepthFromGroundTruth (Frame.cpp:245-293) */
 int lsdhip_frame_set_depth_gt(lsdhip_frame* f, const float* depth_host, float cov_scale);
@@ -487,6 +490,16 @@ int lsdhip_depth_finalize(lsdhip_depthmap* dm);
  * rescale_out: NULL or n floats (asking for them waits for the device).  More than 85 maps are processed in consecutive parts of at most
  * 85 (three deferred-result slots per map, 256 slots per context); a failing part leaves the parts before it changed. */
 int lsdhip_depth_change_keyframe_batch(int n, lsdhip_depthmap** maps, lsdhip_frame** new_keyframes, float* rescale_out);
+/* DepthMap::finalizeKeyFrame() (DepthMap.cpp:1363-1395) on each map's active keyframe, followed by
+ * DepthMap::setFromExistingKF(old_keyframes[j]) (DepthMap.cpp:920-962), for n maps of one context: the keyframe change of
+ * SlamSystem::changeKeyframe when findRePositionCandidate found a banked keyframe (SlamSystem.cpp:507-540).  Three launches shared by all
+ * maps (blockIdx.z = map): [finalize pass + Frame::setDepth + takeReActivationData] -> [the old keyframe's re-activation planes into the
+ * map + regularizeDepthMap(false)] -> the finalised keyframes' idepth pyramids.  Planes, re-activation data, pyramid and deferred
+ * statistics as lsdhip_depth_finalize + lsdhip_depth_set_from_existing leave them; on an asynchronous context the call returns with its
+ * launches queued and waits for nothing.  LSDHIP_E_STATE: a keyframe without re-activation data, a map without an active keyframe;
+ * LSDHIP_E_ARG: a null, a map or keyframe named twice, old_keyframes[j] the active keyframe of a map of the call; no map changes on
+ * either.  More than 256 maps go in consecutive parts (one deferred-result slot per map). */
+int lsdhip_depth_reactivate_keyframe_batch(int n, lsdhip_depthmap** maps, lsdhip_frame** old_keyframes);
 /* Which form the last lsdhip_depth_update_batch (which = 0) or lsdhip_depth_change_keyframe_batch (which = 1) on this context took: a
  * read-only record the calls keep on the host (a call that nobody asks about does no extra device work).  out[0] = maps of the call
  * (0: no such call yet), out[1] = 1 if observe ran as select + walk launches (0: one launch), out[2] = 1 if the select pass walked the

@@ -48,6 +48,18 @@ int lsdloop_keyframe_log(lsdloop* l, double* scales_out, long long* points_out, 
 /* on != 0: tracking beside mapping (the reference's two threads with blockUntilMapped == false, C/SlamSystem.cpp:1026-1040), the mapper
  * exactly one frame behind the tracker: see lsd_slam_hip::SlamLoop.  Call before the first lsdloop_run.  Default 0 (blockUntilMapped). */
 int lsdloop_set_pipeline(lsdloop* l, int on);
+/* Re-activation of old keyframes (lsd_slam_hip::SlamLoop::enableReactivation): every finished keyframe goes into a device bank of
+ * max_keyframes slots, and each keyframe change first asks TrackableKeyFrameSearch::findRePositionCandidate for a banked keyframe to
+ * go back to (C/SlamSystem.cpp:507-540); one is then re-activated (lsdhip_depth_reactivate_keyframe_batch) instead of the frame being
+ * promoted.  Call before the first lsdloop_run.  Off by default.
+ * lsdloop_keyframe_changes: the keyframe changes since then, 7 ints each — frame id, finished keyframe's id, next keyframe's id, 1 if
+ * that one was re-activated, then the search's numPotential / numChecked / numTracked; writes up to max records, returns their number.
+ * lsdloop_reactivation_counts: out2[0] = re-activations, out2[1] = finished keyframes the full bank could not take. */
+int lsdloop_enable_reactivation(lsdloop* l, int max_keyframes);
+int lsdloop_keyframe_changes(lsdloop* l, int* out, int max);
+int lsdloop_reactivation_counts(lsdloop* l, long long out2[2]);
+/* the loop's depth map (w * h hypotheses), with every mapping iteration queued so far applied; waits for the device */
+int lsdloop_download_map(lsdloop* l, lsdhip_hypothesis* out);
 /* frames handed to DepthMap::updateKeyframe per mapping iteration (1 = blockUntilMapped, the default; K > 1 restates live
  * operation where the mapper finds up to K tracked frames queued, C/SlamSystem.cpp:559-571) */
 int lsdloop_set_live_queue(lsdloop* l, int frames);

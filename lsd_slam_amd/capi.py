@@ -203,6 +203,7 @@ def _signatures():
         "lsdhip_depth_update_batch": (i, [i, pvp, pvp]),
         "lsdhip_depth_create_keyframe": (i, [vp, vp, C.POINTER(C.c_float)]),
         "lsdhip_depth_change_keyframe_batch": (i, [i, pvp, pvp, C.POINTER(C.c_float)]),
+        "lsdhip_depth_reactivate_keyframe_batch": (i, [i, pvp, pvp]),
         "lsdhip_ctx_batch_form": (i, [vp, i, vp, vp, i]),
         "lsdhip_depth_finalize": (i, [vp]),
         "lsdhip_depth_download": (i, [vp, vp]),

@@ -1013,12 +1013,19 @@ __global__ __launch_bounds__(256) void k_fill_holes(RegArgs a) {
 //                     Frame::takeReActivationData (KfExtra::react*) and phase A of propagateDepth into the new keyframe (prop_candidate
 //                     on KfExtra::prop) — while the values are in its registers;
 //   SumValid          per-workgroup (sum of idepth_smoothed, count) over the valid pixels after the pass (createKeyFrame's rescale sums).
-struct PassBase { static constexpr bool FillHoles = false, RemoveOcclusions = false, SetDepth = false, KeyframeChange = false, SumValid = false; };
+//   Propagate         with KeyframeChange: the keyframe that follows is a new one (createKeyFrame); without it a banked one comes back
+//                     (setFromExistingKF) and nothing steps over;
+//   FromReact         the tile is loaded from a keyframe's re-activation planes (ReactSrc) instead of the map, and the owner of a pixel
+//                     stores what setFromExistingKF makes of the pixel (DepthMap.cpp:937-959) before K6's outcome.
+struct PassBase { static constexpr bool FillHoles = false, RemoveOcclusions = false, SetDepth = false, KeyframeChange = false, SumValid = false,
+                                        Propagate = false, FromReact = false; };
 struct PassRegOnly : PassBase {};                                               // regularizeDepthMap(false, th) alone (lsdhip_depth_stage)
 struct PassRegOcc : PassBase { static constexpr bool RemoveOcclusions = true; };   // regularizeDepthMap(true, th): createKeyFrame :1263
 struct PassUpdate : PassBase { static constexpr bool FillHoles = true; };          // updateKeyframe :1135-1143: fill holes + regularizeDepthMap(false, th)
 struct PassUpdateSetDepth : PassUpdate { static constexpr bool SetDepth = true; }; // ... + Frame::setDepth where the keyframe is due for it (:1150-1153)
-struct PassKfFinalize : PassUpdateSetDepth { static constexpr bool KeyframeChange = true; };   // finalizeKeyFrame :1363-1395, then the step into createKeyFrame
+struct PassKfFinalizeOnly : PassUpdateSetDepth { static constexpr bool KeyframeChange = true; };   // finalizeKeyFrame :1363-1395 (KfExtra::prop unused)
+struct PassKfFinalize : PassKfFinalizeOnly { static constexpr bool Propagate = true; };        // ... then the step into createKeyFrame
+struct PassFromReact : PassBase { static constexpr bool FromReact = true; };       // setFromExistingKF :937-961: the planes + regularizeDepthMap(false, th)
 struct PassKfFillSums : PassUpdate { static constexpr bool SumValid = true; };     // createKeyFrame :1270-1294
 struct KfExtra {
   LSD_G float* reactId;        // old keyframe's re-activation planes
@@ -1034,6 +1041,13 @@ struct RegItem {
   LSD_G double* partials;    // SetDepth / SumValid: (sum, count) per workgroup
 };
 struct KfItem : RegItem { KfExtra x; };      // KeyframeChange
+// a keyframe's re-activation planes (Frame::takeReActivationData, Frame.cpp:107-145), read-only
+struct ReactSrc {
+  LSD_G const float* id;
+  LSD_G const float* var;      // > 0: a valid pixel's variance; -2: blacklisted; -1: neither
+  LSD_G const uint8_t* val;    // a valid pixel's validity counter
+};
+struct ReactItem : RegItem { ReactSrc src; };      // FromReact
 static_assert(sizeof(KfItem) == sizeof(RegItem) + sizeof(KfExtra), "argument records: a KfItem is a RegItem followed by its KfExtra");
 
 // Per tile entry ONE 16-byte word (idepth, idepth_var, (float)pk) with pk = validity_counter of a valid pixel (never negative), -1 for an
@@ -1071,9 +1085,30 @@ struct RegTile {
     return true;
   }
 };
+// Where a tile's entries come from: entry(g, inb, id, var, pk) issues the source's loads of pixel g together (one memory round trip for
+// the tile, whichever the source) and forms pk.
+struct TileFromMap {         // the map's planes and the snapshot validity plane
+  const RegArgs& a;
+  __device__ __forceinline__ void entry(const int g, const bool inb, float& id, float& var, int& pk) const {
+    const uint8_t v = a.validIn[g];
+    const int vc = a.m.validity[g];
+    id = a.m.idepth[g];
+    var = a.m.var[g];
+    pk = (inb && v) ? vc : -1;
+  }
+};
+struct TileFromReact {       // setFromExistingKF's reading of the re-activation planes (DepthMap.cpp:940-958): var > 0 <=> a hypothesis
+  const ReactSrc& r;
+  __device__ __forceinline__ void entry(const int g, const bool inb, float& id, float& var, int& pk) const {
+    const int vc = r.val[g];
+    id = r.id[g];
+    var = r.var[g];
+    pk = (inb && var > 0) ? vc : -1;
+  }
+};
 // tile load (unconditional, clamped addresses; out-of-image entries are invalid)
-template <class T>
-__device__ __forceinline__ void tile_load(const RegArgs& a, const T& t, const TileLds& s, float (&mg)[T::MG]) {
+template <class T, class Src>
+__device__ __forceinline__ void tile_load(const RegArgs& a, const Src& src, const T& t, const TileLds& s, float (&mg)[T::MG]) {
   const int tid = threadIdx.x, w = a.w, h = a.h;
 #pragma unroll
   for (int it = 0; it < (T::TN + 255) / 256; it++) {
@@ -1082,11 +1117,9 @@ __device__ __forceinline__ void tile_load(const RegArgs& a, const T& t, const Ti
       const int gx = t.x0 + e % T::TW, gy = t.y0 + e / T::TW;
       const bool inb = gx >= 0 && gx < w && gy >= 0 && gy < h;
       const int g = inb ? gx + gy * w : 0;
-      const uint8_t v = a.validIn[g];
-      const int vc = a.m.validity[g];
-      const float id = a.m.idepth[g];
-      const float var = a.m.var[g];
-      const int pk = (inb && v) ? vc : -1;
+      float id, var;
+      int pk;
+      src.entry(g, inb, id, var, pk);
       s.pk0[e] = pk;
       s.created[e] = 0;
       s.e[e] = reg_entry{id, var, (float)pk, 0.f};             // (the counter as a float: K6 adds it to a float sum once per neighbour)
@@ -1162,6 +1195,17 @@ __device__ __forceinline__ bool store_outcome(const RegArgs& a, const int idx, c
   if (o.smoothed) { a.m.idepth_s[idx] = o.ids; a.m.var_s[idx] = o.vars; }
   return blKnown;
 }
+// what the owner of a pixel stores in a pass loaded from re-activation planes: setFromExistingKF's pixel (DepthMap.cpp:940-958; c_e.y is
+// the plane's variance entry, sign and all), then K6's outcome on it
+__device__ __forceinline__ void store_react_outcome(const RegArgs& a, const int idx, const reg_entry c_e, const int c_pk, const K6Outcome& o) {
+  a.validOut[idx] = o.nowValid;
+  if (c_pk >= 0) {
+    store_fresh_hypothesis(a.m, idx, c_e.x, c_e.y, c_pk, o.blacklistDec ? -1 : 0);
+    if (o.smoothed) { a.m.idepth_s[idx] = o.ids; a.m.var_s[idx] = o.vars; }
+  } else {
+    a.m.blacklisted[idx] = (c_e.y == -2) ? MIN_BLACKLIST - 1 : 0;
+  }
+}
 // Frame::takeReActivationData for one pixel (Frame.cpp:107-145): a valid pixel's hypothesis, else whether it is blacklisted
 __device__ __forceinline__ void take_react_pixel(float* id, float* var, uint8_t* val, const int i, const bool valid, const float idepth, const float v,
                                                  const int validity, const int blacklisted) {
@@ -1181,7 +1225,7 @@ __device__ __forceinline__ bool set_depth_pixel(float* id0, float* var0, const i
 }
 
 template <class Pass, int PY>
-__device__ __forceinline__ void reg_fused_tile(const RegItem& it, const KfExtra* __restrict__ kx = nullptr) {
+__device__ __forceinline__ void reg_fused_tile(const RegItem& it, const KfExtra* __restrict__ kx = nullptr, const ReactSrc* __restrict__ rs = nullptr) {
   constexpr bool FILL = Pass::FillHoles, SUMS = Pass::SetDepth || Pass::SumValid;
   typedef RegTile<FILL, PY> T;
   __shared__ int s_pk0[T::TN];
@@ -1193,7 +1237,8 @@ __device__ __forceinline__ void reg_fused_tile(const RegItem& it, const KfExtra*
   T t;
   if (!t.place(a)) return;
   float mg[T::MG];
-  tile_load<T>(a, t, s, mg);
+  if (Pass::FromReact) tile_load<T>(a, TileFromReact{*rs}, t, s, mg);
+  else tile_load<T>(a, TileFromMap{a}, t, s, mg);
   __syncthreads();
   if (FILL) {
     tile_fill_holes<T>(a, t, s, mg);
@@ -1267,7 +1312,9 @@ __device__ __forceinline__ void reg_fused_tile(const RegItem& it, const KfExtra*
     }
     if (!inImage) continue;
     int blFinal = 0;
-    const bool blKnown = store_outcome(a, idx, c_e, created, o, blFinal);
+    bool blKnown = false;
+    if (Pass::FromReact) store_react_outcome(a, idx, c_e, c_pk, o);
+    else blKnown = store_outcome(a, idx, c_e, created, o, blFinal);
     // the pixel's smoothed pair after the pass
     float ids = -1.f, vars = -1.f;
     if (SUMS || Pass::KeyframeChange) {
@@ -1283,7 +1330,7 @@ __device__ __forceinline__ void reg_fused_tile(const RegItem& it, const KfExtra*
       // the keyframe being finalised hands the pixel to its re-activation planes, then the hypothesis steps into the new keyframe
       if (o.nowValid) {
         take_react_pixel(kx->reactId, kx->reactVar, kx->reactVal, idx, true, c_e.x, c_e.y, c_pk, 0);
-        prop_candidate(kx->prop, x, y, idx, ids, c_e.y, c_pk);
+        if (Pass::Propagate) prop_candidate(kx->prop, x, y, idx, ids, c_e.y, c_pk);
       } else {
         take_react_pixel(kx->reactId, kx->reactVar, kx->reactVal, idx, false, 0.f, 0.f, 0, blKnown ? blFinal : a.m.blacklisted[idx]);
       }
@@ -1325,6 +1372,22 @@ __global__ __launch_bounds__(256) void k_kf_finalize_prop(const KfItem* __restri
 template <class Pass, int PY>
 __global__ __launch_bounds__(256) void k_kf_reg(const RegItem* __restrict__ items) {
   reg_fused_tile<Pass, PY>(items[blockIdx.z]);
+}
+// ---- re-activation of n maps' banked keyframes in shared launches (lsdhip_depth_reactivate_keyframe_batch), blockIdx.z = map -------------
+//   k_kf_finalize             PassKfFinalizeOnly: finalizeKeyFrame's pass + takeReActivationData per owner pixel; nothing propagates
+//   k_kf_from_react           PassFromReact: setFromExistingKF's planes and its regularizeDepthMap(false, ...) in one pass: every read comes
+//                             from the old keyframe's re-activation planes, every write goes to the map, so the pass needs neither the
+//                             snapshot of the validity plane nor a conversion launch in front of it
+//   k_idepth_pyramid_batch    the finalised keyframe's pyramid and its (sum, count) record
+template <int PY>
+__global__ __launch_bounds__(256) void k_kf_finalize(const KfItem* __restrict__ items) {
+  const KfItem& it = items[blockIdx.z];
+  reg_fused_tile<PassKfFinalizeOnly, PY>(it, &it.x);
+}
+template <int PY>
+__global__ __launch_bounds__(256) void k_kf_from_react(const ReactItem* __restrict__ items) {
+  const ReactItem& it = items[blockIdx.z];
+  reg_fused_tile<PassFromReact, PY>(it, nullptr, &it.src);
 }
 struct RescaleItem {
   HypPlanes m;
@@ -2622,6 +2685,151 @@ extern "C" int lsdhip_depth_change_keyframe_batch(int n, lsdhip_depthmap** maps,
     if (int rcp = change_keyframe_part(c, part, maps + j0, new_keyframes + j0, rescale_out ? rescale_out + j0 : nullptr)) return rcp;
   }
   c->batchForm[1].n = n;     // (py: that of the last part)
+  return LSDHIP_OK;
+}
+
+// A re-activating change edits the same kinds of host-side state as a creating one (ChangeTxn), less of it: the maps' validity planes and
+// active keyframe, the finalised keyframes' statistics slot, the old keyframes' counters.  Undone unless the last launch gets queued.
+struct ReactivateTxn {
+  lsdhip_ctx* c; int n; lsdhip_depthmap** maps; lsdhip_frame** olds;
+  struct M { HypPlanes cur; uint8_t* snap; lsdhip_frame* kf; bool react, lowGrad; int kfStats; int mapped, tracked; };
+  std::vector<M> m;
+  std::vector<int> slots;
+  int slotNext; int ev = EV_SKIP; bool timing = false; bool done = false;
+  ReactivateTxn(lsdhip_ctx* c_, int n_, lsdhip_depthmap** maps_, lsdhip_frame** olds_) : c(c_), n(n_), maps(maps_), olds(olds_), m((size_t)n_), slotNext(c_->slot_next) {
+    for (int j = 0; j < n; j++) {
+      lsdhip_depthmap* dm = maps[j];
+      m[j] = M{dm->cur, dm->d_validSnap, dm->activeKeyFrame, dm->activeKeyFrameIsReactivated, dm->lowGradHypPossible, dm->activeKeyFrame->pendStats,
+               olds[j]->numMappedOnThis, olds[j]->numFramesTrackedOnThis};
+    }
+  }
+  int stats_slot(lsdhip_frame* f) { const int s = lsd_ctx_claim_stats_slot(c, f); if (s >= 0) slots.push_back(s); return s; }
+  ~ReactivateTxn() {
+    if (done) return;
+    for (int s : slots) c->slot_stats_owner[s] = nullptr;
+    c->slot_next = slotNext;
+    for (int j = 0; j < n; j++) {
+      lsdhip_depthmap* dm = maps[j];
+      dm->cur = m[j].cur; dm->d_validSnap = m[j].snap; dm->activeKeyFrame = m[j].kf; dm->activeKeyFrameIsReactivated = m[j].react;
+      dm->lowGradHypPossible = m[j].lowGrad;
+      m[j].kf->pendStats = m[j].kfStats;
+      if (m[j].kfStats >= 0) c->slot_stats_owner[m[j].kfStats] = m[j].kf;
+      olds[j]->numMappedOnThis = m[j].mapped; olds[j]->numFramesTrackedOnThis = m[j].tracked;
+    }
+    if (timing) (void)timing_end(maps[0], ev);
+  }
+};
+// The argument record of a re-activating change: KfItem x n | ReactItem x n, the second on a 256-byte boundary
+struct ReactivateRecord {
+  size_t srcOff, bytes;
+  explicit ReactivateRecord(int n) : srcOff(up256(sizeof(KfItem) * (size_t)n)), bytes(srcOff + up256(sizeof(ReactItem) * (size_t)n)) {}
+  KfItem* kf(void* base) const { return (KfItem*)base; }
+  ReactItem* src(void* base) const { return (ReactItem*)((uint8_t*)base + srcOff); }
+};
+static int reactivate_check(lsdhip_ctx* c, int n, lsdhip_depthmap** maps, lsdhip_frame** olds) {
+  for (int j = 0; j < n; j++) {
+    lsdhip_depthmap* dm = maps[j];
+    if (dm->ctx != c || olds[j]->ctx != c) { lsd_set_error("keyframe re-activation batch: maps and frames of one batch live on one context"); return LSDHIP_E_ARG; }
+    for (int i = 0; i < j; i++)
+      if (maps[i] == dm || olds[i] == olds[j]) { lsd_set_error("keyframe re-activation batch: entry %d appears twice", j); return LSDHIP_E_ARG; }
+    // (a keyframe that another map of the call finalises would have its planes written and read by launches of one call)
+    for (int i = 0; i < n; i++)
+      if (maps[i] && olds[j] == maps[i]->activeKeyFrame) {
+        lsd_set_error("keyframe re-activation batch: entry %d: frame %d is the current keyframe of map %d", j, olds[j]->id, i);
+        return LSDHIP_E_ARG;
+      }
+  }
+  for (int j = 0; j < n; j++) {
+    if (!maps[j]->activeKeyFrame) { lsd_set_error("keyframe re-activation batch: depth map %d has no active keyframe", j); return LSDHIP_E_STATE; }
+    if (!olds[j]->reActValid) { lsd_set_error("setFromExistingKF: frame %d has no re-activation data", olds[j]->id); return LSDHIP_E_STATE; }
+  }
+  return LSDHIP_OK;
+}
+// Map j's two records, and the host-side state of the map and of both keyframes as the three launches will leave it.  As in
+// change_build_map each record describes the planes as the launch before it leaves them: the finalise pass reads cur.valid and writes the
+// spare plane, the pass from the re-activation planes writes the first again, and the map ends on the plane it began on.
+static int reactivate_build_map(ReactivateTxn& txn, int j, const ReactivateRecord& L, void* host, int ntiles, PyramidJobs& pyr) {
+  lsdhip_depthmap* dm = txn.maps[j];
+  lsdhip_frame* cur = dm->activeKeyFrame;
+  lsdhip_frame* old = txn.olds[j];
+  double* setA = dm->d_red + 16;
+  // finalizeKeyFrame (DepthMap.cpp:1363-1395)
+  KfItem& k = L.kf(host)[j];
+  memset((void*)&k, 0, sizeof(k));
+  k.a = reg_args(dm, VAL_SUM_MIN_FOR_KEEP);
+  k.id0 = lsd_g(lsd_depth_w(cur)[0]); k.var0 = lsd_g(lsd_depthvar_w(cur)[0]); k.partials = lsd_g(setA);
+  k.x.reactId = lsd_g(cur->d_idepth_reAct); k.x.reactVar = lsd_g(cur->d_idepthVar_reAct); k.x.reactVal = lsd_g(cur->d_validity_reAct);
+  swap_valid(dm);
+  const int slot = txn.stats_slot(cur);
+  if (slot < 0) return slot;
+  pyr.set(j, cur, setA, ntiles, slot);
+  // setFromExistingKF (DepthMap.cpp:920-962)
+  dm->lowGradHypPossible = true;
+  dm->activeKeyFrame = old;
+  old->numMappedOnThis = 0;
+  old->numFramesTrackedOnThis = 0;
+  dm->activeKeyFrameIsReactivated = true;
+  ReactItem& r = L.src(host)[j];
+  memset((void*)&r, 0, sizeof(r));
+  r.a = reg_args(dm, VAL_SUM_MIN_FOR_KEEP);
+  r.src.id = lsd_g((const float*)old->d_idepth_reAct); r.src.var = lsd_g((const float*)old->d_idepthVar_reAct);
+  r.src.val = lsd_g((const uint8_t*)old->d_validity_reAct);
+  swap_valid(dm);
+  return LSDHIP_OK;
+}
+// the re-activation of at most LSD_NUM_SLOTS maps (validated by the caller): one deferred-result slot per map
+static int reactivate_keyframe_part(lsdhip_ctx* c, int n, lsdhip_depthmap** maps, lsdhip_frame** olds) {
+  HIPCHK(hipSetDevice(c->device));
+  const double t0 = now_ms();
+  if (int rcb = lsd_m_begin(c)) return rcb;
+  const hipStream_t ms = lsd_map_stream(c);
+  const RegGrid g = reg_grid(c, tile_rows(c), n);
+  if (int rcl = lsd_frames_require_level0(olds, n)) return rcl;   // a DepthMap's keyframe is asked for gradients(0) / maxGradients(0)
+  ReactivateTxn txn(c, n, maps, olds);
+  const int ev = timing_begin(maps[0], 2);
+  if (ev < 0 && ev != EV_SKIP) return ev;
+  txn.ev = ev; txn.timing = true;
+  const ReactivateRecord L(n);
+  void *host = nullptr, *dev = nullptr;
+  if (int rc = lsd_args_begin(c, L.bytes, &host, &dev)) return rc;
+  PyramidJobs pyr((size_t)n);
+  for (int j = 0; j < n; j++) if (int rc = reactivate_build_map(txn, j, L, host, g.tiles(), pyr)) return rc;
+  if (int rc = lsd_args_commit(c, ms)) return rc;
+  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL(k_kf_finalize<PYV>, g.grid, dim3(256), 0, ms, (const KfItem*)L.kf(dev)));
+  LSD_REG_DISPATCH(g.py, hipLaunchKernelGGL(k_kf_from_react<PYV>, g.grid, dim3(256), 0, ms, (const ReactItem*)L.src(dev)));
+  HIPCHK(hipGetLastError());
+  if (int rc = lsd_args_release(c, dev, ms)) return rc;
+  if (int rc = pyr.launch()) return rc;
+  txn.done = true;            // every launch is queued: the new state stands
+  for (int j = 0; j < n; j++) {
+    txn.m[j].kf->depthHasBeenUpdatedFlag = true;
+    txn.m[j].kf->reActValid = true;
+  }
+  if (int rc = timing_end(maps[0], ev)) return rc;
+  if (lsd_m_record(c) < 0) return LSDHIP_E_HIP;
+  if (!c->async)
+    for (int j = 0; j < n; j++) { if (int rc = lsd_frame_resolve(txn.m[j].kf)) return rc; }
+  const double dt = now_ms() - t0;
+  for (int j = 0; j < n; j++) maps[j]->msFinalize = ema(maps[j]->msFinalize, dt / n);
+  return LSDHIP_OK;
+}
+
+// DepthMap::finalizeKeyFrame (DepthMap.cpp:1363-1395) on the current keyframes of n maps followed by DepthMap::setFromExistingKF(old_keyframes[j])
+// (:920-962), in three launches shared by all maps (kernels above) and without a host wait on an asynchronous context.  Per map every
+// plane, the finalised keyframe's level-0 planes, pyramid, re-activation data and deferred statistics are those of lsdhip_depth_finalize +
+// lsdhip_depth_set_from_existing (tests/test_reactivate_batch_gpu.py).
+extern "C" int lsdhip_depth_reactivate_keyframe_batch(int n, lsdhip_depthmap** maps, lsdhip_frame** old_keyframes) {
+  if (n <= 0 || !maps || !old_keyframes) return LSDHIP_E_ARG;
+  for (int j = 0; j < n; j++) if (!maps[j] || !old_keyframes[j]) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = maps[0]->ctx;
+  LSD_CTX_LOCK(c);
+  if (int rcv = reactivate_check(c, n, maps, old_keyframes)) return rcv;
+  // (one slot per map: a part never wraps the ring onto itself, see lsdhip_depth_change_keyframe_batch)
+  constexpr int maxPerPart = LSD_NUM_SLOTS;
+  for (int j0 = 0; j0 < n; j0 += maxPerPart) {
+    const int part = n - j0 < maxPerPart ? n - j0 : maxPerPart;
+    if (int rcp = reactivate_keyframe_part(c, part, maps + j0, old_keyframes + j0)) return rcp;
+  }
   return LSDHIP_OK;
 }
 

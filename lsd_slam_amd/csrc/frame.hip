@@ -1740,6 +1740,14 @@ extern "C" int lsdhip_frame_download(lsdhip_frame* f, int what, int level, float
     }
     // the keyframe planes' gradient candidates (k_grad_candidates), as uint16: ceil(pixels / 1024) groups of 1024 offsets, then one count per group
     case 6: if (level != 0) return LSDHIP_E_ARG; src = f->d_gradCand; bytes = lsd_gradcand_bytes((int)n); break;
+    // Frame::takeReActivationData's planes (Frame.cpp:107-145)
+    case 7: case 8: case 9:
+      if (level != 0) return LSDHIP_E_ARG;
+      if (!f->reActValid) return LSDHIP_E_STATE;
+      if (what == 7) src = f->d_idepth_reAct;
+      else if (what == 8) src = f->d_idepthVar_reAct;
+      else { src = f->d_validity_reAct; bytes = n; }
+      break;
     default: return LSDHIP_E_ARG;
   }
   return copy_and_wait(out, src, bytes, hipMemcpyDeviceToHost, c->stream);

@@ -20,7 +20,7 @@ class LoopStats(C.Structure):
 
 EXPORTED_SYMBOLS = ["lsdloop_create", "lsdloop_destroy", "lsdloop_run", "lsdloop_get_stats", "lsdloop_reset_stats",
                     "lsdloop_copy_keyframe_planes", "lsdloop_set_keyframe_ring", "lsdloop_keyframes_exported", "lsdloop_ctx",
-                    "lsdloop_last_error", "lsdloop_keep_keyframes", "lsdloop_keyframe_log", "lsdloop_set_live_queue", "lsdloop_set_pipeline", "lsdloop_set_speculation", "lsdloop_observe_time", "lsdloop_comm_unique_id", "lsdloop_comm_init", "lsdloop_comm_destroy",
+                    "lsdloop_last_error", "lsdloop_keep_keyframes", "lsdloop_keyframe_log", "lsdloop_set_live_queue", "lsdloop_set_pipeline", "lsdloop_enable_reactivation", "lsdloop_keyframe_changes", "lsdloop_reactivation_counts", "lsdloop_download_map", "lsdloop_set_speculation", "lsdloop_observe_time", "lsdloop_comm_unique_id", "lsdloop_comm_init", "lsdloop_comm_destroy",
                     "lsdloop_gather_keyframes", "lsdband_create", "lsdband_destroy", "lsdband_window_rows", "lsdband_layout", "lsdband_load",
                     "lsdband_get", "lsdband_comm_init", "lsdband_run", "lsdband_synchronize", "lsdband_halo_bytes_per_pass", "lsdband_set_packed_exchange", "lsdband_set_overlap", "lsdband_tile_runs", "lsdband_plan", "lsdband_ipc_init", "lsdband_ipc_connect", "lsdband_ipc_failed", "lsdloop_gather_counts", "lsdloop_ipc_init", "lsdloop_ipc_connect", "lsdloop_ipc_result", "lsdloop_observe_work",
                     "lsdloopbatch_create", "lsdloopbatch_destroy", "lsdloopbatch_run", "lsdloopbatch_get_stats", "lsdloopbatch_ctx", "lsdloopbatch_set_keyframe_phases", "lsdloopbatch_set_pipeline", "lsdloopbatch_set_coarse_min_jobs", "lsdloopbatch_dropped",
@@ -56,6 +56,14 @@ def lib():
         L.lsdloop_keep_keyframes.argtypes = [vp, i]
         L.lsdloop_keyframe_log.restype = i
         L.lsdloop_keyframe_log.argtypes = [vp, vp, vp, i]
+        L.lsdloop_enable_reactivation.restype = i
+        L.lsdloop_enable_reactivation.argtypes = [vp, i]
+        L.lsdloop_keyframe_changes.restype = i
+        L.lsdloop_keyframe_changes.argtypes = [vp, vp, i]
+        L.lsdloop_reactivation_counts.restype = i
+        L.lsdloop_reactivation_counts.argtypes = [vp, vp]
+        L.lsdloop_download_map.restype = i
+        L.lsdloop_download_map.argtypes = [vp, vp]
         L.lsdloop_set_live_queue.restype = i
         L.lsdloop_set_live_queue.argtypes = [vp, i]
         L.lsdloop_set_pipeline.restype = i
@@ -330,6 +338,30 @@ class DriverLoop:
     def set_pipeline(self, on=True):
         """tracking beside mapping, the mapper one frame behind (lsdloop_set_pipeline); before the first run()"""
         _check(self.L.lsdloop_set_pipeline(self.h_, int(bool(on))))
+
+    def enable_reactivation(self, max_keyframes):
+        """keep finished keyframes in a device bank of max_keyframes slots and go back to one of them where
+        findRePositionCandidate finds one (lsdloop_enable_reactivation); before the first run()"""
+        _check(self.L.lsdloop_enable_reactivation(self.h_, int(max_keyframes)))
+
+    def keyframe_changes(self, max_entries=4096):
+        """the keyframe changes of a loop with re-activation on: int array [n, 7] of (frame id, finished keyframe's id, next keyframe's
+        id, re-activated, numPotential, numChecked, numTracked)"""
+        out = np.zeros((max_entries, 7), np.int32)
+        n = _check(self.L.lsdloop_keyframe_changes(self.h_, out.ctypes.data, max_entries))
+        return out[:min(n, max_entries)].copy()
+
+    def download_map(self):
+        """the loop's depth map [h, w] (HYP_DTYPE) with every queued mapping iteration applied; waits for the device"""
+        out = np.zeros(self.w * self.h, dtype=capi.HYP_DTYPE)
+        _check(self.L.lsdloop_download_map(self.h_, out.ctypes.data))
+        return out.reshape(self.h, self.w)
+
+    def reactivation_counts(self):
+        """(re-activations, finished keyframes the full bank could not take)"""
+        out = np.zeros(2, np.int64)
+        _check(self.L.lsdloop_reactivation_counts(self.h_, out.ctypes.data))
+        return int(out[0]), int(out[1])
 
     def observe_time(self):
         """(ms, calls) of the observe kernel alone, sampled while profiling is on; synchronises"""

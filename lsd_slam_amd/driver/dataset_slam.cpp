@@ -5,7 +5,7 @@
 // keyframe, and the viewer's PLY point cloud.
 //
 //   dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both]
-//                [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]]
+//                [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]] [--reactivate N]
 //
 // --cloud host (default): pc.ply and keyframe_<id>.msg from the host functions (three plane downloads and a host loop per keyframe).
 // --cloud device: every finished keyframe is appended to one PointCloud on the GPU behind the keyframe change (no split of the change; the
@@ -17,6 +17,9 @@
 // --depth-images DIR: after every mapping iteration the depth map's debug image (DepthMap::debugPlotDepthMap, drawn on the device: the
 //   keyframe in grey, the hypotheses in the colours of --debug-display N, the reference's debugDisplay 0 .. 5, default 0) is written to
 //   DIR/depth_<frame id>.ppm.  A file writer may wait: this is the host-output form, one launch and a copy of 3 bytes per pixel per frame.
+// --reactivate N (default 0 = off): finished keyframes are kept in a device bank of N slots and a keyframe change goes back to a banked
+//   keyframe where TrackableKeyFrameSearch::findRePositionCandidate finds one (SlamLoop::enableReactivation; C/SlamSystem.cpp:507-540).
+//   One line per re-activation on stdout, and the totals at the end.  A keyframe that is finished a second time is output a second time.
 // --constraints 1 additionally aligns every new keyframe with the keyframe it replaces by Sim3Tracker::trackFrameSim3 (the
 // tracking-parent edge the reference's constraint search always tests, C/SlamSystem.cpp:1253-1262) and writes constraints.txt.
 #include <cstdlib>
@@ -48,10 +51,10 @@ static Sim3 sim3_mul(const Sim3& a, const Sim3& b) {
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::cerr << "usage: dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both] [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]]\n";
+    std::cerr << "usage: dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both] [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]] [--reactivate N]\n";
     return 2;
   }
-  int kfEvery = 0, device = 0, constraints = 0, debugDisplay = 0;
+  int kfEvery = 0, device = 0, constraints = 0, debugDisplay = 0, reactivate = 0;
   std::string cloudMode = "host", depthImages;
   long long cloudCapacity = 0;
   for (int i = 4; i + 1 < argc; i += 2) {
@@ -62,6 +65,7 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "--cloud-capacity")) cloudCapacity = atoll(argv[i + 1]);
     if (!strcmp(argv[i], "--depth-images")) depthImages = argv[i + 1];
     if (!strcmp(argv[i], "--debug-display")) debugDisplay = atoi(argv[i + 1]);
+    if (!strcmp(argv[i], "--reactivate")) reactivate = atoi(argv[i + 1]);
   }
   if (cloudMode != "host" && cloudMode != "device" && cloudMode != "both") { std::cerr << "--cloud takes host, device or both\n"; return 2; }
   const bool hostCloud = cloudMode != "device", devCloud = cloudMode != "host";
@@ -81,6 +85,7 @@ int main(int argc, char** argv) {
     if (!readPGM(files[0], w, h, img)) { std::cerr << "cannot read " << files[0] << " as " << w << "x" << h << " P5\n"; return 2; }
     srand(0);   // initializeRandomly draws from rand() in pixel order (DepthMap.cpp:883-916)
     SlamLoop loop(w, h, cal.K, img.data(), false, nullptr, kfEvery);
+    if (reactivate > 0) loop.enableReactivation(reactivate);
     std::ofstream traj(outDir + "/trajectory.txt");
     traj << "# frame keyframe frameToKeyframe(qw qx qy qz tx ty tz) camToWorld(qw qx qy qz tx ty tz s) pointUsage goodRatio trackingWasGood\n";
     Sim3 kfToWorld;   // identity
@@ -131,7 +136,13 @@ int main(int argc, char** argv) {
       std::shared_ptr<Frame> parentKF = loop.keyframe;
       currentFrame = (int)i;
       SE3 f2k = loop.step(img.data());
-      if (constraints && loop.newKeyframe) {
+      const bool reactivated = loop.newKeyframe && loop.reactivateKeyframes && loop.keyframeChanges.back().reactivated;
+      if (reactivated) {
+        const SlamLoop::KeyframeChange& c = loop.keyframeChanges.back();
+        std::cout << "reactivated frame " << c.frameId << " keyframe " << c.previousKfId << " -> " << c.newKfId << " potential " << c.numPotential
+                  << " checked " << c.numChecked << " tracked " << c.numTracked << "\n";
+      }
+      if (constraints && loop.newKeyframe && !reactivated) {
         // new keyframe -> replaced keyframe, starting from the tracked pose with the depth rescale as scale
         TrackingReference parentRef;
         parentRef.importFrame(parentKF.get());
@@ -151,7 +162,13 @@ int main(int argc, char** argv) {
       for (int k = 0; k < 4; k++) rel.q[k] = f2k.q[k];
       for (int k = 0; k < 3; k++) rel.t[k] = f2k.t[k];
       Sim3 c2w = sim3_mul(kfToWorld, rel);
-      if (loop.newKeyframe) {
+      if (reactivated) {
+        // a banked keyframe came back: its pose is the one it was finished with
+        const std::array<double, 8>& p = loop.worldPose(*loop.keyframe);
+        for (int k = 0; k < 4; k++) kfToWorld.q[k] = p[k];
+        for (int k = 0; k < 3; k++) kfToWorld.t[k] = p[4 + k];
+        kfToWorld.s = p[7];
+      } else if (loop.newKeyframe) {
         // the new keyframe's pose relative to its parent now carries the depth rescale (DepthMap.cpp:1305)
         Sim3 tp = loop.keyframe->thisToParent_raw();
         kfToWorld = sim3_mul(kfToWorld, tp);
@@ -180,7 +197,9 @@ int main(int argc, char** argv) {
       if (!hostCloud) points = stored;
     }
     std::cout << "frames " << files.size() - 1 << " tracked_good " << good << " keyframes " << nKeyframes << " points " << points
-              << " constraints " << nConstraints << "\n";
+              << " constraints " << nConstraints;
+    if (reactivate > 0) std::cout << " reactivations " << loop.numReactivations << " unbanked " << loop.numUnbanked;
+    std::cout << "\n";
     return 0;
   } catch (const Error& e) {
     std::cerr << "dataset_slam: " << e.what() << "\n";

@@ -411,6 +411,36 @@ extern "C" int lsdloop_set_pipeline(lsdloop* l, int on) {
   try { l->loop->setPipelined(on != 0); return LSDHIP_OK; }
   catch (const Error& e) { g_err = e.what(); return e.status; }
 }
+extern "C" int lsdloop_enable_reactivation(lsdloop* l, int max_keyframes) {
+  if (!l) return LSDHIP_E_ARG;
+  try { l->loop->enableReactivation(max_keyframes); return LSDHIP_OK; }
+  catch (const Error& e) { g_err = e.what(); return e.status; }
+}
+extern "C" int lsdloop_keyframe_changes(lsdloop* l, int* out, int max) {
+  if (!l || (max > 0 && !out)) return LSDHIP_E_ARG;
+  const auto& log = l->loop->keyframeChanges;
+  for (int i = 0; i < (int)log.size() && i < max; i++) {
+    const SlamLoop::KeyframeChange& c = log[(size_t)i];
+    int* o = out + 7 * (size_t)i;
+    o[0] = c.frameId; o[1] = c.previousKfId; o[2] = c.newKfId; o[3] = c.reactivated ? 1 : 0;
+    o[4] = c.numPotential; o[5] = c.numChecked; o[6] = c.numTracked;
+  }
+  return (int)log.size();
+}
+extern "C" int lsdloop_download_map(lsdloop* l, lsdhip_hypothesis* out) {
+  if (!l || !out) return LSDHIP_E_ARG;
+  try {
+    l->loop->flushDeferredMapping();
+    const std::vector<lsdhip_hypothesis> m = l->loop->map.currentDepthMap();
+    std::memcpy(out, m.data(), m.size() * sizeof(lsdhip_hypothesis));
+    return LSDHIP_OK;
+  } catch (const Error& e) { g_err = e.what(); return e.status < 0 ? e.status : LSDHIP_E_STATE; }
+}
+extern "C" int lsdloop_reactivation_counts(lsdloop* l, long long out2[2]) {
+  if (!l || !out2) return LSDHIP_E_ARG;
+  out2[0] = l->loop->numReactivations; out2[1] = l->loop->numUnbanked;
+  return LSDHIP_OK;
+}
 extern "C" int lsdloop_set_live_queue(lsdloop* l, int frames) {
   if (!l || frames < 1) return LSDHIP_E_ARG;
   l->loop->liveQueueLength = frames;

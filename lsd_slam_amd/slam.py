@@ -198,6 +198,13 @@ class Frame:
     def idepthVar(self, level=0):
         return self._plane(4, level)
 
+    def reActivationData(self):
+        """(idepth_reAct f4, idepthVar_reAct f4, validity_reAct u1) [h, w] as Frame::takeReActivationData left them (Frame.cpp:107-145;
+        lsdhip_frame_download what = 7, 8, 9); the first and the last are defined where idepthVar_reAct > 0"""
+        val = np.zeros((self.height(0), self.width(0)), np.uint8)
+        check(self.L.lsdhip_frame_download(self.h_, 9, 0, val.ctypes.data), False)
+        return self._plane(7, 0), self._plane(8, 0), val
+
     def keyframePoints(self):
         """the keyframeMsg payload packed on the device (lsdhip_frame_pack_keyframe_points): structured array [h, w] of
         (idepth f4, idepth_var f4, color u1 x 4), the InputPointDense records of V/KeyFrameDisplay.h:39-44"""
@@ -788,6 +795,20 @@ class DepthMap:
         s = (C.c_float * n)()
         check(maps[0].L.lsdhip_depth_change_keyframe_batch(n, ma, fa, s), False)
         return [float(v) for v in s]
+
+    @staticmethod
+    def reactivateKeyframeBatch(maps, old_keyframes):
+        """finalizeKeyFrame() + setFromExistingKF(old_keyframes[j]) of several sequences' maps in three shared launches
+        (lsdhip_depth_reactivate_keyframe_batch)"""
+        n = len(maps)
+        for m, f in zip(maps, old_keyframes):
+            m._keep.append(f)
+        ma = (C.c_void_p * n)(*[m.h_ for m in maps])
+        fa = (C.c_void_p * n)(*[f.h_ for f in old_keyframes])
+        check(maps[0].L.lsdhip_depth_reactivate_keyframe_batch(n, ma, fa), False)
+
+    def reactivateKeyframe(self, old_keyframe):
+        DepthMap.reactivateKeyframeBatch([self], [old_keyframe])
 
     def currentDepthMap(self):
         out = np.zeros((self.ctx.h, self.ctx.w), dtype=HYP_DTYPE)
