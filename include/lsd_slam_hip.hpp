@@ -129,6 +129,38 @@ class Context {
 
 class TrackingReference;
 
+// util/Undistorter.h — UndistorterPTAM's remap tables on the device (lsdhip_undistorter_*), bound to the Context of the OUTPUT size and
+// K: one camera serves every frame and loop of that context.  The tables come from lsd_slam_hip::Undistorter (lsd_slam_hip_io.hpp):
+//   Undistorter u = Undistorter::fromFile("camera.cfg");
+//   DeviceUndistorter d(u.in_width, u.in_height, u.out_width, u.out_height, u.K, u.remapX.data(), u.remapY.data());
+// A pass-through calibration (no tables) needs none: its images are the rectified ones.
+class DeviceUndistorter {
+ public:
+  DeviceUndistorter(int inWidth, int inHeight, int width, int height, const Mat3f& K, const float* remapX, const float* remapY)
+      : ctx_(Context::get(width, height, K)), inW_(inWidth), inH_(inHeight) {
+    check(lsdhip_undistorter_create(ctx_->handle(), inWidth, inHeight, remapX, remapY, &h_), "lsdhip_undistorter_create");
+  }
+  DeviceUndistorter(const DeviceUndistorter&) = delete;
+  DeviceUndistorter& operator=(const DeviceUndistorter&) = delete;
+  ~DeviceUndistorter() { lsdhip_undistorter_destroy(h_); }
+  // UndistorterPTAM::undistort: inWidth * inHeight raw bytes -> width * height rectified bytes, either side on the host or the device
+  void undistort(const unsigned char* raw, bool rawOnDevice, unsigned char* out, bool outOnDevice) const {
+    check(lsdhip_undistorter_apply(h_, raw, rawOnDevice ? 1 : 0, out, outOnDevice ? 1 : 0), "lsdhip_undistorter_apply");
+  }
+  int inputWidth() const { return inW_; }
+  int inputHeight() const { return inH_; }
+  int width() const { return ctx_->width(); }
+  int height() const { return ctx_->height(); }
+  const Mat3f& K() const { return ctx_->K(); }
+  lsdhip_undistorter* handle() const { return h_; }
+  const std::shared_ptr<Context>& context() const { return ctx_; }
+
+ private:
+  std::shared_ptr<Context> ctx_;
+  lsdhip_undistorter* h_ = nullptr;
+  int inW_, inH_;
+};
+
 // DataStructures/Frame.h — a frame whose pyramids live on the device
 class Frame {
  public:
@@ -149,9 +181,38 @@ class Frame {
       : ctx_(Context::get(width, height, K)), id_(id), timestamp_(timestamp) {
     check(lsdhip_frame_create_async(ctx_->handle(), id, image.ptr, &h_), "lsdhip_frame_create_async");
   }
+  // Raw camera images (inputWidth * inputHeight bytes of the undistorter's camera), rectified inside frame creation
+  // (lsdhip_frame_create_undistorted*): host memory, device memory, host memory without the wait — as the three forms above.
+  struct RawImage { const unsigned char* ptr; };
+  struct RawDeviceImage { const unsigned char* ptr; };
+  struct RawHostImageAsync { const unsigned char* ptr; };
+  Frame(int id, const DeviceUndistorter& undistorter, double timestamp, RawImage image)
+      : ctx_(undistorter.context()), id_(id), timestamp_(timestamp) {
+    check(lsdhip_frame_create_undistorted(undistorter.handle(), id, image.ptr, &h_), "lsdhip_frame_create_undistorted");
+  }
+  Frame(int id, const DeviceUndistorter& undistorter, double timestamp, RawDeviceImage image)
+      : ctx_(undistorter.context()), id_(id), timestamp_(timestamp) {
+    check(lsdhip_frame_create_undistorted_from_device(undistorter.handle(), id, image.ptr, &h_), "lsdhip_frame_create_undistorted_from_device");
+  }
+  Frame(int id, const DeviceUndistorter& undistorter, double timestamp, RawHostImageAsync image)
+      : ctx_(undistorter.context()), id_(id), timestamp_(timestamp) {
+    check(lsdhip_frame_create_undistorted_async(undistorter.handle(), id, image.ptr, &h_), "lsdhip_frame_create_undistorted_async");
+  }
   Frame(const Frame&) = delete;
   Frame& operator=(const Frame&) = delete;
   ~Frame() { lsdhip_frame_destroy(h_); }
+  // ... from raw images of the undistorter's camera (lsdhip_frame_create_undistorted_batch)
+  static std::vector<std::shared_ptr<Frame>> createBatch(const DeviceUndistorter& undistorter, const std::vector<int>& ids,
+                                                         const unsigned char* const* rawImages, bool imagesOnDevice) {
+    const int n = (int)ids.size();
+    std::vector<lsdhip_frame*> hs((size_t)n, nullptr);
+    check(lsdhip_frame_create_undistorted_batch(undistorter.handle(), n, ids.data(), rawImages, imagesOnDevice ? 1 : 0, hs.data()),
+          "lsdhip_frame_create_undistorted_batch");
+    std::vector<std::shared_ptr<Frame>> out;
+    out.reserve((size_t)n);
+    for (int j = 0; j < n; j++) out.push_back(std::shared_ptr<Frame>(new Frame(undistorter.context(), ids[j], hs[j])));
+    return out;
+  }
   // the new frames of n sequences (one context) in two launches instead of two per frame (lsdhip_frame_create_batch)
   static std::vector<std::shared_ptr<Frame>> createBatch(int width, int height, const Mat3f& K, const std::vector<int>& ids,
                                                          const unsigned char* const* images, bool imagesOnDevice) {
@@ -775,6 +836,27 @@ class SlamLoop {
   // kfEvery == 0: the reference's distance / usage score (SlamSystem.cpp:997-1015 with doSlam = false, see keyframeScore).
   SlamLoop(int w, int h, const Mat3f& K, const unsigned char* firstImage, bool imagesOnDevice, const float* gtDepth0, int kfEvery)
       : tracker(w, h, K), map(w, h, K), w_(w), h_(h), K_(K), onDevice_(imagesOnDevice), kfEvery_(kfEvery) {
+    init(firstImage, gtDepth0);
+  }
+  // Raw camera images: w, h, K are those of the RECTIFIED images (Undistorter::out_width / out_height / K), firstRawImage and every
+  // image given to step() are raw inputWidth x inputHeight images of the undistorter's camera, rectified inside frame creation.
+  SlamLoop(int w, int h, const Mat3f& K, std::shared_ptr<DeviceUndistorter> undistorter, const unsigned char* firstRawImage,
+           bool imagesOnDevice, const float* gtDepth0, int kfEvery)
+      : tracker(w, h, K), map(w, h, K), w_(w), h_(h), K_(K), onDevice_(imagesOnDevice), kfEvery_(kfEvery) {
+    setUndistorter(std::move(undistorter));
+    init(firstRawImage, gtDepth0);
+  }
+  // From the next step() on images are raw images of this camera (null: rectified w x h images again).  One camera serves all loops of
+  // a context; an image announced as nextImage stays what it was announced as.
+  void setUndistorter(std::shared_ptr<DeviceUndistorter> undistorter) {
+    if (undistorter && undistorter->context() != Context::get(w_, h_, K_))
+      throw Error(LSDHIP_E_ARG, "SlamLoop::setUndistorter: the undistorter belongs to another output size / K");
+    undistorter_ = std::move(undistorter);
+  }
+  const std::shared_ptr<DeviceUndistorter>& undistorter() const { return undistorter_; }
+
+ private:
+  void init(const unsigned char* firstImage, const float* gtDepth0) {
     const int its[LSDHIP_PYRAMID_LEVELS] = {5, 20, 50, 100, 0};  // SlamSystem.cpp:80-81 (no level-4 iterations are run by the tracker)
     std::memcpy(tracker.settings.maxItsPerLvl, its, sizeof(its));
     keyframe = makeFrame(0, firstImage);
@@ -795,6 +877,8 @@ class SlamLoop {
       prefetchedSrc_ = pendingNext_;
     });
   }
+
+ public:
   SlamLoop(const SlamLoop&) = delete;
   SlamLoop& operator=(const SlamLoop&) = delete;
   // Tracking beside mapping with the mapper one frame behind (see above).  Switch before the first step() call.
@@ -1139,6 +1223,11 @@ class SlamLoop {
   }
   std::shared_ptr<Frame> deferredMap_;
   std::shared_ptr<Frame> makeFrame(int id, const unsigned char* img, bool mayDefer = false) {
+    if (undistorter_) {     // raw images: the same three forms
+      if (onDevice_) return std::make_shared<Frame>(id, *undistorter_, 0.0, Frame::RawDeviceImage{img});
+      if (mayDefer && pipelined_) return std::make_shared<Frame>(id, *undistorter_, 0.0, Frame::RawHostImageAsync{img});
+      return std::make_shared<Frame>(id, *undistorter_, 0.0, Frame::RawImage{img});
+    }
     if (onDevice_) return std::make_shared<Frame>(id, w_, h_, K_, 0.0, Frame::DeviceImage{img});
     // a prefetched host image on a pipelined context: the copy is queued on the mapping stream and nothing waits for it (the caller
     // keeps the bytes unchanged until the frame has been tracked: step()'s nextImage contract)
@@ -1148,6 +1237,7 @@ class SlamLoop {
   int w_, h_;
   Mat3f K_;
   bool onDevice_;
+  std::shared_ptr<DeviceUndistorter> undistorter_;   // set: images are raw images of this camera
   bool pipelined_ = false;
   int kfEvery_, sinceKF_ = 0, frameId_ = 0;
   int mappedOnKF_ = 0;            // Frame::numMappedOnThisTotal of the current keyframe
@@ -1188,13 +1278,35 @@ class SlamLoopBatch {
   SlamLoopBatch(int w, int h, const Mat3f& K, int S, const unsigned char* const* firstImages, bool imagesOnDevice,
                 const float* const* gtDepth0, int kfEvery)
       : tracker(w, h, K), w_(w), h_(h), K_(K), onDevice_(imagesOnDevice), kfEvery_(kfEvery) {
+    init(S, firstImages, gtDepth0);
+  }
+  // Raw camera images of one camera for all sequences: w, h, K are those of the RECTIFIED images, firstRawImages and every image given
+  // to step() are raw inputWidth x inputHeight images, rectified inside frame creation (SlamLoop's raw-image constructor).
+  SlamLoopBatch(int w, int h, const Mat3f& K, std::shared_ptr<DeviceUndistorter> undistorter, int S, const unsigned char* const* firstRawImages,
+                bool imagesOnDevice, const float* const* gtDepth0, int kfEvery)
+      : tracker(w, h, K), w_(w), h_(h), K_(K), onDevice_(imagesOnDevice), kfEvery_(kfEvery) {
+    setUndistorter(std::move(undistorter));
+    init(S, firstRawImages, gtDepth0);
+  }
+  // From the next step() on images are raw images of this camera (null: rectified w x h images again); images announced as nextImages
+  // stay what they were announced as.
+  void setUndistorter(std::shared_ptr<DeviceUndistorter> undistorter) {
+    if (undistorter && undistorter->context() != Context::get(w_, h_, K_))
+      throw Error(LSDHIP_E_ARG, "SlamLoopBatch::setUndistorter: the undistorter belongs to another output size / K");
+    undistorter_ = std::move(undistorter);
+  }
+
+ private:
+  void init(int S, const unsigned char* const* firstImages, const float* const* gtDepth0) {
+    const int w = w_, h = h_, kfEvery = kfEvery_;
+    const Mat3f& K = K_;
     if (S <= 0 || kfEvery <= 0) throw Error(LSDHIP_E_ARG, "SlamLoopBatch: S > 0 sequences, a fixed keyframe interval > 0");
     const int its[LSDHIP_PYRAMID_LEVELS] = {5, 20, 50, 100, 0};
     std::memcpy(tracker.settings.maxItsPerLvl, its, sizeof(its));
     tracker.setBatchCoarseMinJobs(coarseMinJobs(false));
     std::vector<int> ids((size_t)S);
     for (int s = 0; s < S; s++) ids[s] = idOf(s, 0);
-    std::vector<std::shared_ptr<Frame>> first = Frame::createBatch(w, h, K, ids, firstImages, imagesOnDevice);
+    std::vector<std::shared_ptr<Frame>> first = createFrames(ids, firstImages);
     for (int s = 0; s < S; s++) {
       seqs_.emplace_back(new Sequence(w, h, K));
       Sequence& q = *seqs_.back();
@@ -1210,6 +1322,13 @@ class SlamLoopBatch {
       q.trackKF = q.keyframe;
     }
   }
+  // rectified images, or raw ones through the undistorter
+  std::vector<std::shared_ptr<Frame>> createFrames(const std::vector<int>& ids, const unsigned char* const* images) {
+    if (undistorter_) return Frame::createBatch(*undistorter_, ids, images, onDevice_);
+    return Frame::createBatch(w_, h_, K_, ids, images, onDevice_);
+  }
+
+ public:
   // Sequences started together change keyframe in the same step; real cameras do not.  phase[s] in [0, kfEvery): sequence s behaves as
   // if its current keyframe were already phase[s] frames old (its first keyframe change comes kfEvery - phase[s] frames in).  Call before
   // the first step().
@@ -1375,7 +1494,7 @@ class SlamLoopBatch {
     for (int s : group) if (!seqs_[s]->trackingLost) { ids.push_back(idOf(s, frameId)); imgs.push_back(images[s]); }
     std::vector<std::shared_ptr<Frame>> out(group.size());
     if (ids.empty()) return out;
-    std::vector<std::shared_ptr<Frame>> made = Frame::createBatch(w_, h_, K_, ids, imgs.data(), onDevice_);
+    std::vector<std::shared_ptr<Frame>> made = createFrames(ids, imgs.data());
     size_t k = 0;
     for (size_t i = 0; i < group.size(); i++) if (!seqs_[group[i]]->trackingLost) out[i] = made[k++];
     return out;
@@ -1512,6 +1631,7 @@ class SlamLoopBatch {
   Mat3f K_;
   bool onDevice_;
   int kfEvery_, frameId_ = 0;
+  std::shared_ptr<DeviceUndistorter> undistorter_;   // set: images are raw images of this camera
   std::vector<std::unique_ptr<Sequence>> seqs_;
 };
 

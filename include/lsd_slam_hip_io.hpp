@@ -1,6 +1,8 @@
 // lsd_slam_hip_io.hpp — host-side data formats either side of the hot path, header-only C++:
 //   * the camera calibration file of lsd_slam_core (calib/*.cfg, parsed by util/Undistorter.cpp:43-140) in its
-//     distortion-free form, with the reference's K convention (Undistorter.cpp:340-344);
+//     distortion-free form, with the reference's K convention (Undistorter.cpp:340-344), and — struct Undistorter — in its FOV-model
+//     form for raw camera images: output intrinsics, remap tables and the bilinear gather of UndistorterPTAM (Undistorter.cpp:91-411),
+//     the yardstick of the device's rectification inside frame creation;
 //   * binary PGM (P5) image files for the image-folder driver (the reference reads through OpenCV, which is not here);
 //   * the keyframe message of lsd_slam_viewer (msg/keyframeMsg.msg; InputPointDense payload V/KeyFrameDisplay.h:39-44,
 //     filled as C/IOWrapper/ROS/ROSOutput3DWrapper.cpp:70-111) in ROS 1 wire serialisation;
@@ -14,8 +16,11 @@
 #ifndef LSD_SLAM_HIP_IO_HPP
 #define LSD_SLAM_HIP_IO_HPP
 
+#include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
+#include <cstring>
 #include <fstream>
 #include <sstream>
 #include <string>
@@ -58,6 +63,204 @@ inline Calibration parseCalibration(const std::string& path) {
   c.K = Mat3f::intrinsics(fx, fy, cx, cy);
   return c;
 }
+
+// UndistorterPTAM (util/Undistorter.cpp:91-411): the FOV ("ATAN") camera model of the reference's calibration files, for raw camera
+// images — what parseCalibration above refuses.  Plain host code: the parser, the output intrinsics, the remap tables and the bilinear
+// gather.  undistort() is the yardstick of the device path (lsdhip_undistorter_apply, lsdhip_frame_create_undistorted*: DeviceUndistorter
+// of lsd_slam_hip.hpp), which is held to it bit for bit.
+//
+// What is pinned and what is not:
+//   * every expression is evaluated in the reference's types and order (float variables; a double literal or factor promotes the
+//     expression it stands in, as in the reference), with the float overloads of tan / atan / sqrt, and without contraction into fused
+//     multiply-adds (the functions below carry their own contraction switch; compile test programs with -ffp-contract=off all the same);
+//   * undistort() converts the interpolated value to a byte by truncation toward zero with the range clamped to [0, 255] (NaN: 0): the
+//     reference's float -> uchar cast is undefined outside that range;
+//   * a reference build whose compiler contracts the interpolation into FMAs (-march=native on an FMA machine) can differ from
+//     undistort() by one grey level on rare pixels, and one whose <cmath> resolves the unqualified tan / atan to the double functions
+//     can differ in the last bits of the tables.  Neither can be pinned from here;
+//   * line 3 == "none" with dist != 0 reads an uninitialised outputCalibration in the reference: refused here.
+// The OpenCV model (8 parameters on line 1, UndistorterOpenCV, Undistorter.cpp:449-) is refused: cv::remap's fixed-point interpolation
+// cannot be restated without OpenCV.  Only the relative form of line 1 is defined (the reference multiplies by the image size
+// unconditionally, :177-180): absolute pixel values (fx > 1) are refused.
+#if defined(__clang__)
+#define LSD_IO_NO_CONTRACT_FN
+#define LSD_IO_NO_CONTRACT_BODY _Pragma("clang fp contract(off)")
+#elif defined(__GNUC__)
+#define LSD_IO_NO_CONTRACT_FN __attribute__((optimize("fp-contract=off")))
+#define LSD_IO_NO_CONTRACT_BODY
+#else
+#define LSD_IO_NO_CONTRACT_FN
+#define LSD_IO_NO_CONTRACT_BODY
+#endif
+struct Undistorter {
+  enum Mode { Crop, Full, None, Explicit };
+  int in_width = 0, in_height = 0, out_width = 0, out_height = 0;
+  float inputCalibration[5] = {0, 0, 0, 0, 0};
+  float outputCalibration[5] = {0, 0, 0, 0, 0};   // relative (fx / w, fy / h, (cx + 0.5) / w, (cy + 0.5) / h, 0) of the rectified images (:276-280)
+  Mat3f K = Mat3f::intrinsics(0, 0, 0, 0);        // of the rectified images, by the convention of :339-344
+  std::vector<float> remapX, remapY;              // out_width * out_height each, -1 outside the input image; empty: pass-through
+  // neither distortion nor resize (:370-375): undistort() copies, no tables
+  bool passThrough() const { return remapX.empty(); }
+
+  // in5 = fx fy cx cy dist (relative), out5 = the five numbers of line 3 (Explicit only, else ignored / null)
+  LSD_IO_NO_CONTRACT_FN Undistorter(const float in5[5], int in_w, int in_h, Mode mode, const float* out5, int out_w, int out_h) {
+    LSD_IO_NO_CONTRACT_BODY
+    if (in_w < 2 || in_h < 2 || out_w <= 0 || out_h <= 0) throw Error(LSDHIP_E_ARG, "calibration: bad image size");
+    if (out_w % 16 || out_h % 16) throw Error(LSDHIP_E_ARG, "image size must be a multiple of 16 (C/SlamSystem.cpp:55-59)");
+    if (in5[0] > 1 || in5[1] > 1)
+      throw Error(LSDHIP_E_ARG, "calibration: fx fy cx cy must be relative to the image size (the reference's FOV undistorter multiplies them by it, Undistorter.cpp:177-180); absolute pixel values are not supported");
+    in_width = in_w; in_height = in_h; out_width = out_w; out_height = out_h;
+    for (int i = 0; i < 5; i++) inputCalibration[i] = in5[i];
+    const float dist = inputCalibration[4];
+    if (mode == None && dist != 0)
+      throw Error(LSDHIP_E_ARG, "calibration: 'none' with a distorted camera (dist != 0) is undefined in the reference; use crop, full or explicit output intrinsics");
+    if (mode == Explicit && !out5) throw Error(LSDHIP_E_ARG, "calibration: explicit output intrinsics missing");
+    const float d2t = 2.0f * std::tan(dist / 2.0f);
+    // current camera parameters (:177-188; the scale factors there are 1)
+    float fx = inputCalibration[0] * in_width;
+    float fy = inputCalibration[1] * in_height;
+    float cx = (float)(inputCalibration[2] * in_width - 0.5);
+    float cy = (float)(inputCalibration[3] * in_height - 0.5);
+    cx = (float)((cx + 0.5) * 1.0 - 0.5);
+    cy = (float)((cy + 0.5) * 1.0 - 0.5);
+    float ofx, ofy, ocx, ocy;
+    if (dist == 0) {                       // :194-200 (whatever line 3 says)
+      ofx = inputCalibration[0] * out_width;
+      ofy = inputCalibration[1] * out_height;
+      ocx = (float)((inputCalibration[2] * out_width) - 0.5);
+      ocy = (float)((inputCalibration[3] * out_height) - 0.5);
+    } else if (mode == Crop) {             // :201-228
+      const float left_radius = (cx) / fx;
+      const float right_radius = (in_width - 1 - cx) / fx;
+      const float top_radius = (cy) / fy;
+      const float bottom_radius = (in_height - 1 - cy) / fy;
+      const float trans_left_radius = std::tan(left_radius * dist) / d2t;
+      const float trans_right_radius = std::tan(right_radius * dist) / d2t;
+      const float trans_top_radius = std::tan(top_radius * dist) / d2t;
+      const float trans_bottom_radius = std::tan(bottom_radius * dist) / d2t;
+      ofy = fy * ((top_radius + bottom_radius) / (trans_top_radius + trans_bottom_radius)) * ((float)out_height / (float)in_height);
+      ocy = (trans_top_radius / top_radius) * ofy * cy / fy;
+      ofx = fx * ((left_radius + right_radius) / (trans_left_radius + trans_right_radius)) * ((float)out_width / (float)in_width);
+      ocx = (trans_left_radius / left_radius) * ofx * cx / fx;
+    } else if (mode == Full) {             // :229-267
+      const float left_radius = cx / fx;
+      const float right_radius = (in_width - 1 - cx) / fx;
+      const float top_radius = cy / fy;
+      const float bottom_radius = (in_height - 1 - cy) / fy;
+      const float tl_radius = std::sqrt(left_radius * left_radius + top_radius * top_radius);
+      const float tr_radius = std::sqrt(right_radius * right_radius + top_radius * top_radius);
+      const float bl_radius = std::sqrt(left_radius * left_radius + bottom_radius * bottom_radius);
+      const float br_radius = std::sqrt(right_radius * right_radius + bottom_radius * bottom_radius);
+      const float trans_tl_radius = std::tan(tl_radius * dist) / d2t;
+      const float trans_tr_radius = std::tan(tr_radius * dist) / d2t;
+      const float trans_bl_radius = std::tan(bl_radius * dist) / d2t;
+      const float trans_br_radius = std::tan(br_radius * dist) / d2t;
+      const float hor = std::max(br_radius, tr_radius) + std::max(bl_radius, tl_radius);
+      const float vert = std::max(tr_radius, tl_radius) + std::max(bl_radius, br_radius);
+      const float trans_hor = std::max(trans_br_radius, trans_tr_radius) + std::max(trans_bl_radius, trans_tl_radius);
+      const float trans_vert = std::max(trans_tr_radius, trans_tl_radius) + std::max(trans_bl_radius, trans_br_radius);
+      ofy = fy * ((vert) / (trans_vert)) * ((float)out_height / (float)in_height);
+      ocy = std::max(trans_tl_radius / tl_radius, trans_tr_radius / tr_radius) * ofy * cy / fy;
+      ofx = fx * ((hor) / (trans_hor)) * ((float)out_width / (float)in_width);
+      ocx = std::max(trans_bl_radius / bl_radius, trans_tl_radius / tl_radius) * ofx * cx / fx;
+    } else {                               // :268-274
+      ofx = out5[0] * out_width;
+      ofy = out5[1] * out_height;
+      ocx = (float)(out5[2] * out_width - 0.5);
+      ocy = (float)(out5[3] * out_height - 0.5);
+    }
+    outputCalibration[0] = ofx / out_width;
+    outputCalibration[1] = ofy / out_height;
+    outputCalibration[2] = (float)((ocx + 0.5) / out_width);
+    outputCalibration[3] = (float)((ocy + 0.5) / out_height);
+    outputCalibration[4] = 0;
+    // :339-344 (a double matrix there, read back as float by the callers)
+    K = Mat3f::intrinsics(outputCalibration[0] * out_width, outputCalibration[1] * out_height,
+                          (float)(outputCalibration[2] * out_width - 0.5), (float)(outputCalibration[3] * out_height - 0.5));
+    if (in_height == out_height && in_width == out_width && dist == 0) return;   // pass-through (:370-375)
+    remapX.resize((size_t)out_width * out_height);
+    remapY.resize((size_t)out_width * out_height);
+    for (int y = 0; y < out_height; y++)
+      for (int x = 0; x < out_width; x++) {      // :285-315
+        float ix = (x - ocx) / ofx;
+        float iy = (y - ocy) / ofy;
+        const float r = std::sqrt(ix * ix + iy * iy);
+        const float fac = (r == 0 || dist == 0) ? 1 : std::atan(r * d2t) / (dist * r);
+        ix = fx * fac * ix + cx;
+        iy = fy * fac * iy + cy;
+        // make rounding resistant.
+        if (ix == 0) ix = (float)0.01;
+        if (iy == 0) iy = (float)0.01;
+        if (ix == in_width - 1) ix = (float)(in_width - 1.01);
+        if (iy == in_height - 1) ix = (float)(in_height - 1.01);   // sic (:302 assigns ix): iy stays in_height - 1, the pixel is invalid below
+        const size_t o = (size_t)x + (size_t)y * out_width;
+        if (ix > 0 && iy > 0 && ix < in_width - 1 && iy < in_height - 1) {
+          remapX[o] = ix;
+          remapY[o] = iy;
+        } else {
+          remapX[o] = -1;
+          remapY[o] = -1;
+        }
+      }
+  }
+
+  // The four lines of a calibration file (:100-166)
+  static Undistorter fromLines(const std::string& l1, const std::string& l2, const std::string& l3in, const std::string& l4) {
+    float ic[8], in5[5], out5[5];
+    int iw, ih, ow, oh;
+    if (std::sscanf(l1.c_str(), "%f %f %f %f %f %f %f %f", &ic[0], &ic[1], &ic[2], &ic[3], &ic[4], &ic[5], &ic[6], &ic[7]) == 8)
+      throw Error(LSDHIP_E_ARG, "calibration: 8 parameters on the first line are the OpenCV camera model (UndistorterOpenCV), which is not supported: only the FOV model (fx fy cx cy dist)");
+    if (std::sscanf(l1.c_str(), "%f %f %f %f %f", &in5[0], &in5[1], &in5[2], &in5[3], &in5[4]) != 5 || std::sscanf(l2.c_str(), "%d %d", &iw, &ih) != 2)
+      throw Error(LSDHIP_E_ARG, "calibration: cannot read 'fx fy cx cy dist' and the input size");
+    std::string l3 = l3in;
+    while (!l3.empty() && isspace((unsigned char)l3.back())) l3.pop_back();
+    Mode mode;
+    if (l3 == "crop") mode = Crop;
+    else if (l3 == "full") mode = Full;
+    else if (l3 == "none") mode = None;
+    else if (std::sscanf(l3.c_str(), "%f %f %f %f %f", &out5[0], &out5[1], &out5[2], &out5[3], &out5[4]) == 5) mode = Explicit;
+    else throw Error(LSDHIP_E_ARG, "calibration: the third line is none of crop, full, none or five output parameters");
+    if (std::sscanf(l4.c_str(), "%d %d", &ow, &oh) != 2) throw Error(LSDHIP_E_ARG, "calibration: cannot read the output size");
+    return Undistorter(in5, iw, ih, mode, mode == Explicit ? out5 : nullptr, ow, oh);
+  }
+  static Undistorter fromFile(const std::string& path) {
+    std::ifstream f(path);
+    if (!f) throw Error(LSDHIP_E_ARG, "cannot open calibration file " + path);
+    std::string l1, l2, l3, l4;
+    std::getline(f, l1); std::getline(f, l2); std::getline(f, l3); std::getline(f, l4);
+    return fromLines(l1, l2, l3, l4);
+  }
+  // The calibration file of the rectified images (what parseCalibration accepts, and reads back to exactly K)
+  std::string rectifiedCalibrationText() const {
+    char b[256];
+    std::snprintf(b, sizeof(b), "%.9g %.9g %.9g %.9g 0\n%d %d\nnone\n%d %d\n", (double)outputCalibration[0], (double)outputCalibration[1],
+                  (double)outputCalibration[2], (double)outputCalibration[3], out_width, out_height, out_width, out_height);
+    return b;
+  }
+
+  // UndistorterPTAM::undistort (:355-411): raw in_width * in_height bytes -> out out_width * out_height bytes
+  LSD_IO_NO_CONTRACT_FN void undistort(const unsigned char* raw, unsigned char* out) const {
+    LSD_IO_NO_CONTRACT_BODY
+    const int n = out_width * out_height;
+    if (passThrough()) { std::memcpy(out, raw, (size_t)n); return; }
+    const float* rx = remapX.data();
+    const float* ry = remapY.data();
+    for (int idx = n - 1; idx >= 0; idx--) {
+      float xx = rx[idx];
+      float yy = ry[idx];
+      if (xx < 0) { out[idx] = 0; continue; }
+      const int xxi = (int)xx;
+      const int yyi = (int)yy;
+      xx -= xxi;
+      yy -= yyi;
+      const float xxyy = xx * yy;
+      const unsigned char* src = raw + xxi + yyi * in_width;
+      const float s00 = src[0], s10 = src[1], s01 = src[in_width], s11 = src[1 + in_width];
+      const float v = ((xxyy * s11 + (yy - xxyy) * s01) + (xx - xxyy) * s10) + (((1 - xx) - yy) + xxyy) * s00;
+      out[idx] = !(v > 0) ? 0 : (v >= 255 ? 255 : (unsigned char)(int)v);
+    }
+  }
+};
 
 inline bool readPGM(const std::string& path, int w, int h, std::vector<unsigned char>& out) {
   FILE* f = fopen(path.c_str(), "rb");

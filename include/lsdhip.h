@@ -44,6 +44,7 @@ typedef struct lsdhip_frame lsdhip_frame;
 typedef struct lsdhip_tracker lsdhip_tracker;
 typedef struct lsdhip_depthmap lsdhip_depthmap;
 typedef struct lsdhip_cloud lsdhip_cloud;
+typedef struct lsdhip_undistorter lsdhip_undistorter;
 
 /* The mutable globals of C/util/settings.cpp:77-88 that the hot path reads. */
 typedef struct lsdhip_params {
@@ -134,6 +135,27 @@ int lsdhip_frame_create_async(lsdhip_ctx* ctx, int id, const uint8_t* gray_host,
  * gray: n image pointers (all device or all host), out: n handles.  Several sequences sharing one GPU (BASELINE.json configs[3]
  * with more sequences than GPUs) enter the device through this call; no reference counterpart (one Frame constructor per image). */
 int lsdhip_frame_create_batch(lsdhip_ctx* ctx, int n, const int* ids, const uint8_t* const* gray, int images_on_device, lsdhip_frame** out);
+/* Raw camera images.  UndistorterPTAM's remap tables (C/util/Undistorter.cpp:282-315, built on the host by lsd_slam_hip::Undistorter of
+ * lsd_slam_hip_io.hpp) for the context's w x h output image, uploaded once and resident: remapX_host / remapY_host hold w * h floats each,
+ * a negative x marks a pixel outside the in_w x in_h input image.  LSDHIP_E_ARG for a table with an entry that is neither negative nor
+ * inside (0 <= x < in_w - 1, 0 <= y < in_h - 1): the kernels read the four taps around an entry without a bounds test.  The object also
+ * owns the device staging of raw host images (a raw image may be larger than a frame's uint8 plane).  Destroy it before its context. */
+int lsdhip_undistorter_create(lsdhip_ctx* ctx, int in_w, int in_h, const float* remapX_host, const float* remapY_host, lsdhip_undistorter** out);
+void lsdhip_undistorter_destroy(lsdhip_undistorter* u);
+/* UndistorterPTAM::undistort (Undistorter.cpp:355-411): the rectified uint8 image (w * h bytes) of a raw one (in_w * in_h bytes), byte for
+ * byte what lsd_slam_hip::Undistorter::undistort writes on the host.  Either side in host memory or in device memory of the context's GPU;
+ * with host memory on either side the call returns when out_gray is written, device to device it is queued on the mapping stream. */
+int lsdhip_undistorter_apply(lsdhip_undistorter* u, const uint8_t* raw, int raw_on_device, uint8_t* out_gray, int out_on_device);
+/* The four frame creators above for raw in_w x in_h images of the undistorter's camera: undistort (Undistorter.cpp:355-411) followed by
+ * Frame::Frame (Frame.cpp:35-48) and the pyramid builders, in the same two launches — the image-pyramid kernel fetches every pixel through
+ * the remap table, no rectified uint8 image is written.  The planes are, bit for bit, those of the plain creator on the output of
+ * lsdhip_undistorter_apply.  Same waiting rules as their counterparts: _undistorted and the batch form with host images return once the
+ * host images may be reused; raw_host of the _async form must stay unchanged until a tracker call on the frame has returned or the
+ * context has been synchronised. */
+int lsdhip_frame_create_undistorted(lsdhip_undistorter* u, int id, const uint8_t* raw_host, lsdhip_frame** out);
+int lsdhip_frame_create_undistorted_async(lsdhip_undistorter* u, int id, const uint8_t* raw_host, lsdhip_frame** out);
+int lsdhip_frame_create_undistorted_from_device(lsdhip_undistorter* u, int id, const uint8_t* raw_dev, lsdhip_frame** out);
+int lsdhip_frame_create_undistorted_batch(lsdhip_undistorter* u, int n, const int* ids, const uint8_t* const* raw, int images_on_device, lsdhip_frame** out);
 /* Frame-memory pool (FrameMemory::getBuffer / returnBuffer keep returned buffers for reuse, C/DataStructures/FrameMemory.cpp:67-117):
  * make sure n frame arenas are allocated and waiting.  A loop that keeps its keyframes alive takes a fresh arena per keyframe; without
  * the pool that is a hipMalloc of ~20 MB (0.5 ms) every keyframe. */

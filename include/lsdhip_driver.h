@@ -25,6 +25,13 @@ typedef struct lsdloop_stats {
 /* K4 = fx, fy, cx, cy.  first_image / images: uint8 w*h, host memory or (images_on_device != 0) memory of `device`. */
 int lsdloop_create(int device, int w, int h, const float K4[4], const uint8_t* first_image, int images_on_device,
                    const float* gt_depth0_host, int kf_every, lsdloop** out);
+/* The same loop fed RAW camera images (lsd_slam_hip::SlamLoop's raw-image constructor): w, h, K4 are those of the rectified images,
+ * remapX_host / remapY_host the w * h entries of UndistorterPTAM's tables (C/util/Undistorter.cpp:282-315; lsd_slam_hip::Undistorter
+ * builds them) for raw in_w x in_h images; first_raw_image and every image given to lsdloop_run hold in_w * in_h bytes and are
+ * rectified inside frame creation (lsdhip_frame_create_undistorted*).  A create variant, not a setter: the first image is raw too. */
+int lsdloop_create_undistorted(int device, int w, int h, const float K4[4], int in_w, int in_h, const float* remapX_host,
+                               const float* remapY_host, const uint8_t* first_raw_image, int images_on_device,
+                               const float* gt_depth0_host, int kf_every, lsdloop** out);
 void lsdloop_destroy(lsdloop* l);
 /* Runs up to n frames; stops early right after a frame that became a keyframe when stop_at_keyframe != 0.
  * Returns the number of frames consumed (>= 0) or a negative lsdhip status.  frameToKeyframe_out: n x 7 doubles or NULL. */
@@ -104,6 +111,10 @@ void* lsdloop_ctx(lsdloop* l);   /* the lsdhip_ctx* the loop runs on (prof hooks
 typedef struct lsdloopbatch lsdloopbatch;
 int lsdloopbatch_create(int device, int w, int h, const float K4[4], int S, const uint8_t* const* first_images, int images_on_device,
                         const float* const* gt_depth0_host, int kf_every, lsdloopbatch** out);
+/* ... fed raw images of ONE camera for all sequences (as lsdloop_create_undistorted) */
+int lsdloopbatch_create_undistorted(int device, int w, int h, const float K4[4], int in_w, int in_h, const float* remapX_host,
+                                    const float* remapY_host, int S, const uint8_t* const* first_raw_images, int images_on_device,
+                                    const float* const* gt_depth0_host, int kf_every, lsdloopbatch** out);
 void lsdloopbatch_destroy(lsdloopbatch* l);
 int lsdloopbatch_run(lsdloopbatch* l, const uint8_t* const* images, int n, double* frameToKeyframe_out);
 int lsdloopbatch_get_stats(lsdloopbatch* l, long long* out6_per_sequence);

@@ -6,4 +6,4 @@ This package holds only what that path needs: csrc/ (HIP kernels + the C ABI), c
 """
 from .capi import HYP_DTYPE, LsdHipError  # noqa: F401
 from .slam import (IDENTITY, Context, DepthMap, Frame, KeyFrameBank, PointCloud, SE3Tracker, Sim3Tracker, SlamLoop,
-                   TrackableKeyFrameSearch, TrackingReference)  # noqa: F401
+                   TrackableKeyFrameSearch, TrackingReference, Undistorter)  # noqa: F401

@@ -106,6 +106,13 @@ def _signatures():
         "lsdhip_ctx_map_stream": (vp, [vp]),
         "lsdhip_frame_create_async": (i, [vp, i, vp, pvp]),
         "lsdhip_frame_create_batch": (i, [vp, i, vp, pvp, i, pvp]),
+        "lsdhip_undistorter_create": (i, [vp, i, i, vp, vp, pvp]),
+        "lsdhip_undistorter_destroy": (None, [vp]),
+        "lsdhip_undistorter_apply": (i, [vp, vp, i, vp, i]),
+        "lsdhip_frame_create_undistorted": (i, [vp, i, vp, pvp]),
+        "lsdhip_frame_create_undistorted_async": (i, [vp, i, vp, pvp]),
+        "lsdhip_frame_create_undistorted_from_device": (i, [vp, i, vp, pvp]),
+        "lsdhip_frame_create_undistorted_batch": (i, [vp, i, vp, pvp, i, pvp]),
         "lsdhip_ctx_reserve_frames": (i, [vp, i]),
         "lsdhip_frame_relative_pose": (i, [vp, vp, vp]),
         "lsdhip_frame_publish_depth": (i, [vp]),

@@ -3,6 +3,7 @@
 //
 // Reference behaviour restated on the device:
 //   Frame::Frame                 C/DataStructures/Frame.cpp:35-48    uint8 -> float copy (no scaling)
+//   UndistorterPTAM::undistort   C/util/Undistorter.cpp:355-411      bilinear gather through the remap table, inside the uint8 -> float copy
 //   Frame::initialize            Frame.cpp:397-459                   per-level intrinsics
 //   Frame::buildImage            Frame.cpp:491-630                   2x2 box mean, SSE association (:532-544)
 //   Frame::buildGradients        Frame.cpp:643-680                   linear-index walk incl. row wrap
@@ -25,7 +26,42 @@
 // HBM traffic: 1 B/px read (uint8) + 4 B * (1 + 1/4 + 1/16 + 1/64 + 1/256) written.
 // The same workgroup also writes the level-0 gradient texels (gx, gy, I, 0) and |grad| of its 16x16 pixels, straight from
 // the uint8 source (the float image is its exact conversion), with the reference's linear-index neighbour rule.
-__device__ __forceinline__ void image_pyramid_tile(const uint8_t* __restrict__ gray, float* __restrict__ i0,
+// The tile has two pixel sources: the frame's own (rectified) uint8 image, and a raw camera image fetched through an undistorter's remap
+// table (lsdhip_frame_create_undistorted*), so that a raw frame is rectified inside the launch that converts it — no extra launch, no
+// rectified uint8 plane in between.
+struct PlainPixels {
+  const uint8_t* __restrict__ gray;
+  __device__ __forceinline__ float at(int i) const { return (float)gray[i]; }
+};
+// UndistorterPTAM::undistort (util/Undistorter.cpp:384-410) for one output pixel, as lsd_slam_hip::Undistorter::undistort
+// (include/lsd_slam_hip_io.hpp) defines it: float32, left to right, every product and sum rounded on its own (the intrinsics keep the
+// compiler from contracting them whatever -ffp-contract says), truncated to a byte with the range clamped.  m = (remapX, remapY) of the
+// pixel; a valid entry lies inside (0, in_w - 1) x (0, in_h - 1) — lsdhip_undistorter_create refuses a table with any other — so the four
+// taps are inside the raw image.  A tile's taps fall into a small window of the raw image: L2 hits; the streamed traffic is the table.
+__device__ __forceinline__ float undistorted_pixel(LSD_G const uint8_t* __restrict__ raw, const float2 m, const int in_w) {
+  float xx = m.x, yy = m.y;
+  if (xx < 0) return 0.f;
+  const int xxi = (int)xx, yyi = (int)yy;
+  xx = __fsub_rn(xx, (float)xxi);
+  yy = __fsub_rn(yy, (float)yyi);
+  const float xxyy = __fmul_rn(xx, yy);
+  LSD_G const uint8_t* src = raw + (xxi + yyi * in_w);
+  const float s00 = (float)src[0], s10 = (float)src[1], s01 = (float)src[in_w], s11 = (float)src[1 + in_w];
+  float v = __fmul_rn(xxyy, s11);
+  v = __fadd_rn(v, __fmul_rn(__fsub_rn(yy, xxyy), s01));
+  v = __fadd_rn(v, __fmul_rn(__fsub_rn(xx, xxyy), s10));
+  v = __fadd_rn(v, __fmul_rn(__fadd_rn(__fsub_rn(__fsub_rn(1.0f, xx), yy), xxyy), s00));
+  return !(v > 0.f) ? 0.f : (v >= 255.f ? 255.f : (float)(int)v);
+}
+// One interleaved (x, y) plane: a lane fetches its coordinate pair in one 8-byte load, a wave four 128-byte row pieces of the table.
+struct RemappedPixels {
+  LSD_G const uint8_t* __restrict__ raw;
+  LSD_G const float2* __restrict__ map;
+  int in_w;
+  __device__ __forceinline__ float at(int i) const { return undistorted_pixel(raw, map[i], in_w); }
+};
+template <class Pixels>
+__device__ __forceinline__ void image_pyramid_tile(const Pixels gray, float* __restrict__ i0,
                                                    float* __restrict__ i1, float* __restrict__ i2,
                                                    float* __restrict__ i3, float* __restrict__ i4, int w, int h,
                                                    float4* __restrict__ grad0, float* __restrict__ absgrad0) {
@@ -39,7 +75,7 @@ __device__ __forceinline__ void image_pyramid_tile(const uint8_t* __restrict__ g
   {
     int x = bx * 16 + tx, y = by * 16 + ty;
     const int i = y * w + x;
-    float v = (float)gray[i];
+    float v = gray.at(i);
     i0[i] = v;
     s0[ty][tx] = v;
     // Frame::buildGradients (Frame.cpp:643-680): rows 1..h-2 by linear index, so x = 0 / w-1 wrap into the neighbouring rows
@@ -49,8 +85,8 @@ __device__ __forceinline__ void image_pyramid_tile(const uint8_t* __restrict__ g
       float4 g = make_float4(0.f, 0.f, 0.f, 0.f);
       const bool inner = (i >= w) && (i < w * (h - 1));
       if (inner) {
-        g.x = 0.5f * ((float)gray[i + 1] - (float)gray[i - 1]);
-        g.y = 0.5f * ((float)gray[i + w] - (float)gray[i - w]);
+        g.x = 0.5f * (gray.at(i + 1) - gray.at(i - 1));
+        g.y = 0.5f * (gray.at(i + w) - gray.at(i - w));
         g.z = v;
       }
       grad0[i] = g;
@@ -95,7 +131,19 @@ __global__ __launch_bounds__(256) void k_image_pyramid(const uint8_t* __restrict
                                                         float* __restrict__ i1, float* __restrict__ i2,
                                                         float* __restrict__ i3, float* __restrict__ i4, int w, int h,
                                                         float4* __restrict__ grad0, float* __restrict__ absgrad0) {
-  image_pyramid_tile(gray, i0, i1, i2, i3, i4, w, h, grad0, absgrad0);
+  image_pyramid_tile(PlainPixels{gray}, i0, i1, i2, i3, i4, w, h, grad0, absgrad0);
+}
+// ... of a raw in_w-wide camera image through an undistorter's table (lsdhip_frame_create_undistorted*)
+__global__ __launch_bounds__(256) void k_image_pyramid_remap(const uint8_t* __restrict__ raw, const float2* __restrict__ map, int in_w,
+                                                              float* __restrict__ i0, float* __restrict__ i1, float* __restrict__ i2,
+                                                              float* __restrict__ i3, float* __restrict__ i4, int w, int h) {
+  image_pyramid_tile(RemappedPixels{lsd_g(raw), lsd_g(map), in_w}, i0, i1, i2, i3, i4, w, h, (float4*)nullptr, (float*)nullptr);
+}
+// The rectified uint8 image itself (lsdhip_undistorter_apply): one output pixel per lane
+__global__ __launch_bounds__(256) void k_undistort(const uint8_t* __restrict__ raw, const float2* __restrict__ map, int in_w,
+                                                    uint8_t* __restrict__ out, int n) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n) out[i] = (uint8_t)undistorted_pixel(lsd_g(raw), map[i], in_w);
 }
 // the same for the new frames of several sequences in one launch (blockIdx.z = frame; lsdhip_frame_create_batch)
 struct ImagePyrItem {
@@ -106,7 +154,14 @@ struct ImagePyrItem {
 };
 __global__ __launch_bounds__(256) void k_image_pyramid_batch(const ImagePyrItem* __restrict__ items, int w, int h) {
   const ImagePyrItem it = items[blockIdx.z];
-  image_pyramid_tile(it.gray, it.img[0], it.img[1], it.img[2], it.img[3], it.img[4], w, h, it.grad0, it.absgrad0);
+  image_pyramid_tile(PlainPixels{it.gray}, it.img[0], it.img[1], it.img[2], it.img[3], it.img[4], w, h, it.grad0, it.absgrad0);
+}
+// ... of raw images (items[].gray) through one undistorter's table (lsdhip_frame_create_undistorted_batch)
+__global__ __launch_bounds__(256) void k_image_pyramid_remap_batch(const ImagePyrItem* __restrict__ items, const float2* __restrict__ map,
+                                                                    int in_w, int w, int h) {
+  const ImagePyrItem it = items[blockIdx.z];
+  image_pyramid_tile(RemappedPixels{it.gray, lsd_g(map), in_w}, it.img[0], it.img[1], it.img[2], it.img[3], it.img[4], w, h, (float4*)nullptr,
+                     (float*)nullptr);
 }
 
 struct GradArgs {
@@ -1313,13 +1368,48 @@ static void frame_pyramids_queued(lsdhip_frame* f) {
   f->wasGoodPristine = true;                       // the mask holds the gradient launch's 0xFF fill
 }
 
-int lsd_frame_build_pyramids(lsdhip_frame* f, const uint8_t* src, hipStream_t stream) {
+// A camera's rectification on the device (lsdhip_undistorter_create): the remap table of the context's w x h output image, resident, and
+// the staging for raw host images — a raw image may be larger than a frame's own uint8 plane (in_w * in_h > w * h), so d_gray cannot take it.
+struct lsdhip_undistorter {
+  lsdhip_ctx* ctx = nullptr;
+  int in_w = 0, in_h = 0;
+  float2* d_map = nullptr;             // (remapX, remapY) interleaved, w * h entries
+  // One slot per batch entry (grown by the first batch that is wider; never per frame).  INVARIANT: a slot's upload and the launch that
+  // reads it are both queued on the mapping stream (lsd_map_stream), so the next upload into the slot is ordered behind that launch by the
+  // stream itself; stageStream remembers the stream, and a call that finds another one current (a lane region, a pipeline switch) drains it first.
+  std::vector<uint8_t*> stage;
+  hipStream_t stageStream = nullptr;
+  uint8_t* d_out = nullptr;            // lsdhip_undistorter_apply with a host destination
+  size_t rawBytes() const { return (size_t)in_w * in_h; }
+};
+// raw host images -> staging slots 0 .. n - 1 on stream `ms` (see the invariant above); dev[j] = where image j is on the device
+static int undistorter_stage(lsdhip_undistorter* u, int n, const uint8_t* const* raw_host, hipStream_t ms, const uint8_t** dev) {
+  if (u->stageStream && u->stageStream != ms) HIPCHK(hipStreamSynchronize(u->stageStream));
+  u->stageStream = ms;
+  while ((int)u->stage.size() < n) {
+    uint8_t* p = nullptr;
+    HIPCHK(hipMalloc((void**)&p, u->rawBytes()));
+    u->stage.push_back(p);
+  }
+  for (int j = 0; j < n; j++) {
+    HIPCHK(hipMemcpyAsync(u->stage[j], raw_host[j], u->rawBytes(), hipMemcpyHostToDevice, ms));
+    dev[j] = u->stage[j];
+  }
+  return LSDHIP_OK;
+}
+
+// src: the image where it is on the device (null: the frame's own uint8 plane); with an undistorter, a raw image (never null)
+static int frame_build_pyramids(lsdhip_frame* f, const uint8_t* src, hipStream_t stream, const lsdhip_undistorter* u) {
   lsdhip_ctx* c = f->ctx;
   LSD_CTX_LOCK(c);
   if (!stream) stream = lsd_map_stream(c);
   lsdhip_host_mark(21);
-  hipLaunchKernelGGL(k_image_pyramid, dim3(c->w / 16, c->h / 16), dim3(256), 0, stream, src ? src : f->d_gray, f->d_image[0], f->d_image[1],
-                     f->d_image[2], f->d_image[3], f->d_image[4], c->w, c->h, (float4*)nullptr, (float*)nullptr);
+  if (u)
+    hipLaunchKernelGGL(k_image_pyramid_remap, dim3(c->w / 16, c->h / 16), dim3(256), 0, stream, src, (const float2*)u->d_map, u->in_w,
+                       f->d_image[0], f->d_image[1], f->d_image[2], f->d_image[3], f->d_image[4], c->w, c->h);
+  else
+    hipLaunchKernelGGL(k_image_pyramid, dim3(c->w / 16, c->h / 16), dim3(256), 0, stream, src ? src : f->d_gray, f->d_image[0], f->d_image[1],
+                       f->d_image[2], f->d_image[3], f->d_image[4], c->w, c->h, (float4*)nullptr, (float*)nullptr);
   const GradMaxArgs ga = grad_max_args(f);
   lsdhip_host_mark(22);
   hipLaunchKernelGGL(k_gradients_max, dim3(ga.blk0[LSD_LEVELS]), dim3(256), 0, stream, ga);   // the gradient blocks only: maxGradients is a keyframe plane (lsd_frames_require_level0)
@@ -1328,6 +1418,7 @@ int lsd_frame_build_pyramids(lsdhip_frame* f, const uint8_t* src, hipStream_t st
   frame_pyramids_queued(f);
   return LSDHIP_OK;
 }
+int lsd_frame_build_pyramids(lsdhip_frame* f, const uint8_t* src, hipStream_t stream) { return frame_build_pyramids(f, src, stream, nullptr); }
 
 // Two item arrays in one argument record (one copy for both launches of a pair): A[n] at its start, B[n] from the next 256-byte boundary
 // on.  Filled in place between args_pair_begin and lsd_args_commit; lsd_args_release(dev) behind the launches.
@@ -1353,8 +1444,8 @@ template <class T> static int args_items_begin(lsdhip_ctx* c, size_t n, T** item
 }
 
 // The pyramids of n new frames in two launches (blockIdx.z / .y = frame).  devGray: the images where they are on the device already
-// (else each frame's own uint8 plane, uploaded by the caller).
-static int frames_build_pyramids_batch(lsdhip_ctx* c, lsdhip_frame** fs, int n, const uint8_t* const* devGray) {
+// (else each frame's own uint8 plane, uploaded by the caller).  With an undistorter devGray holds raw images (never null).
+static int frames_build_pyramids_batch(lsdhip_ctx* c, lsdhip_frame** fs, int n, const uint8_t* const* devGray, const lsdhip_undistorter* u = nullptr) {
   const hipStream_t ms = lsd_map_stream(c);
   ArgPair<ImagePyrItem, GradMaxArgs> args;
   if (int rc = args_pair_begin(c, n, args)) return rc;
@@ -1369,7 +1460,8 @@ static int frames_build_pyramids_batch(lsdhip_ctx* c, lsdhip_frame** fs, int n, 
   if (int rc = lsd_args_commit(c, ms)) return rc;
   const int bp = lsd_bprof_begin(c, 0, ms);
   if (bp < -1) return bp;
-  hipLaunchKernelGGL(k_image_pyramid_batch, dim3(c->w / 16, c->h / 16, n), dim3(256), 0, ms, args.devA, c->w, c->h);
+  if (u) hipLaunchKernelGGL(k_image_pyramid_remap_batch, dim3(c->w / 16, c->h / 16, n), dim3(256), 0, ms, args.devA, (const float2*)u->d_map, u->in_w, c->w, c->h);
+  else hipLaunchKernelGGL(k_image_pyramid_batch, dim3(c->w / 16, c->h / 16, n), dim3(256), 0, ms, args.devA, c->w, c->h);
   hipLaunchKernelGGL(k_gradients_max_batch, dim3(gradBlocks, n), dim3(256), 0, ms, args.devB);
   if (int rc = lsd_bprof_end(c, bp, ms, (double)n * (c->w * c->h))) return rc;
   HIPCHK(hipGetLastError());
@@ -1598,18 +1690,28 @@ int lsd_frame_ensure_wasgood(lsdhip_frame* f) {
 // The steps every creator shares, on the mapping stream: arenas, upload of host images, pyramids (two launches per frame, or — batched —
 // two for all), the record point the frames are complete at, and for host images the wait after which the caller may reuse its buffers.
 // gray[j] on the device is read by the pyramid kernel directly (stream-ordered; nothing else needs the uint8 plane).
-static int frames_create_steps(lsdhip_ctx* c, int n, const int* ids, const uint8_t* const* gray, bool onDevice, bool batched, bool wait, lsdhip_frame** fs) {
+// With an undistorter (lsdhip_frame_create_undistorted*) gray[j] are raw in_w x in_h images: host ones go to the undistorter's staging
+// slots instead of the frames' uint8 planes, and the pyramid kernel fetches its pixels through the remap table.
+static int frames_create_steps(lsdhip_ctx* c, int n, const int* ids, const uint8_t* const* gray, bool onDevice, bool batched, bool wait, lsdhip_frame** fs,
+                               lsdhip_undistorter* u) {
   HIPCHK(hipSetDevice(c->device));
   for (int j = 0; j < n; j++)
     if (int rc = frame_alloc(c, ids[j], &fs[j])) return rc;
   const hipStream_t ms = lsd_map_stream(c);
   if (int rc = lsd_m_begin(c)) return rc;
+  std::vector<const uint8_t*> staged;
+  if (u && !onDevice) {
+    staged.resize((size_t)n);
+    if (int rc = undistorter_stage(u, n, gray, ms, staged.data())) return rc;
+    gray = staged.data();
+    onDevice = true;
+  }
   if (!onDevice)
     for (int j = 0; j < n; j++) HIPCHK(hipMemcpyAsync(fs[j]->d_gray, gray[j], (size_t)c->w * c->h, hipMemcpyHostToDevice, ms));
   if (batched) {
-    if (int rc = frames_build_pyramids_batch(c, fs, n, onDevice ? gray : nullptr)) return rc;
+    if (int rc = frames_build_pyramids_batch(c, fs, n, onDevice ? gray : nullptr, u)) return rc;
   } else {
-    if (int rc = lsd_frame_build_pyramids(fs[0], onDevice ? gray[0] : nullptr, nullptr)) return rc;
+    if (int rc = frame_build_pyramids(fs[0], onDevice ? gray[0] : nullptr, nullptr, u)) return rc;
     if (onDevice) lsd_trace_sum(c, ms, 2, ids[0], fs[0]->d_image[0], (size_t)((char*)fs[0]->d_idepth[0] - (char*)fs[0]->d_image[0]));
   }
   const long long seq = lsd_m_record(c);
@@ -1622,17 +1724,18 @@ static int frames_create_steps(lsdhip_ctx* c, int n, const int* ids, const uint8
   return LSDHIP_OK;
 }
 // fs[0 .. n) null on entry; a failing call destroys the frames it made and leaves them null
-static int frames_create(lsdhip_ctx* c, int n, const int* ids, const uint8_t* const* gray, bool onDevice, bool batched, bool wait, lsdhip_frame** fs) {
+static int frames_create(lsdhip_ctx* c, int n, const int* ids, const uint8_t* const* gray, bool onDevice, bool batched, bool wait, lsdhip_frame** fs,
+                         lsdhip_undistorter* u = nullptr) {
   LSD_CTX_LOCK(c);
-  const int rc = frames_create_steps(c, n, ids, gray, onDevice, batched, wait, fs);
+  const int rc = frames_create_steps(c, n, ids, gray, onDevice, batched, wait, fs, u);
   if (rc)
     for (int j = 0; j < n; j++) { lsdhip_frame_destroy(fs[j]); fs[j] = nullptr; }
   return rc;
 }
-static int frame_create_one(lsdhip_ctx* c, int id, const uint8_t* gray, bool onDevice, bool wait, lsdhip_frame** out) {
+static int frame_create_one(lsdhip_ctx* c, int id, const uint8_t* gray, bool onDevice, bool wait, lsdhip_frame** out, lsdhip_undistorter* u = nullptr) {
   if (!c || !gray || !out) return LSDHIP_E_ARG;
   lsdhip_frame* f = nullptr;
-  const int rc = frames_create(c, 1, &id, &gray, onDevice, false, wait, &f);
+  const int rc = frames_create(c, 1, &id, &gray, onDevice, false, wait, &f, u);
   if (rc == LSDHIP_OK) *out = f;
   return rc;
 }
@@ -1654,6 +1757,91 @@ extern "C" int lsdhip_frame_create_batch(lsdhip_ctx* c, int n, const int* ids, c
   if ((size_t)(2 * n + 8) > c->arena_keep) c->arena_keep = (size_t)(2 * n + 8);   // a round of n frames retires n arenas at once
   for (int j = 0; j < n; j++) out[j] = nullptr;
   return frames_create(c, n, ids, gray, images_on_device != 0, true, !images_on_device, out);
+}
+
+// ---- raw camera images: UndistorterPTAM (util/Undistorter.cpp) on the device ----------------------------------------------------------------
+extern "C" int lsdhip_undistorter_create(lsdhip_ctx* c, int in_w, int in_h, const float* remapX_host, const float* remapY_host, lsdhip_undistorter** out) {
+  if (!c || !remapX_host || !remapY_host || !out) return LSDHIP_E_ARG;
+  if (in_w < 2 || in_h < 2 || (long long)in_w * in_h > 0x7fffffffLL) {
+    lsd_set_error("lsdhip_undistorter_create: input size %dx%d", in_w, in_h);
+    return LSDHIP_E_ARG;
+  }
+  // The kernels read four taps around every valid entry without a bounds test: the table must keep them inside the raw image
+  // (Undistorter.cpp:304: 0 < ix < in_width - 1 and 0 < iy < in_height - 1, everything else is written as -1).
+  const size_t n = (size_t)c->w * c->h;
+  std::vector<float2> map(n);
+  for (size_t i = 0; i < n; i++) {
+    const float x = remapX_host[i], y = remapY_host[i];
+    if (!(x < 0) && !(x >= 0 && x < (float)(in_w - 1) && y >= 0 && y < (float)(in_h - 1))) {
+      lsd_set_error("lsdhip_undistorter_create: remap entry %zu = (%g, %g) is neither negative nor inside the %dx%d input image", i, (double)x, (double)y, in_w, in_h);
+      return LSDHIP_E_ARG;
+    }
+    map[i] = make_float2(x, y);
+  }
+  LSD_CTX_LOCK(c);
+  HIPCHK(hipSetDevice(c->device));
+  lsdhip_undistorter* u = new lsdhip_undistorter();
+  u->ctx = c; u->in_w = in_w; u->in_h = in_h;
+  hipError_t e = hipMalloc((void**)&u->d_map, n * sizeof(float2));
+  if (e == hipSuccess) e = hipMemcpy(u->d_map, map.data(), n * sizeof(float2), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    lsd_set_error("lsdhip_undistorter_create: %s", hipGetErrorString(e));
+    if (u->d_map) (void)hipFree(u->d_map);
+    delete u;
+    return LSDHIP_E_HIP;
+  }
+  *out = u;
+  return LSDHIP_OK;
+}
+extern "C" void lsdhip_undistorter_destroy(lsdhip_undistorter* u) {
+  if (!u) return;
+  lsdhip_ctx* c = u->ctx;
+  LSD_CTX_LOCK(c);
+  (void)hipSetDevice(c->device);
+  (void)lsd_sync_all(c);     // frames created through it may still be queued
+  if (u->stageStream) (void)hipStreamSynchronize(u->stageStream);
+  for (uint8_t* p : u->stage) (void)hipFree(p);
+  if (u->d_out) (void)hipFree(u->d_out);
+  (void)hipFree(u->d_map);
+  delete u;
+}
+extern "C" int lsdhip_undistorter_apply(lsdhip_undistorter* u, const uint8_t* raw, int raw_on_device, uint8_t* out_gray, int out_on_device) {
+  if (!u || !raw || !out_gray) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = u->ctx;
+  LSD_CTX_LOCK(c);
+  HIPCHK(hipSetDevice(c->device));
+  const hipStream_t ms = lsd_map_stream(c);
+  if (int rc = lsd_m_begin(c)) return rc;
+  const int n = c->w * c->h;
+  const uint8_t* src = raw;
+  if (!raw_on_device)
+    if (int rc = undistorter_stage(u, 1, &raw, ms, &src)) return rc;
+  if (!out_on_device && !u->d_out) HIPCHK(hipMalloc((void**)&u->d_out, (size_t)n));
+  uint8_t* dst = out_on_device ? out_gray : u->d_out;
+  hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, ms, src, (const float2*)u->d_map, u->in_w, dst, n);
+  HIPCHK(hipGetLastError());
+  if (!out_on_device) HIPCHK(hipMemcpyAsync(out_gray, dst, (size_t)n, hipMemcpyDeviceToHost, ms));
+  // host memory on either side: the caller may touch it when the call returns; device to device: queued on the mapping stream, no wait
+  if (!out_on_device || !raw_on_device) HIPCHK(hipStreamSynchronize(ms));
+  return LSDHIP_OK;
+}
+extern "C" int lsdhip_frame_create_undistorted(lsdhip_undistorter* u, int id, const uint8_t* raw_host, lsdhip_frame** out) {
+  return u ? frame_create_one(u->ctx, id, raw_host, false, true, out, u) : LSDHIP_E_ARG;
+}
+extern "C" int lsdhip_frame_create_undistorted_async(lsdhip_undistorter* u, int id, const uint8_t* raw_host, lsdhip_frame** out) {
+  return u ? frame_create_one(u->ctx, id, raw_host, false, false, out, u) : LSDHIP_E_ARG;
+}
+extern "C" int lsdhip_frame_create_undistorted_from_device(lsdhip_undistorter* u, int id, const uint8_t* raw_dev, lsdhip_frame** out) {
+  return u ? frame_create_one(u->ctx, id, raw_dev, true, false, out, u) : LSDHIP_E_ARG;
+}
+extern "C" int lsdhip_frame_create_undistorted_batch(lsdhip_undistorter* u, int n, const int* ids, const uint8_t* const* raw, int images_on_device, lsdhip_frame** out) {
+  if (!u || n <= 0 || !ids || !raw || !out) return LSDHIP_E_ARG;
+  for (int j = 0; j < n; j++) if (!raw[j]) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = u->ctx;
+  LSD_CTX_LOCK(c);
+  if ((size_t)(2 * n + 8) > c->arena_keep) c->arena_keep = (size_t)(2 * n + 8);
+  for (int j = 0; j < n; j++) out[j] = nullptr;
+  return frames_create(c, n, ids, raw, images_on_device != 0, true, !images_on_device, out, u);
 }
 // Frame-memory pool (the reference's FrameMemory keeps returned buffers for reuse, util/... FrameMemory.cpp): make sure n arenas are
 // allocated and waiting, so that a loop which keeps its keyframes alive does not pay a hipMalloc (0.5 ms for 20 MB) per keyframe.

@@ -25,7 +25,8 @@ EXPORTED_SYMBOLS = ["lsdloop_create", "lsdloop_destroy", "lsdloop_run", "lsdloop
                     "lsdband_get", "lsdband_comm_init", "lsdband_run", "lsdband_synchronize", "lsdband_halo_bytes_per_pass", "lsdband_set_packed_exchange", "lsdband_set_overlap", "lsdband_tile_runs", "lsdband_plan", "lsdband_ipc_init", "lsdband_ipc_connect", "lsdband_ipc_failed", "lsdloop_gather_counts", "lsdloop_ipc_init", "lsdloop_ipc_connect", "lsdloop_ipc_result", "lsdloop_observe_work",
                     "lsdloopbatch_create", "lsdloopbatch_destroy", "lsdloopbatch_run", "lsdloopbatch_get_stats", "lsdloopbatch_ctx", "lsdloopbatch_set_keyframe_phases", "lsdloopbatch_set_pipeline", "lsdloopbatch_set_coarse_min_jobs", "lsdloopbatch_dropped",
                     "lsdloopbatch_keep_keyframes", "lsdloopbatch_keyframe_log", "lsdloopbatch_last_result", "lsdloopbatch_download_map",
-                    "lsdloopbatch_set_cloud_sinks", "lsdloopbatch_cloud", "lsdloopbatch_cloud_pose", "lsdloopbatch_keyframe_handle"]
+                    "lsdloopbatch_set_cloud_sinks", "lsdloopbatch_cloud", "lsdloopbatch_cloud_pose", "lsdloopbatch_keyframe_handle",
+                    "lsdloop_create_undistorted", "lsdloopbatch_create_undistorted"]
 
 
 def lib():
@@ -38,6 +39,8 @@ def lib():
         vp, i = C.c_void_p, C.c_int
         L.lsdloop_create.restype = i
         L.lsdloop_create.argtypes = [i, i, i, vp, vp, i, vp, i, C.POINTER(vp)]
+        L.lsdloop_create_undistorted.restype = i
+        L.lsdloop_create_undistorted.argtypes = [i, i, i, vp, i, i, vp, vp, vp, i, vp, i, C.POINTER(vp)]
         L.lsdloop_destroy.restype = None
         L.lsdloop_destroy.argtypes = [vp]
         L.lsdloop_run.restype = i
@@ -100,6 +103,8 @@ def lib():
         L.lsdloop_ctx.argtypes = [vp]
         L.lsdloopbatch_create.restype = i
         L.lsdloopbatch_create.argtypes = [i, i, i, vp, i, vp, i, vp, i, C.POINTER(vp)]
+        L.lsdloopbatch_create_undistorted.restype = i
+        L.lsdloopbatch_create_undistorted.argtypes = [i, i, i, vp, i, i, vp, vp, i, vp, i, vp, i, C.POINTER(vp)]
         L.lsdloopbatch_destroy.restype = None
         L.lsdloopbatch_destroy.argtypes = [vp]
         L.lsdloopbatch_run.restype = i
@@ -148,7 +153,8 @@ class DriverLoopBatch:
     """lsd_slam_hip::SlamLoopBatch: S sequences sharing one GPU, one frame of each per step.  Images are raw pointers (device pointers when
     images_on_device, else host pointers)."""
 
-    def __init__(self, w, h, K, first_image_ptrs, depth0s, kf_every=10, images_on_device=True, device=0):
+    def __init__(self, w, h, K, first_image_ptrs, depth0s, kf_every=10, images_on_device=True, device=0, undistort=None):
+        """undistort = (in_w, in_h, remapX, remapY): the loop is fed raw in_w x in_h images of that camera (lsdloopbatch_create_undistorted)"""
         self.L = lib()
         self.S = len(first_image_ptrs)
         K4 = np.ascontiguousarray(K, dtype=np.float32)
@@ -156,7 +162,14 @@ class DriverLoopBatch:
         imgs = (C.c_void_p * self.S)(*first_image_ptrs)
         d0s = (C.c_void_p * self.S)(*[d.ctypes.data for d in self._d0])
         h_ = C.c_void_p()
-        _check(self.L.lsdloopbatch_create(device, w, h, K4.ctypes.data, self.S, imgs, int(images_on_device), d0s, kf_every, C.byref(h_)))
+        if undistort is not None:
+            in_w, in_h, rx, ry = undistort
+            rx, ry = np.ascontiguousarray(rx, dtype=np.float32), np.ascontiguousarray(ry, dtype=np.float32)
+            assert rx.size == w * h and ry.size == w * h
+            _check(self.L.lsdloopbatch_create_undistorted(device, w, h, K4.ctypes.data, int(in_w), int(in_h), rx.ctypes.data, ry.ctypes.data, self.S, imgs,
+                                                          int(images_on_device), d0s, kf_every, C.byref(h_)))
+        else:
+            _check(self.L.lsdloopbatch_create(device, w, h, K4.ctypes.data, self.S, imgs, int(images_on_device), d0s, kf_every, C.byref(h_)))
         self.h_ = h_
 
     def close(self):
@@ -252,13 +265,21 @@ class DriverLoop:
     """lsd_slam_hip::SlamLoop (include/lsd_slam_hip.hpp).  Images are raw pointers: device pointers when
     images_on_device, else host pointers (numpy .ctypes.data)."""
 
-    def __init__(self, w, h, K, first_image_ptr, depth0, kf_every=10, images_on_device=True, device=0):
+    def __init__(self, w, h, K, first_image_ptr, depth0, kf_every=10, images_on_device=True, device=0, undistort=None):
+        """undistort = (in_w, in_h, remapX, remapY): the loop is fed raw in_w x in_h images of that camera (lsdloop_create_undistorted)"""
         self.L = lib()
         K4 = np.ascontiguousarray(K, dtype=np.float32)
         d0 = np.ascontiguousarray(depth0, dtype=np.float32)
         h_ = C.c_void_p()
-        _check(self.L.lsdloop_create(device, w, h, K4.ctypes.data, C.c_void_p(first_image_ptr), int(images_on_device),
-                                     d0.ctypes.data, kf_every, C.byref(h_)))
+        if undistort is not None:
+            in_w, in_h, rx, ry = undistort
+            rx, ry = np.ascontiguousarray(rx, dtype=np.float32), np.ascontiguousarray(ry, dtype=np.float32)
+            assert rx.size == w * h and ry.size == w * h
+            _check(self.L.lsdloop_create_undistorted(device, w, h, K4.ctypes.data, int(in_w), int(in_h), rx.ctypes.data, ry.ctypes.data,
+                                                     C.c_void_p(first_image_ptr), int(images_on_device), d0.ctypes.data, kf_every, C.byref(h_)))
+        else:
+            _check(self.L.lsdloop_create(device, w, h, K4.ctypes.data, C.c_void_p(first_image_ptr), int(images_on_device),
+                                         d0.ctypes.data, kf_every, C.byref(h_)))
         self.h_ = h_
         self.w, self.h = w, h
 

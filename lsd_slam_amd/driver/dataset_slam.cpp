@@ -5,8 +5,14 @@
 // keyframe, and the viewer's PLY point cloud.
 //
 //   dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both]
-//                [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]] [--reactivate N]
+//                [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]] [--reactivate N] [--undistort 1 [--rectified-images DIR]]
 //
+// --undistort 1: the calibration file may be any FOV-model file of the reference (Undistorter::fromFile: distortion, crop / full / explicit
+//   output intrinsics, resizing — what UndistorterPTAM reads, C/util/Undistorter.cpp:91-345), the PGMs are RAW camera images of the file's input
+//   size, and the loop is fed the raw bytes: every frame is rectified on the device inside frame creation (DeviceUndistorter).  The calibration
+//   of the rectified images is written to <out_dir>/rectified.cfg.  Without the flag such a file is refused, as before.
+// --rectified-images DIR (with --undistort 1): the rectified image of every frame is also written to DIR/<file name> (one extra launch and a
+//   copy per frame: lsdhip_undistorter_apply).
 // --cloud host (default): pc.ply and keyframe_<id>.msg from the host functions (three plane downloads and a host loop per keyframe).
 // --cloud device: every finished keyframe is appended to one PointCloud on the GPU behind the keyframe change (no split of the change; the
 //   append waits for nothing), downloaded once at the end into pc.ply; keyframe_<id>.msg comes from makeKeyframeMsgDevice, which does
@@ -51,11 +57,11 @@ static Sim3 sim3_mul(const Sim3& a, const Sim3& b) {
 
 int main(int argc, char** argv) {
   if (argc < 4) {
-    std::cerr << "usage: dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both] [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]] [--reactivate N]\n";
+    std::cerr << "usage: dataset_slam <calib.cfg> <image_list.txt> <out_dir> [--kf-every N] [--device D] [--constraints 1] [--cloud host|device|both] [--cloud-capacity POINTS] [--depth-images DIR [--debug-display N]] [--reactivate N] [--undistort 1 [--rectified-images DIR]]\n";
     return 2;
   }
-  int kfEvery = 0, device = 0, constraints = 0, debugDisplay = 0, reactivate = 0;
-  std::string cloudMode = "host", depthImages;
+  int kfEvery = 0, device = 0, constraints = 0, debugDisplay = 0, reactivate = 0, undistort = 0;
+  std::string cloudMode = "host", depthImages, rectifiedImages;
   long long cloudCapacity = 0;
   for (int i = 4; i + 1 < argc; i += 2) {
     if (!strcmp(argv[i], "--kf-every")) kfEvery = atoi(argv[i + 1]);
@@ -66,11 +72,28 @@ int main(int argc, char** argv) {
     if (!strcmp(argv[i], "--depth-images")) depthImages = argv[i + 1];
     if (!strcmp(argv[i], "--debug-display")) debugDisplay = atoi(argv[i + 1]);
     if (!strcmp(argv[i], "--reactivate")) reactivate = atoi(argv[i + 1]);
+    if (!strcmp(argv[i], "--undistort")) undistort = atoi(argv[i + 1]);
+    if (!strcmp(argv[i], "--rectified-images")) rectifiedImages = argv[i + 1];
   }
   if (cloudMode != "host" && cloudMode != "device" && cloudMode != "both") { std::cerr << "--cloud takes host, device or both\n"; return 2; }
   const bool hostCloud = cloudMode != "device", devCloud = cloudMode != "host";
   try {
-    const Calibration cal = parseCalibration(argv[1]);
+    // --undistort 1: raw images of the file's input size, rectified on the device; cal describes the rectified images either way
+    Calibration cal;
+    int inW = 0, inH = 0;
+    std::shared_ptr<DeviceUndistorter> dundist;
+    if (undistort) {
+      const Undistorter u = Undistorter::fromFile(argv[1]);
+      cal.width = u.out_width; cal.height = u.out_height; cal.K = u.K;
+      inW = u.in_width; inH = u.in_height;
+      Context::defaultDevice() = device;
+      if (!u.passThrough()) dundist = std::make_shared<DeviceUndistorter>(inW, inH, cal.width, cal.height, cal.K, u.remapX.data(), u.remapY.data());
+      std::ofstream rc(std::string(argv[3]) + "/rectified.cfg");
+      rc << u.rectifiedCalibrationText();
+    } else {
+      cal = parseCalibration(argv[1]);
+      inW = cal.width; inH = cal.height;
+    }
     std::vector<std::string> files;
     {
       std::ifstream f(argv[2]);
@@ -82,9 +105,25 @@ int main(int argc, char** argv) {
     Context::defaultDevice() = device;
     const int w = cal.width, h = cal.height;
     std::vector<unsigned char> img;
-    if (!readPGM(files[0], w, h, img)) { std::cerr << "cannot read " << files[0] << " as " << w << "x" << h << " P5\n"; return 2; }
+    if (!readPGM(files[0], inW, inH, img)) { std::cerr << "cannot read " << files[0] << " as " << inW << "x" << inH << " P5\n"; return 2; }
+    // --rectified-images: the rectified bytes of the image just read, under its own file name
+    std::vector<unsigned char> rect;
+    auto dumpRectified = [&](const std::string& file) {
+      if (rectifiedImages.empty() || !undistort) return;
+      const unsigned char* bytes = img.data();
+      if (dundist) { rect.resize((size_t)w * h); dundist->undistort(img.data(), false, rect.data(), false); bytes = rect.data(); }
+      const std::string path = rectifiedImages + "/" + file.substr(file.find_last_of('/') + 1);
+      if (!writePGM(path, w, h, bytes)) std::cerr << "dataset_slam: cannot write " << path << "\n";
+    };
+    dumpRectified(files[0]);
+    // The context exists before the seed is set: bringing up the HIP runtime draws from rand() itself, a varying number of times, and a loop
+    // whose context was created behind srand(0) started from a different random depth map in every run.
+    const std::shared_ptr<Context> ctx = Context::get(w, h, cal.K);
+    ctx->synchronize();
     srand(0);   // initializeRandomly draws from rand() in pixel order (DepthMap.cpp:883-916)
-    SlamLoop loop(w, h, cal.K, img.data(), false, nullptr, kfEvery);
+    std::unique_ptr<SlamLoop> loopOwner(dundist ? new SlamLoop(w, h, cal.K, dundist, img.data(), false, nullptr, kfEvery)
+                                                : new SlamLoop(w, h, cal.K, img.data(), false, nullptr, kfEvery));
+    SlamLoop& loop = *loopOwner;
     if (reactivate > 0) loop.enableReactivation(reactivate);
     std::ofstream traj(outDir + "/trajectory.txt");
     traj << "# frame keyframe frameToKeyframe(qw qx qy qz tx ty tz) camToWorld(qw qx qy qz tx ty tz s) pointUsage goodRatio trackingWasGood\n";
@@ -132,7 +171,8 @@ int main(int argc, char** argv) {
       cons << "# parentKeyframe newKeyframe init(qw qx qy qz tx ty tz s) estimate(qw qx qy qz tx ty tz s) residual depthResidual photoResidual usage diverged\n";
     }
     for (size_t i = 1; i < files.size(); i++) {
-      if (!readPGM(files[i], w, h, img)) { std::cerr << "skipping " << files[i] << " (wrong size or unreadable)\n"; continue; }
+      if (!readPGM(files[i], inW, inH, img)) { std::cerr << "skipping " << files[i] << " (wrong size or unreadable)\n"; continue; }
+      dumpRectified(files[i]);
       std::shared_ptr<Frame> parentKF = loop.keyframe;
       currentFrame = (int)i;
       SE3 f2k = loop.step(img.data());

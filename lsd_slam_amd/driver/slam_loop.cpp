@@ -86,15 +86,20 @@ static double now_s() { return std::chrono::duration<double>(std::chrono::steady
 
 extern "C" const char* lsdloop_last_error(void) { return g_err.c_str(); }
 
-extern "C" int lsdloop_create(int device, int w, int h, const float K4[4], const uint8_t* first_image, int images_on_device,
-                              const float* gt_depth0_host, int kf_every, lsdloop** out) {
+// remapX != null: the loop takes raw in_w x in_h images through a DeviceUndistorter of these tables (lsdloop_create_undistorted)
+static int loop_create(int device, int w, int h, const float K4[4], int in_w, int in_h, const float* remapX, const float* remapY,
+                       const uint8_t* first_image, int images_on_device, const float* gt_depth0_host, int kf_every, lsdloop** out) {
   if (!K4 || !first_image || !gt_depth0_host || !out || kf_every < 1) return LSDHIP_E_ARG;
   try {
     Context::defaultDevice() = device;
     Mat3f K = Mat3f::intrinsics(K4[0], K4[1], K4[2], K4[3]);
     std::unique_ptr<lsdloop> l(new lsdloop());
     l->ctx = Context::get(w, h, K, device);
-    l->loop.reset(new SlamLoop(w, h, K, first_image, images_on_device != 0, gt_depth0_host, kf_every));
+    if (remapX)
+      l->loop.reset(new SlamLoop(w, h, K, std::make_shared<DeviceUndistorter>(in_w, in_h, w, h, K, remapX, remapY), first_image, images_on_device != 0,
+                                 gt_depth0_host, kf_every));
+    else
+      l->loop.reset(new SlamLoop(w, h, K, first_image, images_on_device != 0, gt_depth0_host, kf_every));
     if (const char* e = std::getenv("LSDHIP_KF_SHARED")) l->loop->sharedKeyframeChange = e[0] != '0';   // developer A/B of round 5
     l->ctx->setAsync(true);   // mapping kernels are enqueued behind the tracker's; the host never waits for them
     *out = l.release();
@@ -106,6 +111,16 @@ extern "C" int lsdloop_create(int device, int w, int h, const float K4[4], const
     g_err = e.what();
     return LSDHIP_E_STATE;
   }
+}
+extern "C" int lsdloop_create(int device, int w, int h, const float K4[4], const uint8_t* first_image, int images_on_device,
+                              const float* gt_depth0_host, int kf_every, lsdloop** out) {
+  return loop_create(device, w, h, K4, 0, 0, nullptr, nullptr, first_image, images_on_device, gt_depth0_host, kf_every, out);
+}
+extern "C" int lsdloop_create_undistorted(int device, int w, int h, const float K4[4], int in_w, int in_h, const float* remapX_host,
+                                          const float* remapY_host, const uint8_t* first_raw_image, int images_on_device,
+                                          const float* gt_depth0_host, int kf_every, lsdloop** out) {
+  if (!remapX_host || !remapY_host) return LSDHIP_E_ARG;
+  return loop_create(device, w, h, K4, in_w, in_h, remapX_host, remapY_host, first_raw_image, images_on_device, gt_depth0_host, kf_every, out);
 }
 extern "C" void lsdloop_destroy(lsdloop* l) {
   if (!l) return;
@@ -140,8 +155,10 @@ static Sim3 batch_cloud_pose(int s, int frameId) {
   T.s = 1.0 + 0.5 * (s % 3);
   return T;
 }
-extern "C" int lsdloopbatch_create(int device, int w, int h, const float K4[4], int S, const uint8_t* const* first_images, int images_on_device,
-                                   const float* const* gt_depth0_host, int kf_every, lsdloopbatch** out) {
+// remapX != null: raw in_w x in_h images through a DeviceUndistorter of these tables (lsdloopbatch_create_undistorted)
+static int loopbatch_create(int device, int w, int h, const float K4[4], int in_w, int in_h, const float* remapX, const float* remapY, int S,
+                            const uint8_t* const* first_images, int images_on_device, const float* const* gt_depth0_host, int kf_every,
+                            lsdloopbatch** out) {
   if (!K4 || !first_images || !out || kf_every < 1 || S < 1) return LSDHIP_E_ARG;
   try {
     Context::defaultDevice() = device;
@@ -149,7 +166,11 @@ extern "C" int lsdloopbatch_create(int device, int w, int h, const float K4[4], 
     std::unique_ptr<lsdloopbatch> l(new lsdloopbatch());
     l->ctx = Context::get(w, h, K, device);
     l->ctx->setPipeline(false);
-    l->loop.reset(new lsd_slam_hip::SlamLoopBatch(w, h, K, S, first_images, images_on_device != 0, gt_depth0_host, kf_every));
+    if (remapX)
+      l->loop.reset(new lsd_slam_hip::SlamLoopBatch(w, h, K, std::make_shared<DeviceUndistorter>(in_w, in_h, w, h, K, remapX, remapY), S, first_images,
+                                                    images_on_device != 0, gt_depth0_host, kf_every));
+    else
+      l->loop.reset(new lsd_slam_hip::SlamLoopBatch(w, h, K, S, first_images, images_on_device != 0, gt_depth0_host, kf_every));
     if (const char* e = std::getenv("LSDHIP_KF_LANES")) l->loop->keyframeLanes = std::atoi(e);   // developer A/B (1: keyframe changes on one stream)
     if (const char* e = std::getenv("LSDHIP_KF_SHARED")) l->loop->sharedKeyframeChange = e[0] != '0';   // developer A/B of round 5
     l->ctx->setAsync(true);
@@ -163,6 +184,16 @@ extern "C" int lsdloopbatch_create(int device, int w, int h, const float K4[4], 
     g_err = e.what();
     return LSDHIP_E_STATE;
   }
+}
+extern "C" int lsdloopbatch_create(int device, int w, int h, const float K4[4], int S, const uint8_t* const* first_images, int images_on_device,
+                                   const float* const* gt_depth0_host, int kf_every, lsdloopbatch** out) {
+  return loopbatch_create(device, w, h, K4, 0, 0, nullptr, nullptr, S, first_images, images_on_device, gt_depth0_host, kf_every, out);
+}
+extern "C" int lsdloopbatch_create_undistorted(int device, int w, int h, const float K4[4], int in_w, int in_h, const float* remapX_host,
+                                               const float* remapY_host, int S, const uint8_t* const* first_raw_images, int images_on_device,
+                                               const float* const* gt_depth0_host, int kf_every, lsdloopbatch** out) {
+  if (!remapX_host || !remapY_host) return LSDHIP_E_ARG;
+  return loopbatch_create(device, w, h, K4, in_w, in_h, remapX_host, remapY_host, S, first_raw_images, images_on_device, gt_depth0_host, kf_every, out);
 }
 extern "C" void lsdloopbatch_destroy(lsdloopbatch* l) {
   if (!l) return;

@@ -295,6 +295,80 @@ class Frame:
                                                int(depthHasBeenUpdatedFlag)))
 
 
+class Undistorter:
+    """A camera's rectification on the device (lsdhip_undistorter_*; UndistorterPTAM, C/util/Undistorter.cpp:282-411): the remap tables
+    of the context's w x h output image — built on the host by lsd_slam_hip::Undistorter of include/lsd_slam_hip_io.hpp — resident on the
+    GPU.  Raw images are uint8 [in_h, in_w] arrays, or device pointers to as many bytes."""
+
+    def __init__(self, ctx, in_w, in_h, remapX, remapY):
+        self.ctx, self.L = ctx, ctx.L
+        self.in_w, self.in_h = int(in_w), int(in_h)
+        rx = np.ascontiguousarray(remapX, dtype=np.float32)
+        ry = np.ascontiguousarray(remapY, dtype=np.float32)
+        if rx.size != ctx.w * ctx.h or ry.size != ctx.w * ctx.h:
+            raise ValueError("remap tables must hold %dx%d entries" % (ctx.w, ctx.h))
+        h_ = C.c_void_p()
+        check(self.L.lsdhip_undistorter_create(ctx.h_, self.in_w, self.in_h, rx.ctypes.data, ry.ctypes.data, C.byref(h_)), False)
+        self.h_ = h_
+
+    def __del__(self):
+        self.close()
+
+    def close(self):
+        if getattr(self, "h_", None) and getattr(self.ctx, "h_", None):
+            self.L.lsdhip_undistorter_destroy(self.h_)
+        self.h_ = None
+
+    def _raw(self, raw):
+        img = np.ascontiguousarray(raw, dtype=np.uint8)
+        if img.shape != (self.in_h, self.in_w):
+            raise ValueError("raw image must be %dx%d uint8" % (self.in_w, self.in_h))
+        return img
+
+    def apply(self, raw=None, device_ptr=None, out_device_ptr=None):
+        """the rectified uint8 image (lsdhip_undistorter_apply) -> [h, w] array, or None when written to out_device_ptr"""
+        img = None if device_ptr is not None else self._raw(raw)
+        out = None if out_device_ptr is not None else np.empty((self.ctx.h, self.ctx.w), np.uint8)
+        src = C.c_void_p(device_ptr) if img is None else img.ctypes.data
+        dst = C.c_void_p(out_device_ptr) if out is None else out.ctypes.data
+        check(self.L.lsdhip_undistorter_apply(self.h_, src, int(img is None), dst, int(out is None)), False)
+        return out
+
+    def _adopt(self, handle, id_):
+        f = Frame.__new__(Frame)
+        f.ctx, f.L, f.h_, f._id, f._parent = self.ctx, self.L, C.c_void_p(handle), int(id_), None
+        return f
+
+    def frame(self, id_, raw=None, device_ptr=None, wait=True):
+        """a Frame of a raw image (lsdhip_frame_create_undistorted / _async / _from_device).  wait=False: the raw host array must stay
+        alive and unchanged until the frame has been tracked or the context synchronised; it is kept on the frame."""
+        h_ = C.c_void_p()
+        if device_ptr is not None:
+            check(self.L.lsdhip_frame_create_undistorted_from_device(self.h_, id_, C.c_void_p(device_ptr), C.byref(h_)), False)
+            return self._adopt(h_.value, id_)
+        img = self._raw(raw)
+        fn = self.L.lsdhip_frame_create_undistorted if wait else self.L.lsdhip_frame_create_undistorted_async
+        check(fn(self.h_, id_, img.ctypes.data, C.byref(h_)), False)
+        f = self._adopt(h_.value, id_)
+        if not wait:
+            f._raw_keepalive = img
+        return f
+
+    def createBatch(self, ids, raws=None, device_ptrs=None):
+        """the new frames of several sequences from raw images in two launches (lsdhip_frame_create_undistorted_batch) -> list of Frame"""
+        n = len(ids)
+        ida = (C.c_int * n)(*[int(v) for v in ids])
+        out = (C.c_void_p * n)()
+        if device_ptrs is not None:
+            ptrs = (C.c_void_p * n)(*[int(p) for p in device_ptrs])
+            check(self.L.lsdhip_frame_create_undistorted_batch(self.h_, n, ida, ptrs, 1, out), False)
+        else:
+            imgs = [self._raw(im) for im in raws]
+            ptrs = (C.c_void_p * n)(*[im.ctypes.data for im in imgs])
+            check(self.L.lsdhip_frame_create_undistorted_batch(self.h_, n, ida, ptrs, 0, out), False)
+        return [self._adopt(out[j], ids[j]) for j in range(n)]
+
+
 class PointCloud:
     """The viewer's accumulated point cloud in device memory (lsdhip_cloud_*; KeyFrameDisplay::flushPC per keyframe,
     V/KeyFrameDisplay.cpp:269-340).  appendKeyframe only queues work on the context's mapping stream; total / stored / segments /
