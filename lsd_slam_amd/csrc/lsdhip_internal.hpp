@@ -107,8 +107,11 @@ struct TrackSpec {
   unsigned long long dbgCum;         // developer build LSD_ORDER_CHECK: workgroups of all launches queued before this one
   unsigned long long* dbgCounters;   // ... [0] workgroups finished, [1] workgroups that started before all earlier ones had finished, [2] largest deficit seen
   int last;                  // 1: the last launch of the enqueued budget — if the job is not finished when it ends it says so (TrackSummary::exhausted)
+  unsigned long long levelTiles;   // single jobs (launch_step): TrackLevel::nblocks of the five levels, 12 bits each, level l at bit 12 l, and ...
+  unsigned levelTrials;            // ... the trials a launch evaluates at each (4 bits each; 1 without speculation): what a workgroup needs to find its
+                                   // role once the state says which level is pending, in the launch's arguments instead of behind dependent loads
 #ifdef LSD_PHASE_TRACE
-  int traceWg;               // developer build: the workgroup (blockIdx.x of job 0) of a batch launch that leaves the per-phase timestamps
+  int traceWg;               // developer build: the workgroup (blockIdx.x; batches: of job 0) of a launch that leaves the per-phase timestamps (LSDHIP_TRACE_WG)
 #endif
 #ifdef LSD_DEVTOOLS
   int* dbgLog;               // developer build: 16 ints per launch of the job (slot = launch ordinal), written by workgroup 0 — tools/launch_count_stress.py

@@ -540,11 +540,17 @@ __device__ __forceinline__ void stage_lm_par(const TrackJob& job, int level, LmP
 // calcWeightsAndResidualSSE's return value: the weighted error over the points its loop visits (SE3Tracker.cpp:572-574).  One
 // definition: the speculation scans and lm_wave must agree on it bit for bit.
 __device__ __forceinline__ float lm_werr(float sumWeightedErr, int M) { return sumWeightedErr * frcp((float)((M >> 2) << 2)); }
-__device__ __forceinline__ float lm_lambda_fail(float LM_lambda, int incTry, float lambdaFailFac) {
-  if (LM_lambda == 0) return 0.2f;
+// lambda after a rejection at retry count incTry: LM_lambda * std::pow(lambdaFailFac, incTry), the power as incTry multiplications from 1.0.
+// A chain of rejections (incTry, incTry + 1, ...) carries the power along instead of restarting it: the power for n + 1 is by definition
+// the power for n times the factor, rounded once — the running product goes through the same f64 roundings as the loop from 1.0 does.
+__device__ __forceinline__ double lambda_fail_pow(int incTry, float lambdaFailFac) {
   double p = 1.0;
   for (int i = 0; i < incTry; i++) p *= (double)lambdaFailFac;   // std::pow(lambdaFailFac, incTry)
-  return (float)((double)LM_lambda * p);
+  return p;
+}
+__device__ __forceinline__ float lm_lambda_fail_pow(float LM_lambda, double pow_incTry) { return LM_lambda == 0 ? 0.2f : (float)((double)LM_lambda * pow_incTry); }
+__device__ __forceinline__ float lm_lambda_fail(float LM_lambda, int incTry, float lambdaFailFac) {
+  return lm_lambda_fail_pow(LM_lambda, lambda_fail_pow(incTry, lambdaFailFac));
 }
 // algorithmic bytes of one evaluation that visits N reference points: 20 N + [mask] 5 N + 12 min(w h, 4 N)
 __device__ __forceinline__ float eval_bytes(const float N, const LmPar& L) {
@@ -605,6 +611,7 @@ __device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const f
   int iteration = S.iteration, incTry = S.incTry;
   lsdm::SE3fH T = S.T;
   bool propose = false, start_iteration = false, accepted = false, rejected = false;
+  double failPow = 1.0;   // lambdaFailFac ^ incTry wherever a proposal is made (lambda_fail_pow)
   if (S.phase == 0) {
     accepted = true;
     lastErr = werr;
@@ -630,7 +637,8 @@ __device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const f
         iteration++;
         start_iteration = true;
       } else {
-        LM_lambda = lm_lambda_fail(LM_lambda, incTry, L.lambdaFailFac);
+        failPow = lambda_fail_pow(incTry, L.lambdaFailFac);
+        LM_lambda = lm_lambda_fail_pow(LM_lambda, failPow);
         propose = true;
         rejected = true;
       }
@@ -651,7 +659,7 @@ __device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const f
     }
     if (lane >= RS_B0 && lane < RS_B0 + 6) S.b[lane - RS_B0] = (0.0f - col) * rn;
   }
-  if (start_iteration && iteration < maxIts) { S.numWarpUpdates = S.numWarpUpdates + 1; incTry = 0; propose = true; }
+  if (start_iteration && iteration < maxIts) { S.numWarpUpdates = S.numWarpUpdates + 1; incTry = 0; failPow = 1.0; propose = true; }
   S.lastErr = lastErr;
   S.LM_lambda = LM_lambda;
   S.iteration = iteration;
@@ -659,7 +667,7 @@ __device__ __forceinline__ bool lm_wave(const LmPar& par, TrackState& S, const f
   if (propose) {
     // this workgroup's own trial: `mycand` retries further down the chain (each retry: incTry++, lambda as after a rejection)
     const int extra = SPEC ? mycand : 0;
-    for (int j = 0; j < extra; j++) { incTry++; LM_lambda = lm_lambda_fail(LM_lambda, incTry, L.lambdaFailFac); }
+    for (int j = 0; j < extra; j++) { incTry++; failPow *= (double)L.lambdaFailFac; LM_lambda = lm_lambda_fail_pow(LM_lambda, failPow); }
     S.ncand = L.trials;
     float inc[6];
     const float damp = 1 + LM_lambda;
@@ -858,6 +866,15 @@ __device__ __forceinline__ void trial_record_adopt(TrackState& S, const TrialRec
 }
 // trials a launch evaluates side by side at `level` (1: no speculation)
 __device__ __forceinline__ int trials_at(const TrackSpec& spec, const int level) { return (spec.specC > 1 && spec.trials[level] > 1) ? spec.trials[level] : 1; }
+
+// What a single job's launch knows of its levels before the state says which one is pending (TrackSpec::levelTiles / levelTrials and the
+// job's last level), taken from the kernel arguments with the prologue's loads: a workgroup's role then costs shifts instead of a chain
+// of scalar loads, each of which waited for the one before it (state -> level -> lv[level].nblocks -> trials[level] -> lv[level - 1].nblocks).
+struct LevelFacts {
+  unsigned long long tiles; unsigned trials; int lastLevel;
+  __device__ __forceinline__ int tiles_at(const int level) const { return (int)(tiles >> (12 * level)) & 0xFFF; }
+  __device__ __forceinline__ int trials_at(const int level) const { return (int)(trials >> (4 * level)) & 0xF; }
+};
 
 #define RS_COLS 44   // RS_END rounded up: floats per partial-sum row
 // Scratch of a tracker in HBM, double-buffered by launch parity (a launch reads [parity], writes [1 - parity]); every array is

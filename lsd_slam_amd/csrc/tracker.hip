@@ -131,9 +131,20 @@ __device__ __forceinline__ StepAddr step_addr(const TrackScratch& sc, const int 
 // the state and writes the summary; leaves: nothing to do, gone before the finishing phase.
 struct StepRole { int cand, bx; bool leader, leaves; };
 template <bool BATCH, int MODE>
-__device__ __forceinline__ void step_role(StepRole& r, const TrackJob& job, const TrackSpec& spec, const TrackState& S) {
-  const int lvlPending = S.level;
-  if (MODE == TS_FUSED) {
+__device__ __forceinline__ void step_role(StepRole& r, const TrackJob& job, const TrackSpec& spec, const LevelFacts& lf, const int lvlPending, const int pending) {
+  if (MODE == TS_FUSED && !BATCH) {
+    // (as below, from the launch's own arguments.  cand = blockIdx.x / nbl without the division: a launch has at most LSD_SPEC_MAX trials, and
+    // of a workgroup past the last of them — cand, bx stop at LSD_SPEC_MAX, blockIdx.x - LSD_SPEC_MAX nbl — all that is ever asked is that it is past them)
+    const int nbl = lf.tiles_at(lvlPending), tr = lf.trials_at(lvlPending);
+    int cand = 0;
+#pragma unroll
+    for (int k = 1; k <= LSD_SPEC_MAX; k++) cand += (int)blockIdx.x >= k * nbl ? 1 : 0;
+    r.cand = cand; r.bx = (int)blockIdx.x - cand * nbl;
+    const bool needTrial = pending ? cand < tr : cand == 0;
+    const bool needNext = pending && lvlPending > lf.lastLevel && (int)blockIdx.x < lf.tiles_at(lvlPending > 0 ? lvlPending - 1 : 0);
+    r.leaves = !r.leader && !needTrial && !needNext;
+  }
+  if (MODE == TS_FUSED && BATCH) {
     // The launch is sized for the level with the most (tiles x trials).  This one either evaluates trials at S.level —
     // workgroup = (trial, tile) of that level — or, if the pending decision ends the level, the first evaluation of
     // S.level - 1 (workgroup = tile).  Workgroups that have no work either way leave before the finishing phase (whose loads
@@ -141,14 +152,14 @@ __device__ __forceinline__ void step_role(StepRole& r, const TrackJob& job, cons
     const int nbl = job.lv[lvlPending].nblocks;
     const int tr = trials_at(spec, lvlPending);
     r.cand = (int)blockIdx.x / nbl; r.bx = (int)blockIdx.x - r.cand * nbl;
-    const bool needTrial = S.pending ? r.cand < tr : r.cand == 0;
-    const bool needNext = S.pending && lvlPending > job.lastLevel && (int)blockIdx.x < job.lv[lvlPending - 1].nblocks;
+    const bool needTrial = pending ? r.cand < tr : r.cand == 0;
+    const bool needNext = pending && lvlPending > job.lastLevel && (int)blockIdx.x < job.lv[lvlPending - 1].nblocks;
     r.leaves = !r.leader && !needTrial && !needNext;
   }
   if (BATCH && MODE == TS_LM) {
     // one workgroup per (trial, job): workgroup `cand` proposes the cand-th retry down the reject chain; those without a trial leave
     r.cand = (int)blockIdx.x; r.bx = 0;
-    r.leaves = !r.leader && !(S.pending && r.cand < trials_at(spec, lvlPending));
+    r.leaves = !r.leader && !(pending && r.cand < trials_at(spec, lvlPending));
   }
   if (BATCH && MODE == TS_EVAL) {
     // workgroup = (trial, strip) of the job's level
@@ -394,13 +405,16 @@ __device__ __forceinline__ void column_sums(const StepAddr& A, const int nb, con
   else if (K <= 10) { for (int base = 0; base < ncandPending; base += 3) colsum<10, 3>(p, trialStrideF4, nb, ncandPending, base, slot, c4, sumLane, s_sumT); }
   else { for (int base = 0; base < ncandPending; base++) colsum<QMAX, 1>(p, trialStrideF4, nb, ncandPending, base, slot, c4, sumLane, s_sumT); }
 }
-// the finishing phase's tables in `buf`, per pending trial: column sums by row slot | its (up to 3) tail rows | how many of them exist
+// the finishing phase's tables in `buf`, per pending trial: column sums by row slot | its (up to 3) tail rows | how many of them exist |
+// the column totals over the slots
+typedef float (*TotalTable)[RS_COLS];
 template <int TRIALS_MAX>
 struct FinishTables {
-  enum { WORDS = TRIALS_MAX * (SUM_NSLOT * RS_COLS + TAIL_ROWS * TAIL_STRIDE + 1) };
-  SumTable sum; TailTable sub; int* nsub;
+  enum { WORDS = TRIALS_MAX * (SUM_NSLOT * RS_COLS + TAIL_ROWS * TAIL_STRIDE + 1 + RS_COLS) };
+  SumTable sum; TailTable sub; int* nsub; TotalTable tot;
   __device__ __forceinline__ explicit FinishTables(float* buf)
-      : sum((SumTable)buf), sub((TailTable)(buf + TRIALS_MAX * SUM_NSLOT * RS_COLS)), nsub((int*)(buf + TRIALS_MAX * (SUM_NSLOT * RS_COLS + TAIL_ROWS * TAIL_STRIDE))) {}
+      : sum((SumTable)buf), sub((TailTable)(buf + TRIALS_MAX * SUM_NSLOT * RS_COLS)), nsub((int*)(buf + TRIALS_MAX * (SUM_NSLOT * RS_COLS + TAIL_ROWS * TAIL_STRIDE))),
+        tot((TotalTable)(buf + TRIALS_MAX * (SUM_NSLOT * RS_COLS + TAIL_ROWS * TAIL_STRIDE + 1))) {}
 };
 // total of column `col` of trial c over the row slots, in slot order
 __device__ __forceinline__ float slot_total(const SumTable s_sumT, const int c, const int col) {
@@ -409,6 +423,14 @@ __device__ __forceinline__ float slot_total(const SumTable s_sumT, const int c, 
   for (int k = 1; k < SUM_NSLOT; k++) s += s_sumT[c][k][col];
   return s;
 }
+// all pending trials' totals at once, thread (trial, column) — TRIALS_MAX x RS_END threads of the workgroup — so that wave 0 reads a total
+// where it used to add sixteen slots, three times one behind the other, while the other waves waited for it.  A barrier follows.
+template <int TRIALS_MAX, int BLOCK>
+__device__ __forceinline__ void slot_totals(const SumTable s_sumT, const TotalTable s_totT, const int ncandPending, const int tid) {
+  static_assert(TRIALS_MAX * RS_END <= BLOCK, "a thread per (trial, column)");
+  const int c = tid / RS_END, col = tid - c * RS_END;
+  if (c < ncandPending) s_totT[c][col] = slot_total(s_sumT, c, col);
+}
 
 // ---- the finishing phase: wave 0 ------------------------------------------------------------------------------------------------
 // Which pending trial does the LM loop stop at?  Trial c stops it when it diverges (M < minWarped), is accepted
@@ -416,12 +438,12 @@ __device__ __forceinline__ float slot_total(const SumTable s_sumT, const int c, 
 // increment, so lane c answers for trial c and the first "yes" wins.  The trials before it were plain rejections: they
 // leave nothing behind but lambda, incTry and the counters, which are advanced in closed form; then ONE LM step runs,
 // on the totals of the trial that stopped the loop (or of the last pending one).
-__device__ __forceinline__ int pick_trial(TrackState& S, const LmPar& par, const int level, const int ncandPending, const SumTable s_sumT, const TailTable s_subT,
+__device__ __forceinline__ int pick_trial(TrackState& S, const LmPar& par, const int level, const int ncandPending, const TotalTable s_totT, const TailTable s_subT,
                                           const int* s_nsubT, const TrialRecord* s_rec, const int tid) {
   if (ncandPending <= 1) return 0;
   const int c = tid < ncandPending ? tid : 0;
-  const int Mc = (int)slot_total(s_sumT, c, RS_M);
-  const float ws = tail_drop(slot_total(s_sumT, c, RS_WERR), Mc, s_nsubT[c], tail_word(RS_WERR), s_subT[c]);
+  const int Mc = (int)s_totT[c][RS_M];
+  const float ws = tail_drop(s_totT[c][RS_WERR], Mc, s_nsubT[c], tail_word(RS_WERR), s_subT[c]);
   const float werrc = lm_werr(ws, Mc);
   const float incdot = inc_norm2(c == 0 ? S.inc : s_rec[c].inc);
   const bool stop = Mc < par.minWarped || werrc < S.lastErr || !(incdot > par.stepSizeMin);
@@ -430,9 +452,10 @@ __device__ __forceinline__ int pick_trial(TrackState& S, const LmPar& par, const
   if (pc > 0) {
     float lam = S.LM_lambda;
     const int it0 = S.incTry;
-    for (int j = 0; j < pc; j++) lam = lm_lambda_fail(lam, it0 + j, par.lambdaFailFac);
+    double failPow = lambda_fail_pow(it0, par.lambdaFailFac);
+    for (int j = 0; j < pc; j++) { lam = lm_lambda_fail_pow(lam, failPow); failPow *= (double)par.lambdaFailFac; }
     // algorithmic bytes of the skipped evaluations (as in lm_wave)
-    const float skipped = eval_bytes(slot_total(s_sumT, 0, RS_NREF), par);
+    const float skipped = eval_bytes(s_totT[0][RS_NREF], par);
     const float bytes0 = S.bytes;
     const int ne0 = S.numEvaluations, le0 = S.levelEvals[level];
     float bytes1 = bytes0;
@@ -447,9 +470,9 @@ __device__ __forceinline__ int pick_trial(TrackState& S, const LmPar& par, const
   return pc;
 }
 // column totals and tail-drop correction of trial pc, one column per lane (0 in the lanes past the columns)
-__device__ __forceinline__ float finish_totals(const SumTable s_sumT, const TailTable s_subT, const int* s_nsubT, const int pc, const int tid) {
-  const int M = (int)slot_total(s_sumT, pc, RS_M);
-  const float s = tid < RS_END ? slot_total(s_sumT, pc, tid) : 0.f;
+__device__ __forceinline__ float finish_totals(const TotalTable s_totT, const TailTable s_subT, const int* s_nsubT, const int pc, const int tid) {
+  const int M = (int)s_totT[pc][RS_M];
+  const float s = tid < RS_END ? s_totT[pc][tid] : 0.f;
   return tail_drop(s, M, s_nsubT[pc], tail_word(tid), s_subT[pc]);
 }
 // the frame's refPixelWasGood must be what the last trial the LM loop executed wrote: trials > 0 wrote side planes
@@ -569,8 +592,12 @@ __device__ __forceinline__ void eval_strip(const EvalCtx& a, const int tilePx, c
 // follow from the first by the uniform stride: one integer division per lane instead of one per point.
 __device__ __forceinline__ void eval_groups_of_four(const EvalCtx& a, int i, const int stride, const int work, gbyte* const wasGood, float (&acc)[RS_END],
                                                     int& key0, int& key1, int& key2) {
-  const int sy = stride / a.w, sx = stride - sy * a.w;   // uniform; sx < w: one carry at most
-  int x = i % a.w, y = i / a.w;
+  // (quotient and remainder by w as pixel_xy16 takes them: a float product and a correction, exact for every index of a level, in front of
+  // the first plane load where two integer divisions were ~60 dependent instructions)
+  const float inv_w = frcp((float)a.w);
+  const unsigned sxy = pixel_xy16(stride, a.w, inv_w), ixy = pixel_xy16(i, a.w, inv_w);
+  const int sy = (int)(sxy >> 16), sx = (int)(sxy & 0xFFFFu);   // uniform; sx < w: one carry at most
+  int x = (int)(ixy & 0xFFFFu), y = (int)(ixy >> 16);
   struct Pt { int i, x, y; bool valid; RefPlanes r; float img, pz; PointWarp q; PointTexels t; };
   while (i < work) {
     Pt P[4];
@@ -645,6 +672,10 @@ __device__ __forceinline__ void reduce_and_store(const EvalCtx& a, const TrackLe
   if (stripRows) {
     block_top3(key0, key1, key2, s_wtop, s_top);
     if (candLane) c.request(a, s_top[tid - (BLOCK - 64)]);
+  } else {
+    // tiles: the keys need no barriers of their own — every wave's three largest go out before the reduction's first barrier, the last
+    // wave merges them between its two (block_top3 in two halves)
+    wave_top3(key0, key1, key2, s_wtop);
   }
 #pragma unroll
   for (int hp = 0; hp < NPASS; hp++) {
@@ -669,6 +700,13 @@ __device__ __forceinline__ void reduce_and_store(const EvalCtx& a, const TrackLe
       const int slice = tid / CPP, k = tid - slice * CPP;
       if (slice < RSLICE) s_sum[slice][k] = slice_sum<BLOCK + 1, RRUN>(s_red, k, slice);
     }
+    if (!stripRows && hp == 0 && tid >= BLOCK - 64) {
+      int top[3];
+      merge_top3(s_wtop, BLOCK / 64, top);
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+        if (tid == BLOCK - 64) s_top[r] = top[r];
+    }
     __syncthreads();
     if (stripRows && hp == 0 && candLane) {
       float* row = topval_out + (size_t)(tile * TAIL_ROWS + (tid - (BLOCK - 64))) * TAIL_STRIDE;
@@ -686,7 +724,6 @@ __device__ __forceinline__ void reduce_and_store(const EvalCtx& a, const TrackLe
       sums_out[(size_t)tile * RS_COLS + (hp * CPP + tid)] = s;
     }
   }
-  if (!stripRows) block_top3(key0, key1, key2, s_wtop, s_top);
   if (tid == 0) topkey_out[tile] = make_int4(s_top[0], s_top[1], s_top[2], -1);
   if (L.singlePass && key0 >= 0) {
     // one point per lane: its accumulators are exactly its K2/K3 contributions (0 + x == x)
@@ -732,6 +769,11 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
   if (!BATCH) warm_job_arguments();
   if (BATCH) { st2 += 2 * (size_t)blockIdx.y; out += blockIdx.y; }
   const StepAddr A = step_addr<BATCH, MODE>(sc, parity);
+  LevelFacts lf = {0ull, 0u, 0};
+  if (!BATCH) {
+    lf = {spec.levelTiles, spec.levelTrials, job.lastLevel};
+    asm volatile("" ::"s"(lf.tiles), "s"(lf.trials), "s"(lf.lastLevel));   // in registers here, with the other argument loads
+  }
   constexpr int WAVES = BLOCK / 64, SUMW = WAVES - 1;                       // SUMW waves sum partials (the last one does the tail work)
   constexpr int NSLICE = (SUMW * 64) / RS_END, CPP = RED_CPP, RSLICE_ = BLOCK / CPP;   // row slices per column: of the column sums, of the reduction
   __shared__ TrackState S;
@@ -759,18 +801,28 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
   __shared__ TrialRecord s_rec[TRIALS_MAX];                 // per pending trial > 0: its increment and pose
 #ifdef LSD_PHASE_TRACE
   __shared__ unsigned long long* s_trp;
-  // the traced workgroup: workgroup 0 (batches: workgroup LSDHIP_TRACE_WG of job 0; tools/phase_trace_batch.py)
-  const bool trOn_ = sc.trace != nullptr && (int)blockIdx.x == (BATCH ? spec.traceWg : 0) && (!BATCH || blockIdx.y == 0);
+  // the traced workgroup: workgroup LSDHIP_TRACE_WG (default 0, the leader) of the job (batches: of job 0; tools/phase_trace_batch.py).  A
+  // workgroup other than the leader shows what the leader skips: the early return's load in the prologue, and the trials > 0.
+  const bool trOn_ = sc.trace != nullptr && (int)blockIdx.x == spec.traceWg && (!BATCH || blockIdx.y == 0);
   unsigned long long* const tr_ = trace_open(sc.trace, trOn_ && tid == 0, &s_trp);
 #endif
   PHASE_MARK(0);
-  if (!BATCH && MODE == TS_FUSED && !first && !leader && st2[parity].done) return;   // launches queued behind the finishing one
   if (!BATCH && MODE == TS_FUSED && leader && tid == 0 && spec.seq != 0) out->seq = spec.seq;   // pinned host memory: fire and forget
   if (first) {
     track_state_begin(S, job, tid);
   } else {
-    copy_words<sizeof(TrackState) / 4>(&S, st2 + parity, tid, BLOCK);
-    if (SPEC_LM && A.cmax > 1 && tid < (int)(sizeof(s_rec) / 4)) ((float*)s_rec)[tid] = ((const float*)A.recs_in)[tid < (int)(sizeof(TrialRecord) / 4) * A.cmax ? tid : 0];
+    // One memory round trip: the state, the trial records and (workgroups that are not the leader) the state's `done` word for the early
+    // return are all requested before anything waits — unconditional loads at clamped indices into registers, the LDS stores behind the
+    // return.  (One after the other they were three cold trips in every workgroup but the leader, which has no early return.)
+    constexpr int NSTATE = (int)(sizeof(TrackState) / 4), NREC = (int)(sizeof(s_rec) / 4);
+    static_assert(NSTATE <= BLOCK && NREC <= BLOCK, "one word of the state and one of the records per thread");
+    const bool haveRecs = SPEC_LM && A.cmax > 1;   // (no record arena when cmax == 1)
+    const unsigned stateWord = ((const unsigned*)(st2 + parity))[tid < NSTATE ? tid : 0];
+    float recWord = 0.f;
+    if (haveRecs) recWord = ((const float*)A.recs_in)[tid < (int)(sizeof(TrialRecord) / 4) * A.cmax && tid < NREC ? tid : 0];
+    if (!BATCH && MODE == TS_FUSED && !leader && st2[parity].done) return;   // launches queued behind the finishing one
+    if (tid < NSTATE) ((unsigned*)&S)[tid] = stateWord;
+    if (haveRecs && tid < NREC) ((float*)s_rec)[tid] = recWord;
   }
   __syncthreads();
   PHASE_MARK(1);
@@ -779,40 +831,43 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
 #endif
   // A finished job's launches leave here.  The host may have read the summary and gone on already (polled jobs and batches do not drain
   // the stream), so two things must stay true: (a) every workgroup of a launch queued behind the finishing one returns at this point,
-  // before it touches frame or keyframe memory — the state is all it has read; (b) the finishing launch requests its next strip
+  // before it touches frame or keyframe memory — the state and the trial records of the tracker's own scratch are all it has read; (b) the finishing launch requests its next strip
   // (strip_request below) before it knows that it finishes: those loads may read kf_refBlk after the host has seen `done`, and their
   // result is always discarded (the S.done return behind the finishing phase).
-  if (S.done) {
+  // (the state words the code up to the LM step branches on, in one batch of LDS reads)
+  const int doneIn = S.done, lvlPending = S.level, pending = S.pending, ncandIn = S.ncand;
+  if (doneIn) {
     LAUNCH_LOG(1, pendingIn_, ncandIn_, -1);
     if (MODE != TS_EVAL && leader) { copy_words<sizeof(TrackState) / 4>(next, &S, tid, BLOCK); }   // keep both buffers "done"
     return;
   }
-  const int lvlPending = S.level;
   // what the finishing launch raises `done` to: the job's tag where the host polls pinned memory for it (single jobs), 1 where it synchronises
   // (batches whose host polls: spec.seq is the batch's tag itself)
   const int doneWord = (MODE == TS_FUSED && spec.seq != 0) ? (BATCH ? spec.seq : (spec.seq >> 12)) : 1;
-  step_role<BATCH, MODE>(role, job, spec, S);
+  step_role<BATCH, MODE>(role, job, spec, lf, lvlPending, pending);
   if (role.leaves) return;
   int cand = role.cand, bx = role.bx;
+  PHASE_MARK(20);   // "role": from the state barrier (1) to here
 
   // the strip's list, requested ahead of time where this workgroup is going to evaluate at the pending level (strip_request)
   int cntv = 0;
   unsigned ow[STRIP_CHMAX];
   bool havePre = false;
-  if (BATCH && MODE == TS_FUSED && S.pending && job.lv[lvlPending].tilePx > 0) {
+  if (BATCH && MODE == TS_FUSED && pending && job.lv[lvlPending].tilePx > 0) {
     havePre = cand < trials_at(spec, lvlPending);
     if (havePre) strip_request(job.lv[lvlPending], xcd_tile(bx, job.lv[lvlPending].nblocks), wave, lane, cntv, ow);
   }
 
-  if (MODE != TS_EVAL && S.pending) {
+  int levelNow = lvlPending, ncandNow = ncandIn;   // the level and the trials to evaluate: the state's, as the LM step leaves it
+  if (MODE != TS_EVAL && pending) {
     // Finish the trials of the previous launch, in the order the LM loop would have run them.  All their partial sums, order
     // keys and tail contributions are fetched TOGETHER (one memory round trip, whatever the number of trials), then wave 0 walks
     // through them without further barriers: totals -> LM decision -> (rejected, retry waiting) next trial, whose increment
     // and pose come from the record the workgroups that evaluated it left behind.
-    const int ncandPending = S.ncand < 1 ? 1 : (S.ncand > TRIALS_MAX ? TRIALS_MAX : S.ncand);
-    const int level = S.level;
-    const int nb = job.lv[level].nblocks;
-    if (tid == SUMW * 64 - 1) stage_lm_par(job, level, s_par, trials_at(spec, level));
+    const int ncandPending = ncandIn < 1 ? 1 : (ncandIn > TRIALS_MAX ? TRIALS_MAX : ncandIn);
+    const int level = lvlPending;
+    const int nb = BATCH ? job.lv[level].nblocks : lf.tiles_at(level);
+    if (tid == SUMW * 64 - 1) stage_lm_par(job, level, s_par, BATCH ? trials_at(spec, level) : lf.trials_at(level));
     if (wave < SUMW) {
       column_sums<TRIALS_MAX>(A, nb, ncandPending, tid, ft.sum);
       TRACE_PUT(tr_, 0, 17, clock64());
@@ -821,10 +876,12 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
     TRACE_PUT(s_trp, SUMW * 64, 18, clock64());
     __syncthreads();
     PHASE_MARK(2);
+    slot_totals<TRIALS_MAX, BLOCK>(ft.sum, ft.tot, ncandPending, tid);
+    __syncthreads();
     if (wave == 0) {
-      const int pc = pick_trial(S, s_par, level, ncandPending, ft.sum, ft.sub, ft.nsub, s_rec, tid);
+      const int pc = pick_trial(S, s_par, level, ncandPending, ft.tot, ft.sub, ft.nsub, s_rec, tid);
       // column totals and tail-drop correction, one column per lane; then the LM decision in the same wave
-      const float s = finish_totals(ft.sum, ft.sub, ft.nsub, pc, tid);
+      const float s = finish_totals(ft.tot, ft.sub, ft.nsub, pc, tid);
       if (tid < RS_NUM) sh.tot[tid] = s;
 #ifdef LSD_ORDER_CHECK
       if (!BATCH && spec.dbgCounters) order_check_totals(spec, s, pc, tid);
@@ -835,15 +892,18 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
     }
     __syncthreads();
     PHASE_MARK(4);
-    if (S.done) {
-      if (!BATCH && MODE == TS_FUSED && S.lastCand > 0 && spec.copyMask != 0 && job.lv[level].writeMask && cand == 0 && bx < nb)
+    // (what the LM step left of the state, as far as the code up to the evaluation branches on it: one batch of LDS reads)
+    const int doneNow = S.done, lastCandNow = S.lastCand, phaseNow = S.phase;
+    levelNow = S.level; ncandNow = S.ncand;
+    if (doneNow) {
+      if (!BATCH && MODE == TS_FUSED && lastCandNow > 0 && spec.copyMask != 0 && job.lv[level].writeMask && cand == 0 && bx < nb)
         copy_side_mask<BLOCK>(job, S, spec, level, bx, nb, tid);
       if (leader) copy_words<sizeof(TrackState) / 4>(next, &S, tid, BLOCK);
       LAUNCH_LOG(2, pendingIn_, ncandIn_, S.lastCand);
       return;
     }
     // a workgroup that evaluates trial c > 0 leaves that trial's increment and pose for the launch that finishes it
-    if (cand > 0 && bx == 0 && S.phase == 1 && cand < S.ncand && tid < TRIAL_RECORD_WORDS) ((float*)&A.recs_out[cand])[tid] = trial_record_word(S, tid);
+    if (cand > 0 && bx == 0 && phaseNow == 1 && cand < ncandNow && tid < TRIAL_RECORD_WORDS) ((float*)&A.recs_out[cand])[tid] = trial_record_word(S, tid);
   }
 
   if (MODE == TS_LM) {
@@ -855,26 +915,31 @@ __device__ __forceinline__ void track_step_impl(const TrackJob& jobv, const Trac
   }
 
   // ---- residual evaluation at S.level / S.R, S.t ------------------------------------------------------------------
-  const int level = S.level;
+  const int level = levelNow;
   const TrackLevel& L = job.lv[level];
-  const int nb = L.nblocks;
+  const int nb = BATCH ? L.nblocks : lf.tiles_at(level);
   if (MODE == TS_FUSED && level != lvlPending) { cand = 0; bx = (int)blockIdx.x; }   // first evaluation of the next level
-  if (bx >= nb || cand >= S.ncand) return;   // workgroup 0 always has work: it publishes the state at the end
-  const int tile = xcd_tile(bx, nb);
+  // everything of lv[level] the evaluation reads is requested here in one batch, unconditionally and in front of the return (the fields
+  // depend on nothing but the level; one after the other, behind the branches that use them, each was a wait of its own)
   EvalCtx a;
   make_ctx_dev(job, S, level, a);   // (fetched beside the finishing phase for the pending level: measured, +-0 — the scalar loads are not what the step behind the LM waits for)
+  const int writeMask = L.writeMask, evalBatch = L.evalBatch, tilePx = L.tilePx;
+  if (bx >= nb || cand >= ncandNow) return;   // workgroup 0 always has work: it publishes the state at the end
+  const int tile = xcd_tile(bx, nb);
   // a retry further down the reject chain: its pose is in the record the LM workgroup that proposed it left
   if (BATCH && MODE == TS_EVAL && cand > 0) ctx_set_pose(a, A.recs_in[cand]);
-  gbyte* wasGood = (gbyte*)(L.writeMask ? (cand == 0 ? job.wasGood : spec.wasGoodSide + (size_t)(cand - 1) * spec.maskStride) : nullptr);
+  gbyte* wasGood = (gbyte*)(writeMask ? (cand == 0 ? job.wasGood : spec.wasGoodSide + (size_t)(cand - 1) * spec.maskStride) : nullptr);
   const int work = a.npts >= 0 ? a.npts : a.w * a.h;
   float acc[RS_END];
 #pragma unroll
   for (int k = 0; k < RS_END; k++) acc[k] = 0.f;
   int key0 = -1, key1 = -1, key2 = -1;   // reference-order keys of this lane's in-image points (descending)
-  if (BATCH && L.tilePx > 0) {
+  PHASE_MARK(21);   // "post-LM glue": from the LM barrier (4) to the evaluation loop
+  TRACE_PUT(tr_, 0, 22, cand);
+  if (BATCH && tilePx > 0) {
     if (!(havePre && level == lvlPending)) strip_request(L, tile, wave, lane, cntv, ow);   // (else: requested next to the state, at the head of the finishing phase)
-    eval_strip<BLOCK>(a, L.tilePx, tile, work, cntv, ow, (unsigned*)s_red /* not live before the reduction */, wasGood, acc, key0, key1, key2, tid TRACE_ARGS);
-  } else if (!BATCH && L.evalBatch != 0) {
+    eval_strip<BLOCK>(a, tilePx, tile, work, cntv, ow, (unsigned*)s_red /* not live before the reduction */, wasGood, acc, key0, key1, key2, tid TRACE_ARGS);
+  } else if (!BATCH && evalBatch != 0) {
     eval_groups_of_four(a, tile * BLOCK + tid, nb * BLOCK, work, wasGood, acc, key0, key1, key2);
   } else {
     eval_plain(a, tile * BLOCK + tid, nb * BLOCK, work, wasGood, acc, key0, key1, key2);
@@ -1726,6 +1791,11 @@ static void launch_step(lsdhip_tracker* t, const TrackJob& job, TrackSpec spec, 
   t->launchOrdinal++;
   spec.seq = launch_seq(t);
   spec.last = last;
+  spec.levelTiles = 0; spec.levelTrials = 0;
+  for (int l = 0; l < LSD_LEVELS; l++) {
+    spec.levelTiles |= (unsigned long long)(job.lv[l].nblocks & 0xFFF) << (12 * l);
+    spec.levelTrials |= (unsigned)((spec.specC > 1 && spec.trials[l] > 1) ? spec.trials[l] : 1) << (4 * l);   // (trials_at)
+  }
   dev_log_pointer(t, spec);
 #ifdef LSD_ORDER_CHECK
   spec.dbgCum = t->dbgCum;
@@ -1986,6 +2056,9 @@ static TrackSpec job_spec(const lsdhip_tracker* t, const SinglePlan& P) {
   spec.wasGoodSide = side_planes(t);
   spec.maskStride = (unsigned)t->maskStride;
   spec.copyMask = t->ctx->pipeline ? 0 : 1;
+#ifdef LSD_PHASE_TRACE
+  spec.traceWg = batch_env().traceWg;
+#endif
   return spec;
 }
 

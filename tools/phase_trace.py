@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Developer tool: per-phase timestamps of k_track_step (LSD_PHASE_TRACE build, lsd_slam_amd/build.py --trace).
 Usage (GPU box): LSDHIP_LIB=lsd_slam_amd/liblsdhip_trace.so LSDHIP_TRACE_FILE=gpurun_out/x/trace.txt python tools/phase_trace.py"""
+# LSDHIP_TRACE_WG=n traces workgroup n of every launch instead of workgroup 0, the leader: another workgroup shows what the leader skips (the
+# early return's load in the prologue) and, where n is past a level's tiles, the trials behind the first.
 import os
 import sys
 import time
@@ -41,6 +43,17 @@ if path and os.path.exists(path):
             dd = np.diff(e, axis=1)
             print("LM (proposing launches, %d): " % len(lm) + ", ".join("%s %.2f us" % (n, np.median(dd[:, k]) / ghz / 1e3) for k, n in
                   enumerate(["epilogue", "decision+A/b", "matrix load", "LDLT", "exp/mul/store"])))
+    if a.shape[1] >= 23:
+        # the code between the phases: 0 -> 1 prologue (state, records, early return), 1 -> 20 role, 4 -> 21 from the LM barrier to the evaluation loop
+        g = full[(full[:, 20] > 0) & (full[:, 21] > 0) & (full[:, 4] > 0)]
+        if len(g):
+            print("glue (workgroup %s, %d launches): prologue %.2f us, role %.2f us, post-LM glue %.2f us" % (
+                os.environ.get("LSDHIP_TRACE_WG", "0"), len(g), np.median(g[:, 1] - g[:, 0]) / ghz / 1e3, np.median(g[:, 20] - g[:, 1]) / ghz / 1e3,
+                np.median(g[:, 21] - g[:, 4]) / ghz / 1e3))
+            for c in sorted(set(g[:, 22].astype(int))):
+                m = g[:, 22].astype(int) == c
+                print("   trial %d (%d launches): LM barrier to loop %.2f us, LM %.2f us" % (c, m.sum(), np.median(g[m][:, 21] - g[m][:, 4]) / ghz / 1e3,
+                                                                                        np.median(g[m][:, 4] - g[m][:, 3]) / ghz / 1e3))
     if a.shape[1] >= 19:
         both = full[(full[:, 17] > 0) & (full[:, 18] > 0)]
         if len(both):
