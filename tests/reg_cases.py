@@ -1,0 +1,518 @@
+"""A designed hypothesis map for fill-holes (K5), the regulariser (K6) and what the fused pass derives from them (Frame::setDepth,
+Frame::takeReActivationData), and a census that predicts every per-pixel DECISION of those stages from the map alone.
+
+Plain numpy: imports neither the oracle nor the device library.  Both take the sheet through DepthMap.set / setCurrentDepthMap and
+Frame.set_maxgrad / setMaxGradients.
+
+The sheet is a lattice of cells, one designed 5x5 neighbourhood per cell.  Cell centres are at least 7 pixels apart in x and in y, so the
+hypotheses of two cells never share a 5x5 window.  Every pixel that holds no hypothesis carries a stale validity counter (57), a
+plausible inverse depth and variance (a kernel that forgets the validity test sums them), and a maxGradients entry below minUseGrad
+unless a class designs it otherwise (K5 creates nothing outside the designed pixels).  Every pixel that holds a hypothesis has
+maxGradients above minUseGrad, so an observe pass whose frame brings an all-zero refPixelWasGood mask leaves the sheet as it is.
+Inverse depths and variances are dyadic: K6's exclusion test  diff * diff > var_j + var_c  is never near equality.
+
+census() predicts decisions only (created or not; kept / rejected-and-blacklisted / occluded; the final blacklisted counter; counted by
+Frame::setDepth or not and from which pair; the code of the re-activation variance plane), from integer sums and float64 comparisons.  It
+never predicts a value: values are the oracle's business.  It raises when a comparison that involves arithmetic lies within relative
+1e-3 of equality (a float32 device and a float64 census could then disagree legitimately).  A comparison of two stored float32 numbers
+(maxGradients against minUseGrad, a stored idepth_smoothed against -0.05) involves no arithmetic and is exempt.
+"""
+import functools
+
+import numpy as np
+
+HYP_DTYPE = np.dtype(
+    [("isValid", np.uint8), ("_pad", np.uint8, 3), ("blacklisted", np.int32), ("nextStereoFrameMinID", np.float32),
+     ("validity_counter", np.int32), ("idepth", np.float32), ("idepth_var", np.float32),
+     ("idepth_smoothed", np.float32), ("idepth_var_smoothed", np.float32)])
+
+# the constants of DepthMap.cpp / settings.h that decide (restated in oracle/orc_depthmap.cpp and lsd_slam_amd/csrc/depthmap.hip)
+VAL_SUM_MIN_FOR_CREATE, VAL_SUM_MIN_FOR_KEEP, VAL_SUM_MIN_FOR_UNBLACKLIST, MIN_BLACKLIST = 30, 24, 100, -1
+VAR_RANDOM_INIT_INITIAL = 0.125           # 0.5 * MAX_VAR, MAX_VAR = 0.5 * 0.5
+REG_DIST_VAR = 0.075 * 0.075              # depthSmoothingFactor = 1
+SET_DEPTH_MIN_IDEPTH = -0.05              # Frame::setDepth
+MIN_USE_GRAD = 5.0
+NEAR = 1e-3
+
+PITCH = 7                                 # smallest distance of two cell centres along an axis
+VARIANTS = 6                              # sheets of one size that fill the class x position table between them
+STALE_COUNTER, STALE_IDEPTH, VAR0 = 57, 1.0, 1.0 / 64
+GRAD_LOW, GRAD_HIGH = 1.0, 20.0
+GRAD_JUST_BELOW = float(np.nextafter(np.float32(MIN_USE_GRAD), np.float32(0)))
+
+STEPS = {"fillholes": ("K5",), "regularize": ("K6",), "regularize_occ": ("K6occ",), "fill_regularize": ("K5", "K6")}
+K6_NONE, K6_KEPT, K6_REJECTED, K6_OCCLUDED = 0, 1, 2, 3
+SD_NOT_COUNTED, SD_SMOOTHED, SD_STORED = 0, 1, 2
+
+
+def N(counter, idepth=1.0, var=VAR0, valid=True, bl=0, maxgrad=None, at=None, smoothed=None, var_smoothed=None):
+    """one designed pixel: a neighbour of a cell's centre (at = preferred offset (dx, dy)) or the centre itself"""
+    return dict(counter=counter, idepth=idepth, var=var, valid=valid, bl=bl, at=at, smoothed=smoothed, var_smoothed=var_smoothed,
+                maxgrad=(GRAD_HIGH if valid else GRAD_LOW) if maxgrad is None else maxgrad)
+
+
+def _sum(counters, **kw):
+    return [N(c, **kw) for c in counters]
+
+
+S30, S31, S100, S101 = [8, 7, 6, 5, 4], [8, 7, 6, 5, 5], [30, 25, 20, 15, 10], [30, 25, 20, 15, 11]
+HOLE = dict(valid=False, maxgrad=GRAD_HIGH)
+EXCLUDED = [N(200, 3.0), N(200, -1.0)]           # |diff| = 2 against a centre at 1.0: 4 > 1/64 + 1/64 (and > 1/64 + 1/8)
+
+
+class Case:
+    """name, centre pixel, neighbours; `expect`: {stage: (created, k6, valid, blacklisted)} of the centre where the whole neighbourhood
+    lies inside every stage's range (cells without an edge tag); `only`: the position tags the class is bound to (None: anywhere)"""
+
+    def __init__(self, name, centre, nbrs, expect, only=None):
+        self.name, self.centre, self.nbrs, self.expect, self.only = name, centre, nbrs, expect, only
+
+
+def _k5(name, counters, bl, created, maxgrad=GRAD_HIGH, nbrs=None, stale=()):
+    e = {"fillholes": (created, K6_NONE, created, 0 if created else bl)}
+    return Case(name, N(STALE_COUNTER, STALE_IDEPTH, valid=False, bl=bl, maxgrad=maxgrad), (nbrs or _sum(counters)) + list(stale), e)
+
+
+def _k6(name, c0, bl, kept):
+    out = (False, K6_KEPT, True, bl) if kept else (False, K6_REJECTED, False, bl - 1)
+    return Case(name, N(c0, bl=bl), _sum([6, 6, 6]) + EXCLUDED, {"regularize": out, "regularize_occ": out, "fill_regularize": out})
+
+
+def _occ(name, n_occluding, removed):
+    nb = _sum([5, 5]) + [N(50, 3.0) for _ in range(n_occluding)] + [N(50, -1.0), N(50, -1.0)]
+    keep = (False, K6_KEPT, True, 0)
+    return Case(name, N(30), nb, {"regularize": keep, "fill_regularize": keep, "regularize_occ": (False, K6_OCCLUDED, False, 0) if removed else keep})
+
+
+def _fused_reject(name, bl):
+    nb = [N(20, 0.25), N(20, 4.25), N(20, 0.25), N(20, 4.25), N(20, 0.25), N(20, 4.25)]      # sum 120, mean 2.25, every |diff| = 2
+    return Case(name, N(STALE_COUNTER, STALE_IDEPTH, valid=False, bl=bl, maxgrad=GRAD_HIGH), nb,
+                {"fillholes": (True, K6_NONE, True, 0), "fill_regularize": (True, K6_REJECTED, False, -1)})
+
+
+def _sees_created(name, c0, kept):
+    # the hole H right of the centre sums 11 + 6 + 6 + 40 + 40 = 103 (or 104) and is created; the centre counts it with validity counter 0
+    nb = [N(STALE_COUNTER, STALE_IDEPTH, at=(1, 0), **HOLE), N(6, at=(-1, 0)), N(6, at=(0, 1)), N(40, 3.0, at=(2, 1)), N(40, 3.0, at=(1, -2))]
+    out = (False, K6_KEPT, True, 0) if kept else (False, K6_REJECTED, False, -1)
+    return Case(name, N(c0), nb, {"fill_regularize": out, "regularize": out})
+
+
+def _plain(name, centre, nbrs, only=None):
+    keep = (False, K6_KEPT, True, 0)
+    return Case(name, centre, nbrs, {"regularize": keep, "regularize_occ": keep, "fill_regularize": keep}, only)
+
+
+BORDER_TAGS = ("x=1", "x=w-2", "y=1", "y=h-2")
+CASES = [
+    # K5: both thresholds, the blacklist clause, the gradient test, stale counters, the weighted mean
+    _k5("K5 sum=30 bl=0", S30, 0, False), _k5("K5 sum=31 bl=0", S31, 0, True),
+    _k5("K5 sum=30 bl=-1", S30, -1, False), _k5("K5 sum=31 bl=-1", S31, -1, True),
+    _k5("K5 sum=31 bl=-2", S31, -2, False), _k5("K5 sum=100 bl=-2", S100, -2, False), _k5("K5 sum=101 bl=-2", S101, -2, True),
+    _k5("K5 sum=31 bl=-5", S31, -5, False), _k5("K5 sum=100 bl=-5", S100, -5, False), _k5("K5 sum=101 bl=-5", S101, -5, True),
+    _k5("K5 maxGrad just below", S101, 0, False, maxgrad=GRAD_JUST_BELOW), _k5("K5 maxGrad == minUseGrad", S31, 0, True, maxgrad=MIN_USE_GRAD),
+    _k5("K5 sum large by stale counters only", S30, 0, False, stale=[N(250, valid=False), N(250, valid=False), N(250, valid=False)]),
+    _k5("K5 unequal variances", None, 0, True, nbrs=[N(11, 0.5), N(10, 2.0, 0.25), N(10, 0.5, 0.25)]),
+    _k5("K5 negative inverse depths", None, 0, True, nbrs=[N(11, -0.5), N(10, -0.5), N(10, 0.25)]),
+    _k5("K5 weighted sum exactly 0 (unzero)", None, 0, True, nbrs=[N(11, 0.5), N(10, -0.5), N(5, 0.5), N(5, -0.5)]),
+    # K6: the keep threshold from both blacklist values, excluded neighbours with large counters, occlusion
+    _k6("K6 val_sum=23 bl=0", 5, 0, False), _k6("K6 val_sum=24 bl=0", 6, 0, True), _k6("K6 val_sum=25 bl=0", 7, 0, True),
+    _k6("K6 val_sum=23 bl=-1", 5, -1, False), _k6("K6 val_sum=24 bl=-1", 6, -1, True), _k6("K6 val_sum=25 bl=-1", 7, -1, True),
+    _occ("K6 occluding == not occluding", 3, False), _occ("K6 occluding == not occluding + 1", 4, True),
+    # K5 + K6 in one launch
+    _fused_reject("fused created then rejected bl=0", 0), _fused_reject("fused created then rejected bl=-3", -3),
+    _sees_created("fused sees created neighbour val_sum=23", 11, False), _sees_created("fused sees created neighbour val_sum=24", 12, True),
+    # Frame::setDepth and the keyframe change
+    _plain("setDepth smoothed -0.0625 not counted", N(30, -0.0625), [N(10, -0.0625), N(10, -0.0625), N(10, -0.0625)]),
+    _plain("setDepth smoothed -0.03125 counted", N(30, -0.03125), [N(10, -0.03125), N(10, -0.03125), N(10, -0.03125)]),
+    _plain("border pixel takes the stored smoothed pair", N(30, 1.0, smoothed=0.625, var_smoothed=1.0 / 32), _sum([10, 10]), only=BORDER_TAGS),
+    _plain("border pixel stored smoothed -0.0625 not counted", N(30, 1.0, smoothed=-0.0625, var_smoothed=1.0 / 32), _sum([10, 10]), only=BORDER_TAGS),
+    _plain("validity counter 255", N(255), _sum([10, 10])),
+]
+CASE_NAMES = [c.name for c in CASES]
+
+OFFS = [(-2, -2), (2, 2), (2, -2), (-2, 2), (0, -2), (0, 2), (-2, 0), (2, 0), (-1, -1), (1, 1), (1, -1), (-1, 1), (-2, -1), (2, 1), (-1, 2), (1, -2),
+        (0, -1), (0, 1), (-1, 0), (1, 0), (-2, 1), (2, -1), (1, 2), (-1, -2)]
+EDGE_TAGS = ("x=1", "x=2", "x=3", "x=w-3", "x=w-2", "y=1", "y=2", "y=3", "y=h-3", "y=h-2")
+SEAM_TAGS = ("x%32=31", "x%32=0", "y%16=7", "y%16=8", "y%16=15", "y%16=0")
+TAGS = ("interior",) + EDGE_TAGS + SEAM_TAGS + ("last tile column",)
+
+
+def tags_of(x, y, w, h):
+    """the position classes of a cell centre: the K5 / K6 range edges, an owned-tile seam right beside the centre (tiles are 32 wide and 8
+    or 16 high), the partial last tile column"""
+    t = []
+    for v, n, a in ((x, w, "x"), (y, h, "y")):
+        for k in (1, 2, 3):
+            if v == k:
+                t.append("%s=%d" % (a, k))
+        for k in (3, 2):
+            if v == n - k:
+                t.append("%s=%s-%d" % (a, "w" if a == "x" else "h", k))
+    if not t:
+        t.append("interior")
+    if x % 32 in (31, 0):
+        t.append("x%%32=%d" % (x % 32))
+    if y % 16 in (7, 8, 15, 0):
+        t.append("y%%16=%d" % (y % 16))
+    if w % 32 and x >= (w // 32) * 32:
+        t.append("last tile column")
+    return t
+
+
+def possible_tags(w, h):
+    return [t for t in TAGS if t != "last tile column" or w % 32]
+
+
+def can_occur(case, tag):
+    return case.only is None or tag in case.only
+
+
+def _axis(n, seam):
+    """centre alternatives per lattice line along one axis: the low band (1, 2, 3), a pair (m - 1, m) at every tile seam m, single
+    lines between them, the high band (n - 3, n - 2); max of a line + PITCH <= min of the next"""
+    lines = [(1, 2, 3)]
+    last = 3
+    hi = n - 3
+    m = seam
+    while m < n:
+        if m - 1 >= last + PITCH and m + PITCH <= hi:
+            v = last + PITCH
+            while v + PITCH <= m - 1:
+                lines.append((v,))
+                v += PITCH
+            lines.append((m - 1, m))
+            last = m
+        m += seam
+    v = last + PITCH
+    while v + PITCH <= hi:
+        lines.append((v,))
+        v += PITCH
+    lines.append((n - 3, n - 2))
+    return lines
+
+
+class _Layout:
+    """the greedy state of one size: variants are laid out in order, each when first asked for"""
+
+    def __init__(self, w, h):
+        self.w, self.h = w, h
+        self.cols, self.rows = _axis(w, 32), _axis(h, 8)
+        self.poss = set(possible_tags(w, h))
+        self.need = {(k, t) for k, c in enumerate(CASES) for t in self.poss if can_occur(c, t)}
+        self.used = [0] * len(CASES)
+        self.seen = {}        # (class, tag) -> cells so far
+        self.variants = []
+
+    def variant(self, v):
+        while len(self.variants) <= v:
+            self.variants.append(self._next())
+        return self.variants[v]
+
+    def _next(self):
+        w, h, need, used, seen = self.w, self.h, self.need, self.used, self.seen
+        cells = []
+        for ys in self.rows:
+            for xs in self.cols:
+                best = None
+                for cx, cy in [(cx, cy) for cy in ys for cx in xs]:
+                    tg = [t for t in tags_of(cx, cy, w, h) if t in self.poss]
+                    ks = [k for k, c in enumerate(CASES) if c.only is None or any(t in c.only for t in tg)]
+                    if not need:          # the table is full: only the classes used least can win
+                        least = min(used[k] for k in ks)
+                        ks = [k for k in ks if used[k] == least]
+                    for k in ks:
+                        key = (sum(1 for t in tg if (k, t) in need), -used[k], -sum(seen.get((k, t), 0) for t in tg))
+                        if best is None or key > best[0]:
+                            best = (key, cx, cy, k, tg)
+                _, cx, cy, k, tg = best
+                used[k] += 1
+                need.difference_update((k, t) for t in tg)
+                for t in tg:
+                    seen[(k, t)] = seen.get((k, t), 0) + 1
+                cells.append((cx, cy, k))
+        return cells
+
+
+@functools.lru_cache(maxsize=None)
+def _layout(w, h):
+    return _Layout(w, h)
+
+
+def layout(w, h, variant=0):
+    """[(cx, cy, case index)] of variant `variant`: every lattice cell gets the centre alternative and the class that fill the most cells
+    of the class x position table still empty, over this and the earlier variants (ties: the class used least, then the positions it has
+    stood at least) — greedy, deterministic"""
+    assert 0 <= variant < VARIANTS
+    return _layout(w, h).variant(variant)
+
+
+def cells(w, h, variant=0):
+    """[(cx, cy, Case, [tags])] of one variant of the sheet"""
+    return [(cx, cy, CASES[k], tags_of(cx, cy, w, h)) for cx, cy, k in layout(w, h, variant)]
+
+
+def _put(hyp, mg, x, y, p):
+    px = hyp[y, x]
+    px["isValid"], px["blacklisted"], px["validity_counter"] = int(p["valid"]), p["bl"], p["counter"]
+    px["idepth"], px["idepth_var"] = p["idepth"], p["var"]
+    px["idepth_smoothed"] = p["idepth"] * 0.75 if p["smoothed"] is None else p["smoothed"]
+    px["idepth_var_smoothed"] = p["var"] * 0.5 if p["var_smoothed"] is None else p["var_smoothed"]
+    mg[y, x] = p["maxgrad"]
+
+
+def build(w, h, variant=0):
+    """(hypothesis array, maxGradients plane) of variant `variant` (0 .. VARIANTS - 1) of the sheet of size w x h"""
+    hyp = np.zeros((h, w), HYP_DTYPE)
+    mg = np.full((h, w), GRAD_LOW, np.float32)
+    hyp["validity_counter"] = STALE_COUNTER
+    hyp["idepth"] = STALE_IDEPTH
+    hyp["idepth_var"] = VAR0
+    hyp["idepth_smoothed"] = STALE_IDEPTH * 0.75
+    hyp["idepth_var_smoothed"] = VAR0 * 0.5
+    for cx, cy, k in layout(w, h, variant):
+        c = CASES[k]
+        _put(hyp, mg, cx, cy, c.centre)
+        free = [o for o in OFFS if 0 <= cx + o[0] < w and 0 <= cy + o[1] < h]
+        for p in c.nbrs:                      # preferred offsets first, the rest in OFFS order
+            if p["at"] in free:
+                free.remove(p["at"])
+        for p in c.nbrs:
+            o = p["at"] if p["at"] is not None and 0 <= cx + p["at"][0] < w and 0 <= cy + p["at"][1] < h else free.pop(0)
+            _put(hyp, mg, cx + o[0], cy + o[1], p)
+    return hyp, mg
+
+
+class NearEquality(ValueError):
+    pass
+
+
+def _shift(a, dx, dy, fill):
+    """b[y, x] = a[y + dy, x + dx], `fill` outside the image"""
+    h, w = a.shape
+    b = np.full_like(a, fill)
+    ys, yd = (slice(dy, h), slice(0, h - dy)) if dy >= 0 else (slice(0, h + dy), slice(-dy, h))
+    xs, xd = (slice(dx, w), slice(0, w - dx)) if dx >= 0 else (slice(0, w + dx), slice(-dx, w))
+    b[yd, xd] = a[ys, xs]
+    return b
+
+
+def _near(a, b):
+    return np.abs(a - b) <= NEAR * np.maximum(np.abs(a), np.abs(b))
+
+
+def census(hyp, maxgrad, min_use_grad=MIN_USE_GRAD, stage="fill_regularize", validity_th=VAL_SUM_MIN_FOR_KEEP, reg_dist_var=REG_DIST_VAR,
+           near="raise", cell_list=None):
+    """The per-pixel decisions of `stage` ("fillholes", "regularize", "regularize_occ", "fill_regularize", or several joined by "+") on
+    the map: dict of planes
+      created      K5 created a hypothesis here
+      k6           K6_NONE (no hypothesis, or outside K6's range) / K6_KEPT / K6_REJECTED (and blacklisted) / K6_OCCLUDED, of the last K6 step
+      valid        holds a hypothesis afterwards
+      blacklisted  the counter afterwards
+      setdepth     what Frame::setDepth makes of the final map: SD_NOT_COUNTED (planes -1) / SD_SMOOTHED (the pair K6 just made) /
+                   SD_STORED (the pair the map held before: K6 did not smooth the pixel)
+      react        Frame::takeReActivationData's variance plane: 1 = a hypothesis, else -2 (blacklisted below MIN_BLACKLIST) or -1
+      uncertain    near="mask" only: decisions that rest on a comparison within NEAR of equality (near="raise" raises NearEquality)
+    and, with cell_list (cells()), "table": {(class name, position tag): number of cells}."""
+    h, w = hyp.shape
+    valid = hyp["isValid"] > 0
+    cnt = hyp["validity_counter"].astype(np.int64)
+    idp = hyp["idepth"].astype(np.float64)
+    var = hyp["idepth_var"].astype(np.float64)
+    ids = hyp["idepth_smoothed"].astype(np.float64)
+    bl = hyp["blacklisted"].astype(np.int64)
+    mg = np.asarray(maxgrad, np.float32)
+    yy, xx = np.mgrid[0:h, 0:w]
+    created = np.zeros((h, w), bool)
+    k6 = np.zeros((h, w), np.uint8)
+    smoothed_now = np.zeros((h, w), bool)
+    unc = np.zeros((h, w), bool)
+    offs = [(dx, dy) for dx in range(-2, 3) for dy in range(-2, 3)]
+
+    def flag(m, what):
+        if m.any():
+            if near == "raise":
+                y, x = np.argwhere(m)[0]
+                raise NearEquality("%s within relative %g of equality at (%d, %d) and %d more pixels" % (what, NEAR, x, y, int(m.sum()) - 1))
+            unc[m] = True
+
+    for name in stage.split("+"):
+        for step in STEPS[name]:
+            if unc.any():       # what rested on an uncertain pixel is uncertain
+                d = np.zeros_like(unc)
+                for dx, dy in offs:
+                    d |= _shift(unc, dx, dy, False)
+                unc |= d
+            if step == "K5":
+                rng = (xx >= 3) & (xx < w - 2) & (yy >= 3) & (yy < h - 2)
+                S = np.zeros((h, w), np.int64)
+                num = np.zeros((h, w))
+                den = np.zeros((h, w))
+                for dx, dy in offs:
+                    v = _shift(valid, dx, dy, False)
+                    S += np.where(v, _shift(cnt, dx, dy, 0), 0)
+                    vj = np.where(v, _shift(var, dx, dy, 1.0), 1.0)
+                    num += np.where(v, _shift(idp, dx, dy, 0.0) / vj, 0.0)
+                    den += np.where(v, 1.0 / vj, 0.0)
+                cand = ~valid & rng & ~(mg < np.float32(min_use_grad))
+                make = cand & ((S > VAL_SUM_MIN_FOR_UNBLACKLIST) | ((S > VAL_SUM_MIN_FOR_CREATE) & (bl >= MIN_BLACKLIST)))
+                mean = np.where(make, num / np.where(den > 0, den, 1.0), 0.0)
+                mean = np.where(mean < 0, np.minimum(mean, -1e-10), np.maximum(mean, 1e-10))
+                valid = valid | make
+                cnt = np.where(make, 0, cnt)
+                idp = np.where(make, mean, idp)
+                ids = np.where(make, -1.0, ids)
+                var = np.where(make, VAR_RANDOM_INIT_INITIAL, var)
+                bl = np.where(make, 0, bl)
+                created |= make
+                smoothed_now &= ~make
+            else:
+                occ = step == "K6occ"
+                rng = (xx >= 2) & (xx < w - 2) & (yy >= 2) & (yy < h - 2) & valid
+                vs = np.zeros((h, w), np.int64)
+                n_occ = np.zeros((h, w), np.int64)
+                n_not = np.zeros((h, w), np.int64)
+                s = np.zeros((h, w))
+                si = np.zeros((h, w))
+                close = np.zeros((h, w), bool)
+                for dx, dy in offs:
+                    v = _shift(valid, dx, dy, False) & rng
+                    idj, vj = _shift(idp, dx, dy, 0.0), _shift(var, dx, dy, 1.0)
+                    diff = idj - idp
+                    lhs, rhs = diff * diff, vj + var
+                    close |= v & _near(lhs, rhs) & (lhs != 0)
+                    excl = lhs > rhs
+                    inc = v & ~excl
+                    vs += np.where(inc, _shift(cnt, dx, dy, 0), 0)
+                    n_not += inc
+                    n_occ += v & excl & (idj > idp)
+                    ivar = 1.0 / np.where(inc, vj + (dx * dx + dy * dy) * reg_dist_var, 1.0)
+                    s += np.where(inc, idj * ivar, 0.0)
+                    si += np.where(inc, ivar, 0.0)
+                flag(close, "K6's exclusion test")
+                rej = rng & (vs < validity_th)
+                gone = rng & ~rej & occ & (n_occ > n_not)
+                kept = rng & ~rej & ~gone
+                k6 = np.where(kept, K6_KEPT, np.where(rej, K6_REJECTED, np.where(gone, K6_OCCLUDED, K6_NONE))).astype(np.uint8)
+                ids = np.where(kept, s / np.where(si > 0, si, 1.0), ids)
+                smoothed_now = (smoothed_now & ~rng) | kept
+                valid = valid & ~rej & ~gone
+                bl = np.where(rej, bl - 1, bl)
+    flag(valid & smoothed_now & _near(ids, np.full_like(ids, SET_DEPTH_MIN_IDEPTH)), "Frame::setDepth's test of a smoothed inverse depth")
+    counted = valid & (ids >= SET_DEPTH_MIN_IDEPTH)
+    out = {"created": created, "k6": k6, "valid": valid, "blacklisted": bl.astype(np.int32),
+           "setdepth": np.where(counted, np.where(smoothed_now, SD_SMOOTHED, SD_STORED), SD_NOT_COUNTED).astype(np.uint8),
+           "react": np.where(valid, 1, np.where(bl < MIN_BLACKLIST, -2, -1)).astype(np.int32), "uncertain": unc}
+    if cell_list is not None:
+        out["table"] = table(cell_list)
+    return out
+
+
+def table(cell_lists):
+    """{(class name, position tag): number of cells} over one or several cells() lists"""
+    if cell_lists and not isinstance(cell_lists[0], list):
+        cell_lists = [cell_lists]
+    t = {}
+    for cl in cell_lists:
+        for cx, cy, c, tg in cl:
+            for g in tg:
+                t[(c.name, g)] = t.get((c.name, g), 0) + 1
+    return t
+
+
+def empty_cells(t, w, h):
+    """the (class, position) pairs that can be filled at this size and are not"""
+    return [(c.name, g) for c in CASES for g in possible_tags(w, h) if can_occur(c, g) and t.get((c.name, g), 0) == 0]
+
+
+def format_table(t, w, h):
+    tg = possible_tags(w, h)
+    short = [g.replace("interior", "int").replace("last tile column", "last").replace("x%32=", "x%").replace("y%16=", "y%") for g in tg]
+    lines = ["%-50s %s" % ("class \\ position (%dx%d)" % (w, h), " ".join("%5s" % s for s in short))]
+    for c in CASES:
+        lines.append("%-50s %s" % (c.name, " ".join("%5s" % (t.get((c.name, g), 0) if can_occur(c, g) else "-") for g in tg)))
+    return "\n".join(lines)
+
+
+def class_masks(cell_list, shape):
+    """{class name: (centre mask, centre mask of the cells without an edge tag)}"""
+    out = {}
+    for cx, cy, c, tg in cell_list:
+        a, b = out.setdefault(c.name, (np.zeros(shape, bool), np.zeros(shape, bool)))
+        a[cy, cx] = True
+        if "interior" in tg:
+            b[cy, cx] = True
+    return out
+
+
+def block_of(cell_list, shape):
+    """int plane: index into cell_list of the cell whose 5x5 neighbourhood holds the pixel, -1 between the cells"""
+    owner = np.full(shape, -1, np.int32)
+    h, w = shape
+    for i, (cx, cy, c, tg) in enumerate(cell_list):
+        owner[max(cy - 2, 0):min(cy + 3, h), max(cx - 2, 0):min(cx + 3, w)] = i
+    return owner
+
+
+DECISIONS = ("created", "k6", "valid", "blacklisted")
+
+
+def assert_decisions(got, want, cell_list, what, keys=DECISIONS, skip=None):
+    """got / want: {decision plane name: array}.  Compares plane by plane and names the class and position of the first cell that differs."""
+    shape = want[keys[0]].shape
+    owner = block_of(cell_list, shape)
+    for k in keys:
+        bad = np.asarray(got[k]) != np.asarray(want[k])
+        if skip is not None:
+            bad &= ~skip
+        if bad.any():
+            y, x = np.argwhere(bad)[0]
+            i = owner[y, x]
+            where = "between the cells" if i < 0 else "class '%s' at %s (centre %d, %d)" % (cell_list[i][2].name, ", ".join(cell_list[i][3]), cell_list[i][0], cell_list[i][1])
+            raise AssertionError("%s: decision '%s' differs at pixel (%d, %d): got %r, census %r — %s; %d pixels differ" %
+                                 (what, k, x, y, np.asarray(got[k])[y, x], np.asarray(want[k])[y, x], where, int(bad.sum())))
+
+
+def assert_expectations(dec, cell_list, stage, what):
+    """the declared outcome of every class at its centre, on the cells without an edge tag: the sheet reaches what it claims to reach"""
+    n = 0
+    for cx, cy, c, tg in cell_list:
+        if "interior" not in tg or stage not in c.expect:
+            continue
+        e = c.expect[stage]
+        g = (bool(dec["created"][cy, cx]), int(dec["k6"][cy, cx]), bool(dec["valid"][cy, cx]), int(dec["blacklisted"][cy, cx]))
+        assert g == e, "%s: class '%s' at (%d, %d) under %s: (created, k6, valid, blacklisted) = %r, designed for %r" % (what, c.name, cx, cy, stage, g, e)
+        n += 1
+    return n
+
+
+def decisions_from_maps(before, after, stage):
+    """the decision planes census() predicts, read off a map before and after `stage` ran on it (oracle, reference or device).  A
+    created pixel is known by what the reference stores there, whether or not K6 then rejects it: variance VAR_RANDOM_INIT_INITIAL and
+    validity counter 0 where no hypothesis was (no other pixel of the sheet carries that pair)."""
+    h, w = before.shape
+    yy, xx = np.mgrid[0:h, 0:w]
+    steps = [s for name in stage.split("+") for s in STEPS[name]]
+    assert len([s for s in steps if s != "K5"]) <= 1, "one K6 step at most can be read off a pair of maps"
+    was = before["isValid"] > 0
+    now = after["isValid"] > 0
+    created = np.zeros((h, w), bool)
+    if "K5" in steps:
+        created = ~was & (after["idepth_var"] == np.float32(VAR_RANDOM_INIT_INITIAL)) & (after["validity_counter"] == 0)
+    k6 = np.zeros((h, w), np.uint8)
+    if steps[-1] != "K5":
+        had = (was | created) & (xx >= 2) & (xx < w - 2) & (yy >= 2) & (yy < h - 2)
+        bl0 = np.where(created, 0, before["blacklisted"])
+        k6 = np.where(had, np.where(now, K6_KEPT, np.where(after["blacklisted"] == bl0 - 1, K6_REJECTED, K6_OCCLUDED)), K6_NONE).astype(np.uint8)
+    return {"created": created, "k6": k6, "valid": now, "blacklisted": after["blacklisted"].astype(np.int32)}
+
+
+def setdepth_from_planes(idepth0, var0, stored):
+    """census()'s "setdepth" plane read off a keyframe's level-0 planes after Frame::setDepth; `stored`: the idepth_smoothed plane the map
+    held before the pass (SD_STORED <=> counted with exactly that value; no smoothed value of the sheet equals a stored one)"""
+    counted = var0 > 0
+    same = np.ascontiguousarray(idepth0).view(np.uint32) == np.ascontiguousarray(stored, dtype=np.float32).view(np.uint32)
+    return np.where(counted, np.where(same, SD_STORED, SD_SMOOTHED), SD_NOT_COUNTED).astype(np.uint8)
+
+
+def react_from_planes(var_react):
+    return np.where(var_react > 0, 1, np.where(var_react == -2, -2, -1)).astype(np.int32)
