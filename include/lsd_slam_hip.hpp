@@ -48,6 +48,7 @@
 #include <vector>
 
 #include "lsdhip.h"
+#include "lsd_slam_hip_loop.hpp"
 #include "lsd_slam_hip_pose.hpp"
 
 namespace lsd_slam_hip {
@@ -82,6 +83,7 @@ struct Sim3 {
   double q[4] = {1, 0, 0, 0};
   double t[3] = {0, 0, 0};
   double s = 1;
+  static Sim3 from8(const double p[8]) { Sim3 r; for (int i = 0; i < 4; i++) r.q[i] = p[i]; for (int i = 0; i < 3; i++) r.t[i] = p[4 + i]; r.s = p[7]; return r; }
 };
 
 // One device context per (device, w, h, K): what the (w, h, K) constructor arguments of Frame / SE3Tracker / DepthMap
@@ -628,7 +630,7 @@ class TrackableKeyFrameSearch {
   // TrackableKeyFrameSearch.h:75-79 with the context's KFDistWeight / KFUsageWeight
   float getRefFrameScore(float distanceSquared, float usage) const {
     const lsdhip_params& p = bank_->context()->params;
-    return distanceSquared * p.KFDistWeight * p.KFDistWeight + (1 - usage) * (1 - usage) * p.KFUsageWeight * p.KFUsageWeight;
+    return lsd_slam::loop::keyframeScore(distanceSquared, usage, p.KFDistWeight, p.KFUsageWeight);
   }
   float relocalizationTH = 0.7f;   // util/settings.cpp:101
   lsdhip_reposition_result last = {};
@@ -829,66 +831,215 @@ class DepthMap {
 //     frame that follows a keyframe change is therefore still tracked on the old keyframe; the mapper drops it (updateKeyframe pops
 //     frames whose tracking parent is not the current keyframe, :559-566) and the first frame tracked on the new keyframe starts from
 //     se3FromSim3(newKeyframe^-1 * lastTrackedFrame) (:918-920).  The lag is fixed at one frame, so results do not depend on timing.
-class SlamLoop {
- public:
-  // gtDepth0 != null: SlamSystem::gtDepthInit (SlamSystem.cpp:831-854); null: SlamSystem::randomInit (:857-881).
-  // kfEvery > 0: a new keyframe every kfEvery frames (deterministic; what bench.py and the parity tests use);
-  // kfEvery == 0: the reference's distance / usage score (SlamSystem.cpp:997-1015 with doSlam = false, see keyframeScore).
-  SlamLoop(int w, int h, const Mat3f& K, const unsigned char* firstImage, bool imagesOnDevice, const float* gtDepth0, int kfEvery)
-      : tracker(w, h, K), map(w, h, K), w_(w), h_(h), K_(K), onDevice_(imagesOnDevice), kfEvery_(kfEvery) {
-    init(firstImage, gtDepth0);
-  }
-  // Raw camera images: w, h, K are those of the RECTIFIED images (Undistorter::out_width / out_height / K), firstRawImage and every
-  // image given to step() are raw inputWidth x inputHeight images of the undistorter's camera, rectified inside frame creation.
-  SlamLoop(int w, int h, const Mat3f& K, std::shared_ptr<DeviceUndistorter> undistorter, const unsigned char* firstRawImage,
-           bool imagesOnDevice, const float* gtDepth0, int kfEvery)
-      : tracker(w, h, K), map(w, h, K), w_(w), h_(h), K_(K), onDevice_(imagesOnDevice), kfEvery_(kfEvery) {
-    setUndistorter(std::move(undistorter));
-    init(firstRawImage, gtDepth0);
-  }
-  // From the next step() on images are raw images of this camera (null: rectified w x h images again).  One camera serves all loops of
-  // a context; an image announced as nextImage stays what it was announced as.
-  void setUndistorter(std::shared_ptr<DeviceUndistorter> undistorter) {
-    if (undistorter && undistorter->context() != Context::get(w_, h_, K_))
-      throw Error(LSDHIP_E_ARG, "SlamLoop::setUndistorter: the undistorter belongs to another output size / K");
-    undistorter_ = std::move(undistorter);
-  }
-  const std::shared_ptr<DeviceUndistorter>& undistorter() const { return undistorter_; }
+//
+// Both loops hold the same two pieces: the camera their frames come from (LoopCamera) and, per sequence, the state SlamSystem keeps and
+// the rules of lsd_slam_hip_loop.hpp applied to it (LoopSequence).  What differs between the loops is stated where it lives.
 
- private:
-  void init(const unsigned char* firstImage, const float* gtDepth0) {
-    const int its[LSDHIP_PYRAMID_LEVELS] = {5, 20, 50, 100, 0};  // SlamSystem.cpp:80-81 (no level-4 iterations are run by the tracker)
-    std::memcpy(tracker.settings.maxItsPerLvl, its, sizeof(its));
-    keyframe = makeFrame(0, firstImage);
+// The camera of a loop: rectified w x h images, or raw inputWidth x inputHeight images rectified inside frame creation, in host or
+// in device memory.  The one place frames of a loop are created.
+struct LoopCamera {
+  int w, h;
+  Mat3f K;
+  bool imagesOnDevice;
+  std::shared_ptr<DeviceUndistorter> undistorter;    // set: images are raw images of this camera
+  std::shared_ptr<Context> context() const { return Context::get(w, h, K); }
+  void setUndistorter(std::shared_ptr<DeviceUndistorter> u) {
+    if (u && u->context() != context()) throw Error(LSDHIP_E_ARG, "SlamLoop / SlamLoopBatch::setUndistorter: the undistorter belongs to another output size / K");
+    undistorter = std::move(u);
+  }
+  // async: a host image whose upload is queued and not waited for (the caller keeps the bytes unchanged until the frame has been
+  // tracked: SlamLoop::step's nextImage contract)
+  std::shared_ptr<Frame> frame(int id, const unsigned char* img, bool async) const {
+    if (undistorter) {
+      if (imagesOnDevice) return std::make_shared<Frame>(id, *undistorter, 0.0, Frame::RawDeviceImage{img});
+      if (async) return std::make_shared<Frame>(id, *undistorter, 0.0, Frame::RawHostImageAsync{img});
+      return std::make_shared<Frame>(id, *undistorter, 0.0, Frame::RawImage{img});
+    }
+    if (imagesOnDevice) return std::make_shared<Frame>(id, w, h, K, 0.0, Frame::DeviceImage{img});
+    if (async) return std::make_shared<Frame>(id, w, h, K, 0.0, Frame::HostImageAsync{img});
+    return std::make_shared<Frame>(id, w, h, K, 0.0, img);
+  }
+  // one frame of several sequences in shared launches
+  std::vector<std::shared_ptr<Frame>> frames(const std::vector<int>& ids, const unsigned char* const* images) const {
+    if (undistorter) return Frame::createBatch(*undistorter, ids, images, imagesOnDevice);
+    return Frame::createBatch(w, h, K, ids, images, imagesOnDevice);
+  }
+};
+inline void setLoopIterations(SE3Tracker& tracker) {
+  static_assert(sizeof(lsd_slam::loop::TRACKER_MAX_ITS_PER_LVL) == sizeof(tracker.settings.maxItsPerLvl), "one entry per pyramid level");
+  std::memcpy(tracker.settings.maxItsPerLvl, lsd_slam::loop::TRACKER_MAX_ITS_PER_LVL, sizeof(lsd_slam::loop::TRACKER_MAX_ITS_PER_LVL));
+}
+
+// What SlamSystem keeps for ONE sequence, and what happens to it around each tracked frame: SlamLoop is one of these, SlamLoopBatch
+// holds S.  The loops own the device work (which call, on which stream, shared with whom, queued when); every counter, flag and pose
+// estimate changes here and nowhere else.
+struct LoopSequence {
+  using MappingStep = lsd_slam::loop::MappingStep;
+  LoopSequence(int w, int h, const Mat3f& K) : map(w, h, K) {}
+  DepthMap map;
+  TrackingReference reference;
+  std::shared_ptr<Frame> keyframe;       // the mapper's current keyframe (DepthMap::activeKeyFrame)
+  std::shared_ptr<Frame> trackKF;        // the keyframe the tracking reference points at (== keyframe unless a promotion is pending)
+  std::shared_ptr<Frame> pendingKF;      // pipelined: made current by the mapping iteration queued last, not yet adopted by the tracker
+  SE3 lastFrameToKF;                     // the next frame's initial estimate
+  int sinceKF = 0;                       // frames tracked since the keyframe change, dropped ones included
+  int mappedOnKF = 0;                    // Frame::numMappedOnThisTotal of the current keyframe: counted here, so that the asynchronous
+                                         // pipeline is not drained every frame by Frame::stats()
+  int numKeyframesFinished = 0;          // keyFrameGraph->keyframesAll.size()
+  long numTracked = 0, numTrackedGood = 0, numUpdates = 0, evaluations = 0;
+  long numDropped = 0;                   // frames tracked on a keyframe the mapper had already replaced (pipelined): not mapped
+  bool trackingLost = false;             // SlamSystem::trackingIsGood == false: the sequence takes no further frames
+  bool newKeyframe = false;              // the last tracked frame led to a keyframe change
+  std::vector<std::shared_ptr<Frame>> keyframeLog;   // every frame promoted while the loop's keepKeyframes was on
+
+  // gtDepth0 != null: SlamSystem::gtDepthInit (SlamSystem.cpp:831-854); null: SlamSystem::randomInit (:857-881)
+  void start(std::shared_ptr<Frame> first, const float* gtDepth0) {
+    keyframe = std::move(first);
     if (gtDepth0) {
       keyframe->setDepthFromGroundTruth(gtDepth0);
       map.initializeFromGTDepth(keyframe.get());
     } else {
       map.initializeRandomly(keyframe.get());
     }
-    trackKF_ = keyframe;
-    reference.importFrame(keyframe.get());
-    keyframe->clearDepthHasBeenUpdatedFlag();
+    trackKF = keyframe;
+    importReference(*keyframe);
+  }
+  void importReference(Frame& kf) {
+    reference.importFrame(&kf);
+    kf.clearDepthHasBeenUpdatedFlag();
+  }
+  // the tracking thread's re-import when the mapper has changed the keyframe's depth (SlamSystem.cpp:907-912).  A one-stream loop
+  // does it before tracking a frame, a pipelined one after (tracked()): there the mapping iteration runs beside the tracking.
+  void importIfUpdated(Frame& kf) { if (kf.depthHasBeenUpdatedFlag()) importReference(kf); }
+  // se3FromSim3(keyframe^-1 * frame) for a frame tracked on the keyframe's tracking parent (SlamSystem.cpp:918-920)
+  static SE3 relativePose(Frame& kf, Frame& frame) {
+    double p[7];
+    check(lsdhip_frame_relative_pose(kf.handle(), frame.handle(), p), "lsdhip_frame_relative_pose");
+    return SE3::from7(p);
+  }
+
+  // `frame` has been tracked on `trackedOn` (trackKF as it was when tracking began; the caller keeps it alive for the step) and gave
+  // `est`: counts the result and decides the frame's mapping step.
+  //   * Lost: the reference is invalidated, the keyframe finalised (finalisedAtLoss() is called then, the map still valid) or discarded,
+  //     the map invalidated.  What follows in the reference is the relocaliser (out of scope).
+  //   * otherwise a pipelined loop adopts what the mapping iteration queued one frame ago has done meanwhile: a new current keyframe
+  //     (the next estimate is estimateOnPending(), SlamSystem.cpp:907-920) or new depth on the old one.
+  //   * Dropped: see MappingStep; the frame still counts towards sinceKF.
+  //   * Update / KeyframeChange by wantsKeyframe(), which is asked only for a frame tracked on the current keyframe.  A one-stream loop
+  //     takes `est` as the next estimate only with an Update: a keyframe change sets its own (install()).
+  template <class FinalisedAtLoss, class EstimateOnPending, class WantsKeyframe>
+  MappingStep tracked(bool pipelined, const std::shared_ptr<Frame>& trackedOn, Frame& frame, const SE3& est, bool diverged, bool trackingWasGood,
+                      int numEvaluations, FinalisedAtLoss&& finalisedAtLoss, EstimateOnPending&& estimateOnPending, WantsKeyframe&& wantsKeyframe) {
+    namespace rules = lsd_slam::loop;
+    numTracked++;
+    evaluations += numEvaluations;
+    if (trackingWasGood) numTrackedGood++;
+    newKeyframe = false;
+    if (rules::trackingLost(diverged, trackingWasGood, numKeyframesFinished)) {
+      trackingLost = true;
+      reference.invalidate();
+      if (map.isValid()) {
+        if (rules::finaliseOnLoss(mappedOnKF)) {
+          map.finalizeKeyFrame();
+          numKeyframesFinished++;
+          finalisedAtLoss();
+        }
+        map.invalidate();
+      }
+      return MappingStep::Lost;
+    }
+    if (pipelined) {
+      if (pendingKF) {
+        lastFrameToKF = estimateOnPending();
+        trackKF = pendingKF;
+        pendingKF.reset();
+        importReference(*trackKF);
+      } else {
+        lastFrameToKF = est;
+        importIfUpdated(*trackKF);
+      }
+    }
+    ++sinceKF;
+    const bool onCurrent = trackedOn == keyframe;
+    const MappingStep step = rules::mappingStep(false, onCurrent, onCurrent && wantsKeyframe());
+    if (step == MappingStep::Dropped) {
+      frame.clear_refPixelWasGood();
+      numDropped++;
+    } else if (step == MappingStep::Update) {
+      if (!pipelined) lastFrameToKF = est;
+    } else {
+      newKeyframe = true;
+    }
+    return step;
+  }
+  // updateKeyframe with `frame` has been queued
+  void mapped(Frame& frame) {
+    mappedOnKF++;
+    numUpdates++;
+    frame.clear_refPixelWasGood();
+  }
+  // `kf` is the mapper's current keyframe from now on.  A pipelined loop's tracker keeps the old keyframe for one more frame
+  // (tracked() adopts the new one); a one-stream loop tracks the next frame on it, from nextEstimate.
+  void install(const std::shared_ptr<Frame>& kf, bool pipelined, const SE3& nextEstimate) {
+    keyframe = kf;
+    mappedOnKF = 0;
+    sinceKF = 0;
+    if (pipelined) {
+      pendingKF = kf;
+    } else {
+      trackKF = kf;
+      importReference(*kf);
+      lastFrameToKF = nextEstimate;
+    }
+  }
+  // createNewCurrentKeyframe (SlamSystem.cpp:458-490): the tracked frame becomes the keyframe, the next frame starts at the identity.
+  // countFinished: the keyframe it replaces enters the graph here (a loop that banks its keyframes counts them there)
+  void promote(const std::shared_ptr<Frame>& frame, bool pipelined, bool keepLog, bool countFinished) {
+    if (countFinished) numKeyframesFinished++;
+    if (keepLog) keyframeLog.push_back(frame);
+    install(frame, pipelined, SE3());
+  }
+};
+
+class SlamLoop : public LoopSequence {
+ public:
+  // gtDepth0: see LoopSequence::start.
+  // kfEvery > 0: a new keyframe every kfEvery frames (deterministic; what bench.py and the parity tests use);
+  // kfEvery == 0: the reference's distance / usage score (SlamSystem.cpp:997-1015 with doSlam = false).  Only this loop has the score rule.
+  SlamLoop(int w, int h, const Mat3f& K, const unsigned char* firstImage, bool imagesOnDevice, const float* gtDepth0, int kfEvery)
+      : SlamLoop(w, h, K, nullptr, firstImage, imagesOnDevice, gtDepth0, kfEvery) {}
+  // Raw camera images: w, h, K are those of the RECTIFIED images (Undistorter::out_width / out_height / K), firstRawImage and every
+  // image given to step() are raw inputWidth x inputHeight images of the undistorter's camera, rectified inside frame creation.
+  SlamLoop(int w, int h, const Mat3f& K, std::shared_ptr<DeviceUndistorter> undistorter, const unsigned char* firstRawImage,
+           bool imagesOnDevice, const float* gtDepth0, int kfEvery)
+      : LoopSequence(w, h, K), tracker(w, h, K), cam_{w, h, K, imagesOnDevice, nullptr}, kfEvery_(kfEvery) {
+    cam_.setUndistorter(std::move(undistorter));
+    setLoopIterations(tracker);
+    start(cam_.frame(0, firstRawImage, false), gtDepth0);
     tracker.setEnqueueHook([this]() {
       // runs once the tracking job's launches are queued: the place for everything the device can do beside it
       flushDeferredMapping();
       if (!pendingNext_) return;
-      prefetched_ = makeFrame(frameId_ + 1, pendingNext_, true);
+      prefetched_ = cam_.frame(frameId_ + 1, pendingNext_, pipelined_);
       prefetchedSrc_ = pendingNext_;
     });
   }
+  // From the next step() on images are raw images of this camera (null: rectified w x h images again).  One camera serves all loops of
+  // a context; an image announced as nextImage stays what it was announced as.
+  void setUndistorter(std::shared_ptr<DeviceUndistorter> undistorter) { cam_.setUndistorter(std::move(undistorter)); }
+  const std::shared_ptr<DeviceUndistorter>& undistorter() const { return cam_.undistorter; }
 
- public:
   SlamLoop(const SlamLoop&) = delete;
   SlamLoop& operator=(const SlamLoop&) = delete;
   // Tracking beside mapping with the mapper one frame behind (see above).  Switch before the first step() call.
   void setPipelined(bool on) {
     if (frameId_ != 0) throw Error(LSDHIP_E_STATE, "SlamLoop::setPipelined: switch before the first frame");
-    Context::get(w_, h_, K_)->setPipeline(on);
+    cam_.context()->setPipeline(on);
     pipelined_ = on;
   }
   bool pipelined() const { return pipelined_; }
-  // Pipelined loops queue a frame's updateKeyframe only once the NEXT frame's tracking launches are queued (from the tracker's enqueue
+  // Only this loop defers ONE frame's update (SlamLoopBatch defers a whole step's mapping work), behind the deferMapping switch:
+  // pipelined loops queue a frame's updateKeyframe only once the NEXT frame's tracking launches are queued (from the tracker's enqueue
   // hook: between two tracking jobs the host queues nothing but the next job).  After the last step() of a batch this queues what is
   // still waiting.
   void flushDeferredMapping() {
@@ -896,11 +1047,6 @@ class SlamLoop {
     std::shared_ptr<Frame> frame = std::move(deferredMap_);
     deferredMap_.reset();
     runUpdate(frame);
-  }
-  // TrackableKeyFrameSearch::getRefFrameScore (GlobalMapping/TrackableKeyFrameSearch.h:75-79) with the default weights
-  // KFDistWeight = 4, KFUsageWeight = 3 (util/settings.cpp:77-78)
-  static float keyframeScore(float distanceSquared, float usage) {
-    return distanceSquared * 4.0f * 4.0f + (1 - usage) * (1 - usage) * 3.0f * 3.0f;
   }
   // called with the keyframe that has just been finalised (before the next one replaces it): output hook (PLY, messages)
   std::function<void(Frame&, DepthMap&)> onKeyframeFinished;
@@ -930,153 +1076,49 @@ class SlamLoop {
     frameId_++;
     std::shared_ptr<Frame> frame;
     if (prefetched_ && prefetchedSrc_ == image) frame = std::move(prefetched_);
-    else frame = makeFrame(frameId_, image);
+    else frame = cam_.frame(frameId_, image, false);
     prefetched_.reset();
     pendingNext_ = nextImage;
-    if (!pipelined_ && keyframe->depthHasBeenUpdatedFlag()) {
-      reference.importFrame(keyframe.get());
-      keyframe->clearDepthHasBeenUpdatedFlag();
-    }
+    if (!pipelined_) importIfUpdated(*trackKF);
     lsdhip_host_mark(1);
-    const std::shared_ptr<Frame> trackedOn = trackKF_;     // == keyframe unless the mapper is promoting a new one right now (pipelined)
-    SE3 est = tracker.trackFrame(&reference, frame.get(), lastFrameToKF_);
+    const std::shared_ptr<Frame> trackedOn = trackKF;      // == keyframe unless the mapper is promoting a new one right now (pipelined)
+    SE3 est = tracker.trackFrame(&reference, frame.get(), lastFrameToKF);
     lsdhip_host_mark(8);
     pendingNext_ = nullptr;
-    evaluations += tracker.numEvaluations;
     launches += tracker.numLaunches;
     for (int l = 0; l < LSDHIP_PYRAMID_LEVELS; l++) levelEvaluations[l] += tracker.levelEvaluations[l];
-    if (tracker.trackingWasGood) numTrackedGood++;
-    numTracked++;
     lastTrackEnd = std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
     onTrackEnd(lastTrackEnd);
-    // SlamSystem::trackFrame (SlamSystem.cpp:946-966): tracking is lost when the tracker diverged, or — once the initialisation
-    // phase is over (more than INITIALIZATION_PHASE_COUNT = 5 keyframes in the graph) — when trackingWasGood is false.  The
-    // frame is then neither mapped nor promoted; doMappingIteration's lost branch (:809-817) finalises the current keyframe if
-    // it has been mapped on at least MIN_NUM_MAPPED = 5 times, discards it otherwise, and invalidates the map.  What follows in
-    // the reference is the relocaliser (out of scope): the loop reports the loss.
-    if (tracker.diverged || (numKeyframesFinished_ > 5 /* INITIALIZATION_PHASE_COUNT */ && !tracker.trackingWasGood)) {
-      trackingLost = true;
-      reference.invalidate();
-      if (map.isValid()) {
-        if (mappedOnKF_ >= 5 /* MIN_NUM_MAPPED */) {
-          map.finalizeKeyFrame();
-          numKeyframesFinished_++;
+    flushDeferredMapping();      // (normally empty: the tracking job's hook has queued it)
+    // ---- this frame's mapping iteration (pipelined: queued on the mapping stream, it runs beside the next frame's tracking) ----------
+    const MappingStep next = tracked(
+        pipelined_, trackedOn, *frame, est, tracker.diverged, tracker.trackingWasGood, tracker.numEvaluations,
+        [&] {   // a keyframe finalised at the loss goes to the output hooks like any other (SlamLoopBatch feeds no sink there)
           if (onKeyframeFinished) onKeyframeFinished(*keyframe, map);
           if (onKeyframeFinishedAsync) onKeyframeFinishedAsync(*keyframe);
-        }   // else discardCurrentKeyframe (:428-456): nothing of it is kept
-        map.invalidate();
-      }
-      throw Error(LSDHIP_DIVERGED, std::string("SlamLoop: tracking lost at frame ") + std::to_string(frameId_) +
-                                       (tracker.diverged ? " (diverged)" : " (trackingWasGood false)"));
-    }
-    if (pipelined_) {
-      // What the tracking thread finds when it comes back for the next frame: the mapping iteration queued one frame ago has finished.
-      if (pendingKF_) {
-        // the mapper promoted pendingKF_ (createNewCurrentKeyframe) while this frame was being tracked on the old keyframe: the next
-        // frame is tracked on the new one, from se3FromSim3(newKeyframe^-1 * thisFrame) (SlamSystem.cpp:907-920)
-        double p[7];
-        if (pendingIsReactivated_) {
-          // a banked keyframe came back: it is neither this frame's tracking parent nor its parent's child, so the estimate is the
-          // general product over the host's world poses, this frame's being camToWorld(its keyframe) * sim3(frameToKeyframe, 1)
-          double f2k[8], frameToWorld[8];
-          est.to7(f2k); f2k[7] = 1;
-          lsd_slam::pose::sim3_mul(worldPose(*trackKF_).data(), f2k, frameToWorld);
-          lsd_slam::pose::relative_se3(worldPose(*pendingKF_).data(), frameToWorld, p);
-          pendingIsReactivated_ = false;
-        } else {
-          check(lsdhip_frame_relative_pose(pendingKF_->handle(), frame->handle(), p), "lsdhip_frame_relative_pose");
-        }
-        lastFrameToKF_ = SE3::from7(p);
-        trackKF_ = pendingKF_;
-        pendingKF_.reset();
-        reference.importFrame(trackKF_.get());
-        trackKF_->clearDepthHasBeenUpdatedFlag();
-      } else {
-        lastFrameToKF_ = est;
-        if (trackKF_->depthHasBeenUpdatedFlag()) {
-          reference.importFrame(trackKF_.get());
-          trackKF_->clearDepthHasBeenUpdatedFlag();
-        }
-      }
-    }
-    // ---- this frame's mapping iteration (pipelined: queued on the mapping stream, it runs beside the next frame's tracking) ----------
-    ++sinceKF_;
-    newKeyframe = false;
-    flushDeferredMapping();      // (normally empty: the tracking job's hook has queued it)
-    if (trackedOn != keyframe) {
-      // tracked on the keyframe the mapper has just replaced: SlamSystem::updateKeyframe pops such frames unmapped (:559-566)
-      frame->clear_refPixelWasGood();
-      numDropped++;
-      return est;
-    }
-    bool createNewKeyFrame = kfEvery_ > 0 && sinceKF_ >= kfEvery_;
-    // numMappedOnThisTotal of the current keyframe = updateKeyframe calls since it was created: counted here, so that the
-    // asynchronous pipeline is not drained every frame by Frame::stats()
-    if (kfEvery_ == 0 && mappedOnKF_ > 5 /* MIN_NUM_MAPPED */) {
-      // SlamSystem.cpp:997-1015: dist = translation * meanIdepth; keyframesAll is empty without the pose graph, so
-      // minVal = 0.2 * 0.7 (SURVEY.md §8(d) driver notes)
-      const float mi = keyframe->meanIdepth();
-      const float d0 = (float)est.t[0] * mi, d1 = (float)est.t[1] * mi, d2 = (float)est.t[2] * mi;
-      float minVal = 0.2f * 0.7f;
-      if (reactivateKeyframes) {
-        // with the keyframes kept, keyframesAll.size() is the bank's size (SlamSystem.cpp:1001-1003)
-        const int size = bank_->size();
-        minVal = std::fmin(0.2f + size * 0.8f / 5 /* INITIALIZATION_PHASE_COUNT */, 1.0f);
-        if (size < 5) minVal = (float)(minVal * 0.7);
-      }
-      createNewKeyFrame = keyframeScore(d0 * d0 + d1 * d1 + d2 * d2, tracker.pointUsage) > minVal;
-    }
-    if (createNewKeyFrame && reactivateKeyframes) {
-      changeKeyframeWithReactivation(frame, est);
-    } else if (createNewKeyFrame) {
-      numKeyframesFinished_++;
-      mappedOnKF_ = 0;
-      if (onKeyframeFinished || !sharedKeyframeChange) {
-        // an output hook reads the finalised map (PLY, keyframe messages, the multi-GPU gather): the two calls, the hook between them
-        map.finalizeKeyFrame();
-        if (onKeyframeFinished) onKeyframeFinished(*keyframe, map);
-        map.createKeyFrame(frame.get());
-      } else {
-        map.changeKeyframe(frame.get());
-      }
-      if (onKeyframeFinishedAsync) onKeyframeFinishedAsync(*keyframe);
-      keyframe = frame;
-      if (keepKeyframes) keyframeLog.push_back(frame);
-      liveQueue_.clear();
-      if (pipelined_) {
-        pendingKF_ = frame;        // the tracker keeps the old keyframe for one more frame
-      } else {
-        trackKF_ = frame;
-        reference.importFrame(keyframe.get());
-        keyframe->clearDepthHasBeenUpdatedFlag();
-        lastFrameToKF_ = SE3();
-      }
-      sinceKF_ = 0;
-      newKeyframe = true;
-      if (onMappingIteration) onMappingIteration(map);
-    } else if (pipelined_ && deferMapping) {
-      deferredMap_ = frame;       // queued from the next tracking job's enqueue hook (or flushDeferredMapping)
-    } else {
-      runUpdate(frame);
-      if (!pipelined_) lastFrameToKF_ = est;
+        },
+        [&] { return estimateOnPending(*frame, est); }, [&] { return wantsNewKeyframe(est); });
+    switch (next) {
+      case MappingStep::Lost:    // this loop reports the loss (SlamLoopBatch marks the sequence and goes on with the others)
+        throw Error(LSDHIP_DIVERGED, std::string("SlamLoop: tracking lost at frame ") + std::to_string(frameId_) +
+                                         (tracker.diverged ? " (diverged)" : " (trackingWasGood false)"));
+      case MappingStep::Dropped: break;
+      case MappingStep::KeyframeChange: changeKeyframe(frame, est); break;
+      case MappingStep::Update:
+        if (pipelined_ && deferMapping) deferredMap_ = frame;       // queued from the next tracking job's enqueue hook (or flushDeferredMapping)
+        else runUpdate(frame);
+        break;
     }
     return est;
   }
   SE3Tracker tracker;
-  DepthMap map;
-  TrackingReference reference;
-  std::shared_ptr<Frame> keyframe;                   // the mapper's current keyframe (DepthMap::activeKeyFrame)
-  bool newKeyframe = false;
-  bool trackingLost = false;                         // set before step() throws: SlamSystem::trackingIsGood == false
-  long evaluations = 0, launches = 0, numTracked = 0, numUpdates = 0, numTrackedGood = 0;
-  long numDropped = 0;                               // frames tracked on a keyframe the mapper had already replaced (pipelined): not mapped
+  long launches = 0;
   long levelEvaluations[LSDHIP_PYRAMID_LEVELS] = {0, 0, 0, 0, 0};
   double lastTrackEnd = 0;
   int liveQueueLength = 1;                           // frames handed to updateKeyframe per mapping iteration
   bool deferMapping = true;                          // pipelined loops: see flushDeferredMapping
   bool sharedKeyframeChange = true;                  // finalizeKeyFrame + createKeyFrame as DepthMap::changeKeyframe (six launches); false: the two calls
   bool keepKeyframes = false;                        // keep every keyframe alive in keyframeLog (validation: rescale factors)
-  std::vector<std::shared_ptr<Frame>> keyframeLog;
 
   // ---- re-activation of banked keyframes: the SLAMEnabled branches of SlamSystem::finishCurrentKeyframe (SlamSystem.cpp:395-426) and
   // SlamSystem::changeKeyframe(false, true, 1.0f) (:507-540).  Off by default: a loop that never calls enableReactivation runs none of it.
@@ -1092,8 +1134,8 @@ class SlamLoop {
   void enableReactivation(int maxKeyframes) {
     if (frameId_ != 0) throw Error(LSDHIP_E_STATE, "SlamLoop::enableReactivation: switch before the first frame");
     if (maxKeyframes <= 0) throw Error(LSDHIP_E_ARG, "SlamLoop::enableReactivation: a bank of at least one keyframe");
-    bank_.reset(new KeyFrameBank(Context::get(w_, h_, K_), maxKeyframes));
-    search_.reset(new TrackableKeyFrameSearch(bank_.get(), w_, h_, K_));
+    bank_.reset(new KeyFrameBank(cam_.context(), maxKeyframes));
+    search_.reset(new TrackableKeyFrameSearch(bank_.get(), cam_.w, cam_.h, cam_.K));
     bankedBySlot_.assign((size_t)maxKeyframes, nullptr);
     std::array<double, 8> I;
     lsd_slam::pose::sim3_identity(I.data());
@@ -1118,40 +1160,59 @@ class SlamLoop {
     const int rc = lsdhip_kfbank_put(bank_->handle(), kf->handle(), &slot);
     if (rc == LSDHIP_E_CAPACITY) {
       numUnbanked++;
-      numKeyframesFinished_++;       // (never banked, so never finished twice)
+      numKeyframesFinished++;        // (never banked, so never finished twice)
       return;
     }
     check(rc, "lsdhip_kfbank_put");
     kf->idxInKeyframes = slot;
-    const std::array<double, 8>& p = worldPose(*kf);
-    Sim3 camToWorld;
-    for (int i = 0; i < 4; i++) camToWorld.q[i] = p[i];
-    for (int i = 0; i < 3; i++) camToWorld.t[i] = p[4 + i];
-    camToWorld.s = p[7];
-    bank_->setMeta(slot, camToWorld, kf->meanIdepth());
+    bank_->setMeta(slot, Sim3::from8(worldPose(*kf).data()), kf->meanIdepth());
     bankedBySlot_[(size_t)slot] = kf;
-    if (firstTime) numKeyframesFinished_++;          // keyframesAll grows for idxInKeyframes < 0 only (SlamSystem.cpp:408-412)
+    if (firstTime) numKeyframesFinished++;           // keyframesAll grows for idxInKeyframes < 0 only (SlamSystem.cpp:408-412)
   }
-  // SlamSystem::doMappingIteration's keyframe change with doKFReActivation (SlamSystem.cpp:783-791): finishCurrentKeyframe, then
-  // changeKeyframe(false, true, 1.0f) — a banked keyframe comes back (loadNewCurrentKeyframe, :491-505) or `frame` is promoted
-  void changeKeyframeWithReactivation(const std::shared_ptr<Frame>& frame, const SE3& est) {
-    // the candidate's getScaledCamToWorld(): camToWorld(current keyframe) * sim3(frameToKeyframe, 1)
-    double f2k[8], cw[8];
+  // pipelined: the next estimate on the keyframe the mapper has made current while `frame` was tracked on the old one
+  SE3 estimateOnPending(Frame& frame, const SE3& est) {
+    if (!pendingIsReactivated_) return relativePose(*pendingKF, frame);
+    // a banked keyframe came back: it is neither this frame's tracking parent nor its parent's child, so the estimate is the
+    // general product over the host's world poses, this frame's being camToWorld(its keyframe) * sim3(frameToKeyframe, 1)
+    double f2k[8], frameToWorld[8], p[7];
     est.to7(f2k); f2k[7] = 1;
-    lsd_slam::pose::sim3_mul(worldPose(*keyframe).data(), f2k, cw);
-    Sim3 candidateCamToWorld;
-    for (int i = 0; i < 4; i++) candidateCamToWorld.q[i] = cw[i];
-    for (int i = 0; i < 3; i++) candidateCamToWorld.t[i] = cw[4 + i];
-    candidateCamToWorld.s = cw[7];
-    // The reference searches after finishCurrentKeyframe.  The search reads the bank entries of EARLIER keyframes only — the current
-    // keyframe is the candidate's tracking parent and is skipped (TrackableKeyFrameSearch.cpp:118) — so it may run before the current
-    // keyframe is finalised and banked, and finalizeKeyFrame can then share its launches with the change that the search decides.
-    const int slot = search_->findRePositionCandidate(frame.get(), candidateCamToWorld, keyframe->id(), 1.0f);
-    const std::shared_ptr<Frame> found = slot >= 0 ? bankedBySlot_[(size_t)slot] : nullptr;
-    if (slot >= 0 && !found) throw Error(LSDHIP_E_STATE, "SlamLoop: the search returned a slot this loop did not fill");
+    lsd_slam::pose::sim3_mul(worldPose(*trackKF).data(), f2k, frameToWorld);
+    lsd_slam::pose::relative_se3(worldPose(*pendingKF).data(), frameToWorld, p);
+    pendingIsReactivated_ = false;
+    return SE3::from7(p);
+  }
+  // the keyframe policy for a frame tracked on the current keyframe (lsd_slam_hip_loop.hpp)
+  bool wantsNewKeyframe(const SE3& est) {
+    namespace rules = lsd_slam::loop;
+    if (kfEvery_ != 0) return rules::wantsNewKeyframe(kfEvery_, sinceKF);
+    if (!rules::scoreRuleApplies(mappedOnKF)) return false;
+    // SlamSystem.cpp:997-1015: dist = translation * meanIdepth; keyframesAll holds what the bank holds (:1001-1003), nothing without one
+    const float mi = keyframe->meanIdepth();
+    const float d0 = (float)est.t[0] * mi, d1 = (float)est.t[1] * mi, d2 = (float)est.t[2] * mi;
+    const float minVal = reactivateKeyframes ? rules::scoreThreshold(bank_->size()) : rules::scoreThreshold();
+    return rules::wantsNewKeyframe(mappedOnKF, rules::keyframeScore(d0 * d0 + d1 * d1 + d2 * d2, tracker.pointUsage), minVal);
+  }
+  // SlamSystem::doMappingIteration's keyframe change (SlamSystem.cpp:783-791): finishCurrentKeyframe, then `frame` is promoted
+  // (createNewCurrentKeyframe) — or, with re-activation on (doKFReActivation), changeKeyframe(false, true, 1.0f) first looks for a
+  // banked keyframe to come back (loadNewCurrentKeyframe, :491-505)
+  void changeKeyframe(const std::shared_ptr<Frame>& frame, const SE3& est) {
     const std::shared_ptr<Frame> finished = keyframe;
-    mappedOnKF_ = 0;
+    std::shared_ptr<Frame> found;
+    double cw[8];
+    if (reactivateKeyframes) {
+      // the candidate's getScaledCamToWorld(): camToWorld(current keyframe) * sim3(frameToKeyframe, 1)
+      double f2k[8];
+      est.to7(f2k); f2k[7] = 1;
+      lsd_slam::pose::sim3_mul(worldPose(*keyframe).data(), f2k, cw);
+      // The reference searches after finishCurrentKeyframe.  The search reads the bank entries of EARLIER keyframes only — the current
+      // keyframe is the candidate's tracking parent and is skipped (TrackableKeyFrameSearch.cpp:118) — so it may run before the current
+      // keyframe is finalised and banked, and finalizeKeyFrame can then share its launches with the change that the search decides.
+      const int slot = search_->findRePositionCandidate(frame.get(), Sim3::from8(cw), keyframe->id(), 1.0f);
+      if (slot >= 0) found = bankedBySlot_[(size_t)slot];
+      if (slot >= 0 && !found) throw Error(LSDHIP_E_STATE, "SlamLoop: the search returned a slot this loop did not fill");
+    }
     if (onKeyframeFinished || !sharedKeyframeChange) {
+      // an output hook reads the finalised map (PLY, keyframe messages, the multi-GPU gather): the two calls, the hook between them
       map.finalizeKeyFrame();
       if (onKeyframeFinished) onKeyframeFinished(*finished, map);
       if (found) map.setFromExistingKF(found.get());
@@ -1162,40 +1223,34 @@ class SlamLoop {
       map.changeKeyframe(frame.get());
     }
     // (the put reads the planes the finalise pass and the pyramid launch wrote: queued behind them)
-    bankFinishedKeyframe(finished);
+    if (reactivateKeyframes) bankFinishedKeyframe(finished);
     if (onKeyframeFinishedAsync) onKeyframeFinishedAsync(*finished);
-    const lsdhip_reposition_result& r = search_->last;
-    keyframeChanges.push_back(KeyframeChange{frame->id(), finished->id(), found ? found->id() : frame->id(), found != nullptr,
-                                             r.numPotential, r.numChecked, r.numTracked});
-    double nextEstimate[7] = {1, 0, 0, 0, 0, 0, 0};
+    if (reactivateKeyframes) {
+      const lsdhip_reposition_result& r = search_->last;
+      keyframeChanges.push_back(KeyframeChange{frame->id(), finished->id(), found ? found->id() : frame->id(), found != nullptr,
+                                               r.numPotential, r.numChecked, r.numTracked});
+    }
     if (found) {
       numReactivations++;
-      keyframe = found;
-      keyframe->clearDepthHasBeenUpdatedFlag();      // loadNewCurrentKeyframe (SlamSystem.cpp:503)
+      found->clearDepthHasBeenUpdatedFlag();         // loadNewCurrentKeyframe (SlamSystem.cpp:503)
       // the next frame starts from se3FromSim3(camToWorld(keyframe)^-1 * camToWorld(lastTrackedFrame)) (SlamSystem.cpp:922-925)
-      lsd_slam::pose::relative_se3(worldPose(*keyframe).data(), cw, nextEstimate);
+      double nextEstimate[7];
+      lsd_slam::pose::relative_se3(worldPose(*found).data(), cw, nextEstimate);
+      install(found, pipelined_, SE3::from7(nextEstimate));
     } else {
-      // camToWorld(new keyframe) = camToWorld(parent) * thisToParent_raw, the scale createKeyFrame gave it included (waits for it once)
-      double raw[8];
-      check(lsdhip_frame_get_pose(frame->handle(), raw), "lsdhip_frame_get_pose");
-      std::array<double, 8> w;
-      lsd_slam::pose::sim3_mul(worldPose(*finished).data(), raw, w.data());
-      worldPoses_[frame->id()] = w;
-      keyframe = frame;
-      if (keepKeyframes) keyframeLog.push_back(frame);
+      if (reactivateKeyframes) {
+        // camToWorld(new keyframe) = camToWorld(parent) * thisToParent_raw, the scale createKeyFrame gave it included (waits for it once)
+        double raw[8];
+        check(lsdhip_frame_get_pose(frame->handle(), raw), "lsdhip_frame_get_pose");
+        std::array<double, 8> w;
+        lsd_slam::pose::sim3_mul(worldPose(*finished).data(), raw, w.data());
+        worldPoses_[frame->id()] = w;
+      }
+      // with re-activation on, numKeyframesFinished grows in bankFinishedKeyframe: for a keyframe banked for the first time or refused
+      promote(frame, pipelined_, keepKeyframes, !reactivateKeyframes);
     }
+    pendingIsReactivated_ = pipelined_ && found;
     liveQueue_.clear();
-    if (pipelined_) {
-      pendingKF_ = keyframe;         // the tracker keeps the old keyframe for one more frame
-      pendingIsReactivated_ = found != nullptr;
-    } else {
-      trackKF_ = keyframe;
-      reference.importFrame(keyframe.get());
-      keyframe->clearDepthHasBeenUpdatedFlag();
-      lastFrameToKF_ = SE3::from7(nextEstimate);
-    }
-    sinceKF_ = 0;
-    newKeyframe = true;
     if (onMappingIteration) onMappingIteration(map);
   }
   std::unique_ptr<KeyFrameBank> bank_;
@@ -1203,7 +1258,7 @@ class SlamLoop {
   std::vector<std::shared_ptr<Frame>> bankedBySlot_;           // every banked keyframe stays alive: its re-activation planes, level-0 image
                                                                // and maxGradients are needed when it comes back
   std::map<int, std::array<double, 8>> worldPoses_;            // camToWorld per keyframe id
-  bool pendingIsReactivated_ = false;                          // pipelined: pendingKF_ is a banked keyframe that came back
+  bool pendingIsReactivated_ = false;                          // pipelined: pendingKF is a banked keyframe that came back
   // DepthMap::updateKeyframe for one tracked frame (SlamSystem::updateKeyframe, SlamSystem.cpp:542-614)
   void runUpdate(const std::shared_ptr<Frame>& frame) {
     // blockUntilMapped = true: the unmapped queue holds exactly this frame (SlamSystem.cpp:559-571, :1030-1039).
@@ -1215,36 +1270,14 @@ class SlamLoop {
     lsdhip_host_mark(9);
     map.updateKeyframe(q);
     lsdhip_host_mark(13);
-    mappedOnKF_++;
-    frame->clear_refPixelWasGood();
-    numUpdates++;
+    mapped(*frame);
     lsdhip_host_mark(14);
     if (onMappingIteration) onMappingIteration(map);
   }
   std::shared_ptr<Frame> deferredMap_;
-  std::shared_ptr<Frame> makeFrame(int id, const unsigned char* img, bool mayDefer = false) {
-    if (undistorter_) {     // raw images: the same three forms
-      if (onDevice_) return std::make_shared<Frame>(id, *undistorter_, 0.0, Frame::RawDeviceImage{img});
-      if (mayDefer && pipelined_) return std::make_shared<Frame>(id, *undistorter_, 0.0, Frame::RawHostImageAsync{img});
-      return std::make_shared<Frame>(id, *undistorter_, 0.0, Frame::RawImage{img});
-    }
-    if (onDevice_) return std::make_shared<Frame>(id, w_, h_, K_, 0.0, Frame::DeviceImage{img});
-    // a prefetched host image on a pipelined context: the copy is queued on the mapping stream and nothing waits for it (the caller
-    // keeps the bytes unchanged until the frame has been tracked: step()'s nextImage contract)
-    if (mayDefer && pipelined_) return std::make_shared<Frame>(id, w_, h_, K_, 0.0, Frame::HostImageAsync{img});
-    return std::make_shared<Frame>(id, w_, h_, K_, 0.0, img);
-  }
-  int w_, h_;
-  Mat3f K_;
-  bool onDevice_;
-  std::shared_ptr<DeviceUndistorter> undistorter_;   // set: images are raw images of this camera
+  LoopCamera cam_;
   bool pipelined_ = false;
-  int kfEvery_, sinceKF_ = 0, frameId_ = 0;
-  int mappedOnKF_ = 0;            // Frame::numMappedOnThisTotal of the current keyframe
-  int numKeyframesFinished_ = 0;  // keyFrameGraph->keyframesAll.size()
-  SE3 lastFrameToKF_;
-  std::shared_ptr<Frame> trackKF_;     // the keyframe the tracker's reference points at
-  std::shared_ptr<Frame> pendingKF_;   // pipelined: promoted by the mapping iteration queued last, not yet adopted by the tracker
+  int kfEvery_, frameId_ = 0;
   std::shared_ptr<Frame> prefetched_;
   const unsigned char* prefetchedSrc_ = nullptr;
   const unsigned char* pendingNext_ = nullptr;
@@ -1257,78 +1290,38 @@ class SlamLoop {
 // (SE3Tracker::trackFrameBatch: throughput mode from 8 jobs on), the updateKeyframe calls (DepthMap::updateKeyframeBatch).  Keyframe
 // changes (finalize + createKeyFrame, once every kfEvery frames per sequence) stay per-sequence calls.  A sequence whose tracking is
 // lost stops taking part (lost(s) == true, SlamLoop's rules); the others go on.
+// Unlike SlamLoop it has the fixed keyframe interval only (kfEvery > 0: no score rule), no re-activation, and no output hooks: a
+// sequence's finalised keyframes go to its cloud sink.
 class SlamLoopBatch {
  public:
-  struct Sequence {
-    Sequence(int w, int h, const Mat3f& K) : map(w, h, K) {}
-    DepthMap map;
-    TrackingReference reference;
-    std::shared_ptr<Frame> keyframe;       // the mapper's current keyframe
-    std::shared_ptr<Frame> trackKF;        // the keyframe the tracking reference points at (== keyframe unless a promotion is pending)
-    std::shared_ptr<Frame> pendingKF;      // pipelined: promoted by the mapping iteration queued last, not yet adopted by the tracker
-    SE3 lastFrameToKF;
-    int sinceKF = 0, mappedOnKF = 0, numKeyframesFinished = 0;
-    long numTracked = 0, numTrackedGood = 0, numUpdates = 0, evaluations = 0, numDropped = 0;
-    bool trackingLost = false, newKeyframe = false;
+  struct Sequence : LoopSequence {
+    using LoopSequence::LoopSequence;
     lsdhip_track_result last = lsdhip_track_result();
-    std::vector<std::shared_ptr<Frame>> keyframeLog;   // every keyframe this sequence promoted (SlamLoopBatch::keepKeyframes)
-    std::shared_ptr<Frame> replacedFirst;              // ... and the keyframe its first keyframe change replaced while keepKeyframes was on (not in the log: it was never promoted)
+    std::shared_ptr<Frame> replacedFirst;              // the keyframe its first keyframe change replaced while keepKeyframes was on (not in the log: it was never promoted)
   };
   // firstImages / gtDepth0: S pointers each (gtDepth0 == null or gtDepth0[s] == null: random initialisation of that sequence)
   SlamLoopBatch(int w, int h, const Mat3f& K, int S, const unsigned char* const* firstImages, bool imagesOnDevice,
                 const float* const* gtDepth0, int kfEvery)
-      : tracker(w, h, K), w_(w), h_(h), K_(K), onDevice_(imagesOnDevice), kfEvery_(kfEvery) {
-    init(S, firstImages, gtDepth0);
-  }
+      : SlamLoopBatch(w, h, K, nullptr, S, firstImages, imagesOnDevice, gtDepth0, kfEvery) {}
   // Raw camera images of one camera for all sequences: w, h, K are those of the RECTIFIED images, firstRawImages and every image given
   // to step() are raw inputWidth x inputHeight images, rectified inside frame creation (SlamLoop's raw-image constructor).
   SlamLoopBatch(int w, int h, const Mat3f& K, std::shared_ptr<DeviceUndistorter> undistorter, int S, const unsigned char* const* firstRawImages,
                 bool imagesOnDevice, const float* const* gtDepth0, int kfEvery)
-      : tracker(w, h, K), w_(w), h_(h), K_(K), onDevice_(imagesOnDevice), kfEvery_(kfEvery) {
-    setUndistorter(std::move(undistorter));
-    init(S, firstRawImages, gtDepth0);
+      : tracker(w, h, K), cam_{w, h, K, imagesOnDevice, nullptr}, kfEvery_(kfEvery) {
+    cam_.setUndistorter(std::move(undistorter));
+    if (S <= 0 || kfEvery <= 0) throw Error(LSDHIP_E_ARG, "SlamLoopBatch: S > 0 sequences, a fixed keyframe interval > 0");
+    setLoopIterations(tracker);
+    tracker.setBatchCoarseMinJobs(coarseMinJobs(false));
+    std::vector<std::shared_ptr<Frame>> first = cam_.frames(std::vector<int>((size_t)S, idOf(0, 0)), firstRawImages);
+    for (int s = 0; s < S; s++) {
+      seqs_.emplace_back(new Sequence(w, h, K));
+      seqs_.back()->start(first[s], gtDepth0 ? gtDepth0[s] : nullptr);
+    }
   }
   // From the next step() on images are raw images of this camera (null: rectified w x h images again); images announced as nextImages
   // stay what they were announced as.
-  void setUndistorter(std::shared_ptr<DeviceUndistorter> undistorter) {
-    if (undistorter && undistorter->context() != Context::get(w_, h_, K_))
-      throw Error(LSDHIP_E_ARG, "SlamLoopBatch::setUndistorter: the undistorter belongs to another output size / K");
-    undistorter_ = std::move(undistorter);
-  }
+  void setUndistorter(std::shared_ptr<DeviceUndistorter> undistorter) { cam_.setUndistorter(std::move(undistorter)); }
 
- private:
-  void init(int S, const unsigned char* const* firstImages, const float* const* gtDepth0) {
-    const int w = w_, h = h_, kfEvery = kfEvery_;
-    const Mat3f& K = K_;
-    if (S <= 0 || kfEvery <= 0) throw Error(LSDHIP_E_ARG, "SlamLoopBatch: S > 0 sequences, a fixed keyframe interval > 0");
-    const int its[LSDHIP_PYRAMID_LEVELS] = {5, 20, 50, 100, 0};
-    std::memcpy(tracker.settings.maxItsPerLvl, its, sizeof(its));
-    tracker.setBatchCoarseMinJobs(coarseMinJobs(false));
-    std::vector<int> ids((size_t)S);
-    for (int s = 0; s < S; s++) ids[s] = idOf(s, 0);
-    std::vector<std::shared_ptr<Frame>> first = createFrames(ids, firstImages);
-    for (int s = 0; s < S; s++) {
-      seqs_.emplace_back(new Sequence(w, h, K));
-      Sequence& q = *seqs_.back();
-      q.keyframe = first[s];
-      if (gtDepth0 && gtDepth0[s]) {
-        q.keyframe->setDepthFromGroundTruth(gtDepth0[s]);
-        q.map.initializeFromGTDepth(q.keyframe.get());
-      } else {
-        q.map.initializeRandomly(q.keyframe.get());
-      }
-      q.reference.importFrame(q.keyframe.get());
-      q.keyframe->clearDepthHasBeenUpdatedFlag();
-      q.trackKF = q.keyframe;
-    }
-  }
-  // rectified images, or raw ones through the undistorter
-  std::vector<std::shared_ptr<Frame>> createFrames(const std::vector<int>& ids, const unsigned char* const* images) {
-    if (undistorter_) return Frame::createBatch(*undistorter_, ids, images, onDevice_);
-    return Frame::createBatch(w_, h_, K_, ids, images, onDevice_);
-  }
-
- public:
   // Sequences started together change keyframe in the same step; real cameras do not.  phase[s] in [0, kfEvery): sequence s behaves as
   // if its current keyframe were already phase[s] frames old (its first keyframe change comes kfEvery - phase[s] frames in).  Call before
   // the first step().
@@ -1344,7 +1337,6 @@ class SlamLoopBatch {
   // frame ids count per sequence, as in S separate SlamLoops (an id is only compared with ids of the same sequence: tracking parent,
   // nextStereoFrameMinID — which is a float, DepthMapPixelHypothesis.h:49: ids beyond 2^24 would round)
   static int idOf(int /*s*/, int t) { return t; }
-  // one frame of every sequence that is still tracking (images[s] is ignored for lost ones); returns frameToKeyframe per sequence
   // Tracking beside mapping for ALL sequences (the context becomes a pipelined one): per sequence exactly SlamLoop::setPipelined — the
   // mapper one frame behind the tracker, frames tracked on a keyframe the mapper has meanwhile replaced are dropped
   // (SlamSystem.cpp:559-566), the first frame on a new keyframe starts from se3FromSim3(newKeyframe^-1 * lastTrackedFrame) (:913-920).
@@ -1360,7 +1352,7 @@ class SlamLoopBatch {
   }
   void setPipelined(bool on) {
     if (frameId_ != 0) throw Error(LSDHIP_E_STATE, "SlamLoopBatch::setPipelined: switch before the first step");
-    Context::get(w_, h_, K_)->setPipeline(on);
+    cam_.context()->setPipeline(on);
     pipelined_ = on;
     tracker.setBatchCoarseMinJobs(coarseMinJobs(on));
     for (auto& q : seqs_) { q->trackKF = q->keyframe; q->pendingKF.reset(); }
@@ -1368,97 +1360,28 @@ class SlamLoopBatch {
       // the tracking batch's launches are queued: now the mapping work of the previous step, then the next step's frames
       flush();
       if (!pendingNext_) return;
-      std::vector<int> all;
-      for (int s = 0; s < size(); s++) all.push_back(s);
-      prefetched_ = makeFrames(all, pendingNext_, frameId_ + 1);
+      prefetched_ = makeFrames(pendingNext_, frameId_ + 1);
       prefetchedId_ = frameId_ + 1;
     });
     else tracker.setEnqueueHook(nullptr);
   }
   bool pipelined() const { return pipelined_; }
+  // one frame of every sequence that is still tracking (images[s] is ignored for lost ones); returns frameToKeyframe per sequence.
   // nextImages (optional, pipelined loops): the images of the following step() call — their upload / pyramids are queued on the mapping
   // stream AHEAD of this step's mapping work, so that the next tracking batch does not wait behind it
   std::vector<SE3> step(const unsigned char* const* images, const unsigned char* const* nextImages = nullptr) {
     frameId_++;
-    const int S = size();
-    std::vector<SE3> out((size_t)S);
-    std::vector<int> all;
-    for (int s = 0; s < S; s++) all.push_back(s);
-    std::vector<std::shared_ptr<Frame>> groupFrames;
-    if (prefetchedId_ == frameId_ && (int)prefetched_.size() == S) groupFrames = std::move(prefetched_);
-    else groupFrames = makeFrames(all, images, frameId_);
+    std::vector<std::shared_ptr<Frame>> frames;
+    if (prefetchedId_ == frameId_ && (int)prefetched_.size() == size()) frames = std::move(prefetched_);
+    else frames = makeFrames(images, frameId_);
     prefetched_.clear();
     prefetchedId_ = -1;
-    if (!pipelined_) {
-      MapWork w = trackGroup(all, groupFrames, out);
-      mapGroup(w);
-      return out;
-    }
-    // ---- pipelined: track, adopt what the mapper did one step ago, then queue [next frames, this step's mapping] ----------------------
-    std::vector<int> alive;
-    std::vector<std::shared_ptr<Frame>> frames, trackedOn;
-    std::vector<TrackingReference*> refs;
-    std::vector<Frame*> frs;
-    std::vector<SE3> inits;
-    for (int s = 0; s < S; s++) {
-      Sequence& q = *seqs_[s];
-      if (q.trackingLost || !groupFrames[s]) continue;
-      alive.push_back(s); frames.push_back(groupFrames[s]); trackedOn.push_back(q.trackKF);
-      refs.push_back(&q.reference); frs.push_back(groupFrames[s].get()); inits.push_back(q.lastFrameToKF);
-    }
-    MapWork work;
-    pendingNext_ = nextImages;
-    if (alive.empty()) { flush(); pendingNext_ = nullptr; }
-    if (!alive.empty()) {
-      std::vector<lsdhip_track_result> res;
-      std::vector<SE3> est = tracker.trackFrameBatch(refs, frs, inits, res);    // (the enqueue hook queues the previous step's mapping and the next frames)
-      pendingNext_ = nullptr;
-      for (size_t k = 0; k < alive.size(); k++) {
-        Sequence& q = *seqs_[alive[k]];
-        q.last = res[k];
-        q.numTracked++;
-        q.evaluations += res[k].numEvaluations;
-        if (res[k].trackingWasGood) q.numTrackedGood++;
-        out[alive[k]] = est[k];
-        q.newKeyframe = false;
-        if (res[k].diverged || (q.numKeyframesFinished > 5 /* INITIALIZATION_PHASE_COUNT */ && !res[k].trackingWasGood)) {
-          q.trackingLost = true;
-          q.reference.invalidate();
-          if (q.map.isValid()) {
-            if (q.mappedOnKF >= 5 /* MIN_NUM_MAPPED */) { q.map.finalizeKeyFrame(); q.numKeyframesFinished++; }
-            q.map.invalidate();
-          }
-          continue;
-        }
-        if (q.pendingKF) {
-          // the mapper promoted pendingKF while this frame was being tracked on the old keyframe (SlamSystem.cpp:907-920)
-          double p[7];
-          check(lsdhip_frame_relative_pose(q.pendingKF->handle(), frames[k]->handle(), p), "lsdhip_frame_relative_pose");
-          q.lastFrameToKF = SE3::from7(p);
-          q.trackKF = q.pendingKF;
-          q.pendingKF.reset();
-          q.reference.importFrame(q.trackKF.get());
-          q.trackKF->clearDepthHasBeenUpdatedFlag();
-        } else {
-          q.lastFrameToKF = est[k];
-          if (q.trackKF->depthHasBeenUpdatedFlag()) {
-            q.reference.importFrame(q.trackKF.get());
-            q.trackKF->clearDepthHasBeenUpdatedFlag();
-          }
-        }
-        ++q.sinceKF;
-        if (trackedOn[k] != q.keyframe) {        // tracked on the keyframe the mapper has just replaced: popped unmapped (:559-566)
-          frames[k]->clear_refPixelWasGood();
-          q.numDropped++;
-          continue;
-        }
-        if (q.sinceKF >= kfEvery_) { work.kfChange.emplace_back(alive[k], frames[k]); q.newKeyframe = true; }
-        else { work.updMaps.push_back(&q.map); work.updFrames.push_back(frames[k]); work.updSeq.push_back(alive[k]); }
-      }
-    }
-    // queued from the NEXT tracking batch's enqueue hook (or flush()): the host's enqueueing of ~10^2 launches then lies under that
-    // batch, and so does the device work
-    deferred_ = std::move(work);
+    std::vector<SE3> out((size_t)size());
+    MapWork work = track(frames, out, nextImages);
+    // One stream: the step's mapping iterations follow its tracking batch.  Pipelined: they are queued from the NEXT tracking batch's
+    // enqueue hook (or flush()): the host's enqueueing of ~10^2 launches then lies under that batch, and so does the device work
+    if (pipelined_) deferred_ = std::move(work);
+    else mapGroup(work);
     return out;
   }
   // queues the mapping work the last step left (a pipelined loop keeps it back for the next tracking batch's enqueue hook); call after the
@@ -1487,68 +1410,52 @@ class SlamLoopBatch {
     std::vector<int> updSeq;
     std::vector<std::pair<int, std::shared_ptr<Frame>>> kfChange;   // (sequence, its new keyframe)
   };
-  // new frames of the sequences in `group` that are still tracking (null entries for lost ones)
-  std::vector<std::shared_ptr<Frame>> makeFrames(const std::vector<int>& group, const unsigned char* const* images, int frameId) {
+  // new frames of the sequences that are still tracking (null entries for lost ones)
+  std::vector<std::shared_ptr<Frame>> makeFrames(const unsigned char* const* images, int frameId) {
     std::vector<int> ids;
     std::vector<const unsigned char*> imgs;
-    for (int s : group) if (!seqs_[s]->trackingLost) { ids.push_back(idOf(s, frameId)); imgs.push_back(images[s]); }
-    std::vector<std::shared_ptr<Frame>> out(group.size());
+    for (int s = 0; s < size(); s++) if (!seqs_[s]->trackingLost) { ids.push_back(idOf(s, frameId)); imgs.push_back(images[s]); }
+    std::vector<std::shared_ptr<Frame>> out((size_t)size());
     if (ids.empty()) return out;
-    std::vector<std::shared_ptr<Frame>> made = createFrames(ids, imgs.data());
+    std::vector<std::shared_ptr<Frame>> made = cam_.frames(ids, imgs.data());
     size_t k = 0;
-    for (size_t i = 0; i < group.size(); i++) if (!seqs_[group[i]]->trackingLost) out[i] = made[k++];
+    for (int s = 0; s < size(); s++) if (!seqs_[s]->trackingLost) out[(size_t)s] = made[k++];
     return out;
   }
-  // SlamSystem::trackFrame for every sequence of the group in shared launches + the decisions of doMappingIteration; the device work
-  // of the mapping iterations is returned, not queued
-  MapWork trackGroup(const std::vector<int>& group, const std::vector<std::shared_ptr<Frame>>& groupFrames, std::vector<SE3>& out) {
+  // SlamSystem::trackFrame for every sequence still tracking in shared launches + the decisions of doMappingIteration; the device work
+  // of the mapping iterations is returned, not queued.  The two execution models differ per sequence only in LoopSequence::tracked
+  // (import before tracking against adoption after it), and in when the caller queues the returned work.
+  MapWork track(const std::vector<std::shared_ptr<Frame>>& groupFrames, std::vector<SE3>& out, const unsigned char* const* nextImages) {
     MapWork work;
     std::vector<int> alive;
-    std::vector<std::shared_ptr<Frame>> frames;
-    for (size_t i = 0; i < group.size(); i++) if (!seqs_[group[i]]->trackingLost && groupFrames[i]) { alive.push_back(group[i]); frames.push_back(groupFrames[i]); }
-    if (alive.empty()) return work;
+    std::vector<std::shared_ptr<Frame>> frames, trackedOn;
     std::vector<TrackingReference*> refs;
     std::vector<Frame*> frs;
     std::vector<SE3> inits;
-    for (size_t k = 0; k < alive.size(); k++) {
-      Sequence& q = *seqs_[alive[k]];
-      if (q.keyframe->depthHasBeenUpdatedFlag()) {        // the tracking thread's import (SlamSystem.cpp:907-912)
-        q.reference.importFrame(q.keyframe.get());
-        q.keyframe->clearDepthHasBeenUpdatedFlag();
-      }
-      refs.push_back(&q.reference);
-      frs.push_back(frames[k].get());
-      inits.push_back(q.lastFrameToKF);
+    for (int s = 0; s < size(); s++) {
+      Sequence& q = *seqs_[s];
+      if (q.trackingLost || !groupFrames[s]) continue;
+      if (!pipelined_) q.importIfUpdated(*q.trackKF);
+      alive.push_back(s); frames.push_back(groupFrames[s]); trackedOn.push_back(q.trackKF);
+      refs.push_back(&q.reference); frs.push_back(groupFrames[s].get()); inits.push_back(q.lastFrameToKF);
     }
+    if (alive.empty()) { flush(); return work; }
+    pendingNext_ = nextImages;
     std::vector<lsdhip_track_result> res;
-    std::vector<SE3> est = tracker.trackFrameBatch(refs, frs, inits, res);
+    std::vector<SE3> est = tracker.trackFrameBatch(refs, frs, inits, res);    // (pipelined: the enqueue hook queues the previous step's mapping and the next frames)
+    pendingNext_ = nullptr;
     for (size_t k = 0; k < alive.size(); k++) {
       Sequence& q = *seqs_[alive[k]];
       q.last = res[k];
-      q.numTracked++;
-      q.evaluations += res[k].numEvaluations;
-      if (res[k].trackingWasGood) q.numTrackedGood++;
       out[alive[k]] = est[k];
-      q.newKeyframe = false;
-      if (res[k].diverged || (q.numKeyframesFinished > 5 /* INITIALIZATION_PHASE_COUNT */ && !res[k].trackingWasGood)) {
-        // SlamSystem::trackFrame's lost branch (:946-966) and doMappingIteration's (:809-817), as in SlamLoop::step
-        q.trackingLost = true;
-        q.reference.invalidate();
-        if (q.map.isValid()) {
-          if (q.mappedOnKF >= 5 /* MIN_NUM_MAPPED */) { q.map.finalizeKeyFrame(); q.numKeyframesFinished++; }
-          q.map.invalidate();
-        }
-        continue;
-      }
-      ++q.sinceKF;
-      if (q.sinceKF >= kfEvery_) {
+      // a lost sequence is marked and feeds no sink, the others go on (SlamLoop reports the loss and calls its output hooks)
+      const LoopSequence::MappingStep next = q.tracked(
+          pipelined_, trackedOn[k], *frames[k], est[k], res[k].diverged != 0, res[k].trackingWasGood != 0, res[k].numEvaluations, [] {},
+          [&] { return LoopSequence::relativePose(*q.pendingKF, *frames[k]); }, [&] { return lsd_slam::loop::wantsNewKeyframe(kfEvery_, q.sinceKF); });
+      if (next == LoopSequence::MappingStep::KeyframeChange) {
         work.kfChange.emplace_back(alive[k], frames[k]);
-        q.newKeyframe = true;
-      } else {
-        work.updMaps.push_back(&q.map);
-        work.updFrames.push_back(frames[k]);
-        work.updSeq.push_back(alive[k]);
-        q.lastFrameToKF = est[k];
+      } else if (next == LoopSequence::MappingStep::Update) {
+        work.updMaps.push_back(&q.map); work.updFrames.push_back(frames[k]); work.updSeq.push_back(alive[k]);
       }
     }
     return work;
@@ -1558,7 +1465,7 @@ class SlamLoopBatch {
   // one-stream context dealt to `keyframeLanes` streams, and queued AFTER the shared launches so that the host's enqueueing lies under them
   void mapGroup(MapWork& work) {
     if (work.updMaps.empty() && work.kfChange.empty()) return;
-    std::shared_ptr<Context> ctx = Context::get(w_, h_, K_);
+    std::shared_ptr<Context> ctx = cam_.context();
     const int nkf = (int)work.kfChange.size();
     const int lanes = !sharedKeyframeChange && keyframeLanes > 1 && nkf > 0 ? (keyframeLanes < nkf ? keyframeLanes : nkf) : 0;
     // (closed by the destructor too: an exception from one of the calls below must not leave the context inside a lane region)
@@ -1590,22 +1497,9 @@ class SlamLoopBatch {
         sinkPoses.push_back(cloudPoseOf_(work.kfChange[i].first, *q.keyframe));
       }
       if (lanes) ctx->laneSelect(i % lanes);
-      if (!sharedKeyframeChange) q.map.finalizeKeyFrame();
-      q.numKeyframesFinished++;
-      q.mappedOnKF = 0;
-      if (!sharedKeyframeChange) q.map.createKeyFrame(frame.get());
+      if (!sharedKeyframeChange) { q.map.finalizeKeyFrame(); q.map.createKeyFrame(frame.get()); }
       if (keepKeyframes && q.keyframeLog.empty() && !q.replacedFirst) q.replacedFirst = q.keyframe;
-      q.keyframe = frame;
-      if (keepKeyframes) q.keyframeLog.push_back(frame);
-      q.sinceKF = 0;
-      if (pipelined_) {
-        q.pendingKF = frame;          // the tracker keeps the old keyframe for one more frame
-      } else {
-        q.trackKF = frame;
-        q.reference.importFrame(q.keyframe.get());
-        q.keyframe->clearDepthHasBeenUpdatedFlag();
-        q.lastFrameToKF = SE3();
-      }
+      q.promote(frame, pipelined_, keepKeyframes, true);
     }
     region.end();
     if (!finished.empty()) {
@@ -1613,12 +1507,7 @@ class SlamLoopBatch {
       for (auto& f : finished) fs.push_back(f.get());
       PointCloud::appendBatch(sinkClouds, fs, sinkPoses, cloudScaledTH, cloudAbsTH, cloudMinNearSupport);
     }
-    for (size_t k = 0; k < work.updSeq.size(); k++) {
-      Sequence& q = *seqs_[work.updSeq[k]];
-      q.mappedOnKF++;
-      q.numUpdates++;
-      work.updFrames[k]->clear_refPixelWasGood();
-    }
+    for (size_t k = 0; k < work.updSeq.size(); k++) seqs_[work.updSeq[k]]->mapped(*work.updFrames[k]);
   }
   std::vector<PointCloud*> cloudSinks_;
   std::function<Sim3(int, Frame&)> cloudPoseOf_;
@@ -1627,11 +1516,8 @@ class SlamLoopBatch {
   int prefetchedId_ = -1;
   const unsigned char* const* pendingNext_ = nullptr;
   MapWork deferred_;
-  int w_, h_;
-  Mat3f K_;
-  bool onDevice_;
+  LoopCamera cam_;
   int kfEvery_, frameId_ = 0;
-  std::shared_ptr<DeviceUndistorter> undistorter_;   // set: images are raw images of this camera
   std::vector<std::unique_ptr<Sequence>> seqs_;
 };
 

@@ -92,7 +92,7 @@ DRIVER_SRC = os.path.join(HERE, "driver", "slam_loop.cpp")
 def build_driver(force=False, verbose=False):
     """liblsdhip_driver.so: the C++ host loop (include/lsd_slam_hip.hpp) — plain g++, links liblsdhip.so."""
     deps = [DRIVER_SRC, os.path.join(HERE, "driver", "dataset_slam.cpp"), os.path.join(HERE, "..", "include", "lsd_slam_hip_io.hpp"),
-            os.path.join(HERE, "..", "include", "lsd_slam_hip_cloud_constants.hpp"), os.path.join(HERE, "..", "include", "lsd_slam_hip.hpp"), os.path.join(HERE, "..", "include", "lsd_slam_hip_pose.hpp"), os.path.join(HERE, "..", "include", "lsdhip.h"),
+            os.path.join(HERE, "..", "include", "lsd_slam_hip_cloud_constants.hpp"), os.path.join(HERE, "..", "include", "lsd_slam_hip.hpp"), os.path.join(HERE, "..", "include", "lsd_slam_hip_pose.hpp"), os.path.join(HERE, "..", "include", "lsd_slam_hip_loop.hpp"), os.path.join(HERE, "..", "include", "lsdhip.h"),
             os.path.join(HERE, "..", "include", "lsdhip_driver.h"), OUT]
     if not force and os.path.exists(DRIVER_OUT) and all(os.path.getmtime(d) <= os.path.getmtime(DRIVER_OUT) for d in deps):
         return DRIVER_OUT

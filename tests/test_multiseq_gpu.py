@@ -445,3 +445,63 @@ def test_batch_loop_8_seeds_640x480_against_the_oracle(hip, pipelined, coarse):
             worst.append((s, member, sl.rmse(g.trajectory(), o_sse.trajectory()), sl.rmse(o_sc.trajectory(), o_sse.trajectory())))
         print("S = 8, 640x480, %s: per sequence (seed, oracle ensemble member used, trajectory RMSE vs oracle-SSE, oracle scalar-vs-SSE): %s"
               % ("pipelined" if pipelined else "blockUntilMapped", ["(%d, %d, %.1e, %.1e)" % w_ for w_ in worst]))
+
+
+@pytest.mark.parametrize("pipelined", [False, True])
+def test_batch_loop_goes_on_when_one_sequence_is_lost(hip, pipelined):
+    """A tracking loss inside a batch (SlamSystem.cpp:946-966, :809-817): sequence 1 of three gets a frame without any gradient as its
+    4th frame — the input of test_cpp_loop_stays_lost_after_a_tracking_loss, a tracking failure and no device fault.  The batch marks
+    it lost and takes no further frame of it; its twin neighbours 0 and 2 go on as if it were not there: bit-identical to each other,
+    every frame tracked good, and within the tolerance of test_batch_loop_follows_the_single_sequence_loops (the batch form of the
+    tracker sums in another order) of a single loop over the same images."""
+    from lsd_slam_amd.driver import DriverLoop, DriverLoopBatch
+    import oracle.pyoracle as po
+    from common import pose_distance
+    w, h, S, n_before, n_after = 320, 240, 3, 4, 8
+    n = n_before + n_after
+    seqs = [sequence(w, h, n + 1, seq_index=s % 2) for s in range(S)]        # sequences 0 and 2 are twins
+    imgs = [[np.ascontiguousarray(f) for f in q[0]] for q in seqs]
+    flat = np.full((h, w), 128, np.uint8)
+    imgs[1][n_before] = flat
+    K = seqs[0][2]
+    steps = [[imgs[s][t].ctypes.data for s in range(S)] for t in range(1, n + 1)]
+    drv = DriverLoop(w, h, K, imgs[0][0].ctypes.data, seqs[0][1], kf_every=10, images_on_device=False)
+    drv.set_pipeline(pipelined)
+    single = []
+    for part in (steps[:n_before], steps[n_before:]):
+        done, poses = drv.run([p[0] for p in part], want_poses=True)
+        assert done == len(part)
+        single.append(np.asarray(poses))
+    single = np.concatenate(single)
+    drv.close()
+    bl = DriverLoopBatch(w, h, K, [imgs[s][0].ctypes.data for s in range(S)], [seqs[s][1] for s in range(S)], kf_every=10, images_on_device=False)
+    bl.set_pipeline(pipelined)
+    done, poses_a = bl.run(steps[:n_before], want_poses=True)
+    assert done == n_before
+    at_loss = bl.stats()[1]
+    done, poses_b = bl.run(steps[n_before:], want_poses=True)
+    assert done == n_after                                   # the run completes all steps
+    st = bl.stats()
+    dropped = bl.dropped()
+    bl.close()
+    poses = np.concatenate([poses_a, poses_b])
+    print("sequence 1 at the loss %r, at the end %r; dropped %r" % (at_loss, st[1], dropped))
+    # The lost sequence, in both execution models:
+    #   frames 4        the frame that loses tracking is counted as tracked (nTrackFrame++ precedes the test, SlamSystem.cpp:940-948),
+    #                   none after it: a lost sequence takes no further frames
+    #   tracked_good 3  the three frames before it
+    #   updates 3       those three were mapped (a pipelined loop queues the third one's update under the 4th frame's tracking batch);
+    #                   the lost frame is neither mapped nor promoted
+    #   keyframes 0     no keyframe change before frame 10, and a loss is none
+    # (the keyframe, mapped on 3 < MIN_NUM_MAPPED times, is discarded, :809-817)
+    assert at_loss["lost"] == 1 and at_loss["frames"] == 4 and at_loss["tracked_good"] == 3 and at_loss["updates"] == 3 and at_loss["keyframes"] == 0
+    assert st[1] == at_loss, (st[1], at_loss)                # ... and nothing of it moves afterwards
+    assert dropped[1] == 0
+    nd = 1 if pipelined else 0                               # the frame after the keyframe change at frame 10 (pipelined: dropped)
+    for s in (0, 2):
+        assert st[s]["lost"] == 0 and st[s]["frames"] == n and st[s]["tracked_good"] == n and st[s]["keyframes"] == 1 and st[s]["updates"] == n - 1 - nd
+        assert dropped[s] == nd
+        worst = max(max(pose_distance(poses[t, s], single[t], po)) for t in range(n))
+        print("sequence %d against the single loop: %.3e" % (s, worst))
+        assert worst < 1e-3, (s, worst)
+    assert np.array_equal(poses[:, 0], poses[:, 2]), "sequence 0 differs from its twin 2"
