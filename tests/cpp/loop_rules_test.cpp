@@ -4,6 +4,7 @@
 //   finalise mappedOnKF                  -> finaliseOnLoss                  (0 / 1)
 //   every kfEvery sinceKF                -> wantsNewKeyframe, fixed interval (0 / 1)
 //   score dist2 usage                    -> keyframeScore                   (bits)
+//   scorew dist2 usage distW usageW      -> keyframeScore with explicit weights (bits)
 //   threshold numKeyframes | threshold - -> scoreThreshold with / without a kept bank (bits)
 //   wants mappedOnKF score threshold     -> wantsNewKeyframe, score rule     (0 / 1)
 //   step lost onCurrent wants            -> mappingStep                     (lost / dropped / update / change)
@@ -46,6 +47,10 @@ int main() {
     } else if (!std::strcmp(op, "score")) {
       if (!readFloat(&x) || !readFloat(&y)) return 2;
       printFloat(keyframeScore(x, y));
+    } else if (!std::strcmp(op, "scorew")) {
+      float wd, wu;
+      if (!readFloat(&x) || !readFloat(&y) || !readFloat(&wd) || !readFloat(&wu)) return 2;
+      printFloat(keyframeScore(x, y, wd, wu));
     } else if (!std::strcmp(op, "threshold")) {
       char arg[16];
       if (std::scanf("%15s", arg) != 1) return 2;

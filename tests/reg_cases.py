@@ -39,6 +39,12 @@ VARIANTS = 6                              # sheets of one size that fill the cla
 STALE_COUNTER, STALE_IDEPTH, VAR0 = 57, 1.0, 1.0 / 64
 GRAD_LOW, GRAD_HIGH = 1.0, 20.0
 GRAD_JUST_BELOW = float(np.nextafter(np.float32(MIN_USE_GRAD), np.float32(0)))
+# maxGradients entries that follow the threshold a sheet is built for (build(..., min_use_grad=)): GRAD_LOW < minUseGrad < GRAD_HIGH
+AT_THRESHOLD, JUST_BELOW_THRESHOLD = "minUseGrad", "one ulp below minUseGrad"
+
+
+def just_below(min_use_grad):
+    return float(np.nextafter(np.float32(min_use_grad), np.float32(0)))
 
 STEPS = {"fillholes": ("K5",), "regularize": ("K6",), "regularize_occ": ("K6occ",), "fill_regularize": ("K5", "K6")}
 K6_NONE, K6_KEPT, K6_REJECTED, K6_OCCLUDED = 0, 1, 2, 3
@@ -109,7 +115,7 @@ CASES = [
     _k5("K5 sum=30 bl=-1", S30, -1, False), _k5("K5 sum=31 bl=-1", S31, -1, True),
     _k5("K5 sum=31 bl=-2", S31, -2, False), _k5("K5 sum=100 bl=-2", S100, -2, False), _k5("K5 sum=101 bl=-2", S101, -2, True),
     _k5("K5 sum=31 bl=-5", S31, -5, False), _k5("K5 sum=100 bl=-5", S100, -5, False), _k5("K5 sum=101 bl=-5", S101, -5, True),
-    _k5("K5 maxGrad just below", S101, 0, False, maxgrad=GRAD_JUST_BELOW), _k5("K5 maxGrad == minUseGrad", S31, 0, True, maxgrad=MIN_USE_GRAD),
+    _k5("K5 maxGrad just below", S101, 0, False, maxgrad=JUST_BELOW_THRESHOLD), _k5("K5 maxGrad == minUseGrad", S31, 0, True, maxgrad=AT_THRESHOLD),
     _k5("K5 sum large by stale counters only", S30, 0, False, stale=[N(250, valid=False), N(250, valid=False), N(250, valid=False)]),
     _k5("K5 unequal variances", None, 0, True, nbrs=[N(11, 0.5), N(10, 2.0, 0.25), N(10, 0.5, 0.25)]),
     _k5("K5 negative inverse depths", None, 0, True, nbrs=[N(11, -0.5), N(10, -0.5), N(10, 0.25)]),
@@ -251,17 +257,21 @@ def cells(w, h, variant=0):
     return [(cx, cy, CASES[k], tags_of(cx, cy, w, h)) for cx, cy, k in layout(w, h, variant)]
 
 
-def _put(hyp, mg, x, y, p):
+def _put(hyp, mg, x, y, p, min_use_grad=MIN_USE_GRAD):
     px = hyp[y, x]
     px["isValid"], px["blacklisted"], px["validity_counter"] = int(p["valid"]), p["bl"], p["counter"]
     px["idepth"], px["idepth_var"] = p["idepth"], p["var"]
     px["idepth_smoothed"] = p["idepth"] * 0.75 if p["smoothed"] is None else p["smoothed"]
     px["idepth_var_smoothed"] = p["var"] * 0.5 if p["var_smoothed"] is None else p["var_smoothed"]
-    mg[y, x] = p["maxgrad"]
+    g = p["maxgrad"]
+    mg[y, x] = np.float32(min_use_grad) if g == AT_THRESHOLD else just_below(min_use_grad) if g == JUST_BELOW_THRESHOLD else g
 
 
-def build(w, h, variant=0):
-    """(hypothesis array, maxGradients plane) of variant `variant` (0 .. VARIANTS - 1) of the sheet of size w x h"""
+def build(w, h, variant=0, min_use_grad=MIN_USE_GRAD):
+    """(hypothesis array, maxGradients plane) of variant `variant` (0 .. VARIANTS - 1) of the sheet of size w x h, for a map whose
+    minUseGrad is `min_use_grad`: the classes 'K5 maxGrad == minUseGrad' and 'K5 maxGrad just below' stand at that value and one ulp
+    below it"""
+    assert GRAD_LOW < float(np.float32(min_use_grad)) < GRAD_HIGH
     hyp = np.zeros((h, w), HYP_DTYPE)
     mg = np.full((h, w), GRAD_LOW, np.float32)
     hyp["validity_counter"] = STALE_COUNTER
@@ -271,14 +281,14 @@ def build(w, h, variant=0):
     hyp["idepth_var_smoothed"] = VAR0 * 0.5
     for cx, cy, k in layout(w, h, variant):
         c = CASES[k]
-        _put(hyp, mg, cx, cy, c.centre)
+        _put(hyp, mg, cx, cy, c.centre, min_use_grad)
         free = [o for o in OFFS if 0 <= cx + o[0] < w and 0 <= cy + o[1] < h]
         for p in c.nbrs:                      # preferred offsets first, the rest in OFFS order
             if p["at"] in free:
                 free.remove(p["at"])
         for p in c.nbrs:
             o = p["at"] if p["at"] is not None and 0 <= cx + p["at"][0] < w and 0 <= cy + p["at"][1] < h else free.pop(0)
-            _put(hyp, mg, cx + o[0], cy + o[1], p)
+            _put(hyp, mg, cx + o[0], cy + o[1], p, min_use_grad)
     return hyp, mg
 
 

@@ -50,7 +50,8 @@ def search(oracle, tracker, keyframes, frame, frameCamToWorld, parent_id, w, h, 
     frame: the oracle Frame searched for, frameCamToWorld its (s, R, t).  Returns (winner slot or None, records, counts)."""
     wd, wu = (F(params.KFDistWeight), F(params.KFUsageWeight)) if params is not None else (F(4), F(3))
     maxScore = F(maxScore)
-    distanceTH = F(maxScore / F(wd * wd))
+    with np.errstate(divide="ignore"):          # KFDistWeight 0 (the cfg's minimum): an infinite threshold, as in the reference
+        distanceTH = F(maxScore / F(wd * wd))
     fowX, fowY = fov(w, h, K)
     cosAngleTH = F(math.cos(F(F(F(0.75) * F(0.5)) * F(fowX + fowY))))
     pos = frameCamToWorld[2]

@@ -74,7 +74,10 @@ class OracleSide:
         self.po, self.frames, self.K, self.L, self.params = po, frames, K, L, params
         h, w = frames[0].shape
         self.kf0 = po.Frame(0, frames[0], K, L=L)
-        self.kf0.set_depth_gt(depth0)
+        if params is None:
+            self.kf0.set_depth_gt(depth0)
+        else:       # (the oracle's frames carry no settings: the threshold of setDepthFromGroundTruth travels as an argument)
+            self.kf0.set_depth_gt(depth0, minUseGrad=params.minUseGrad)
         self.dm = po.DepthMap(w, h, K, params=params, L=L)
         self.dm.init_gt(self.kf0)
         self.ref = po.TrackingReference(L=L)

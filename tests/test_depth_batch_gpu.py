@@ -16,8 +16,8 @@ import numpy as np
 import pytest
 
 from common import assert_bit_equal, sequence
-from test_gpu_parity import (STEREO, _noisy_hyp, _ref_pose, assert_created_keyframe_exact, assert_hyp_equal, expected_rescale, oracle_params,
-                             oracle_prerescale_after_propagate)
+from test_gpu_parity import (STEREO, _noisy_hyp, _ref_pose, assert_created_keyframe_exact, assert_gradient_candidates, assert_hyp_equal,
+                             expected_rescale, oracle_params, oracle_prerescale_after_propagate)
 
 pytestmark = pytest.mark.gpu
 
@@ -44,9 +44,9 @@ def interior(h, w, b=3):
     return m
 
 
-def low_grad_valid(hyp, maxgrad):
+def low_grad_valid(hyp, maxgrad, min_use_grad=MIN_USE_GRAD):
     """valid hypotheses on pixels the observe pass would drop (inside the 3-pixel border, maxGradients below minUseGrad)"""
-    return int(((hyp["isValid"] > 0) & (maxgrad < MIN_USE_GRAD) & interior(*hyp.shape)).sum())
+    return int(((hyp["isValid"] > 0) & (maxgrad < np.float32(min_use_grad)) & interior(*hyp.shape)).sum())
 
 
 def changed_pixels(a, b):
@@ -63,6 +63,7 @@ def build_twins(oracle, w, h, n, kind="S1", params=None, seed0=100, sigma=0.1, f
     every-pixel select pass, which drops them, from the candidate select, which never sees them).  source: common.sequence or another
     callable with its arguments and results (tests/test_observe_motions_gpu.py: frames of general camera motions)."""
     op = oracle_params(oracle, params)
+    th = np.float32(op.minUseGrad)
     for s in range(min(n, nseq)):
         source(w, h, nframes, s, kind)      # (rendered once per size, before the pool asks for them)
 
@@ -71,7 +72,7 @@ def build_twins(oracle, w, h, n, kind="S1", params=None, seed0=100, sigma=0.1, f
         t.frames, t.depth0, t.K, t.gt = source(w, h, nframes, j % nseq, kind)
         t.w, t.h, t.base, t.react, t.op = w, h, 0, j in reactivated, op
         t.kf = oracle.Frame(0, t.frames[0], t.K)
-        t.kf.set_depth_gt(t.depth0)
+        t.kf.set_depth_gt(t.depth0, minUseGrad=op.minUseGrad)
         t.dm = oracle.DepthMap(w, h, t.K, params=op, threads=1)
         t.dm.init_gt(t.kf)
         hyp = _noisy_hyp(t.dm.get(), sigma, seed0 + j)
@@ -82,7 +83,7 @@ def build_twins(oracle, w, h, n, kind="S1", params=None, seed0=100, sigma=0.1, f
                 hyp[k] *= np.float32(0.02 * 0.02)
         rng = np.random.default_rng(7000 + seed0 + j)
         mg = t.kf.plane("maxGradients", 0)
-        plant = (mg < MIN_USE_GRAD) & (rng.uniform(size=mg.shape) < 0.02) & interior(h, w) & np.isfinite(t.depth0) & (t.depth0 > 0)
+        plant = (mg < th) & (rng.uniform(size=mg.shape) < 0.02) & interior(h, w) & np.isfinite(t.depth0) & (t.depth0 > 0)
         idp = (np.float32(1) / np.where(plant, t.depth0, np.float32(1))).astype(np.float32)
         hyp["isValid"][plant] = 1
         hyp["blacklisted"][plant] = 0
@@ -96,7 +97,7 @@ def build_twins(oracle, w, h, n, kind="S1", params=None, seed0=100, sigma=0.1, f
         if regularize:
             t.dm.stage("regularize")
             hyp = t.dm.get()
-        t.planted = low_grad_valid(hyp, mg)
+        t.planted = low_grad_valid(hyp, mg, th)
         assert t.planted > 0, "map %d: no hypothesis below minUseGrad in the uploaded state" % j
         t.hyp0 = hyp
         t.dev = None
@@ -178,7 +179,7 @@ def update_round(oracle, hip, ctx, twins, fids, what, masks=None, due=None, form
     inputs = [frame_inputs(oracle, t, fids[j], masks[j], 31 * fids[j] + j) for j, t in enumerate(twins)]
     before = [t.dm.get() for t in twins]
     mgs = [t.kf.plane("maxGradients", 0) for t in twins]
-    low = [low_grad_valid(before[j], mgs[j]) for j in range(n)]
+    low = [low_grad_valid(before[j], mgs[j], twins[j].op.minUseGrad) for j in range(n)]
     if expect_low_grad is True:
         assert all(v > 0 for v in low), (what, low)
     if expect_low_grad is False:     # a candidate-select call: nothing below the threshold is left, and only because an earlier pass removed it
@@ -419,6 +420,9 @@ def change_round(oracle, hip, ctx, twins, nk, what, masks, change_py, zoom_out=(
             assert_mean_idepth(olds[j].stats(), r["old"].plane("idepth", 0), r["old"].plane("idepthVar", 0), tag + " old keyframe")
             want = assert_created_keyframe_exact(oracle, tag, pre, scales[j], r["s_o"], t.dev["dm"].currentDepthMap(), nkgs[j], r["pose_o"], t.K,
                                                  t.frames[nks[j]])
+            # the new keyframe's gradient candidates, built with its level-0 planes inside the call (k_maxgrad_candidates, or its batch
+            # form from two maps on): the pixels the next candidate-select update may search, at the context's threshold
+            assert_gradient_candidates(nkgs[j], t.w, t.h, t.op.minUseGrad)
             t.dev["kf"] = nkgs[j]
             t.dev.setdefault("old", []).append(olds[j])
         else:
@@ -435,15 +439,15 @@ def change_round(oracle, hip, ctx, twins, nk, what, masks, change_py, zoom_out=(
     return res
 
 
-def change_flow(oracle, hip, w, h, n, py, zoom_out=(), mixed_masks=True, dev=True, min_changed=1000, change_py="same"):
+def change_flow(oracle, hip, w, h, n, py, zoom_out=(), mixed_masks=True, dev=True, min_changed=1000, change_py="same", params=None):
     """update with frame 1, change to frame 2, update with frame 3, change to frame 4 (starts from the propagation scratch the first left), update with frame 5.
     From 4 maps on the updates behind a change take the candidate select on lists built for the NEW keyframes while lowGradHypPossible is
     still false: the oracle's new map must hold no hypothesis below minUseGrad then (asserted from the oracle), and the device must agree
     bit for bit."""
-    twins = build_twins(oracle, w, h, n, sigma=0.03, regularize=True, seed0=900)
+    twins = build_twins(oracle, w, h, n, sigma=0.03, regularize=True, seed0=900, params=params)
     ctx = None
     if dev:
-        ctx = hip.Context(w, h, twins[0].K)
+        ctx = hip.Context(w, h, twins[0].K, params=params)
         upload_twins(hip, ctx, twins)
     masks = [(j % 2 == 0) or not mixed_masks for j in range(n)]
     split = 4 <= n <= 256

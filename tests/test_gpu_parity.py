@@ -121,18 +121,7 @@ def test_gradient_candidates_are_the_pixels_observe_can_search(oracle, hip, w, h
     th = 5.0     # lsdhip_default_params: minUseGrad
 
     def check():
-        mg = fg.maxGradients(0)
-        ok = ~(mg < th)
-        ok[:3, :] = False; ok[-3:, :] = False; ok[:, :3] = False; ok[:, -3:] = False
-        flat = ok.reshape(-1)
-        offs, cnts = fg.gradientCandidates()
-        ng = (w * h + 1023) // 1024
-        assert offs.shape == (ng, 1024) and cnts.shape == (ng,)
-        for g in range(ng):
-            want = np.flatnonzero(flat[g * 1024:(g + 1) * 1024])
-            assert cnts[g] == len(want), "group %d: count" % g
-            assert np.array_equal(offs[g, :len(want)], want.astype(np.uint16)), "group %d: offsets" % g
-        return int(flat.sum())
+        return assert_gradient_candidates(fg, w, h, th)
 
     n1 = check()
     assert 0 < n1 < w * h
@@ -140,6 +129,22 @@ def test_gradient_candidates_are_the_pixels_observe_can_search(oracle, hip, w, h
     fg.setMaxGradients(rng.uniform(0, 12, (h, w)).astype(np.float32))
     n2 = check()
     assert n2 != n1
+
+
+def assert_gradient_candidates(fg, w, h, th):
+    """Frame.gradientCandidates() of `fg` against the numpy statement at threshold `th`; returns the number of candidates"""
+    mg = fg.maxGradients(0)
+    ok = ~(mg < np.float32(th))
+    ok[:3, :] = False; ok[-3:, :] = False; ok[:, :3] = False; ok[:, -3:] = False
+    flat = ok.reshape(-1)
+    offs, cnts = fg.gradientCandidates()
+    ng = (w * h + 1023) // 1024
+    assert offs.shape == (ng, 1024) and cnts.shape == (ng,)
+    for g in range(ng):
+        want = np.flatnonzero(flat[g * 1024:(g + 1) * 1024])
+        assert cnts[g] == len(want), "group %d: count" % g
+        assert np.array_equal(offs[g, :len(want)], want.astype(np.uint16)), "group %d: offsets" % g
+    return int(flat.sum())
 
 
 def test_pointcloud_order_and_bits(oracle, hip):
@@ -295,7 +300,7 @@ def test_trackframe_parity(oracle, hip, w, h, params):
     op = oracle_params(oracle, params)
     kfo = oracle.Frame(0, frames[0], K)
     kfg = hip.Frame(ctx, 0, frames[0])
-    kfo.set_depth_gt(depth0)
+    kfo.set_depth_gt(depth0, minUseGrad=op.minUseGrad)
     kfg.setDepthFromGroundTruth(depth0)
     ro = oracle.TrackingReference()
     ro.import_frame(kfo)
@@ -384,14 +389,19 @@ def test_trackframe_divergence_returns_identity(oracle, hip):
 
 
 def test_permaref_paths(oracle, hip):
-    w, h = 640, 480
-    frames, depth0, K, gt, ctx = make_pair(oracle, hip, w, h, 4)
+    run_permaref_paths(oracle, hip, 640, 480)
+
+
+def run_permaref_paths(oracle, hip, w, h, params=None):
+    """params: overrides of the context's settings, handed to the oracle as well (tests/test_settings_gpu.py)"""
+    frames, depth0, K, gt, ctx = make_pair(oracle, hip, w, h, 4, params=params)
+    op = oracle_params(oracle, params)
     kfo = oracle.Frame(0, frames[0], K)
-    kfo.set_depth_gt(depth0)
+    kfo.set_depth_gt(depth0, minUseGrad=op.minUseGrad)
     ro = oracle.TrackingReference()
     ro.import_frame(kfo)
     pos, cv, _, _ = ro.pointcloud(4)
-    tro = oracle.SE3Tracker(w, h, K, mode=oracle.SSE_EXACT_RCP)
+    tro = oracle.SE3Tracker(w, h, K, params=op, mode=oracle.SSE_EXACT_RCP)
     trg = hip.SE3Tracker(ctx)
     fo = oracle.Frame(3, frames[3], K)
     fg = hip.Frame(ctx, 3, frames[3])
@@ -404,6 +414,7 @@ def test_permaref_paths(oracle, hip):
     u_o = tro.check_overlap(pos, kfo, T0)
     u_g = trg.checkPermaRefOverlap(pos, T0)
     assert u_g == pytest.approx(u_o, rel=1e-5)
+    return r
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -431,7 +442,7 @@ def _noisy_hyp(hyp, sigma=0.1, seed=1):
 def _noisy_map(oracle, hip, ctx, frames, depth0, K, w, h, sigma=0.1, seed=1, op=None, threads=None):
     kfo = oracle.Frame(0, frames[0], K)
     kfg = hip.Frame(ctx, 0, frames[0])
-    kfo.set_depth_gt(depth0)
+    kfo.set_depth_gt(depth0, minUseGrad=ctx.params.minUseGrad)     # (the oracle's frames carry no settings: the threshold is an argument)
     kfg.setDepthFromGroundTruth(depth0)
     dmo = oracle.DepthMap(w, h, K, params=op) if threads is None else oracle.DepthMap(w, h, K, params=op, threads=threads)
     dmg = hip.DepthMap(ctx)

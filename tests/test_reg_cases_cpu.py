@@ -24,11 +24,13 @@ def image(w, h, seed=0):
 class Side:
     """one library's keyframe + map holding a sheet (L = None: the oracle, else the compiled reference)"""
 
-    def __init__(self, oracle, w, h, hyp, mg, L=None):
+    def __init__(self, oracle, w, h, hyp, mg, L=None, min_use_grad=None):
         self.o, self.L, self.w, self.h = oracle, L, w, h
         self.K = camera(w, h)
         self.op = oracle.default_params(L) if L is not None else oracle.default_params()
         assert self.op.minUseGrad == rc.MIN_USE_GRAD
+        if min_use_grad is not None:          # a sheet built for a moved threshold (rc.build(..., min_use_grad=))
+            self.op.minUseGrad = min_use_grad
         self.kf = oracle.Frame(0, image(w, h), self.K, L=L)
         self.kf.set_maxgrad(mg)
         none = np.full((h, w), -1, np.float32)
@@ -101,11 +103,18 @@ def test_class_position_table_1024x512_one_sheet():
 @pytest.mark.parametrize("variant", range(rc.VARIANTS))
 @pytest.mark.parametrize("w,h", SIZES)
 def test_oracle_decides_as_the_census_predicts(oracle, w, h, variant):
-    hyp, mg = rc.build(w, h, variant)
+    oracle_decides_as_the_census_predicts(oracle, w, h, variant)
+
+
+def oracle_decides_as_the_census_predicts(oracle, w, h, variant, min_use_grad=None):
+    """min_use_grad: None = the default threshold, else the sheet, the oracle's map and the census all at that value"""
+    th = rc.MIN_USE_GRAD if min_use_grad is None else float(np.float32(min_use_grad))
+    hyp, mg = rc.build(w, h, variant, th)
     cl = rc.cells(w, h, variant)
-    s = Side(oracle, w, h, hyp, mg)
+    s = Side(oracle, w, h, hyp, mg, min_use_grad=min_use_grad)
+    assert s.op.minUseGrad == np.float32(th)
     for entry, stage in ENTRIES:
-        what = "oracle %dx%d variant %d %s" % (w, h, variant, entry)
+        what = "oracle %dx%d variant %d minUseGrad %g %s" % (w, h, variant, th, entry)
         s.reset()
         after = s.run(entry)
         want = rc.census(hyp, mg, s.op.minUseGrad, stage)

@@ -40,10 +40,11 @@ def workgroups(w, h, n=1):
 _TRUTH = {}
 
 
-def truth(oracle, w, h, v, entry):
-    key = (w, h, v, entry)
+def truth(oracle, w, h, v, entry, th=rc.MIN_USE_GRAD):
+    """th: the minUseGrad the sheet is built for and the oracle's map runs at"""
+    key = (w, h, v, entry, float(th))
     if key not in _TRUTH:
-        _TRUTH[key] = _compute(oracle, w, h, v, entry)
+        _TRUTH[key] = _compute(oracle, w, h, v, entry, th)
     return _TRUTH[key]
 
 
@@ -73,9 +74,10 @@ def react_sheet(fin):
     return hyp
 
 
-def _compute(oracle, w, h, v, entry):
-    hyp, mg = rc.build(w, h, v)
-    s = Side(oracle, w, h, hyp, mg)
+def _compute(oracle, w, h, v, entry, th=rc.MIN_USE_GRAD):
+    hyp, mg = rc.build(w, h, v, th)
+    moved = None if th == rc.MIN_USE_GRAD else th
+    s = Side(oracle, w, h, hyp, mg, min_use_grad=moved)
     r = {"side": s}
     if entry in ("fillholes", "regularize", "regularize_occ"):
         r["map"] = s.run(entry)
@@ -96,7 +98,7 @@ def _compute(oracle, w, h, v, entry):
         s.dm.stage("propagate", [nk])
         r["prop"] = s.dm.get()
         r["pre"] = oracle_prerescale_after_propagate(s.dm)
-        b = Side(oracle, w, h, hyp, mg)
+        b = Side(oracle, w, h, hyp, mg, min_use_grad=moved)
         nkb = oracle_new_keyframe(oracle, b)
         r["s_o"], r["pose_o"], r["keep"] = b.dm.create_keyframe(nkb), nkb.pose(), (nk, nkb, b)
     elif entry == "change":          # finalizeKeyFrame + createKeyFrame
@@ -105,7 +107,7 @@ def _compute(oracle, w, h, v, entry):
         s.dm.stage("propagate", [nk])
         r["prop"] = s.dm.get()
         r["pre"] = oracle_prerescale_after_propagate(s.dm)
-        b = Side(oracle, w, h, hyp, mg)
+        b = Side(oracle, w, h, hyp, mg, min_use_grad=moved)
         b.run("finalize")
         nkb = oracle_new_keyframe(oracle, b)
         r["s_o"], r["pose_o"], r["keep"] = b.dm.create_keyframe(nkb), nkb.pose(), (nk, nkb, b)
@@ -120,7 +122,8 @@ def _compute(oracle, w, h, v, entry):
 class Dev:
     def __init__(self, hip, ctx, w, h, v, kf_id=0):
         self.hip, self.ctx, self.w, self.h, self.v = hip, ctx, w, h, v
-        self.hyp, self.mg = rc.build(w, h, v)
+        self.th = float(ctx.params.minUseGrad)        # the context's threshold: the sheet and the census follow it
+        self.hyp, self.mg = rc.build(w, h, v, self.th)
         self.cells = rc.cells(w, h, v)
         self.kf = hip.Frame(ctx, kf_id, image(w, h))
         self.kf.setMaxGradients(self.mg)
@@ -147,16 +150,16 @@ class Dev:
         return f
 
 
-def context(hip, w, h):
-    ctx = hip.Context(w, h, camera(w, h))
-    assert ctx.params.minUseGrad == rc.MIN_USE_GRAD
+def context(hip, w, h, params=None):
+    ctx = hip.Context(w, h, camera(w, h), params=params)
+    assert ctx.params.minUseGrad == np.float32((params or {}).get("minUseGrad", rc.MIN_USE_GRAD))
     return ctx
 
 
 def check_map(d, got, t, stage, what):
     """the device's decisions against the census of the sheet (first: a wrong decision is then reported by class and position), and its map
     against the oracle's"""
-    want = rc.census(d.hyp, d.mg, rc.MIN_USE_GRAD, stage)
+    want = rc.census(d.hyp, d.mg, d.th, stage)
     rc.assert_decisions(rc.decisions_from_maps(d.hyp, got, stage), want, d.cells, what)
     assert_hyp_equal(got, t["map"], what)
     return want
@@ -204,7 +207,7 @@ def check_created(oracle, d, got, nkg, s_g, t, what):
     left to the oracle)"""
     img, sim3, itr, mask, mg = new_keyframe_inputs(oracle, d.w, d.h)
     assert_created_keyframe_exact(oracle, what, t["pre"], s_g, t["s_o"], got, nkg, t["pose_o"], camera(d.w, d.h), img)
-    want = rc.census(t["prop"], mg, rc.MIN_USE_GRAD, "regularize_occ+fill_regularize", near="mask")
+    want = rc.census(t["prop"], mg, d.th, "regularize_occ+fill_regularize", near="mask")
     ok = ~want["uncertain"]
     assert ok.mean() > 0.9, what
     for k, plane in (("valid", got["isValid"] > 0), ("blacklisted", got["blacklisted"])):
@@ -219,21 +222,30 @@ def check_created(oracle, d, got, nkg, s_g, t, what):
 @pytest.mark.parametrize("v", VARIANTS)
 def test_stages(oracle, hip, v):
     """k_fill_holes, k_reg_fused<PassRegOnly, 1>, <PassRegOcc, 1>, <PassUpdate, 1>, each on the sheet itself"""
+    run_stages(oracle, hip, v)
+
+
+def run_stages(oracle, hip, v, params=None):
+    """params: overrides of the context's settings (tests/test_settings_gpu.py runs the sheets at moved thresholds)"""
     assert workgroups(W, H) < 2048
-    d = Dev(hip, context(hip, W, H), W, H, v)
+    d = Dev(hip, context(hip, W, H, params), W, H, v)
     for stage in ("fillholes", "regularize", "regularize_occ", "fill_regularize"):
         d.reset()
         d.dm.stage(stage)
-        check_map(d, d.dm.currentDepthMap(), truth(oracle, W, H, v, stage), stage, "variant %d stage %s" % (v, stage))
+        check_map(d, d.dm.currentDepthMap(), truth(oracle, W, H, v, stage, d.th), stage, "variant %d minUseGrad %g stage %s" % (v, d.th, stage))
 
 
 @pytest.mark.parametrize("v", VARIANTS)
 def test_update_keyframe_due_and_not_due(oracle, hip, v):
     """k_reg_fused<PassUpdateSetDepth, 1> (the keyframe is due for Frame::setDepth) and <PassUpdate, 1> (it is not)"""
-    d = Dev(hip, context(hip, W, H), W, H, v)
+    run_update_keyframe_due_and_not_due(oracle, hip, v)
+
+
+def run_update_keyframe_due_and_not_due(oracle, hip, v, params=None):
+    d = Dev(hip, context(hip, W, H, params), W, H, v)
     for entry, flag in (("update_due", 0), ("update_not_due", 1)):
-        what = "variant %d %s" % (v, entry)
-        t = truth(oracle, W, H, v, entry)
+        what = "variant %d minUseGrad %g %s" % (v, d.th, entry)
+        t = truth(oracle, W, H, v, entry, d.th)
         d.reset()
         d.kf.setCounters(7, 3, 3, flag)
         before = [(d.kf.idepth(l), d.kf.idepthVar(l)) for l in range(5)]
@@ -250,9 +262,13 @@ def test_update_keyframe_due_and_not_due(oracle, hip, v):
 
 @pytest.mark.parametrize("v", VARIANTS)
 def test_finalize_then_set_from_existing(oracle, hip, v):
-    d = Dev(hip, context(hip, W, H), W, H, v)
-    what = "variant %d finalizeKeyFrame" % v
-    t = truth(oracle, W, H, v, "finalize")
+    run_finalize_then_set_from_existing(oracle, hip, v)
+
+
+def run_finalize_then_set_from_existing(oracle, hip, v, params=None):
+    d = Dev(hip, context(hip, W, H, params), W, H, v)
+    what = "variant %d minUseGrad %g finalizeKeyFrame" % (v, d.th)
+    t = truth(oracle, W, H, v, "finalize", d.th)
     d.dm.finalizeKeyFrame()
     want = check_map(d, d.dm.currentDepthMap(), t, "fill_regularize", what)
     check_set_depth(d, d.kf, t, want, what)
@@ -265,16 +281,20 @@ def test_finalize_then_set_from_existing(oracle, hip, v):
 def test_create_keyframe(oracle, hip, v):
     """createKeyFrame into a second frame at a small general pose: k_reg_fused<PassRegOcc, 1> and the fill + regularise pass with the rescale
     sums on the propagated sheet"""
-    d = Dev(hip, context(hip, W, H), W, H, v)
+    run_create_keyframe(oracle, hip, v)
+
+
+def run_create_keyframe(oracle, hip, v, params=None):
+    d = Dev(hip, context(hip, W, H, params), W, H, v)
     nkg = d.new_keyframe(oracle)
     s_g = d.dm.createKeyFrame(nkg)
-    check_created(oracle, d, d.dm.currentDepthMap(), nkg, s_g, truth(oracle, W, H, v, "create"), "variant %d createKeyFrame" % v)
+    check_created(oracle, d, d.dm.currentDepthMap(), nkg, s_g, truth(oracle, W, H, v, "create", d.th), "variant %d minUseGrad %g createKeyFrame" % (v, d.th))
 
 
-def run_change_batch(oracle, hip, w, h, variants, py):
+def run_change_batch(oracle, hip, w, h, variants, py, params=None):
     """changeKeyframeBatch = finalizeKeyFrame + createKeyFrame per map in shared launches: k_kf_finalize_prop (PassKfFinalize), k_kf_reg<PassRegOcc>,
     k_kf_reg<PassKfFillSums>"""
-    ctx = context(hip, w, h)
+    ctx = context(hip, w, h, params)
     n = len(variants)
     devs = [Dev(hip, ctx, w, h, v, kf_id=10 * j) for j, v in enumerate(variants)]
     nkgs = [d.new_keyframe(oracle) for d in devs]
@@ -282,8 +302,8 @@ def run_change_batch(oracle, hip, w, h, variants, py):
     assert_form(ctx, "change", {"n": n, "py": py}, "changeKeyframeBatch n = %d" % n)
     for j, d in enumerate(devs):
         what = "changeKeyframeBatch n = %d map %d (variant %d)" % (n, j, d.v)
-        tf, tc = truth(oracle, w, h, d.v, "finalize"), truth(oracle, w, h, d.v, "change")
-        want = rc.census(d.hyp, d.mg, rc.MIN_USE_GRAD, "fill_regularize")
+        tf, tc = truth(oracle, w, h, d.v, "finalize", d.th), truth(oracle, w, h, d.v, "change", d.th)
+        want = rc.census(d.hyp, d.mg, d.th, "fill_regularize")
         check_set_depth(d, d.kf, tf, want, what + " old keyframe")
         check_react_planes(d, d.kf, tf, want, what + " old keyframe")
         m2 = hip.DepthMap(ctx)
@@ -292,11 +312,11 @@ def run_change_batch(oracle, hip, w, h, variants, py):
         check_created(oracle, d, d.dm.currentDepthMap(), nkgs[j], scales[j], tc, what)
 
 
-def run_reactivate_batch(oracle, hip, w, h, variants):
+def run_reactivate_batch(oracle, hip, w, h, variants, params=None):
     """reactivateKeyframeBatch = finalizeKeyFrame of the current keyframe (k_kf_finalize: PassKfFinalizeOnly) + setFromExistingKF of a banked
     one (k_kf_from_react: PassFromReact).  Map j stands on variant v_j of the sheet; the banked keyframe it goes back to was finalised on
     variant v_j + 1, so the planes PassFromReact reads are a designed sheet's too."""
-    ctx = context(hip, w, h)
+    ctx = context(hip, w, h, params)
     n = len(variants)
     olds = []
     for j, v in enumerate(variants):
@@ -307,11 +327,11 @@ def run_reactivate_batch(oracle, hip, w, h, variants):
     hip.DepthMap.reactivateKeyframeBatch([d.dm for d in devs], [o.kf for o in olds])
     for j, d in enumerate(devs):
         what = "reactivateKeyframeBatch n = %d map %d (variant %d)" % (n, j, d.v)
-        tf = truth(oracle, w, h, d.v, "finalize")
-        want = rc.census(d.hyp, d.mg, rc.MIN_USE_GRAD, "fill_regularize")
+        tf = truth(oracle, w, h, d.v, "finalize", d.th)
+        want = rc.census(d.hyp, d.mg, d.th, "fill_regularize")
         check_set_depth(d, d.kf, tf, want, what + " finalised keyframe")
         check_react_planes(d, d.kf, tf, want, what + " finalised keyframe")
-        check_from_react(olds[j].cells, d.dm.currentDepthMap(), truth(oracle, w, h, olds[j].v, "finalize"), what + " re-activated map")
+        check_from_react(olds[j].cells, d.dm.currentDepthMap(), truth(oracle, w, h, olds[j].v, "finalize", d.th), what + " re-activated map")
 
 
 @pytest.mark.parametrize("variants", [(0,), (1, 2, 3)], ids=["n1", "n3"])

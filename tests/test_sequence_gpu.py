@@ -85,8 +85,10 @@ def test_sequence_50_frames_hip_vs_oracle(oracle, params, seq_index, live_queue,
         raise AssertionError("%s | a second HIP run gives %s poses" % (e, "IDENTICAL" if same else "DIFFERENT")) from e
 
 
-def _compare(g, o_sse, o_sc, gt, affine_on=True, decision_edges=None, residual_ensemble=None, residual_abs_floor=0.0):
-    """decision_edges (a list, or None): frames on which the device's LM loop ran a different number of evaluations than the oracle's — a
+def _compare(g, o_sse, o_sc, gt, affine_on=True, decision_edges=None, residual_ensemble=None, residual_abs_floor=0.0, n_frames=N_FRAMES,
+             kf_frames=(10, 20, 30, 40, 50)):
+    """n_frames, kf_frames: the length of the run and the frames that became keyframes (a shorter loop: tests/test_settings_gpu.py).
+    decision_edges (a list, or None): frames on which the device's LM loop ran a different number of evaluations than the oracle's — a
     stopping test that fell the other way under a different summation order; the pose bounds hold there as everywhere, but `lastResidual`
     is then the error of a different iterate — possibly of a different pyramid level: trackFrame reports the error of the last ACCEPTED
     step, and a level whose first retry is already rejected leaves the coarser level's value (SE3Tracker.cpp:399-401) — so on such frames it
@@ -99,16 +101,16 @@ def _compare(g, o_sse, o_sc, gt, affine_on=True, decision_edges=None, residual_e
     lighting on: the device's estimate of the offset b differs from the reference's by up to 0.07 grey levels (the reference's sequential
     float32 sums being the less accurate side, test_affine_lighting_estimate_against_float64_truth), which is ~2e-3 of weighted residual
     however small that residual is; both of the oracle's paths add in the same order and therefore do not show this in their spread."""
-    assert len(g.frameToKF) == len(o_sse.frameToKF) == N_FRAMES
+    assert len(g.frameToKF) == len(o_sse.frameToKF) == n_frames
     # identical verdicts, frame for frame
     assert g.diverged == o_sse.diverged and not any(g.diverged)
     assert g.good == o_sse.good
-    assert g.kf_frames == o_sse.kf_frames == [10, 20, 30, 40, 50]
+    assert g.kf_frames == o_sse.kf_frames == list(kf_frames)
 
     # trajectory: camera centres in the world frame (keyframe chain with the createKeyFrame rescale factors)
     spread = sl.rmse(o_sse.trajectory(), o_sc.trajectory())
     err = sl.rmse(g.trajectory(), o_sse.trajectory())
-    gtc = np.array([gt[i % N_FRAMES][4:7] for i in range(1, N_FRAMES + 1)])
+    gtc = np.array([gt[i % n_frames][4:7] for i in range(1, n_frames + 1)])
     err_gt_g, err_gt_o = sl.rmse(g.trajectory(), gtc), sl.rmse(o_sse.trajectory(), gtc)
     print("trajectory RMSE: HIP vs oracle-SSE %.3e, oracle scalar vs SSE %.3e, vs GT: HIP %.3e oracle %.3e"
           % (err, spread, err_gt_g, err_gt_o))

@@ -48,24 +48,29 @@ def gamma(npix):
 
 
 class Case:
-    def __init__(self, oracle, hip, w, h, k, scale, holes=False, no_depth=False):
+    def __init__(self, oracle, hip, w, h, k, scale, holes=False, no_depth=False, params=None):
+        """params: overrides of the context's settings, handed to the oracle's tracker as well (tests/test_settings_gpu.py)"""
         P = scene_pair(oracle, w, h, k, scale, holes)
         if no_depth:                    # the frame has depth, but no warped point lands on it
             d = np.zeros_like(P["depthB"]); d[0, 0] = P["depthB"][0, 0]; P["depthB"] = d
         self.P, self.w, self.h = P, w, h
         self.fa, self.fb = oracle.Frame(0, P["imgA"], P["K"]), oracle.Frame(k, P["imgB"], P["K"])
-        self.fa.set_depth_gt(P["depthA"]); self.fb.set_depth_gt(P["depthB"])
+        self.op = oracle.default_params()
+        for key, val in (params or {}).items():
+            setattr(self.op, key, val)
+        self.fa.set_depth_gt(P["depthA"], minUseGrad=self.op.minUseGrad); self.fb.set_depth_gt(P["depthB"], minUseGrad=self.op.minUseGrad)
         self.ra = oracle.TrackingReference(); self.ra.import_frame(self.fa)
-        self.tro = oracle.Sim3Tracker(w, h, P["K"], mode=oracle.SSE_EXACT_RCP)
-        self.ctx = hip.Context(w, h, P["K"])
+        self.tro = oracle.Sim3Tracker(w, h, P["K"], params=self.op, mode=oracle.SSE_EXACT_RCP)
+        self.ctx = hip.Context(w, h, P["K"], params=params)
         self.ga, self.gb = hip.Frame(self.ctx, 0, P["imgA"]), hip.Frame(self.ctx, k, P["imgB"])
         self.ga.setDepthFromGroundTruth(P["depthA"]); self.gb.setDepthFromGroundTruth(P["depthB"])
         self.trg = hip.Sim3Tracker(self.ctx)
 
 
-def hold(tag, A, b, sumResP, sumResD, ro_size, T, gam, worst):
+def hold(tag, A, b, sumResP, sumResD, ro_size, T, gam, worst, slack_A=None):
     """per-entry check of a device system against the float64 sums of the terms T (b, sumResP, sumResD: None to leave out);
-    worst[tag] = max |device - sum64| / (EPS sum|terms|)"""
+    worst[tag] = max |device - sum64| / (EPS sum|terms|).  slack_A (7x7, or None): added to the bound of A's entries — what an input of
+    the terms that the caller cannot pin down moves the float64 sums by (test_sim3_fused_hessian_per_entry, affine_spread)"""
     A64, Aa, b64, ba, rP, rPa, rD, rDa = sums64(T)
     n = T["n"]
     tail = 0 if ro_size == n else 3
@@ -87,6 +92,8 @@ def hold(tag, A, b, sumResP, sumResD, ro_size, T, gam, worst):
     for name, got, want, mag, g in rows:
         err = np.abs(got - want)
         bound = g * EPS * mag + 1e-30
+        if name == "A" and slack_A is not None:
+            bound = bound + np.asarray(slack_A, np.float64).ravel()
         bad = ~(err <= bound)
         assert not bad.any(), "%s %s: entries %s outside gamma %d: device %r float64 %r sum|terms| %r" % (
             tag, name, np.flatnonzero(bad).tolist(), g, got[bad], want[bad], mag[bad])
@@ -188,13 +195,23 @@ def cast_moves(T):
 
 
 @pytest.mark.parametrize("w,h,first,last", [(320, 240, 3, 1), (1280, 1024, 3, 1)])
-def test_sim3_fused_hessian_per_entry(oracle, hip, w, h, first, last):
+def test_sim3_fused_hessian_per_entry(oracle, hip, w, h, first, last, params=None, affine_spread=False):
     """trackFrameSim3 (k_sim3_fused): lastSim3Hessian per entry.  The system is the one of the last calcSim3LGS: the evaluation at the
     accepted transformation, recomputed on the final level when the last evaluation was accepted (Sim3Tracker.cpp:354-360).  Its buffers
     were computed with the affine pair in effect at that calcSim3Buffers call: after the final re-evaluation, the pair the call returns;
     when the last step was rejected, the pair before the last acceptance's update.  The oracle run of the same call records which
-    (Sim3Tracker::lgs_affine_a / _b); both runs take the same steps (same number of evaluations)."""
-    C = Case(oracle, hip, w, h, 3, 1.25)
+    (Sim3Tracker::lgs_affine_a / _b); both runs take the same steps (same number of evaluations).
+
+    params, affine_spread (tests/test_settings_gpu.py): settings overrides on both sides.  The pair is an input of every term, and the
+    device's own pair is not the oracle's: the estimate is a difference of float32 sums (test_sim3_gpu.py holds it to 3e-4 / 5e-2 only), and
+    the reference's own arithmetic modes disagree on it.  At the default cameraPixelNoise2 that does not matter here (320x240: the modes'
+    pairs differ by 2.6e-5 relative in a, which moves an entry by 2 of the bound's 93 units of EPS sum|terms|).  At cameraPixelNoise2 =
+    5.29 most points are in the Huber regime, where the weight goes with 1 / |r|: the oracle's modes differ by 4.8e-5 in a and 6e-3 in b,
+    and 1e-5 in a alone moves the entries by 14 .. 18 units (measured on the CPU with the oracle alone).  With affine_spread the bound of
+    an entry therefore grows by 3 x the largest shift of its float64 sum between the pair of this (exact-reciprocal) run and the pairs
+    of the oracle's SSE and scalar runs of the same call: the reference's own spread, never the device's value.  Without it the device
+    misses the bound at that setting by a factor 1.16 on five photometric entries (relative error 1.3e-5)."""
+    C = Case(oracle, hip, w, h, 3, 1.25, params=params)
     init = C.P["exp"].copy()
     init[7] = 1.0
     ro = C.tro.track(C.ra, C.fb, init, first, last)
@@ -207,13 +224,27 @@ def test_sim3_fused_hessian_per_entry(oracle, hip, w, h, first, last):
     # a cast that moves under the round trip changes the warp of every point by up to an ulp of its coordinates: the interpolated
     # gradients move with it by (image curvature) x (pixel shift), not a rounding of the term; such a case is held to 4x the bound
     widen = 4 if cast_moves(T) else 1
+    slack = None
+    if affine_spread:
+        slack = np.zeros((7, 7))
+        for mode in (oracle.SSE, oracle.SCALAR):
+            alt = oracle.Sim3Tracker(w, h, C.P["K"], params=C.op, mode=mode)
+            r_alt = alt.track(C.ra, C.fb, init, first, last)
+            assert r_alt.numEvaluations == ro.numEvaluations      # (the same steps: its pair belongs to the same evaluation)
+            a2, b2 = alt.system_affine()
+            C.tro.evaluate(C.ra, C.fb, T, last, a2, b2)
+            A_alt = sums64(sse_terms(C.tro))[0]
+            C.tro.evaluate(C.ra, C.fb, T, last, a, b)
+            slack = np.maximum(slack, 3 * np.abs(A_alt - sums64(sse_terms(C.tro))[0]))
     ro2 = C.tro.evaluate(C.ra, C.fb, T, last, a, b)
     Tm = sse_terms(C.tro)
     g = widen * gamma((w >> last) * (h >> last))
     worst = {}
     H = np.array(rg.lastSim3Hessian)
     assert np.allclose(H, H.T, rtol=0, atol=0)
-    hold("fused %dx%d L%d" % (w, h, last), H, None, None, None, ro2.warped_size, Tm, g, worst)
+    hold("fused %dx%d L%d" % (w, h, last), H, None, None, None, ro2.warped_size, Tm, g, worst, slack_A=slack)
+    if slack is not None:
+        print("affine spread of the reference's modes: up to %.1f units of EPS sum|terms| added to an entry's bound" % float((slack / (EPS * np.maximum(sums64(Tm)[1], 1e-300))).max()))
     print("fused %dx%d levels %d..%d: %d evaluations, affine (%.4f, %.3f), ppl %d, gamma %d%s, worst ratio %.1f" % (
         w, h, first, last, rg.numEvaluations, a, b, strips((w >> last) * (h >> last))[0], g, " (widened)" if widen > 1 else "",
         max(worst.values())))

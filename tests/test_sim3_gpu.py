@@ -14,7 +14,8 @@ def hip():
     return la
 
 
-def pair(oracle, hip, w, h, k, scale, holes=False):
+def pair(oracle, hip, w, h, k, scale, holes=False, params=None):
+    """params: overrides of the context's settings (the caller hands the same to the oracle's tracker; tests/test_settings_gpu.py)"""
     from lsd_slam_amd import synth
     sc = synth.Scene(0)
     K = synth.intrinsics(w, h)
@@ -27,9 +28,9 @@ def pair(oracle, hip, w, h, k, scale, holes=False):
         depthA[rng.uniform(size=depthA.shape) < 0.5] = 0
         depthB[rng.uniform(size=depthB.shape) < 0.5] = 0
     fa, fb = oracle.Frame(0, imgA, K), oracle.Frame(k, imgB, K)
-    fa.set_depth_gt(depthA); fb.set_depth_gt(depthB)
+    ctx = hip.Context(w, h, K, params=params)
+    fa.set_depth_gt(depthA, minUseGrad=ctx.params.minUseGrad); fb.set_depth_gt(depthB, minUseGrad=ctx.params.minUseGrad)
     ra = oracle.TrackingReference(); ra.import_frame(fa)
-    ctx = hip.Context(w, h, K)
     ga, gb = hip.Frame(ctx, 0, imgA), hip.Frame(ctx, k, imgB)
     ga.setDepthFromGroundTruth(depthA); gb.setDepthFromGroundTruth(depthB)
     R, t = sc.frame_to_ref(k, 0)
@@ -91,7 +92,7 @@ def _rel(a, b):
 
 
 @pytest.mark.parametrize("scale", [1.0, 1.25, 0.8])
-def test_sim3_track_recovers_pose_and_scale_like_the_oracle(oracle, hip, scale):
+def test_sim3_track_recovers_pose_and_scale_like_the_oracle(oracle, hip, scale, params=None, only=None):
     """Whole trackFrameSim3 calls AND prefixes of the Levenberg-Marquardt loop (the first n iterations of the coarsest level, then the
     finer levels added) against the oracle's three arithmetic modes.  Since round 6 the device solves the damped 7x7 system with diagonal
     pivoting like the reference's LDL^T, and the two loops stay in step: the NUMBER OF EVALUATIONS is equal at every prefix and for the
@@ -100,16 +101,21 @@ def test_sim3_track_recovers_pose_and_scale_like_the_oracle(oracle, hip, scale):
     profiles/r06_notes.md section 3): pose within 2e-5 / 5e-6 / 5e-6 (translation / quaternion / relative scale; round 5: 2e-3 / 1e-3 /
     2e-3), residuals within 3x that spread with a floor of 5e-4 (round 5: 2e-2 / 5e-2), Hessian within 3x the spread, floor 1e-4 (3e-2)."""
     w, h = 320, 240
-    P = pair(oracle, hip, w, h, 3, scale)
+    P = pair(oracle, hip, w, h, 3, scale, params=params)
+    op = oracle.default_params()          # params / only (tests/test_settings_gpu.py): settings overrides on both sides; the schedules to run
+    for key, val in (params or {}).items():
+        setattr(op, key, val)
     init = P["exp"].copy()
     init[7] = 1.0
     tg = hip.Sim3Tracker(P["ctx"])
     full = [5, 20, 50, 100, 100]
     schedules = [("level 3, %d iterations" % n, [0, 0, 0, n, 0], 3, 3) for n in (1, 2, 3, 4, 100)] + [("levels 3-2", full, 3, 2), ("levels 3-1", full, 3, 1)]
     for name, its, first, last in schedules:
+        if only is not None and name not in only:
+            continue
         runs = {}
         for mname, mode in (("exact", oracle.SSE_EXACT_RCP), ("sse", oracle.SSE), ("scalar", oracle.SCALAR)):
-            to = oracle.Sim3Tracker(w, h, P["K"], mode=mode)
+            to = oracle.Sim3Tracker(w, h, P["K"], params=op, mode=mode)
             to.set_max_its(its)
             runs[mname] = to.track(P["ra"], P["fb"], init, first, last)
         tg.setMaxItsPerLvl(its)

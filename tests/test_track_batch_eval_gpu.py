@@ -70,10 +70,14 @@ def depth_of(form, px, tilePx):
 class Scene:
     """one image size: its sequence, a HIP context, keyframes of each kind on both sides"""
 
-    def __init__(self, oracle, hip, w, h):
+    def __init__(self, oracle, hip, w, h, params=None):
+        """params: overrides of the context's settings, handed to the oracle's tracker as well (tests/test_settings_gpu.py)"""
         self.w, self.h = w, h
         self.frames, self.depth0, self.K, self.gt = sequence(w, h, 4, 0)
-        self.ctx = hip.Context(w, h, self.K)
+        self.ctx = hip.Context(w, h, self.K, params=params)
+        self.op = oracle.default_params()
+        for k, v in (params or {}).items():
+            setattr(self.op, k, v)
         self.oracle, self.hip = oracle, hip
         self.kfs = {}
 
@@ -103,7 +107,7 @@ class Scene:
             kfo = self.oracle.Frame(0, self.frames[0], self.K)
             kfg = self.hip.Frame(self.ctx, 1000 + len(self.kfs), self.frames[0])
             if var is None:
-                kfo.set_depth_gt(d)
+                kfo.set_depth_gt(d, minUseGrad=self.op.minUseGrad)
                 kfg.setDepthFromGroundTruth(d)
             else:
                 kfo.set_depth_planes(d.astype(np.float32), var.astype(np.float32))
@@ -127,8 +131,10 @@ KINDS = ["gt", "ragged", "dense"]
 AFFINE = [(1.0, 0.0), (1.03, -2.5), (0.97, 1.5)]
 
 
-def run_batch(oracle, hip, sc, n, lvl, coarse, stats, form_name):
-    """n jobs at level lvl; checks every job; returns the forms the device reported"""
+def run_batch(oracle, hip, sc, n, lvl, coarse, stats, form_name, witness=None):
+    """n jobs at level lvl; checks every job; returns the forms the device reported.  witness (a list, or None): per checked job
+    (form, (oracle reference, oracle frame, pose, level, a, b), float64 sums, the weighted error's bound), for a caller that wants to
+    evaluate the same job again under other settings"""
     tr = hip.SE3Tracker(sc.ctx)
     if coarse is not None:
         tr.set_batch_coarse_min_jobs(coarse)
@@ -152,7 +158,7 @@ def run_batch(oracle, hip, sc, n, lvl, coarse, stats, form_name):
     recs2, form2 = tr.evaluateBatch(refs_g, frs_g, np.array(Ts), lvl, np.array(ab, np.float32))
     assert np.array_equal(form, form2)
     masks = [f.refPixelWasGoodNoCreate() for f in frs_g] if lvl == 1 else None
-    tro = oracle.SE3Tracker(sc.w, sc.h, sc.K, mode=oracle.SSE_EXACT_RCP)
+    tro = oracle.SE3Tracker(sc.w, sc.h, sc.K, params=sc.op, mode=oracle.SSE_EXACT_RCP)
     px = (sc.w >> lvl) * (sc.h >> lvl)
     for j in range(n):
         tag = "%s %dx%d n=%d level %d job %d" % (form_name, sc.w, sc.h, n, lvl, j)
@@ -197,6 +203,8 @@ def run_batch(oracle, hip, sc, n, lvl, coarse, stats, form_name):
                     if np.any(np.abs(dev[k] - sums64(P, wrong)[k]) > bound):
                         st["wrong_tail"] = True
         G = S["good"]
+        if witness is not None:
+            witness.append((fname, (refs_o[j], frs_o[j], Ts[j], lvl, a, b), S, (depth + C_TERM["werr"]) * EPS * S["werr_abs"] + 1e-30))
         bound = (depth + 1) * EPS * S["res2_abs"] + EPS * abs(S["res2"])     # + retval's division
         assert abs(np.float64(g.retval) * G - S["res2"]) <= bound, tag
         sbound = (depth + 1) * EPS * S["signed_abs"] + EPS * abs(S["signed"]) + 1e-30     # meanRes: the signed residuals of the good points
