@@ -478,6 +478,12 @@ int lsdhip_host_ldlt7(const float A[49], const float b[7], float x[7]);
 int lsdhip_devtest_se3f_lm_step(lsdhip_ctx* ctx, int n, const float* A, const float* b, const float* damp, const float* T, float* inc, float* Tn);
 int lsdhip_devtest_sim3_lm_step(lsdhip_ctx* ctx, int n, const float* A, const float* b, const double* nconstraints, const float* lambda,
                                 const double* T, float* inc, double* Tn);
+/* test hooks for the lifetime of device resources (process-wide, no context needed).
+ * live_resources: how many device allocations, pinned allocations, events and streams the library holds right now, in that order.
+ * fail_alloc_after(n): the n-th creation of such a resource from now on (0 = the next one) is refused as out of memory, once, without
+ *   the runtime being asked — the call that needed it returns LSDHIP_E_HIP; n < 0 turns the hook off.  Host bookkeeping only. */
+void lsdhip_live_resources(long long out[4]);
+void lsdhip_devtest_fail_alloc_after(int n);
 /* test hook: one evaluation at referenceToFrame on `level` with affine (a, b) */
 int lsdhip_sim3tracker_evaluate(lsdhip_sim3tracker* t, lsdhip_frame* keyframe, lsdhip_frame* frame, const double referenceToFrame[8],
                                 int level, float aff_a, float aff_b, lsdhip_sim3_eval_record* out);

@@ -196,6 +196,8 @@ def _signatures():
         "lsdhip_host_ldlt7": (i, [vp, vp, vp]),
         "lsdhip_devtest_se3f_lm_step": (i, [vp, i, vp, vp, vp, vp, vp, vp]),
         "lsdhip_devtest_sim3_lm_step": (i, [vp, i, vp, vp, vp, vp, vp, vp, vp]),
+        "lsdhip_live_resources": (None, [C.POINTER(C.c_longlong * 4)]),
+        "lsdhip_devtest_fail_alloc_after": (None, [i]),
         "lsdhip_sim3tracker_evaluate": (i, [vp, vp, vp, vp, i, f, f, C.POINTER(Sim3EvalRecord)]),
         "lsdhip_depth_create": (i, [vp, pvp]),
         "lsdhip_depth_destroy": (None, [vp]),

@@ -41,7 +41,7 @@ struct lsdhip_cloud {
   int maxSeg = 0;
   int nchunks = 0;
   int appended = 0;            // appends queued since creation / the last reset (each takes one segment row while there is room)
-  char* base = nullptr;        // one allocation: points (+ guard) | state | segments | mask | chunk counts | chunk offsets
+  LsdDev<char> base;           // one allocation: points (+ guard) | state | segments | mask | chunk counts | chunk offsets
   float4* d_pts = nullptr;
   CloudState* d_state = nullptr;
   CloudSeg* d_segs = nullptr;
@@ -203,11 +203,11 @@ extern "C" int lsdhip_frame_pack_keyframe_points(lsdhip_frame* f, uint8_t* out_h
   HIPCHK(hipSetDevice(c->device));
   if (!f->hasIDepth && !f->depthPending) { lsd_set_error("lsdhip_frame_pack_keyframe_points: frame %d has no depth", f->id); return LSDHIP_E_STATE; }
   const int npix = c->w * c->h;
-  if (!c->d_kfPoints) HIPCHK(hipMalloc((void**)&c->d_kfPoints, (size_t)npix * 12));
+  if (!c->d_kfPoints) { if (int rc = lsd_dev_alloc(c->d_kfPoints, (size_t)npix * 12)) return rc; }
   if (c->pipeline) { if (int rc = lsd_sync_all(c)) return rc; }
   else if (lsd_map_stream(c) != c->stream) HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));   // (an open lane region)
   hipLaunchKernelGGL(k_pack_keyframe_points, dim3((npix / 4 + 255) / 256), dim3(256), 0, c->stream, (const float*)lsd_depth_latest(f)[0],
-                     (const float*)lsd_depthvar_latest(f)[0], (const float*)f->d_image[0], (uint4*)c->d_kfPoints, npix);
+                     (const float*)lsd_depthvar_latest(f)[0], (const float*)f->d_image[0], (uint4*)c->d_kfPoints.get(), npix);
   HIPCHK(hipGetLastError());
   HIPCHK(hipMemcpyAsync(out_host, c->d_kfPoints, (size_t)npix * 12, hipMemcpyDeviceToHost, c->stream));
   HIPCHK(hipStreamSynchronize(c->stream));
@@ -218,7 +218,7 @@ extern "C" int lsdhip_cloud_create(lsdhip_ctx* c, int64_t capacity_points, int m
   if (!c || !out || capacity_points < 0 || max_keyframes <= 0) return LSDHIP_E_ARG;
   LSD_CTX_LOCK(c);
   HIPCHK(hipSetDevice(c->device));
-  lsdhip_cloud* q = new lsdhip_cloud();
+  std::unique_ptr<lsdhip_cloud> q(new lsdhip_cloud());
   q->ctx = c;
   q->capacity = capacity_points;
   q->maxSeg = max_keyframes;
@@ -232,8 +232,7 @@ extern "C" int lsdhip_cloud_create(lsdhip_ctx* c, int64_t capacity_points, int m
   take((size_t)q->nchunks * 256);
   take((size_t)q->nchunks * sizeof(int));
   take((size_t)q->nchunks * sizeof(long long));
-  hipError_t e = hipMalloc((void**)&q->base, cloud_align(off));
-  if (e != hipSuccess) { lsd_set_error("lsdhip_cloud_create: hipMalloc(%zu) failed: %s", off, hipGetErrorString(e)); delete q; return LSDHIP_E_HIP; }
+  if (int rc = lsd_dev_alloc(q->base, cloud_align(off))) return rc;
   q->d_pts = (float4*)(q->base + offs[0]);
   q->d_state = (CloudState*)(q->base + offs[1]);
   q->d_segs = (CloudSeg*)(q->base + offs[2]);
@@ -242,10 +241,9 @@ extern "C" int lsdhip_cloud_create(lsdhip_ctx* c, int64_t capacity_points, int m
   q->d_chunkOff = (long long*)(q->base + offs[5]);
   const hipStream_t ms = lsd_map_stream(c);
   // the guard behind the buffer keeps this fill for the life of the cloud: nothing is ever written beyond `capacity`
-  e = hipMemsetAsync(q->d_pts + capacity_points, 0xFF, (size_t)LSDHIP_CLOUD_GUARD_POINTS * sizeof(float4), ms);
-  if (e == hipSuccess) e = hipMemsetAsync(q->d_state, 0, sizeof(CloudState), ms);
-  if (e != hipSuccess) { lsd_set_error("lsdhip_cloud_create: %s", hipGetErrorString(e)); (void)hipFree(q->base); delete q; return LSDHIP_E_HIP; }
-  *out = q;
+  HIPCHK(hipMemsetAsync(q->d_pts + capacity_points, 0xFF, (size_t)LSDHIP_CLOUD_GUARD_POINTS * sizeof(float4), ms));
+  HIPCHK(hipMemsetAsync(q->d_state, 0, sizeof(CloudState), ms));
+  *out = q.release();
   return LSDHIP_OK;
 }
 
@@ -255,7 +253,6 @@ extern "C" void lsdhip_cloud_destroy(lsdhip_cloud* q) {
   LSD_CTX_LOCK(c);
   (void)hipSetDevice(c->device);
   (void)lsd_sync_all(c);      // appends still queued read and write the allocation
-  (void)hipFree(q->base);
   delete q;
 }
 

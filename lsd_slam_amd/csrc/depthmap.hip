@@ -1643,12 +1643,9 @@ static int map_call_end(lsdhip_ctx* c) {
   return LSDHIP_OK;
 }
 
-static int alloc_planes(HypPlanes& p, size_t n, void** base_out) {
-  char* base = nullptr;
-  size_t bytes = n * 29 + 8 * 256;
-  HIPCHK(hipMalloc((void**)&base, bytes));
-  HIPCHK(hipMemset(base, 0, bytes));
-  HIPCHK(hipStreamSynchronize(nullptr));   // (hipMemset runs on the null stream, which this library's non-blocking streams do not wait for)
+static int alloc_planes(HypPlanes& p, size_t n, LsdDev<char>& arena) {
+  if (int rc = lsd_dev_alloc_zeroed(arena, n * 29 + 8 * 256)) return rc;
+  char* base = arena;
   size_t off = 0;
   p.blacklisted = lsd_g((int32_t*)(base + off)); off = up256(off + n * 4);
   p.nextID = lsd_g((float*)(base + off)); off = up256(off + n * 4);
@@ -1658,50 +1655,43 @@ static int alloc_planes(HypPlanes& p, size_t n, void** base_out) {
   p.idepth_s = lsd_g((float*)(base + off)); off = up256(off + n * 4);
   p.var_s = lsd_g((float*)(base + off)); off = up256(off + n * 4);
   p.valid = lsd_g((uint8_t*)(base + off));
-  *base_out = base;
   return LSDHIP_OK;
 }
 
 static int depth_create_impl(lsdhip_ctx* c, lsdhip_depthmap* dm) {
   size_t n = (size_t)c->w * c->h;
-  int rc = alloc_planes(dm->cur, n, &dm->bases[0]);
-  if (rc) return rc;
-  rc = alloc_planes(dm->oth, n, &dm->bases[1]);
-  if (rc) return rc;
-  HIPCHK(hipMalloc((void**)&dm->d_validSnap, n));
-  dm->bases[2] = dm->d_validSnap;
-  HIPCHK(hipMemset(dm->d_validSnap, 0, n));
-  HIPCHK(hipStreamSynchronize(nullptr));
-  HIPCHK(hipMalloc((void**)&dm->d_slotCount, n * 4));
-  HIPCHK(hipMalloc((void**)&dm->d_slots, n * 4 * PROP_SLOT_CAP));
-  HIPCHK(hipMalloc((void**)&dm->d_ovfHead, n * 4));
-  HIPCHK(hipMalloc((void**)&dm->d_ovf, n * sizeof(int2)));
-  HIPCHK(hipMalloc((void**)&dm->d_cand, n * 16));
-  HIPCHK(hipMalloc((void**)&dm->d_flags, 64));
+  if (int rc = alloc_planes(dm->cur, n, dm->arenas[0])) return rc;
+  if (int rc = alloc_planes(dm->oth, n, dm->arenas[1])) return rc;
+  if (int rc = lsd_dev_alloc_zeroed(dm->arenas[2], n)) return rc;
+  dm->d_validSnap = (uint8_t*)dm->arenas[2].get();
+  if (int rc = lsd_dev_alloc(dm->d_slotCount, n)) return rc;
+  if (int rc = lsd_dev_alloc(dm->d_slots, n * PROP_SLOT_CAP)) return rc;
+  if (int rc = lsd_dev_alloc(dm->d_ovfHead, n)) return rc;
+  if (int rc = lsd_dev_alloc(dm->d_ovf, n)) return rc;
+  if (int rc = lsd_dev_alloc(dm->d_cand, n)) return rc;
+  if (int rc = lsd_dev_alloc(dm->d_flags, 16)) return rc;
   HIPCHK(hipMemsetAsync(dm->d_flags, 0, 64, lsd_map_stream(c)));
   const int nb = (int)px_blocks(c);
   const int ntiles = ((c->w + 31) / 32) * tile_rows(c);   // partials of the fused regulariser: one pair per 32x8 tile
   // (sum, count) partials: [16, ...) the setDepth / rescale passes of the single calls; the keyframe change in shared launches keeps
   // three sets alive at once (old keyframe's setDepth | rescale sums | new keyframe's setDepth)
   dm->redStride = (size_t)2 * (nb > ntiles ? nb : ntiles);
-  HIPCHK(hipMalloc((void**)&dm->d_red, (3 * dm->redStride + 16) * sizeof(double)));
+  if (int rc = lsd_dev_alloc(dm->d_red, 3 * dm->redStride + 16)) return rc;
   // K7 scratch is clean at rest (k_prop_resolve / the reader of the flags leave it so)
   HIPCHK(hipMemsetAsync(dm->d_slotCount, 0, n * 4, lsd_map_stream(c)));
   HIPCHK(hipMemsetAsync(dm->d_ovfHead, 0xFF, n * 4, lsd_map_stream(c)));
   dm->propClean = true;
-  HIPCHK(hipHostMalloc((void**)&dm->h_red, 16 * sizeof(double), hipHostMallocMapped));
-  return LSDHIP_OK;
+  return lsd_pinned_alloc(dm->h_red, 16, hipHostMallocMapped);
 }
 extern "C" int lsdhip_depth_create(lsdhip_ctx* c, lsdhip_depthmap** out) {
   if (!c || !out) return LSDHIP_E_ARG;
   HIPCHK(hipSetDevice(c->device));
   LSD_CTX_LOCK(c);
-  lsdhip_depthmap* dm = new lsdhip_depthmap();
+  std::unique_ptr<lsdhip_depthmap> dm(new lsdhip_depthmap());
   dm->ctx = c;
-  c->depthmaps.push_back(dm);
-  const int rc = depth_create_impl(c, dm);
-  if (rc) { lsdhip_depth_destroy(dm); return rc; }   // frees whatever was allocated (null pointers are fine)
-  *out = dm;
+  if (int rc = depth_create_impl(c, dm.get())) return rc;
+  c->depthmaps.push_back(dm.get());
+  *out = dm.release();
   return LSDHIP_OK;
 }
 // a frame is going away: no depth map may keep it as its active keyframe (a later frame can get the same heap address)
@@ -1718,15 +1708,6 @@ extern "C" void lsdhip_depth_destroy(lsdhip_depthmap* dm) {
   }
   (void)hipSetDevice(dm->ctx->device);
   (void)hipStreamSynchronize(lsd_map_stream(dm->ctx));
-  for (int i = 0; i < 3; i++) (void)hipFree(dm->bases[i]);  // plane pointers get swapped around; free the arenas
-  (void)hipFree(dm->d_slotCount);
-  (void)hipFree(dm->d_slots);
-  (void)hipFree(dm->d_ovfHead);
-  (void)hipFree(dm->d_ovf);
-  (void)hipFree(dm->d_cand);
-  (void)hipFree(dm->d_flags);
-  (void)hipFree(dm->d_red);
-  (void)hipHostFree(dm->h_red);
 #ifdef LSD_PHASE_TRACE
   if (const char* path = getenv("LSDHIP_OBS_TRACE_FILE")) {
     if (dm->d_obs_trace) {
@@ -1740,11 +1721,6 @@ extern "C" void lsdhip_depth_destroy(lsdhip_depthmap* dm) {
     }
   }
 #endif
-  for (int i = 0; i < 8; i++) if (dm->ev[i][0]) { (void)hipEventDestroy(dm->ev[i][0]); (void)hipEventDestroy(dm->ev[i][1]); }
-  if (dm->d_stage) (void)hipFree(dm->d_stage);
-  if (dm->h_stage) (void)hipHostFree(dm->h_stage);
-  if (dm->d_obsCounters) (void)hipFree(dm->d_obsCounters);
-  if (dm->d_obsQueue) (void)hipFree(dm->d_obsQueue);
   delete dm;
 }
 extern "C" int lsdhip_depth_is_valid(lsdhip_depthmap* dm) { return dm && dm->activeKeyFrame != nullptr; }
@@ -1980,15 +1956,14 @@ static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n, bool countWo
     const size_t need = refsBytes + sizeof(int) * byIDCount;
     HIPCHK(hipStreamSynchronize(lsd_map_stream(c)));
     if (need > dm->stage_bytes) {
-      if (dm->h_stage) { (void)hipHostFree(dm->h_stage); dm->h_stage = nullptr; }   // never leave a freed pointer behind
-      if (dm->d_stage) { (void)hipFree(dm->d_stage); dm->d_stage = nullptr; }
-      dm->stage_bytes = 0;
       const size_t want = need > 65536 ? need * 2 : 65536;
-      HIPCHK(hipHostMalloc((void**)&dm->h_stage, want, hipHostMallocDefault));
-      HIPCHK(hipMalloc((void**)&dm->d_stage, want));
+      LsdPinned<char> h; LsdDev<char> d;      // (the new pair exists before the old one goes)
+      if (int rc = lsd_pinned_alloc(h, want, hipHostMallocDefault)) return rc;
+      if (int rc = lsd_dev_alloc(d, want)) return rc;
+      dm->h_stage = std::move(h); dm->d_stage = std::move(d);
       dm->stage_bytes = want;
     }
-    StereoRef* hrefs = (StereoRef*)dm->h_stage;
+    StereoRef* hrefs = (StereoRef*)dm->h_stage.get();
     int* byID = (int*)(dm->h_stage + refsBytes);
     for (int i = 0; i < n; i++) {
       prepare_stereo(dm, refs[i], hrefs[i]);
@@ -1996,7 +1971,7 @@ static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n, bool countWo
     }
     HIPCHK(hipMemcpyAsync(dm->d_stage, dm->h_stage, refsBytes + sizeof(int) * nByID, hipMemcpyHostToDevice, lsd_map_stream(c)));
     memset((void*)&a, 0, sizeof(a));
-    a.refs = lsd_g((const StereoRef*)dm->d_stage);
+    a.refs = lsd_g((const StereoRef*)dm->d_stage.get());
     a.refByID = lsd_g((const int*)(dm->d_stage + refsBytes));
     a.nByID = (int)nByID;
     a.byIDOffset = offset;
@@ -2006,9 +1981,9 @@ static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n, bool countWo
 #ifdef LSD_PHASE_TRACE
   {
     const size_t words = (size_t)((c->w + 31) / 32) * tile_rows(c) * 16;
-    if (!dm->d_obs_trace) HIPCHK(hipMalloc((void**)&dm->d_obs_trace, words * 8));
+    if (!dm->d_obs_trace) { if (int rc = lsd_dev_alloc(dm->d_obs_trace, words)) return rc; }
     HIPCHK(hipMemsetAsync(dm->d_obs_trace, 0, words * 8, lsd_map_stream(c)));
-    a.trace = (decltype(a.trace))dm->d_obs_trace;
+    a.trace = (decltype(a.trace))dm->d_obs_trace.get();
     dm->obs_trace_words = words;
   }
 #endif
@@ -2024,7 +1999,7 @@ static int observe(lsdhip_depthmap* dm, lsdhip_frame** refs, int n, bool countWo
       // searches and walk steps, per wave, summed behind the launch (bench.py: stereo_steps_per_s,
       // roofline_depth on the bytes of the pixels that were actually searched)
       if (!dm->d_obsCounters) {
-        HIPCHK(hipMalloc((void**)&dm->d_obsCounters, (size_t)nwaves * 16 + 32));
+        if (int rc = lsd_dev_alloc(dm->d_obsCounters, (size_t)nwaves * 2 + 4)) return rc;
         dm->d_obsAcc = dm->d_obsCounters + (size_t)nwaves * 2;
         HIPCHK(hipMemsetAsync(dm->d_obsAcc, 0, 32, lsd_map_stream(c)));
         dm->obsCounterWaves = nwaves;
@@ -2148,7 +2123,7 @@ static int timing_begin(lsdhip_depthmap* dm, int kind) {
     HIPCHK(hipEventSynchronize(dm->ev[i][1]));
     timing_collect(dm, false);
   }
-  if (!dm->ev[i][0]) { HIPCHK(hipEventCreate(&dm->ev[i][0])); HIPCHK(hipEventCreate(&dm->ev[i][1])); }
+  if (!dm->ev[i][1]) { if (int rc = lsd_event_create(dm->ev[i][0])) return rc; if (int rc = lsd_event_create(dm->ev[i][1])) return rc; }
   dm->ev_kind[i] = kind;
   HIPCHK(hipEventRecord(dm->ev[i][0], lsd_map_stream(dm->ctx)));
   return i;
@@ -2346,7 +2321,7 @@ static int update_batch_observe(lsdhip_ctx* c, int n, const ObserveArgs* dobs, c
   if (form.split) {
     unsigned long long* acc = nullptr;
     if (bp >= 0) {     // a sampled call also counts its searches and walk steps
-      if (!c->d_obsBatchAcc) { HIPCHK(hipMalloc((void**)&c->d_obsBatchAcc, 66 * 8)); HIPCHK(hipMemsetAsync(c->d_obsBatchAcc, 0, 66 * 8, ms)); }
+      if (!c->d_obsBatchAcc) { if (int rc = lsd_dev_alloc(c->d_obsBatchAcc, 66)) return rc; HIPCHK(hipMemsetAsync(c->d_obsBatchAcc, 0, 66 * 8, ms)); }
       acc = c->d_obsBatchAcc;
     }
     if (form.candidates) hipLaunchKernelGGL(k_observe_select_cand_batch, dim3((lsd_gradcand_groups(c->w * c->h) + 3) / 4, 1, n), dim3(256), 0, ms, dobs);
@@ -2409,7 +2384,7 @@ extern "C" int lsdhip_depth_update_batch(int n, lsdhip_depthmap** maps, lsdhip_f
   form.walkWorkgroups = form.split ? LSD_OBS_WALK_WAVES : 0;
   if (form.split)
     for (int j = 0; j < n; j++)
-      if (!maps[j]->d_obsQueue) HIPCHK(hipMalloc((void**)&maps[j]->d_obsQueue, (size_t)c->w * c->h * sizeof(float4)));
+      if (!maps[j]->d_obsQueue) { if (int rc = lsd_dev_alloc(maps[j]->d_obsQueue, (size_t)c->w * c->h)) return rc; }
   const UpdateRecord L(n);
   void *host = nullptr, *dev = nullptr;
   if (int rc = lsd_args_begin(c, L.bytes, &host, &dev)) return rc;

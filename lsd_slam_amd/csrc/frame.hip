@@ -1,5 +1,5 @@
-// Context + device-resident Frame: image / gradient / maxGradient / inverse-depth pyramids (K-pyr-*), point-cloud
-// export (K0), ground-truth depth initialisation.  gfx950 only.
+// Device-resident Frame: image / gradient / maxGradient / inverse-depth pyramids (K-pyr-*), point-cloud
+// export (K0), ground-truth depth initialisation.  gfx950 only.  (The context the frames live on: context.hip.)
 //
 // Reference behaviour restated on the device:
 //   Frame::Frame                 C/DataStructures/Frame.cpp:35-48    uint8 -> float copy (no scaling)
@@ -13,9 +13,6 @@
 //   TrackingReference::makePointCloud C/Tracking/TrackingReference.cpp:96-147
 // Unwritten pool memory of the reference is defined as 0 here (rows 0 / h-1 of gradients etc.).
 #include <algorithm>
-#include <atomic>
-#include <chrono>
-#include <mutex>
 #include "lsdhip_internal.hpp"
 
 // ---------------------------------------------------------------------------------------------------------
@@ -597,357 +594,6 @@ __global__ __launch_bounds__(256) void k_pc_write(const float* __restrict__ id, 
 // ---------------------------------------------------------------------------------------------------------
 // host
 // ---------------------------------------------------------------------------------------------------------
-#define LSD_FLAG_WGS 16
-#ifdef LSD_DEVTOOLS
-static void trace_dump(lsdhip_ctx* c);
-#endif
-extern "C" void lsdhip_default_params(lsdhip_params* p) {
-  p->minUseGrad = 5;
-  p->cameraPixelNoise2 = 4 * 4;
-  p->depthSmoothingFactor = 1;
-  p->allowNegativeIdepths = 1;
-  p->useSubpixelStereo = 1;
-  p->useAffineLightningEstimation = 1;
-  p->KFDistWeight = 4;
-  p->KFUsageWeight = 3;
-}
-
-extern "C" int lsdhip_ctx_create(int device, int w, int h, const float K[4], const lsdhip_params* params, lsdhip_ctx** out) {
-  if (!out || !K || w <= 0 || h <= 0 || (w % 16) != 0 || (h % 16) != 0) {
-    lsd_set_error("lsdhip_ctx_create: image dimensions must be positive multiples of 16 (got %dx%d)", w, h);
-    return LSDHIP_E_ARG;
-  }
-  int ndev = 0;
-  HIPCHK(hipGetDeviceCount(&ndev));
-  if (device < 0 || device >= ndev) {
-    lsd_set_error("lsdhip_ctx_create: device %d not available (%d visible)", device, ndev);
-    return LSDHIP_E_HIP;
-  }
-  HIPCHK(hipSetDevice(device));
-  lsdhip_ctx* c = new lsdhip_ctx();
-  LSD_CTX_LOCK(c);
-  c->device = device;
-  c->w = w;
-  c->h = h;
-  if (params) c->params = *params; else lsdhip_default_params(&c->params);
-  // Frame::initialize (Frame.cpp:397-459)
-  float fx[LSD_LEVELS], fy[LSD_LEVELS], cx[LSD_LEVELS], cy[LSD_LEVELS];
-  fx[0] = K[0]; fy[0] = K[1]; cx[0] = K[2]; cy[0] = K[3];
-  for (int l = 0; l < LSD_LEVELS; l++) {
-    c->wl[l] = w >> l;
-    c->hl[l] = h >> l;
-    if (l > 0) {
-      fx[l] = fx[l - 1] * 0.5;
-      fy[l] = fy[l - 1] * 0.5;
-      cx[l] = (cx[0] + 0.5) / ((int)1 << l) - 0.5;
-      cy[l] = (cy[0] + 0.5) / ((int)1 << l) - 0.5;
-    }
-    float Kl[9] = {fx[l], 0.f, cx[l], 0.f, fy[l], cy[l], 0.f, 0.f, 1.f};
-    float Ki[9];
-    lsdm::inverse3_eigen(Kl, Ki);
-    c->intr[l] = {fx[l], fy[l], cx[l], cy[l], Ki[0], Ki[4], Ki[2], Ki[5]};
-    if (l == 0) { memcpy(c->K0, Kl, sizeof(Kl)); memcpy(c->K0inv, Ki, sizeof(Ki)); }
-  }
-  // (the tracking stream at the highest queue priority: 36.3 k against 37.1 k frames/s at S = 32, profiles/r05_notes.md — not kept)
-  HIPCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  HIPCHK(hipEventCreate(&c->ev_a));
-  HIPCHK(hipEventCreate(&c->ev_b));
-  HIPCHK(hipHostMalloc((void**)&c->h_slots, LSD_NUM_SLOTS * sizeof(DeferredSlot), hipHostMallocMapped));
-  memset(c->h_slots, 0, LSD_NUM_SLOTS * sizeof(DeferredSlot));
-  *out = c;
-  return LSDHIP_OK;
-}
-// Developer instrumentation (LSDHIP_HOST_TRACE=1): host-side time between consecutive marks of the calling thread, summed per mark
-// id and printed when a context is destroyed.  Costs one steady_clock read per mark when on, one branch when off.
-#ifdef LSD_DEVTOOLS
-static const bool g_hostTraceOn = getenv("LSDHIP_HOST_TRACE") != nullptr;
-static long long g_htNs[32], g_htN[32], g_htHist[32][9];
-static thread_local long long g_htLast = 0;
-extern "C" void lsdhip_host_mark(int k) {
-  if (!g_hostTraceOn) return;
-  const long long now = std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now().time_since_epoch()).count();
-  if (k > 0 && k < 32 && g_htLast) {
-    const long long d = now - g_htLast;
-    g_htNs[k] += d; g_htN[k]++;
-    static const long long edges[8] = {2000, 5000, 10000, 20000, 50000, 100000, 200000, 500000};
-    int b = 0;
-    while (b < 8 && d >= edges[b]) b++;
-    g_htHist[k][b]++;
-  }
-  g_htLast = now;
-}
-static void host_trace_print() {
-  if (!g_hostTraceOn) return;
-  for (int k = 0; k < 32; k++)
-    if (g_htN[k]) {
-      fprintf(stderr, "HOSTTRACE mark %2d: n %6lld  mean %7.2f us   <2 <5 <10 <20 <50 <100 <200 <500 >=500 us:", k, g_htN[k], g_htNs[k] / 1e3 / g_htN[k]);
-      for (int b = 0; b < 9; b++) fprintf(stderr, " %lld", g_htHist[k][b]);
-      fprintf(stderr, "\n");
-    }
-}
-#else
-extern "C" void lsdhip_host_mark(int) {}      // (the C++ loop of include/lsd_slam_hip.hpp marks its phases: a no-op in the default library)
-static void host_trace_print() {}
-#endif
-extern "C" void lsdhip_ctx_destroy(lsdhip_ctx* c) {
-  if (!c) return;
-  host_trace_print();
-  (void)hipSetDevice(c->device);
-  (void)hipStreamSynchronize(c->stream);
-  if (c->mstream) (void)hipStreamSynchronize(c->mstream);
-#ifdef LSD_DEVTOOLS
-  trace_dump(c);
-#endif
-  if (c->d_sums) (void)hipFree(c->d_sums);
-  if (c->mstream) {
-    for (int i = 0; i < LSD_EVR; i++) if (c->mEv[i]) (void)hipEventDestroy(c->mEv[i]);
-    (void)hipStreamDestroy(c->mstream);
-  }
-  for (int i = 0; i < lsdhip_ctx::MAX_LANES; i++) if (c->lanes[i]) { (void)hipStreamSynchronize(c->lanes[i]); (void)hipEventDestroy(c->lane_done[i]); (void)hipStreamDestroy(c->lanes[i]); }
-  if (c->lane_fork) (void)hipEventDestroy(c->lane_fork);
-  if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipEventDestroy(c->aux_fork); (void)hipEventDestroy(c->aux_done); (void)hipStreamDestroy(c->aux_stream); }
-  for (void* a : c->free_arenas) (void)hipFree(a);
-  for (hipEvent_t e : c->prof_events) (void)hipEventDestroy(e);
-  if (c->h_slots) (void)hipHostFree(c->h_slots);
-  if (c->args.h) (void)hipHostFree(c->args.h);
-  if (c->args.d) (void)hipFree(c->args.d);
-  for (hipEvent_t e : c->args.ev) if (e) (void)hipEventDestroy(e);
-  for (int i = 0; i < LSD_BPROF_SLOTS; i++) if (c->bprof[i].a) { (void)hipEventDestroy(c->bprof[i].a); (void)hipEventDestroy(c->bprof[i].b); }
-  if (c->d_obsBatchAcc) (void)hipFree(c->d_obsBatchAcc);
-  if (c->d_gtStage) (void)hipFree(c->d_gtStage);
-  if (c->d_kfPoints) (void)hipFree(c->d_kfPoints);
-  if (c->d_plotStage) (void)hipFree(c->d_plotStage);
-  if (c->d_flagArrive) (void)hipFree(c->d_flagArrive);
-  if (c->d_gate) (void)hipFree(c->d_gate);
-  if (c->ev_a) (void)hipEventDestroy(c->ev_a);
-  if (c->ev_b) (void)hipEventDestroy(c->ev_b);
-  (void)hipStreamDestroy(c->stream);
-  delete c;
-}
-extern "C" void* lsdhip_ctx_stream(lsdhip_ctx* c) { return c ? (void*)c->stream : nullptr; }
-extern "C" int lsdhip_ctx_alloc_dev(lsdhip_ctx* c, size_t bytes, void** out) {
-  if (!c || !out || bytes == 0) return LSDHIP_E_ARG;
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMalloc(out, bytes));
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_free_dev(lsdhip_ctx* c, void* p) {
-  if (!c) return LSDHIP_E_ARG;
-  if (!p) return LSDHIP_OK;
-  HIPCHK(hipSetDevice(c->device));
-  if (int rc = lsd_sync_all(c)) return rc;
-  HIPCHK(hipFree(p));
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_synchronize(lsdhip_ctx* c) {
-  if (!c) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  for (int i = 0; i < LSD_NUM_SLOTS; i++) {   // pick up every deferred result
-    if (c->slot_stats_owner[i]) { int rc = lsd_frame_resolve(c->slot_stats_owner[i]); if (rc) return rc; }
-    if (c->slot_rescale_owner[i]) { int rc = lsd_frame_resolve(c->slot_rescale_owner[i]); if (rc) return rc; }
-  }
-  if (c->aux_stream) HIPCHK(hipStreamSynchronize(c->aux_stream));
-  return lsd_sync_all(c);
-}
-// ---- pipelined contexts: tracking stream beside mapping stream ---------------------------------------------------------------------
-extern "C" int lsdhip_ctx_set_pipeline(lsdhip_ctx* c, int on) {
-  if (!c) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  if (int rc = lsd_sync_all(c)) return rc;
-  if (on && !c->mstream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->mstream, hipStreamNonBlocking));
-    for (int i = 0; i < LSD_EVR; i++) {
-      HIPCHK(hipEventCreateWithFlags(&c->mEv[i], hipEventDisableTiming));
-    }
-  }
-  if (!on && c->pipeline) {
-    // back to one stream: everything is drained, so every recorded point counts as passed and waited for
-    c->mDoneSeq = c->tWaitedM = c->mSeq;
-  }
-  c->pipeline = on != 0;
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_pipeline(lsdhip_ctx* c) { return c ? (c->pipeline ? 1 : 0) : LSDHIP_E_ARG; }
-extern "C" void* lsdhip_ctx_map_stream(lsdhip_ctx* c) { return c ? (void*)lsd_map_stream(c) : nullptr; }
-int lsd_sync_all(lsdhip_ctx* c) {
-  if (c->pipeline && !c->pendingMerges.empty()) { if (int rc = lsd_flush_merges(c)) return rc; }
-  for (int i = 0; i < c->lanes_open; i++) if (c->lane_used[i]) HIPCHK(hipStreamSynchronize(c->lanes[i]));   // (inside an open lane region)
-  if (c->mstream) {
-    HIPCHK(hipStreamSynchronize(c->mstream));
-    c->mDoneSeq = c->mSeq;
-  }
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return LSDHIP_OK;
-}
-// Tracking -> mapping ordering.  A mapping-stream operation that consumes a tracking job's results is queued by the host AFTER it has
-// seen the job's `done` (pinned memory, written behind a system-scope fence by the finishing launch); what the operation reads — the
-// frame's mask, and through the host the pose — was written by launches that had completed before the finishing launch started, and
-// the launches still queued behind it touch only the tracker's own state.  So no event is recorded on the tracking stream: a record
-// behind every job is a barrier packet in the queue the launch chain runs through (the first form of the pipeline had one, plus a
-// hipStreamWaitEvent on the mapping stream; profiles/r04_notes.md).
-int lsd_m_begin(lsdhip_ctx* c) {
-  if (!c->pendingMerges.empty()) return lsd_flush_merges(c);
-  return LSDHIP_OK;
-}
-#ifdef LSD_DEVTOOLS
-// Experiment: kernels that touch nothing but their own buffer, queued on the mapping stream right when a tracking job starts.
-// kind 1: memory streaming (32 MB read-modify-write), 2: LDS-heavy workgroups (9.6 KB each, like k_reg_fused), 3: ALU spin.
-static const int g_pipeDummy = getenv("LSDHIP_PIPE_DUMMY") ? atoi(getenv("LSDHIP_PIPE_DUMMY")) : 0;
-__global__ __launch_bounds__(256) void k_dummy_stream(float* p, size_t n) {
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) p[i] = p[i] * 1.0001f + 1.0f;
-}
-__global__ __launch_bounds__(256) void k_dummy_lds(float* p) {
-  __shared__ float s[2400];
-  for (int i = threadIdx.x; i < 2400; i += 256) s[i] = (float)(i + blockIdx.x);
-  __syncthreads();
-  float acc = 0;
-  for (int r = 0; r < 40; r++) for (int i = threadIdx.x; i < 2400; i += 256) acc += s[(i * 7 + r) % 2400];
-  p[(size_t)blockIdx.x * 256 + threadIdx.x] = acc;
-}
-// kind 4: workgroup barriers, no LDS; kind 5: LDS, no barrier (64-lane workgroups, lane-private slots); kind 6: like 2 with 40 KB
-__global__ __launch_bounds__(256) void k_dummy_barrier(float* p) {
-  float acc = (float)threadIdx.x;
-  for (int r = 0; r < 400; r++) { acc = acc * 1.0001f + 0.5f; __syncthreads(); }
-  p[(size_t)blockIdx.x * 256 + threadIdx.x] = acc;
-}
-__global__ __launch_bounds__(64) void k_dummy_lds_nobar(float* p) {
-  __shared__ float s[2400];
-  float acc = 0;
-  for (int r = 0; r < 60; r++) {
-    for (int i = threadIdx.x; i < 2400; i += 64) s[i] = (float)(i + r);
-    for (int i = threadIdx.x; i < 2400; i += 64) acc += s[i];
-  }
-  p[(size_t)blockIdx.x * 64 + threadIdx.x] = acc;
-}
-__global__ __launch_bounds__(256) void k_dummy_lds_big(float* p) {
-  __shared__ float s[10000];
-  for (int i = threadIdx.x; i < 10000; i += 256) s[i] = (float)(i + blockIdx.x);
-  __syncthreads();
-  float acc = 0;
-  for (int r = 0; r < 10; r++) for (int i = threadIdx.x; i < 10000; i += 256) acc += s[(i * 7 + r) % 10000];
-  p[(size_t)blockIdx.x * 256 + threadIdx.x] = acc;
-}
-__global__ __launch_bounds__(64) void k_dummy_spin(float* p, long long spin) {
-  long long t0 = clock64();
-  float a = (float)threadIdx.x;
-  while (clock64() - t0 < spin) a = a * 1.0001f + 0.5f;
-  p[(size_t)blockIdx.x * 64 + threadIdx.x] = a;
-}
-int lsd_pipe_dummy(lsdhip_ctx* c) {
-  if (!g_pipeDummy || !c->pipeline) return LSDHIP_OK;
-  static float* buf = nullptr;
-  const size_t n = 8u << 20;
-  if (!buf) { HIPCHK(hipMalloc((void**)&buf, n * 4)); HIPCHK(hipMemset(buf, 0, n * 4)); HIPCHK(hipStreamSynchronize(nullptr)); }
-  for (int rep = 0; rep < 4; rep++) {
-    if (g_pipeDummy == 1) hipLaunchKernelGGL(k_dummy_stream, dim3(2048), dim3(256), 0, c->mstream, buf, n);
-    else if (g_pipeDummy == 2) hipLaunchKernelGGL(k_dummy_lds, dim3(1200), dim3(256), 0, c->mstream, buf);
-    else if (g_pipeDummy == 4) hipLaunchKernelGGL(k_dummy_barrier, dim3(1200), dim3(256), 0, c->mstream, buf);
-    else if (g_pipeDummy == 5) hipLaunchKernelGGL(k_dummy_lds_nobar, dim3(4800), dim3(64), 0, c->mstream, buf);
-    else if (g_pipeDummy == 6) hipLaunchKernelGGL(k_dummy_lds_big, dim3(1200), dim3(256), 0, c->mstream, buf);
-    else hipLaunchKernelGGL(k_dummy_spin, dim3(4800), dim3(64), 0, c->mstream, buf, 20000LL);
-  }
-  return LSDHIP_OK;
-}
-#endif   // LSD_DEVTOOLS
-long long lsd_m_record(lsdhip_ctx* c) {
-  if (!c->pipeline) return 0;
-  if (c->lanes_open) { c->lane_record_pending = true; return c->mSeq + 1; }   // recorded once, where the lanes join (lsdhip_ctx_lanes_end)
-  const long long s = c->mSeq + 1;
-  if (hipEventRecord(c->mEv[s % LSD_EVR], c->mstream) != hipSuccess) { lsd_set_error("hipEventRecord on the mapping stream failed"); return LSDHIP_E_HIP; }
-  c->mSeq = s;
-  return s;
-}
-int lsd_t_wait_m(lsdhip_ctx* c, long long seq) {
-  if (!c->pipeline || seq <= c->tWaitedM || seq <= c->mDoneSeq) return LSDHIP_OK;
-  if (seq > c->mSeq) {
-    // a sequence number beyond the last record point: handed out inside an open lane region (recorded where the lanes join) — there is
-    // no event to wait for yet
-    if (c->lanes_open) { lsd_set_error("tracking job depends on mapping work of an open lane region (call lsdhip_ctx_lanes_end first)"); return LSDHIP_E_STATE; }
-    seq = c->mSeq;
-  }
-  // the ring slot holds the event of `seq` or, once the ring has wrapped, of a later point of the in-order stream: either orders us
-  HIPCHK(hipStreamWaitEvent(c->stream, c->mEv[seq % LSD_EVR], 0));
-  c->tWaitedM = seq;
-  return LSDHIP_OK;
-}
-bool lsd_m_done(lsdhip_ctx* c, long long seq) {
-  if (seq <= c->mDoneSeq) return true;
-  if (seq > c->mSeq) return false;
-  if (hipEventQuery(c->mEv[seq % LSD_EVR]) != hipSuccess) return false;
-  // (after a wrap the slot's event is a later point: then more than `seq` is done, which is still true of `seq`)
-  if (c->mSeq - seq < LSD_EVR) c->mDoneSeq = seq;
-  return true;
-}
-#ifdef LSD_DEVTOOLS
-static const char* g_traceSums = getenv("LSDHIP_TRACE_SUMS");
-#define LSD_TRACE_SLOTS 65536
-__global__ __launch_bounds__(256) void k_trace_sum(const uint32_t* __restrict__ p, size_t nwords, unsigned long long* out) {
-  unsigned long long acc = 0;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < nwords; i += (size_t)gridDim.x * 256)
-    acc += (unsigned long long)p[i] * (unsigned long long)(i * 2654435761ull + 1ull);
-  for (int off = 32; off > 0; off >>= 1) acc += __shfl_xor(acc, off);
-  if ((threadIdx.x & 63) == 0) atomicAdd(out, acc);
-}
-void lsd_trace_sum(lsdhip_ctx* c, hipStream_t s, int kind, int id, const void* p, size_t bytes) {
-  if (!g_traceSums) return;
-  if (!c->d_sums) { if (hipMalloc((void**)&c->d_sums, LSD_TRACE_SLOTS * 8) != hipSuccess) return; (void)hipMemset(c->d_sums, 0, LSD_TRACE_SLOTS * 8); (void)hipStreamSynchronize(nullptr); }
-  const size_t slot = c->sums_meta.size() / 2;
-  if (slot >= LSD_TRACE_SLOTS) return;
-  c->sums_meta.push_back(kind); c->sums_meta.push_back(id);
-  c->sums_host.push_back(0);
-  const size_t nwords = bytes / 4;
-  int grid = (int)((nwords + 255) / 256); if (grid > 64) grid = 64; if (grid < 1) grid = 1;
-  hipLaunchKernelGGL(k_trace_sum, dim3(grid), dim3(256), 0, s, (const uint32_t*)p, nwords, c->d_sums + slot);
-}
-void lsd_trace_val(lsdhip_ctx* c, int kind, int id, unsigned long long v) {
-  if (!g_traceSums) return;
-  if (c->sums_meta.size() / 2 >= LSD_TRACE_SLOTS) return;
-  c->sums_meta.push_back(-kind); c->sums_meta.push_back(id);
-  c->sums_host.push_back(v);
-}
-static void trace_dump(lsdhip_ctx* c) {
-  if (!g_traceSums || c->sums_meta.empty()) return;
-  const size_t n = c->sums_meta.size() / 2;
-  std::vector<unsigned long long> h(n, 0);
-  if (c->d_sums) (void)hipMemcpy(h.data(), c->d_sums, n * 8, hipMemcpyDeviceToHost);
-  if (FILE* f = fopen(g_traceSums, "a")) {
-    for (size_t i = 0; i < n; i++) {
-      const int kind = c->sums_meta[2 * i];
-      fprintf(f, "%d %d %016llx\n", kind < 0 ? -kind : kind, c->sums_meta[2 * i + 1], kind < 0 ? c->sums_host[i] : h[i]);
-    }
-    fclose(f);
-  }
-}
-// Developer hook (LSDHIP_PIPE_GATE=1): forces the overlap the pipelined mode is about, whatever the host's pace — a DepthMap::updateKeyframe
-// queued on the mapping stream holds (a one-lane spin, bounded) until the NEXT tracking job's launches are about to start, so that its
-// kernels run exactly beside that job's first launches even when the caller is a slow Python loop (tools/pipe_overlap_debug.py).
-static const bool g_pipeGate = getenv("LSDHIP_PIPE_GATE") != nullptr;
-__global__ void k_gate_wait(const int* flag, int value) {
-  if (threadIdx.x != 0) return;
-  for (unsigned spins = 0; spins < (1u << 22); spins++) {
-    if (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_AGENT) >= value) return;
-    __builtin_amdgcn_s_sleep(4);
-  }
-}
-__global__ void k_gate_open(int* flag, int value) {
-  if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-int lsd_gate_wait(lsdhip_ctx* c) {
-  if (!g_pipeGate || !c->pipeline) return LSDHIP_OK;
-  if (!c->d_gate) { HIPCHK(hipMalloc((void**)&c->d_gate, 64)); HIPCHK(hipMemset(c->d_gate, 0, 64)); HIPCHK(hipStreamSynchronize(nullptr)); }
-  c->gateWaited = c->gateSeq + 1;
-  hipLaunchKernelGGL(k_gate_wait, dim3(1), dim3(64), 0, c->mstream, c->d_gate, c->gateWaited);
-  return LSDHIP_OK;
-}
-int lsd_gate_open(lsdhip_ctx* c) {
-  if (!g_pipeGate || !c->pipeline) return LSDHIP_OK;
-  if (!c->d_gate) { HIPCHK(hipMalloc((void**)&c->d_gate, 64)); HIPCHK(hipMemset(c->d_gate, 0, 64)); HIPCHK(hipStreamSynchronize(nullptr)); }
-  c->gateSeq++;
-  hipLaunchKernelGGL(k_gate_open, dim3(1), dim3(64), 0, c->stream, c->d_gate, c->gateSeq);
-  return LSDHIP_OK;
-}
-#endif   // LSD_DEVTOOLS
 // TrackingReference::importFrame (C/Tracking/TrackingReference.cpp:71-87) as the tracking side's hand-over point: the newest
 // Frame::setDepth result of the mapping stream becomes what SE3Tracker jobs read.  A no-op on non-pipelined contexts.
 int lsd_frame_publish_depth(lsdhip_frame* f) {
@@ -964,235 +610,6 @@ extern "C" int lsdhip_frame_publish_depth(lsdhip_frame* f) {
   if (!f) return LSDHIP_E_ARG;
   LSD_CTX_LOCK(f->ctx);
   return lsd_frame_publish_depth(f);
-}
-extern "C" int lsdhip_ctx_copy_dev(lsdhip_ctx* c, void* dst, const void* src, size_t bytes) {
-  if (!c || !dst || !src) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, lsd_transport_stream(c)));
-  return LSDHIP_OK;
-}
-// ---- lanes: the DepthMap call chains of DIFFERENT depth maps are independent of each other; between lanes_begin and lanes_end the
-// caller routes each map's calls to one of n extra streams (lane_select), so that the chains of several sequences (finalizeKeyFrame +
-// createKeyFrame: ~18 small dependent launches each) run side by side instead of one after the other.  Everything queued on the
-// context's stream before lanes_begin is visible to every lane; lanes_end orders the context's stream behind all lanes.
-extern "C" int lsdhip_ctx_lanes_begin(lsdhip_ctx* c, int n) {
-  if (!c || n < 1 || n > lsdhip_ctx::MAX_LANES) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  if (c->lanes_open) { lsd_set_error("lsdhip_ctx_lanes_begin: already open"); return LSDHIP_E_STATE; }
-  const hipStream_t base = c->pipeline ? c->mstream : c->stream;     // lanes branch off the stream the DepthMap calls run on
-  HIPCHK(hipSetDevice(c->device));
-  if (!c->lane_fork) HIPCHK(hipEventCreateWithFlags(&c->lane_fork, hipEventDisableTiming));
-  for (int i = 0; i < n; i++) {
-    if (!c->lanes[i]) {
-      HIPCHK(hipStreamCreateWithFlags(&c->lanes[i], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&c->lane_done[i], hipEventDisableTiming));
-    }
-    c->lane_used[i] = false;
-  }
-  // a lane waits for the fork point only: whatever the lanes' calls read must be queued before it — also the merges of speculative
-  // trials' refPixelWasGood planes that the tracking calls have noted but not queued yet (createKeyFrame reads the new keyframe's mask)
-  if (c->pipeline && !c->pendingMerges.empty()) { if (int rcf = lsd_flush_merges(c)) return rcf; }
-  HIPCHK(hipEventRecord(c->lane_fork, base));
-  c->lanes_open = n;
-  c->lane_cur = -1;
-  c->lane_record_pending = false;
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_lane_select(lsdhip_ctx* c, int lane) {
-  if (!c) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  if (!c->lanes_open || lane < -1 || lane >= c->lanes_open) { lsd_set_error("lsdhip_ctx_lane_select: lane %d of %d", lane, c->lanes_open); return LSDHIP_E_ARG; }
-  if (lane >= 0 && !c->lane_used[lane]) {
-    HIPCHK(hipSetDevice(c->device));
-    HIPCHK(hipStreamWaitEvent(c->lanes[lane], c->lane_fork, 0));
-    c->lane_used[lane] = true;
-  }
-  c->lane_cur = lane;
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_lanes_end(lsdhip_ctx* c) {
-  if (!c) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  if (!c->lanes_open) return LSDHIP_OK;
-  HIPCHK(hipSetDevice(c->device));
-  c->lane_cur = -1;
-  const hipStream_t base = c->pipeline ? c->mstream : c->stream;
-  for (int i = 0; i < c->lanes_open; i++) {
-    if (!c->lane_used[i]) continue;
-    HIPCHK(hipEventRecord(c->lane_done[i], c->lanes[i]));
-    HIPCHK(hipStreamWaitEvent(base, c->lane_done[i], 0));
-  }
-  c->lanes_open = 0;
-  // pipelined contexts: the calls inside the region were all given the mapping-stream sequence number of THIS point (lsd_m_record), the
-  // first one at which the mapping stream is behind every lane
-  if (c->lane_record_pending) { c->lane_record_pending = false; if (lsd_m_record(c) < 0) return LSDHIP_E_HIP; }
-  return LSDHIP_OK;
-}
-// ---- transport stream: exchange under compute (halo rows of the row-band loop travel while the interior rows are computed) -------
-extern "C" int lsdhip_ctx_aux_begin(lsdhip_ctx* c) {
-  if (!c) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  if (c->aux_active) { lsd_set_error("lsdhip_ctx_aux_begin: already between begin and end"); return LSDHIP_E_STATE; }
-  if (!c->aux_stream) {
-    HIPCHK(hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking));
-    HIPCHK(hipEventCreateWithFlags(&c->aux_fork, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&c->aux_done, hipEventDisableTiming));
-  }
-  HIPCHK(hipEventRecord(c->aux_fork, c->stream));
-  HIPCHK(hipStreamWaitEvent(c->aux_stream, c->aux_fork, 0));
-  c->aux_active = true;
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_aux_end(lsdhip_ctx* c) {
-  if (!c) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  if (!c->aux_active) { lsd_set_error("lsdhip_ctx_aux_end without lsdhip_ctx_aux_begin"); return LSDHIP_E_STATE; }
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipEventRecord(c->aux_done, c->aux_stream));
-  c->aux_active = false;
-  c->aux_pending = true;
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_aux_join(lsdhip_ctx* c) {
-  if (!c) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  if (c->aux_active) { lsd_set_error("lsdhip_ctx_aux_join between begin and end"); return LSDHIP_E_STATE; }
-  if (!c->aux_pending) return LSDHIP_OK;
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamWaitEvent(c->stream, c->aux_done, 0));
-  c->aux_pending = false;
-  return LSDHIP_OK;
-}
-extern "C" void* lsdhip_ctx_aux_stream(lsdhip_ctx* c) { return c ? (void*)c->aux_stream : nullptr; }
-// ---- inter-process exchange on one node without RCCL (lsdhip_driver's second transport): IPC-mapped device memory + flags ---------
-// A flag is an int in device memory that both processes map; values only grow.  Both operations are stream-ordered one-lane kernels:
-// set publishes everything the stream did before it (system-scope release), wait spins — bounded — until the flag has reached the
-// value and raises *fail otherwise.
-// Both run as LSD_FLAG_WGS one-wave workgroups, dealt round-robin over the chip's 8 XCDs: the writes a set publishes may sit dirty in
-// any XCD's L2 and the data a wait is followed by may be cached stale in any XCD's L2 — and the other side is another process, whose
-// accesses this runtime's own cache bookkeeping between consecutive launches knows nothing about.  So every XCD runs the
-// system-scope release (set: before the last arriving workgroup raises the flag) or acquire (wait: after it has seen the flag).
-__global__ void k_flag_set(int* flag, int value, unsigned* arrive) {
-  if (threadIdx.x != 0) return;
-  __threadfence_system();
-  const unsigned n = __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-  if (n + 1 == gridDim.x) {
-    __hip_atomic_store(arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // the next set on this stream starts from zero
-    __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-  }
-}
-__global__ void k_flag_wait(const int* flag, int value, int* fail) {
-  if (threadIdx.x != 0) return;
-  for (unsigned spins = 0; spins < (1u << 26); spins++) {          // ~8 s (2 s proved too tight once for a peer process's first launches on a shared GPU)
-    if (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) >= value) {
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");                // system scope: this XCD's L2 drops what it cached of foreign memory
-      return;
-    }
-    __builtin_amdgcn_s_sleep(8);
-  }
-  *fail = value;
-}
-extern "C" int lsdhip_ctx_ipc_export(lsdhip_ctx* c, void* dev, unsigned char handle64[64]) {
-  if (!c || !dev || !handle64) return LSDHIP_E_ARG;
-  static_assert(sizeof(hipIpcMemHandle_t) == 64, "hipIpcMemHandle_t is 64 bytes");
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  hipIpcMemHandle_t h;
-  HIPCHK(hipIpcGetMemHandle(&h, dev));
-  memcpy(handle64, &h, 64);
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_ipc_open(lsdhip_ctx* c, const unsigned char handle64[64], void** out_dev) {
-  if (!c || !handle64 || !out_dev) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  hipIpcMemHandle_t h;
-  memcpy(&h, handle64, 64);
-  HIPCHK(hipIpcOpenMemHandle(out_dev, h, hipIpcMemLazyEnablePeerAccess));
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_ipc_close(lsdhip_ctx* c, void* dev) {
-  if (!c || !dev) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  HIPCHK(hipIpcCloseMemHandle(dev));
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_flag_set(lsdhip_ctx* c, int* flag_dev, int value) {
-  if (!c || !flag_dev) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  if (!c->d_flagArrive) {
-    HIPCHK(hipMalloc((void**)&c->d_flagArrive, 64));
-    HIPCHK(hipMemset(c->d_flagArrive, 0, 64));
-    // the memset runs on the null stream, which the (non-blocking) streams of this library do not wait for: without this the first
-    // k_flag_set could count arrivals on top of whatever the allocation held, never reach its grid size and never raise its flag —
-    // every wait of both processes then times out at value 1 (seen twice on the GPU box, tests/test_bands_gpu.py)
-    HIPCHK(hipStreamSynchronize(nullptr));
-  }
-  // (sets of one context are stream-ordered, on either of its streams in turn: one arrival counter serves them all)
-  hipLaunchKernelGGL(k_flag_set, dim3(LSD_FLAG_WGS), dim3(64), 0, lsd_transport_stream(c), flag_dev, value, c->d_flagArrive);
-  HIPCHK(hipGetLastError());
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_flag_wait(lsdhip_ctx* c, const int* flag_dev, int value, int* fail_dev) {
-  if (!c || !flag_dev || !fail_dev) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  hipLaunchKernelGGL(k_flag_wait, dim3(LSD_FLAG_WGS), dim3(64), 0, lsd_transport_stream(c), flag_dev, value, fail_dev);
-  HIPCHK(hipGetLastError());
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_memset_dev(lsdhip_ctx* c, void* dev, int byte, size_t bytes) {
-  if (!c || !dev) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  HIPCHK(hipMemsetAsync(dev, byte, bytes, c->stream));
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_read_dev(lsdhip_ctx* c, void* host, const void* dev, size_t bytes) {
-  if (!c || !host || !dev) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  if (c->pipeline) { if (int rc = lsd_sync_all(c)) return rc; }
-  HIPCHK(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, c->stream));
-  HIPCHK(hipStreamSynchronize(c->stream));
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_ctx_set_async(lsdhip_ctx* c, int on) {
-  if (!c) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  c->async = on != 0;
-  return LSDHIP_OK;
-}
-int lsd_ctx_take_slot(lsdhip_ctx* c) {
-  LSD_CTX_LOCK(c);
-  const int i = c->slot_next;
-  c->slot_next = (c->slot_next + 1) % LSD_NUM_SLOTS;
-  if (c->slot_stats_owner[i]) { int rc = lsd_frame_resolve(c->slot_stats_owner[i]); if (rc) return rc; }
-  if (c->slot_rescale_owner[i]) { int rc = lsd_frame_resolve(c->slot_rescale_owner[i]); if (rc) return rc; }
-  c->slot_epoch[i] = c->enqEpoch;
-  c->slot_mseq[i] = c->mSeq + 1;     // pipelined contexts: the calling DepthMap entry ends with the record point of this number
-  return i;
-}
-int lsd_ctx_claim_stats_slot(lsdhip_ctx* c, lsdhip_frame* f) {
-  const int slot = lsd_ctx_take_slot(c);
-  if (slot < 0) return slot;
-  if (f->pendStats >= 0) c->slot_stats_owner[f->pendStats] = nullptr;
-  f->pendStats = slot;
-  c->slot_stats_owner[slot] = f;
-  return slot;
-}
-int lsd_ctx_claim_rescale_slot(lsdhip_ctx* c, lsdhip_frame* f) {
-  const int slot = lsd_ctx_take_slot(c);
-  if (slot < 0) return slot;
-  if (f->pendRescale >= 0) c->slot_rescale_owner[f->pendRescale] = nullptr;
-  f->pendRescale = slot;
-  c->slot_rescale_owner[slot] = f;
-  return slot;
 }
 int lsd_frame_resolve(lsdhip_frame* f) {
   if (f->pendStats < 0 && f->pendRescale < 0) return LSDHIP_OK;
@@ -1244,80 +661,6 @@ int lsd_frame_resolve(lsdhip_frame* f) {
   }
   return rc;
 }
-extern "C" int lsdhip_ctx_intrinsics(lsdhip_ctx* c, int level, float out[8]) {
-  if (!c || level < 0 || level >= LSD_LEVELS) return LSDHIP_E_ARG;
-  memcpy(out, &c->intr[level], sizeof(LevelIntr));
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_prof_enable(lsdhip_ctx* c, int on) { if (!c) return LSDHIP_E_ARG; c->prof_on = on != 0; return LSDHIP_OK; }
-static void bprof_collect(lsdhip_ctx* c, bool wait) {
-  for (int i = 0; i < LSD_BPROF_SLOTS; i++) {
-    lsdhip_ctx::BProfSlot& p = c->bprof[i];
-    if (!p.pending) continue;
-    if (wait) (void)hipEventSynchronize(p.b);
-    else if (hipEventQuery(p.b) != hipSuccess) continue;
-    float ms = 0;
-    if (hipEventElapsedTime(&ms, p.a, p.b) == hipSuccess) { c->bprof_ms[p.kind] += ms; c->bprof_units[p.kind] += p.units; c->bprof_calls[p.kind]++; }
-    p.pending = false;
-  }
-}
-int lsd_bprof_begin(lsdhip_ctx* c, int kind, hipStream_t s) {
-  if (!c->prof_on || kind < 0 || kind >= LSD_BPROF_KINDS) return -1;
-  if ((c->bprof_tick[kind]++ % LSD_BPROF_PERIOD) != 0) return -1;
-  const int i = c->bprof_next;
-  c->bprof_next = (c->bprof_next + 1) % LSD_BPROF_SLOTS;
-  lsdhip_ctx::BProfSlot& p = c->bprof[i];
-  if (p.pending) { bprof_collect(c, false); if (p.pending) { if (hipEventSynchronize(p.b) != hipSuccess) return LSDHIP_E_HIP; bprof_collect(c, false); } }
-  if (!p.a) { if (hipEventCreate(&p.a) != hipSuccess || hipEventCreate(&p.b) != hipSuccess) return LSDHIP_E_HIP; }
-  p.kind = kind;
-  if (hipEventRecord(p.a, s) != hipSuccess) return LSDHIP_E_HIP;
-  return i;
-}
-int lsd_bprof_end(lsdhip_ctx* c, int slot, hipStream_t s, double units) {
-  if (slot < 0) return slot == -1 ? LSDHIP_OK : slot;
-  lsdhip_ctx::BProfSlot& p = c->bprof[slot];
-  if (hipEventRecord(p.b, s) != hipSuccess) return LSDHIP_E_HIP;
-  p.units = units;
-  p.pending = true;
-  return LSDHIP_OK;
-}
-// ms / calls / units per kind (LSD_BPROF_KINDS of each) of the sampled shared launches since the last reset, and the sampled walk launches'
-// work: obs[0] = launches counted, obs[1] = searches, obs[2] = walk steps.  Waits for the brackets still in flight.
-extern "C" int lsdhip_ctx_batch_prof_read(lsdhip_ctx* c, double* ms, long long* calls, double* units, double obs[3]) {
-  if (!c || !ms || !calls || !units) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  HIPCHK(hipSetDevice(c->device));
-  bprof_collect(c, true);
-  for (int k = 0; k < LSD_BPROF_KINDS; k++) { ms[k] = c->bprof_ms[k]; calls[k] = c->bprof_calls[k]; units[k] = c->bprof_units[k]; }
-  if (obs) {
-    obs[0] = obs[1] = obs[2] = 0;
-    if (c->d_obsBatchAcc) {
-      unsigned long long h[66];
-      if (int rc = lsd_sync_all(c)) return rc;
-      HIPCHK(hipMemcpy(h, c->d_obsBatchAcc, sizeof(h), hipMemcpyDeviceToHost));
-      obs[0] = (double)h[65]; obs[1] = (double)h[0];
-      for (int i = 1; i <= 64; i++) obs[2] += (double)h[i];
-    }
-  }
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_prof_reset(lsdhip_ctx* c) {
-  if (!c) return LSDHIP_E_ARG;
-  LSD_CTX_LOCK(c);
-  c->prof_ms = 0; c->prof_bytes = 0; c->prof_launches = 0;
-  bprof_collect(c, true);
-  for (int k = 0; k < LSD_BPROF_KINDS; k++) { c->bprof_ms[k] = 0; c->bprof_units[k] = 0; c->bprof_calls[k] = 0; }
-  if (c->d_obsBatchAcc) HIPCHK(hipMemsetAsync(c->d_obsBatchAcc, 0, 66 * 8, lsd_map_stream(c)));
-  return LSDHIP_OK;
-}
-extern "C" int lsdhip_prof_read(lsdhip_ctx* c, double* ms, long long* launches, double* bytes) {
-  if (c) { int rc = lsd_prof_collect(c); if (rc) return rc; }
-  if (!c) return LSDHIP_E_ARG;
-  if (ms) *ms = c->prof_ms;
-  if (launches) *launches = c->prof_launches;
-  if (bytes) *bytes = c->prof_bytes;
-  return LSDHIP_OK;
-}
 
 // ---- frames: arena, pyramids, planes on demand ------------------------------------------------------------------------------------------
 // One arena per frame, out of the context's pool where it holds one.  Which planes it has and where: lsd_frame_planes (frame_layout.hpp).
@@ -1329,22 +672,18 @@ static int frame_alloc(lsdhip_ctx* c, int id, lsdhip_frame** out) {
     c->arena_bytes = lay.bytes;
   }
   if (lay.n > LsdFrameLayout::MAX_PLANES) { lsd_set_error("frame_alloc: %d planes do not fit the layout table", lay.n); return LSDHIP_E_STATE; }
-  char* base = nullptr;
+  std::unique_ptr<lsdhip_frame> f(new lsdhip_frame());
   if (!c->free_arenas.empty()) {
-    base = (char*)c->free_arenas.back();
+    f->arena = std::move(c->free_arenas.back());
     c->free_arenas.pop_back();
-  } else {
-    hipError_t e = hipMalloc((void**)&base, c->arena_bytes);
-    if (e != hipSuccess) { lsd_set_error("hipMalloc(%zu) failed: %s", c->arena_bytes, hipGetErrorString(e)); return LSDHIP_E_HIP; }
-  }
-  lsdhip_frame* f = new lsdhip_frame();
+  } else if (int rc = lsd_dev_alloc(f->arena, c->arena_bytes)) return rc;
   f->ctx = c;
   f->id = id;
   f->thisToParent_raw.q = {1, 0, 0, 0};
   f->thisToParent_raw.t[0] = f->thisToParent_raw.t[1] = f->thisToParent_raw.t[2] = 0;
   f->thisToParent_raw.s = 1;
-  lsd_frame_bind(*f, lay, c->wl, c->hl, base);
-  *out = f;
+  lsd_frame_bind(*f, lay, c->wl, c->hl, f->arena.get());
+  *out = f.release();
   return LSDHIP_OK;
 }
 
@@ -1373,13 +712,13 @@ static void frame_pyramids_queued(lsdhip_frame* f) {
 struct lsdhip_undistorter {
   lsdhip_ctx* ctx = nullptr;
   int in_w = 0, in_h = 0;
-  float2* d_map = nullptr;             // (remapX, remapY) interleaved, w * h entries
+  LsdDev<float2> d_map;                // (remapX, remapY) interleaved, w * h entries
   // One slot per batch entry (grown by the first batch that is wider; never per frame).  INVARIANT: a slot's upload and the launch that
   // reads it are both queued on the mapping stream (lsd_map_stream), so the next upload into the slot is ordered behind that launch by the
   // stream itself; stageStream remembers the stream, and a call that finds another one current (a lane region, a pipeline switch) drains it first.
-  std::vector<uint8_t*> stage;
-  hipStream_t stageStream = nullptr;
-  uint8_t* d_out = nullptr;            // lsdhip_undistorter_apply with a host destination
+  std::vector<LsdDev<uint8_t>> stage;
+  hipStream_t stageStream = nullptr;   // (one of the context's streams: not owned)
+  LsdDev<uint8_t> d_out;               // lsdhip_undistorter_apply with a host destination
   size_t rawBytes() const { return (size_t)in_w * in_h; }
 };
 // raw host images -> staging slots 0 .. n - 1 on stream `ms` (see the invariant above); dev[j] = where image j is on the device
@@ -1387,9 +726,9 @@ static int undistorter_stage(lsdhip_undistorter* u, int n, const uint8_t* const*
   if (u->stageStream && u->stageStream != ms) HIPCHK(hipStreamSynchronize(u->stageStream));
   u->stageStream = ms;
   while ((int)u->stage.size() < n) {
-    uint8_t* p = nullptr;
-    HIPCHK(hipMalloc((void**)&p, u->rawBytes()));
-    u->stage.push_back(p);
+    LsdDev<uint8_t> p;
+    if (int rc = lsd_dev_alloc(p, u->rawBytes())) return rc;
+    u->stage.push_back(std::move(p));
   }
   for (int j = 0; j < n; j++) {
     HIPCHK(hipMemcpyAsync(u->stage[j], raw_host[j], u->rawBytes(), hipMemcpyHostToDevice, ms));
@@ -1616,66 +955,6 @@ int lsd_frame_build_idepth_pyramid_batch(lsdhip_frame** fs, int n, const double*
   return LSDHIP_OK;
 }
 
-// Kernel-argument records of the batched launches: a ring of pinned slots with device twins.  A slot is handed out again only once the
-// event recorded behind its last use has completed: lsd_args_commit records it behind the copy, lsd_args_release — called after the
-// launches that read the device twin — moves it behind them (whatever stream they were queued on).
-int lsd_args_begin(lsdhip_ctx* c, size_t bytes, void** host_out, void** dev_out) {
-  LSD_CTX_LOCK(c);
-  lsdhip_ctx::ArgRing& r = c->args;
-  constexpr int NS = lsdhip_ctx::ArgRing::NS;
-  if (bytes > r.slotBytes) {
-    // grow: nothing may still read the old block
-    HIPCHK(hipDeviceSynchronize());
-    if (r.h) { (void)hipHostFree(r.h); r.h = nullptr; }
-    if (r.d) { (void)hipFree(r.d); r.d = nullptr; }
-    r.slotBytes = 0;
-    const size_t want = lsd_align_up(bytes * 2 > 65536 ? bytes * 2 : 65536, 256);
-    HIPCHK(hipHostMalloc((void**)&r.h, want * NS, hipHostMallocDefault));
-    HIPCHK(hipMalloc((void**)&r.d, want * NS));
-    r.slotBytes = want;
-    r.gen++;
-    for (int i = 0; i < NS; i++) { r.used[i] = false; if (!r.ev[i]) HIPCHK(hipEventCreateWithFlags(&r.ev[i], hipEventDisableTiming)); }
-  }
-  const int i = r.next;
-  r.next = (r.next + 1) % NS;
-  r.serial++;
-  if (r.used[i]) HIPCHK(hipEventSynchronize(r.ev[i]));   // (NS - 1 uses ago: long finished)
-  r.cur = i;
-  r.curBytes = bytes;
-  *host_out = r.h + (size_t)i * r.slotBytes;
-  *dev_out = r.d + (size_t)i * r.slotBytes;
-  return LSDHIP_OK;
-}
-int lsd_args_commit(lsdhip_ctx* c, hipStream_t s) {
-  LSD_CTX_LOCK(c);
-  lsdhip_ctx::ArgRing& r = c->args;
-  const int i = r.cur;
-  HIPCHK(hipMemcpyAsync(r.d + (size_t)i * r.slotBytes, r.h + (size_t)i * r.slotBytes, r.curBytes, hipMemcpyHostToDevice, s));
-  HIPCHK(hipEventRecord(r.ev[i], s));
-  r.used[i] = true;
-  return LSDHIP_OK;
-}
-// `dev`: the device address lsd_args_begin / lsd_args_push handed out — the slot is identified by it, not by "the slot begun last": a
-// helper that pushes arguments of its own between a commit and its release (lsd_frame_build_idepth_pyramid_batch inside the keyframe
-// change) must not make the release guard the wrong slot
-int lsd_args_release(lsdhip_ctx* c, const void* dev, hipStream_t s) {
-  LSD_CTX_LOCK(c);
-  lsdhip_ctx::ArgRing& r = c->args;
-  constexpr int NS = lsdhip_ctx::ArgRing::NS;
-  const uint8_t* p = (const uint8_t*)dev;
-  if (!r.d || r.slotBytes == 0 || p < (const uint8_t*)r.d || p >= (const uint8_t*)r.d + r.slotBytes * NS) return LSDHIP_OK;   // (the ring was regrown since: the device was drained then)
-  const int i = (int)((size_t)(p - (const uint8_t*)r.d) / r.slotBytes);
-  if (!r.used[i]) return LSDHIP_OK;
-  HIPCHK(hipEventRecord(r.ev[i], s));
-  return LSDHIP_OK;
-}
-int lsd_args_push(lsdhip_ctx* c, const void* src, size_t bytes, hipStream_t s, void** dev_out) {
-  LSD_CTX_LOCK(c);
-  void* h = nullptr;
-  if (int rc = lsd_args_begin(c, bytes, &h, dev_out)) return rc;
-  memcpy(h, src, bytes);
-  return lsd_args_commit(c, s);
-}
 
 int lsd_frame_ensure_wasgood(lsdhip_frame* f) {
   if (!f->wasGoodValid) {
@@ -1780,17 +1059,11 @@ extern "C" int lsdhip_undistorter_create(lsdhip_ctx* c, int in_w, int in_h, cons
   }
   LSD_CTX_LOCK(c);
   HIPCHK(hipSetDevice(c->device));
-  lsdhip_undistorter* u = new lsdhip_undistorter();
+  std::unique_ptr<lsdhip_undistorter> u(new lsdhip_undistorter());
   u->ctx = c; u->in_w = in_w; u->in_h = in_h;
-  hipError_t e = hipMalloc((void**)&u->d_map, n * sizeof(float2));
-  if (e == hipSuccess) e = hipMemcpy(u->d_map, map.data(), n * sizeof(float2), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    lsd_set_error("lsdhip_undistorter_create: %s", hipGetErrorString(e));
-    if (u->d_map) (void)hipFree(u->d_map);
-    delete u;
-    return LSDHIP_E_HIP;
-  }
-  *out = u;
+  if (int rc = lsd_dev_alloc(u->d_map, n)) return rc;
+  HIPCHK(hipMemcpy(u->d_map, map.data(), n * sizeof(float2), hipMemcpyHostToDevice));
+  *out = u.release();
   return LSDHIP_OK;
 }
 extern "C" void lsdhip_undistorter_destroy(lsdhip_undistorter* u) {
@@ -1800,9 +1073,6 @@ extern "C" void lsdhip_undistorter_destroy(lsdhip_undistorter* u) {
   (void)hipSetDevice(c->device);
   (void)lsd_sync_all(c);     // frames created through it may still be queued
   if (u->stageStream) (void)hipStreamSynchronize(u->stageStream);
-  for (uint8_t* p : u->stage) (void)hipFree(p);
-  if (u->d_out) (void)hipFree(u->d_out);
-  (void)hipFree(u->d_map);
   delete u;
 }
 extern "C" int lsdhip_undistorter_apply(lsdhip_undistorter* u, const uint8_t* raw, int raw_on_device, uint8_t* out_gray, int out_on_device) {
@@ -1816,7 +1086,7 @@ extern "C" int lsdhip_undistorter_apply(lsdhip_undistorter* u, const uint8_t* ra
   const uint8_t* src = raw;
   if (!raw_on_device)
     if (int rc = undistorter_stage(u, 1, &raw, ms, &src)) return rc;
-  if (!out_on_device && !u->d_out) HIPCHK(hipMalloc((void**)&u->d_out, (size_t)n));
+  if (!out_on_device && !u->d_out) { if (int rc = lsd_dev_alloc(u->d_out, (size_t)n)) return rc; }
   uint8_t* dst = out_on_device ? out_gray : u->d_out;
   hipLaunchKernelGGL(k_undistort, dim3((n + 255) / 256), dim3(256), 0, ms, src, (const float2*)u->d_map, u->in_w, dst, n);
   HIPCHK(hipGetLastError());
@@ -1845,8 +1115,7 @@ extern "C" int lsdhip_frame_create_undistorted_batch(lsdhip_undistorter* u, int 
 }
 // Frame-memory pool (the reference's FrameMemory keeps returned buffers for reuse, util/... FrameMemory.cpp): make sure n arenas are
 // allocated and waiting, so that a loop which keeps its keyframes alive does not pay a hipMalloc (0.5 ms for 20 MB) per keyframe.
-extern "C" int lsdhip_ctx_reserve_frames(lsdhip_ctx* c, int n) {
-  if (!c || n < 0) return LSDHIP_E_ARG;
+int lsd_frames_reserve(lsdhip_ctx* c, int n) {
   LSD_CTX_LOCK(c);
   HIPCHK(hipSetDevice(c->device));
   if ((size_t)n > c->arena_keep) c->arena_keep = (size_t)n;
@@ -1865,11 +1134,11 @@ extern "C" void lsdhip_frame_destroy(lsdhip_frame* f) {
   lsdhip_ctx* c = f->ctx;
   LSD_CTX_LOCK(c);
   if (c->free_arenas.size() < c->arena_keep) {
-    c->free_arenas.push_back(f->d_gray);   // arena base; reuse is ordered by the stream itself
+    c->free_arenas.push_back(std::move(f->arena));   // reuse is ordered by the stream itself
   } else {
     (void)hipSetDevice(c->device);
     (void)lsd_sync_all(c);
-    (void)hipFree(f->d_gray);
+    f->arena.reset();
   }
   if (f->pendStats >= 0) c->slot_stats_owner[f->pendStats] = nullptr;
   if (f->pendRescale >= 0) c->slot_rescale_owner[f->pendRescale] = nullptr;
@@ -1956,7 +1225,7 @@ extern "C" int lsdhip_frame_set_depth_gt(lsdhip_frame* f, const float* depth_hos
   LSD_CTX_LOCK(c);
   const int n0 = c->w * c->h;
   // staging plane kept by the context (ground-truth depth arrives once per keyframe in the GT-initialised modes)
-  if (!c->d_gtStage) HIPCHK(hipMalloc((void**)&c->d_gtStage, (size_t)n0 * 4));
+  if (!c->d_gtStage) { if (int rc = lsd_dev_alloc(c->d_gtStage, (size_t)n0)) return rc; }
   if (int rc = drain_for_host(c)) return rc;
   const hipStream_t ms = lsd_map_stream(c);
   if (int rc = lsd_frame_require_level0(f)) return rc;   // Frame::setDepthFromGroundTruth reads maxGradients(0) (Frame.cpp:259)
@@ -2090,10 +1359,10 @@ extern "C" int lsdhip_ref_pointcloud(lsdhip_frame* kf, int level, float* pos, fl
   int w = c->wl[level], h = c->hl[level];
   size_t nmax = (size_t)w * h;
   if (int rc = drain_for_host(c)) return rc;
-  char* scratch = nullptr;
   size_t bytes = (size_t)(w + 1) * 4 + nmax * (12 + 8 + 8 + 4) + 1024;
-  HIPCHK(hipMalloc((void**)&scratch, bytes));
-  int* d_col = (int*)scratch;
+  LsdDev<char> scratch;
+  if (int rc = lsd_dev_alloc(scratch, bytes)) return rc;
+  int* d_col = (int*)scratch.get();
   int* d_total = d_col + w;
   float* d_pos = (float*)(scratch + lsd_align_up((size_t)(w + 1) * 4, 256));
   float* d_cv = d_pos + nmax * 3;
@@ -2110,6 +1379,5 @@ extern "C" int lsdhip_ref_pointcloud(lsdhip_frame* kf, int level, float* pos, fl
   if (colvar) HIPCHK(hipMemcpy(colvar, d_cv, (size_t)total * 8, hipMemcpyDeviceToHost));
   if (grad) HIPCHK(hipMemcpy(grad, d_gr, (size_t)total * 8, hipMemcpyDeviceToHost));
   if (idx) HIPCHK(hipMemcpy(idx, d_idx, (size_t)total * 4, hipMemcpyDeviceToHost));
-  HIPCHK(hipFree(scratch));
   return total;
 }

@@ -49,7 +49,7 @@ extern "C" int lsdhip_kfbank_create(lsdhip_ctx* c, int max_keyframes, lsdhip_kfb
   LSD_CTX_LOCK(c);
   HIPCHK(hipSetDevice(c->device));
   const int L = LSD_QUICK_KF_CHECK_LVL;
-  lsdhip_kfbank* b = new lsdhip_kfbank();
+  std::unique_ptr<lsdhip_kfbank> b(new lsdhip_kfbank());
   b->ctx = c;
   b->maxSlots = max_keyframes;
   b->capacity = (c->wl[L] - 2) * (c->hl[L] - 2);
@@ -57,10 +57,9 @@ extern "C" int lsdhip_kfbank_create(lsdhip_ctx* c, int max_keyframes, lsdhip_kfb
   b->slotFloats = ((size_t)b->capacity * 5 + 63) / 64 * 64;
   b->slots.reserve((size_t)max_keyframes);
   const size_t bytes = (size_t)max_keyframes * b->slotFloats * sizeof(float) + (size_t)max_keyframes * sizeof(int);
-  const hipError_t e = hipMalloc((void**)&b->d_base, bytes);
-  if (e != hipSuccess) { lsd_set_error("lsdhip_kfbank_create: hipMalloc(%zu) failed: %s", bytes, hipGetErrorString(e)); delete b; return LSDHIP_E_HIP; }
+  if (int rc = lsd_dev_alloc(b->d_base, bytes / sizeof(float))) return rc;     // (bytes is a multiple of 4: floats, then ints)
   b->d_count = (int*)(b->d_base + (size_t)max_keyframes * b->slotFloats);
-  *out = b;
+  *out = b.release();
   return LSDHIP_OK;
 }
 
@@ -70,7 +69,6 @@ extern "C" void lsdhip_kfbank_destroy(lsdhip_kfbank* b) {
   LSD_CTX_LOCK(c);
   (void)hipSetDevice(c->device);
   (void)lsd_sync_all(c);      // searches and puts still queued read and write the allocation
-  (void)hipFree(b->d_base);
   delete b;
 }
 

@@ -10,7 +10,9 @@
 #include <cstdio>
 #include <cstring>
 #include <mutex>
+#include <memory>
 #include <string>
+#include <type_traits>
 #include <vector>
 #include "../../include/lsdhip.h"
 
@@ -28,6 +30,39 @@ void lsd_set_error(const char* fmt, ...);
       return LSDHIP_E_HIP;                                                                 \
     }                                                                                      \
   } while (0)
+
+// ---- owners of device resources (owned.hpp): every hipMalloc / hipHostMalloc / event / stream is held by one from the line that creates
+// it, so a `return` on any path — HIPCHK's included — gives it back.  The four Release functions are the only places that free ...
+#include "owned.hpp"
+struct LsdDevRelease { static hipError_t call(void* p) { return hipFree(p); } };   // (the status: for lsdhip_ctx_free_dev, which reports it)
+struct LsdPinnedRelease { static void call(void* p) { (void)hipHostFree(p); } };
+struct LsdEventRelease { static void call(hipEvent_t e) { (void)hipEventDestroy(e); } };
+struct LsdStreamRelease { static void call(hipStream_t s) { (void)hipStreamDestroy(s); } };
+template <class T> using LsdDev = LsdOwned<T*, LsdDevRelease>;
+template <class T> using LsdPinned = LsdOwned<T*, LsdPinnedRelease>;
+using LsdEvent = LsdOwned<hipEvent_t, LsdEventRelease>;
+using LsdStream = LsdOwned<hipStream_t, LsdStreamRelease>;
+// ... and these the only places that create (context.hip).  `count` elements of T (bytes for void); an owner that already holds something
+// gives it up only once the new value exists, so a failed call leaves it as it was.  LSDHIP_E_HIP with the error text set on failure.
+int lsd_dev_alloc_bytes(void** out, size_t bytes, bool zeroed);
+int lsd_pinned_alloc_bytes(void** out, size_t bytes, unsigned flags, void** deviceAlias);
+int lsd_event_create(LsdEvent& owner, unsigned flags = hipEventDefault);
+int lsd_stream_create(LsdStream& owner);      // non-blocking, as every stream of the library
+template <class T> constexpr size_t lsd_elem_bytes() { if constexpr (std::is_void<T>::value) return 1; else return sizeof(T); }
+template <class T> inline int lsd_dev_alloc(LsdDev<T>& owner, size_t count, bool zeroed = false) {
+  void* p = nullptr;
+  if (int rc = lsd_dev_alloc_bytes(&p, count * lsd_elem_bytes<T>(), zeroed)) return rc;
+  owner.reset((T*)p);
+  return LSDHIP_OK;
+}
+template <class T> inline int lsd_dev_alloc_zeroed(LsdDev<T>& owner, size_t count) { return lsd_dev_alloc(owner, count, true); }   // zero-filled, and safe to hand to a kernel on any stream
+// flags: hipHostMallocDefault / hipHostMallocMapped; the mapped form also fetches the address the device reads the block at
+template <class T> inline int lsd_pinned_alloc(LsdPinned<T>& owner, size_t count, unsigned flags, T** deviceAlias = nullptr) {
+  void* p = nullptr;
+  if (int rc = lsd_pinned_alloc_bytes(&p, count * lsd_elem_bytes<T>(), flags, (void**)deviceAlias)) return rc;
+  owner.reset((T*)p);
+  return LSDHIP_OK;
+}
 
 #include "pose_math.hpp"  // lsdm:: pose algebra (host + device)
 
@@ -186,8 +221,11 @@ struct lsdhip_frame;
 struct lsdhip_ctx {
   std::recursive_mutex mtx;
   int device = 0;
+  // Members are destroyed in reverse order of declaration: `stream` is declared first and goes last, and every other stream is declared
+  // before the events recorded on it.  Buffers do not depend on the order: lsdhip_ctx_destroy drains every stream before `delete c`.
+  LsdStream stream;
   bool async = LSD_DEFAULT_ASYNC != 0;                 // lsdhip_ctx_set_async: mapping calls return after enqueueing
-  DeferredSlot* h_slots = nullptr;       // pinned, device-mapped ring
+  LsdPinned<DeferredSlot> h_slots;      // pinned, device-mapped ring
   lsdhip_frame* slot_stats_owner[LSD_NUM_SLOTS] = {};
   lsdhip_frame* slot_rescale_owner[LSD_NUM_SLOTS] = {};
   int slot_next = 0;
@@ -202,7 +240,6 @@ struct lsdhip_ctx {
   LevelIntr intr[LSD_LEVELS];
   float K0[9], K0inv[9];
   lsdhip_params params;
-  hipStream_t stream = nullptr;
   // Pipelined operation (lsdhip_ctx_set_pipeline; the reference's tracking thread beside its mapping thread, C/SlamSystem.h:124-132):
   // SE3Tracker jobs run on `stream`, frame creation (upload + pyramids) and every DepthMap call on `mstream`.  The two are ordered by
   // events where mapping products reach the tracker: a tracking job waits for the M-sequence point its frame's pyramids / its
@@ -213,8 +250,8 @@ struct lsdhip_ctx {
   // started (the mask of a speculative trial is merged into the frame's plane by a kernel on mstream, see lsdhip_tracker_track).
 #define LSD_EVR 64
   bool pipeline = LSD_DEFAULT_PIPELINE != 0;
-  hipStream_t mstream = nullptr;
-  hipEvent_t mEv[LSD_EVR] = {};
+  LsdStream mstream;
+  LsdEvent mEv[LSD_EVR];
   long long mSeq = 0;                    // record points on mstream so far
   long long mDoneSeq = 0;                // newest M-sequence the host knows to be complete
   long long tWaitedM = 0;                // newest M-sequence `stream` has been ordered behind
@@ -224,59 +261,63 @@ struct lsdhip_ctx {
   // operation queues them first (lsd_m_begin)
   struct PendingMerge { uint8_t* plane; const uint8_t* side; long long* doneSeq; };
   std::vector<PendingMerge> pendingMerges;
-  unsigned long long* d_sums = nullptr;  // LSDHIP_TRACE_SUMS: checksum slots
-  std::vector<int> sums_meta;            // (kind, id) per slot; kind < 0: host value stored in sums_host
-  std::vector<unsigned long long> sums_host;
-  int* d_gate = nullptr;                 // developer hook LSDHIP_PIPE_GATE: the next tracking job's first launch releases the mapping work queued before it
-  int gateSeq = 0, gateWaited = 0;
+#ifdef LSD_DEVTOOLS
+  struct DevTools {                      // state of the developer experiments (devtools.hip)
+    LsdDev<unsigned long long> d_sums;   // LSDHIP_TRACE_SUMS: checksum slots
+    std::vector<int> sums_meta;          // (kind, id) per slot; kind < 0: host value stored in sums_host
+    std::vector<unsigned long long> sums_host;
+    LsdDev<int> d_gate;                  // developer hook LSDHIP_PIPE_GATE: the next tracking job's first launch releases the mapping work queued before it
+    int gateSeq = 0, gateWaited = 0;
+    LsdDev<float> dummyBuf;              // LSDHIP_PIPE_DUMMY: what the unrelated kernels write
+  } dev;
+#endif
   // Second stream for the transport primitives of the multi-process loops (row copies, flags, device copies, the caller's RCCL
   // calls): between lsdhip_ctx_aux_begin and lsdhip_ctx_aux_end they are queued there, ordered behind what the main stream held at
   // `begin`; lsdhip_ctx_aux_join makes the main stream wait for them.  Created on first use.
   // lanes: independent DepthMap call chains of different maps side by side (lsdhip_ctx_lanes_begin / _lane_select / _lanes_end)
   static constexpr int MAX_LANES = 16;
-  hipStream_t lanes[MAX_LANES] = {};
-  hipEvent_t lane_done[MAX_LANES] = {};
-  hipEvent_t lane_fork = nullptr;
+  LsdStream lanes[MAX_LANES];
+  LsdEvent lane_done[MAX_LANES];
+  LsdEvent lane_fork;
   int lanes_open = 0;      // > 0 between lanes_begin and lanes_end: number of lanes
   int lane_cur = -1;       // lane the mapping calls currently go to (-1: the context's own stream)
   bool lane_used[MAX_LANES] = {};
   bool lane_record_pending = false;   // pipelined: a DepthMap call inside the open region asked for a record point
-  hipStream_t aux_stream = nullptr;
-  unsigned* d_flagArrive = nullptr;      // arrival counter of k_flag_set's workgroups
-  hipEvent_t aux_fork = nullptr, aux_done = nullptr;
+  LsdStream aux_stream;
+  LsdDev<unsigned> d_flagArrive;         // arrival counter of k_flag_set's workgroups
+  LsdEvent aux_fork, aux_done;
   bool aux_active = false, aux_pending = false;
   // profiling of the residual kernel (bench.py roofline leg)
   bool prof_on = false;
   unsigned prof_tick = 0;                // trackFrame jobs seen while profiling (every 8th is timed)
-  hipEvent_t ev_a = nullptr, ev_b = nullptr;
+  LsdEvent ev_a, ev_b;
   bool prof_pending = false;             // ev_a / ev_b of the last launch batch not yet read
   double prof_ms = 0, prof_bytes = 0;
   long long prof_launches = 0;
-  std::vector<hipEvent_t> prof_events;   // per-launch event pairs for the device-resident LM loop
   // sampled event brackets around the shared launches of the batched entries (bench.py: extra_configs.multi_seq.*.roofline), while
   // prof_on: every LSD_BPROF_PERIOD-th call of a kind.  kinds: 0 frame pyramids (lsdhip_frame_create_batch), 1 observe, 2 fill holes +
   // regularise (+ setDepth), 3 idepth pyramids of lsdhip_depth_update_batch, 4 the keyframe change chain; units = map pixels processed
 #define LSD_BPROF_KINDS 5
 #define LSD_BPROF_SLOTS 16
 #define LSD_BPROF_PERIOD 3
-  struct BProfSlot { hipEvent_t a = nullptr, b = nullptr; int kind = -1; double units = 0; bool pending = false; } bprof[LSD_BPROF_SLOTS];
+  struct BProfSlot { LsdEvent a, b; int kind = -1; double units = 0; bool pending = false; } bprof[LSD_BPROF_SLOTS];
   int bprof_next = 0;
   unsigned bprof_tick[LSD_BPROF_KINDS] = {};
   double bprof_ms[LSD_BPROF_KINDS] = {}, bprof_units[LSD_BPROF_KINDS] = {};
   long long bprof_calls[LSD_BPROF_KINDS] = {};
-  unsigned long long* d_obsBatchAcc = nullptr;   // [0] searches, [1 .. 64] walk steps (by wave), [65] counted launches — of the sampled walk launches
+  LsdDev<unsigned long long> d_obsBatchAcc;      // [0] searches, [1 .. 64] walk steps (by wave), [65] counted launches — of the sampled walk launches
   // recycled frame arenas (the FrameMemory idea, C/DataStructures/FrameMemory.cpp:67-127, for device buffers);
   // reuse is stream-ordered, so no synchronisation is needed when a frame dies
-  std::vector<void*> free_arenas;
+  std::vector<LsdDev<char>> free_arenas;
   size_t arena_keep = 16;                // arenas of destroyed frames kept for reuse (grows with the batch width of lsdhip_frame_create_batch)
-  float* d_gtStage = nullptr;                        // w x h floats: staging of lsdhip_frame_set_depth_gt
-  uint8_t* d_kfPoints = nullptr;                     // w x h x 12 bytes: staging of lsdhip_frame_pack_keyframe_points (cloud.hip)
-  uint8_t* d_plotStage = nullptr;                    // w x h x 3 bytes: staging of lsdhip_depth_debug_plot (plot.hip)
+  LsdDev<float> d_gtStage;                           // w x h floats: staging of lsdhip_frame_set_depth_gt
+  LsdDev<uint8_t> d_kfPoints;                        // w x h x 12 bytes: staging of lsdhip_frame_pack_keyframe_points (cloud.hip)
+  LsdDev<uint8_t> d_plotStage;                       // w x h x 3 bytes: staging of lsdhip_depth_debug_plot (plot.hip)
   // kernel-argument arrays of the batched launches (several sequences per launch): pinned staging slots and their device twins,
   // reused round-robin; a slot is rewritten only after the launches that read it have completed (lsd_args_push / lsd_args_release)
   struct ArgRing {
     static constexpr int NS = 32;
-    uint8_t* h = nullptr; uint8_t* d = nullptr; size_t slotBytes = 0; int next = 0; hipEvent_t ev[NS] = {}; bool used[NS] = {};
+    LsdPinned<uint8_t> h; LsdDev<uint8_t> d; size_t slotBytes = 0; int next = 0; LsdEvent ev[NS]; bool used[NS] = {};
     int cur = -1; size_t curBytes = 0;   // the slot being filled / last committed
     unsigned long long serial = 0, gen = 0;   // slots handed out so far / times the ring was regrown: a device address handed out at serial s
                                               // still holds its record while gen is unchanged and serial < s + NS (lsdhip_ctx_batch_form)
@@ -296,6 +337,7 @@ struct lsdhip_ctx {
 struct lsdhip_frame {
   lsdhip_ctx* ctx = nullptr;
   int id = 0;
+  LsdDev<char> arena;                   // every plane below points into it (frame_layout.hpp); goes back to the context's pool when the frame dies
   uint8_t* d_gray = nullptr;            // level-0 source (uint8)
   float* d_image[LSD_LEVELS] = {};      // float planes
   float4* d_grad[LSD_LEVELS] = {};      // (gx, gy, I, 0)
@@ -347,7 +389,7 @@ struct lsdhip_frame {
 };
 
 struct lsdhip_tracker {
-  lsdhip_ctx* ctx = nullptr;
+  lsdhip_ctx* ctx = nullptr;   // (owns the streams: the tracker's buffers go after lsdhip_tracker_destroy has drained the tracking stream)
   // DenseDepthTrackerSettings (C/util/settings.h:355-402)
   float lambdaSuccessFac = 0.5f, lambdaFailFac = 2.0f;
   float lambdaInitial[LSD_LEVELS], stepSizeMin[LSD_LEVELS], convergenceEps[LSD_LEVELS];
@@ -364,9 +406,9 @@ struct lsdhip_tracker {
   bool spinWait = true;           // poll the pinned summary instead of hipStreamSynchronize (LSDHIP_SPIN=0 disables)
   bool hostLM = false;            // debugging: run the LM control loop on the host, one evaluation per round trip
   // device scratch
-  float* d_partials = nullptr;    // TrackScratch arena (sums | topkey | topval), see tracker.hip
+  LsdDev<float> d_partials;       // TrackScratch arena (sums | topkey | topval), see tracker.hip
   int max_blocks = 0;
-  TrackState* d_state = nullptr;  // [2], double-buffered by launch parity
+  LsdDev<TrackState> d_state;     // [2], double-buffered by launch parity
   int levelEvaluations[LSD_LEVELS] = {};   // evaluations of the last job per pyramid level
   int block = 256;                // workgroup size of k_track_step (LSDHIP_TRACK_BLOCK)
   int grid_cap = 304;             // most workgroups one evaluation uses (LSDHIP_TRACK_CAP); larger levels grid-stride
@@ -378,7 +420,7 @@ struct lsdhip_tracker {
   int specCaps[LSD_LEVELS] = {0, 0, 0, 0, 0};    // per-level workgroups per trial (LSDHIP_SPEC_CAPS; 0 = automatic)
   int specLevel[LSD_LEVELS] = {0, 0, 0, 0, 0};   // per-level trials (LSDHIP_SPEC_LEVELS = "l0,l1,l2,l3,l4"; 0 = automatic / specC)
   int specCap = LSD_SPEC_CAP_WORKGROUPS;              // workgroups per trial on levels of 24 K - 88 K pixels when speculating (0 = grid_cap / 2)
-  uint8_t* d_maskSide = nullptr;  // 2 sets (alternating by job) of (SPEC_MAX - 1) mask planes of (w >> 1) x (h >> 1) bytes
+  LsdDev<uint8_t> d_maskSide;     // 2 sets (alternating by job) of (SPEC_MAX - 1) mask planes of (w >> 1) x (h >> 1) bytes
   int maskSet = 0;                // set the job being launched writes
   long long maskMergeSeq[2] = {0, 0};   // pipelined contexts: M-sequence behind which the merge that reads set s has completed
   size_t maskStride = 0;
@@ -389,9 +431,9 @@ struct lsdhip_tracker {
   int sumLateFirstWord = -1, sumLateLastWord = -1;   // lowest / highest word index ever seen stale
   unsigned long long dbgCum = 0;
   std::vector<unsigned> dumpL0;   // developer dump (LSDHIP_DUMP_L0): what the job's first launch left in the scratch
-  unsigned long long* d_dbg = nullptr;
+  LsdDev<unsigned long long> d_dbg;
 #ifdef LSD_DEVTOOLS
-  int* d_log = nullptr;      // launch log of the current job (TrackSpec::dbgLog), 4096 x 16 ints
+  LsdDev<int> d_log;         // launch log of the current job (TrackSpec::dbgLog), 4096 x 16 ints
   std::vector<int> lastLog;  // ... of the last finished job, read by lsdhip_tracker_debug_log
 #endif
   const lsdhip_frame* jobKf = nullptr;   // keyframe whose planes the job being run reads (trackFrame jobs), and their version at its start
@@ -400,22 +442,22 @@ struct lsdhip_tracker {
   int budgetExtra = 2;                 // launches queued beyond the most the recent jobs needed (finishing step + margin; LSDHIP_BUDGET_EXTRA)
   int budgetFixed = 0;   // LSDHIP_BUDGET_FIXED (test hook): launches per budget, however many the job needs
   long long dbgJobs = 0, dbgEnqueued = 0, dbgMisses = 0, dbgWaitNs = 0, dbgLaunchNs = 0;   // LSDHIP_TRACK_DEBUG=1: printed at destroy
-  TrackSummary* h_summary = nullptr;  // pinned, device-mapped
+  LsdPinned<TrackSummary> h_summary;  // pinned, device-mapped
   TrackSummary* d_summary = nullptr;  // device alias of h_summary
-  unsigned long long* d_trace = nullptr;  // LSD_PHASE_TRACE developer build only
+  LsdDev<unsigned long long> d_trace;     // LSD_PHASE_TRACE developer build only
   // batch tracking (lsdhip_tracker_track_batch): per-job descriptions, states, scratch and summaries
   int batch_capacity = 0;
-  TrackJob* d_bjobs = nullptr;
-  TrackJob* h_bjobs = nullptr;        // pinned staging
-  TrackState* d_bstate = nullptr;     // [capacity][2]
-  float* d_bscratch = nullptr;        // TrackScratch arena x capacity (sums | topkey | topval | recs, each [job][parity][trial][...])
+  LsdDev<TrackJob> d_bjobs;
+  LsdPinned<TrackJob> h_bjobs;        // pinned staging
+  LsdDev<TrackState> d_bstate;        // [capacity][2]
+  LsdDev<float> d_bscratch;           // TrackScratch arena x capacity (sums | topkey | topval | recs, each [job][parity][trial][...])
   LaunchHistory batchRecent;          // rounds the last batches needed: size the launch budget of the next one
   int batchTag = 1;                   // what `done` of a polled batch's summaries is raised to (>= 2; 1 = a batch the host synchronises for)
-  TrackSummary* h_bsummary = nullptr; // pinned, device-mapped
-  float* d_pts = nullptr;         // permaref point upload
+  LsdPinned<TrackSummary> h_bsummary; // pinned, device-mapped
+  LsdDev<float> d_pts;            // permaref point upload
   int pts_capacity = 0;
   float relocalizationTH = 0.7f;  // C/util/settings.cpp:101 (lsdhip_tracker_set_relocalization_th)
-  float* h_overlapSums = nullptr;   // pinned, device-mapped: the sums of lsdhip_tracker_check_overlap_bank's pairs
+  LsdPinned<float> h_overlapSums;   // pinned, device-mapped: the sums of lsdhip_tracker_check_overlap_bank's pairs
   int overlapSumsCapacity = 0;
   std::vector<lsdhip_reposition_record> repoRecords;   // per-keyframe records of the last lsdhip_tracker_find_reposition_candidate
 };
@@ -427,7 +469,7 @@ struct lsdhip_kfbank {
   lsdhip_ctx* ctx = nullptr;
   int maxSlots = 0, capacity = 0;   // points per slot: (w4 - 2) * (h4 - 2)
   size_t slotFloats = 0;            // floats from one slot to the next (a multiple of 64: slots start on 256-byte boundaries)
-  float* d_base = nullptr;
+  LsdDev<float> d_base;
   int* d_count = nullptr;           // one int per slot, behind the clouds in the same allocation
   struct Slot { int frameId; int numPoints; float meanIdepth; double camToWorld[8]; };
   std::vector<Slot> slots;          // reserved to maxSlots at creation
@@ -448,6 +490,7 @@ struct lsdhip_kfbank {
 #define LSD_G
 #endif
 template <typename T> __host__ __device__ inline LSD_G T* lsd_g(T* p) { return (LSD_G T*)p; }    // what the host code fills such a field with
+template <typename T, class R> inline LSD_G T* lsd_g(const LsdOwned<T*, R>& owner) { return (LSD_G T*)owner.get(); }
 struct HypPlanes {
   LSD_G uint8_t* valid;       // isValid
   LSD_G int32_t* blacklisted;
@@ -473,25 +516,25 @@ struct StereoRef {      // one reference (tracked) frame as K4 sees it
 };
 
 struct lsdhip_depthmap {
-  lsdhip_ctx* ctx = nullptr;
+  lsdhip_ctx* ctx = nullptr;       // (owns the streams: everything below goes after lsdhip_depth_destroy has drained the mapping stream)
   HypPlanes cur;         // currentDepthMap
   HypPlanes oth;         // otherDepthMap (propagation target; swapped)
   uint8_t* d_validSnap = nullptr;  // spare validity plane (ping-pong target of K5/K6)
-  void* bases[3] = {nullptr, nullptr, nullptr};  // arena base pointers (for hipFree)
+  LsdDev<char> arenas[3];          // what the planes of cur / oth and the spare validity plane point into (the plane pointers get swapped around)
   lsdhip_frame* activeKeyFrame = nullptr;
   bool activeKeyFrameIsReactivated = false;
   int referenceFrameByIDOffset = 0;   // id of the oldest frame of the last updateKeyframe (DepthMap.cpp:1082; 0 before the first): debugPlotDepthMap's refID
-  char* h_stage = nullptr;         // pinned staging block (refs | refByID) and its device twin
-  char* d_stage = nullptr;
+  LsdPinned<char> h_stage;         // pinned staging block (refs | refByID) and its device twin
+  LsdDev<char> d_stage;
   size_t stage_bytes = 0;
   // K7 scratch
-  int* d_slotCount = nullptr;      // per target
-  int* d_slots = nullptr;          // per target x capacity source indices
-  int* d_ovfHead = nullptr;        // per target: head of the chain of sources beyond the capacity (-1: none)
-  int2* d_ovf = nullptr;           // chain entries (source index, next entry), w*h of them
-  float4* d_cand = nullptr;        // per source candidate (new_idepth, new_var, validity as float bits, target)
-  int* d_flags = nullptr;          // overflow flag etc.
-  double* d_red = nullptr;         // reduction scratch (sum, count)
+  LsdDev<int> d_slotCount;         // per target
+  LsdDev<int> d_slots;             // per target x capacity source indices
+  LsdDev<int> d_ovfHead;           // per target: head of the chain of sources beyond the capacity (-1: none)
+  LsdDev<int2> d_ovf;              // chain entries (source index, next entry), w*h of them
+  LsdDev<float4> d_cand;           // per source candidate (new_idepth, new_var, validity as float bits, target)
+  LsdDev<int> d_flags;             // overflow flag etc.
+  LsdDev<double> d_red;            // reduction scratch (sum, count)
   size_t redStride = 0;            // doubles per set of partials (three sets behind the first 16 doubles)
   bool propClean = false;          // slot counts / chain heads / flags of the K7 scratch are in their rest state
   // A hypothesis on a pixel below the gradient threshold can only come from outside the update loop (ground-truth / random initialisation,
@@ -499,21 +542,21 @@ struct lsdhip_depthmap {
   // observe pass drops them (:125).  While this is set the select pass of a batched update scans every pixel; afterwards the keyframe's
   // gradient candidates.
   bool lowGradHypPossible = true;
-  double* h_red = nullptr;         // pinned
+  LsdPinned<double> h_red;         // pinned
   // GPU-side timing of the mapping calls (events on the context's stream; read back lazily)
-  hipEvent_t ev[8][2] = {};
+  LsdEvent ev[8][2];
   int ev_kind[8] = {};
   bool ev_pending[8] = {};
   int ev_next = 0;
-  unsigned long long* d_obs_trace = nullptr;   // LSD_PHASE_TRACE developer build only
+  LsdDev<unsigned long long> d_obs_trace;      // LSD_PHASE_TRACE developer build only
   size_t obs_trace_words = 0;
   double gpu_ms[4] = {0, 0, 0, 0};    // update, createKeyFrame, finalizeKeyFrame, k_observe alone (sampled while profiling)
   long long gpu_calls[4] = {0, 0, 0, 0};
   unsigned obs_tick = 0;
-  unsigned long long* d_obsCounters = nullptr;   // per wave (searches, steps) of the last counted launch | d_obsAcc: totals (searches, steps, launches)
+  LsdDev<unsigned long long> d_obsCounters;      // per wave (searches, steps) of the last counted launch | d_obsAcc: totals (searches, steps, launches)
   unsigned long long* d_obsAcc = nullptr;
   int obsCounterWaves = 0;
-  float4* d_obsQueue = nullptr;                  // w x h entries: search queue of the two-launch observe of batches (created on first use)
+  LsdDev<float4> d_obsQueue;                     // w x h entries: search queue of the two-launch observe of batches (created on first use)
   unsigned ev_tick[3] = {0, 0, 0};   // calls per kind: every 8th updateKeyframe / 2nd createKeyFrame, finalizeKeyFrame is timed
   float msUpdate = 0, msCreate = 0, msFinalize = 0, msObserve = 0, msRegularize = 0, msPropagate = 0, msFillHoles = 0,
         msSetDepth = 0;
@@ -523,30 +566,29 @@ struct lsdhip_depthmap {
 inline hipStream_t lsd_transport_stream(lsdhip_ctx* c) { return c->aux_active ? c->aux_stream : c->stream; }
 // the stream frame creation and the DepthMap calls run on
 inline hipStream_t lsd_map_stream(lsdhip_ctx* c) { return c->lane_cur >= 0 ? c->lanes[c->lane_cur] : (c->pipeline ? c->mstream : c->stream); }
-int lsd_m_begin(lsdhip_ctx* c);                    // an mstream operation starts (developer switches only: see the note on tracking -> mapping ordering in frame.hip)
+int lsd_m_begin(lsdhip_ctx* c);                    // an mstream operation starts (developer switches only: see the note on tracking -> mapping ordering in context.hip)
 long long lsd_m_record(lsdhip_ctx* c);             // record point on mstream -> its M-sequence (0 when the context is not pipelined, < 0: error)
 int lsd_t_wait_m(lsdhip_ctx* c, long long seq);    // order `stream` behind M-sequence `seq`
 bool lsd_m_done(lsdhip_ctx* c, long long seq);     // has mstream passed M-sequence `seq`?  (never blocks)
 int lsd_sync_all(lsdhip_ctx* c);                   // both streams drained
-// The device test hooks (lsdhip_devtest_*): one device buffer for all inputs and outputs of a call, freed on every return path
-struct LsdDevBuf {
-  void* p = nullptr;
-  ~LsdDevBuf() { if (p) (void)hipFree(p); }
-};
 // Developer instrumentation of the pipeline bug hunt of round 4 (profiles/r04_notes.md §1a) — compiled only into the LSD_DEVTOOLS build
 // (lsd_slam_amd/build.py build_variant("devtools", ["LSD_DEVTOOLS"]), loaded through LSDHIP_LIB); the default library carries none of it:
 //   LSDHIP_PIPE_GATE=1      mapping stream holds until the next tracking job starts (lsd_gate_wait / lsd_gate_open)
 //   LSDHIP_PIPE_DUMMY=<k>   unrelated kernels on the mapping stream beside a tracking job (lsd_pipe_dummy)
 //   LSDHIP_TRACE_SUMS=<f>   order-independent checksums of device buffers, queued on a stream at chosen points of the loop and written
 //                           out when the context is destroyed — two runs of the same loop are compared entry by entry (tools/trace_cmp.py)
-//   LSDHIP_TRACK_REPLAY / LSDHIP_DUMP_L0 / LSDHIP_TRACE_INPUTS / LSDHIP_TRACK_DEBUG / LSDHIP_HOST_TRACE   (tracker.hip, frame.hip)
+//   LSDHIP_TRACK_REPLAY / LSDHIP_DUMP_L0 / LSDHIP_TRACE_INPUTS / LSDHIP_TRACK_DEBUG / LSDHIP_HOST_TRACE   (tracker.hip, devtools.hip)
 #ifdef LSD_DEVTOOLS
 int lsd_gate_wait(lsdhip_ctx* c);
 int lsd_gate_open(lsdhip_ctx* c);
 int lsd_pipe_dummy(lsdhip_ctx* c);
 void lsd_trace_sum(lsdhip_ctx* c, hipStream_t s, int kind, int id, const void* p, size_t bytes);
 void lsd_trace_val(lsdhip_ctx* c, int kind, int id, unsigned long long v);
+void lsd_host_trace_print();          // what a context's destruction prints / writes out
+void lsd_trace_dump(lsdhip_ctx* c);
 #else
+inline void lsd_host_trace_print() {}
+inline void lsd_trace_dump(lsdhip_ctx*) {}
 inline int lsd_gate_wait(lsdhip_ctx*) { return LSDHIP_OK; }
 inline int lsd_gate_open(lsdhip_ctx*) { return LSDHIP_OK; }
 inline int lsd_pipe_dummy(lsdhip_ctx*) { return LSDHIP_OK; }
@@ -562,7 +604,7 @@ int lsd_frame_publish_depth(lsdhip_frame* f);
 int lsd_flush_merges(lsdhip_ctx* c);               // tracker.hip: queue the pending mask merges on the mapping stream
 // A job on the tracking stream of a pipelined context: entered behind everything the mapping stream holds (lsdhip_tracker_track
 // needs less and says so itself); left with the tracking stream DRAINED, because mapping-stream operations are ordered behind tracking
-// work by the host having seen it complete (see frame.hip).  lsdhip_tracker_track, the one hot entry, does not drain: it leaves only
+// work by the host having seen it complete (see context.hip).  lsdhip_tracker_track, the one hot entry, does not drain: it leaves only
 // launches behind that touch nothing but the tracker's own state.
 struct LsdTrackJobScope {
   lsdhip_ctx* c;
@@ -639,7 +681,7 @@ int lsd_frames_require_level0(lsdhip_frame** fs, int n);    // Frame::gradients(
 int lsd_frame_require_level0(lsdhip_frame* f);
 int lsd_frame_require_level0_for_tracking(lsdhip_frame* f);
 // copies `bytes` of kernel-argument records to the device on `s` (stream-ordered) and returns the device address; lsd_args_release after
-// the launches that read them (frame.hip).  begin / commit: the same in two steps, for records that hold their own device address
+// the launches that read them (context.hip).  begin / commit: the same in two steps, for records that hold their own device address
 int lsd_args_push(lsdhip_ctx* c, const void* src, size_t bytes, hipStream_t s, void** dev_out);
 int lsd_args_begin(lsdhip_ctx* c, size_t bytes, void** host_out, void** dev_out);
 int lsd_args_commit(lsdhip_ctx* c, hipStream_t s);
@@ -654,6 +696,7 @@ void lsd_depthmaps_forget_frame(lsdhip_ctx* c, lsdhip_frame* f);   // depthmap.h
 int lsd_prof_collect(lsdhip_ctx* c);
 int lsd_bprof_begin(lsdhip_ctx* c, int kind, hipStream_t s);               // slot (>= 0) when this call is sampled, -1 otherwise, < -1: error
 int lsd_bprof_end(lsdhip_ctx* c, int slot, hipStream_t s, double units);
+int lsd_frames_reserve(lsdhip_ctx* c, int n);  // frame.hip: n arenas allocated and waiting in the pool (lsdhip_ctx_reserve_frames)
 int lsd_frame_resolve(lsdhip_frame* f);        // reads the frame's deferred results (synchronises the stream if any)
 int lsd_ctx_take_slot(lsdhip_ctx* c);          // next slot of the ring (resolving whoever still waits on it)
 // The next slot of the ring becomes the home of f's statistics (Frame::setDepth: mean inverse depth, point count) / of f's rescale factor

@@ -169,7 +169,7 @@ extern "C" int lsdhip_depth_debug_plot(lsdhip_depthmap* dm, int debugDisplay, ui
   LSD_CTX_LOCK(c);
   HIPCHK(hipSetDevice(c->device));
   const size_t bytes = (size_t)c->w * c->h * 3;
-  if (!c->d_plotStage) HIPCHK(hipMalloc((void**)&c->d_plotStage, bytes));
+  if (!c->d_plotStage) { if (int rc = lsd_dev_alloc(c->d_plotStage, bytes)) return rc; }
   if (int rc = lsdhip_depth_debug_plot_dev(dm, debugDisplay, c->d_plotStage)) return rc;
   const hipStream_t ms = lsd_map_stream(c);
   HIPCHK(hipMemcpyAsync(out_host, c->d_plotStage, bytes, hipMemcpyDeviceToHost, ms));

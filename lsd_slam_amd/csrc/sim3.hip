@@ -542,38 +542,38 @@ struct lsdhip_sim3tracker {
   int maxItsPerLvl[LSD_LEVELS] = {5, 20, 50, 100, 100};
   float lambdaSuccessFac = 0.5f, lambdaFailFac = 2.0f, lambdaInitial = 0, stepSizeMin = 1e-8f, convergenceEps = 0.999f;
   float huber_d = 3, var_weight = 1.0f;
-  float* d_rows = nullptr;     // [2][S3_MAXB][S3_NBMAX][64]  (two launch parities: k_sim3_fused)
-  int4* d_topkey = nullptr;    // [2][S3_MAXB][S3_NBMAX]
-  float* h_record = nullptr;   // [S3_MAXB][64] pinned, device-mapped
+  LsdDev<float> d_rows;        // [2][S3_MAXB][S3_NBMAX][64]  (two launch parities: k_sim3_fused)
+  LsdDev<int4> d_topkey;       // [2][S3_MAXB][S3_NBMAX]
+  LsdPinned<float> h_record;   // [S3_MAXB][64] pinned, device-mapped
   float* d_record = nullptr;   // device alias of h_record
   int seq = 0;                 // launch counter, echoed by k_sim3_finalize in word 63 of every active slot's record
   // trackFrameSim3 on the device (k_sim3_fused): per batch slot the job's level descriptions and LM state
+  LsdPinned<char> h_jobBlock;  LsdDev<char> d_jobBlock;               // one block on each side (sim3_block_bytes): the sets, then the states
   Sim3Set* h_sets = nullptr;  Sim3Set* d_sets = nullptr;              // [S3_MAXB]; h_*: pinned staging
   Sim3Track* h_states = nullptr;  Sim3Track* d_states = nullptr;      // [S3_MAXB] ([2][S3_MAXB] on the device: launch parities)
-  lsdhip_sim3_result* h_results = nullptr;  lsdhip_sim3_result* d_results = nullptr;   // [S3_MAXB] pinned, device-mapped
-  int* h_done = nullptr;  int* d_done = nullptr;                              // [2][S3_MAXB] pinned, device-mapped: flags, then the records' check words
+  LsdPinned<lsdhip_sim3_result> h_results;  lsdhip_sim3_result* d_results = nullptr;   // [S3_MAXB] pinned, device-mapped
+  LsdPinned<int> h_done;  int* d_done = nullptr;                              // [2][S3_MAXB] pinned, device-mapped: flags, then the records' check words
   long long lateRecords = 0;                                                  // result records that were incomplete when their flag arrived
   int recentRounds = 0;        // evaluations the longest job of the last call needed: the next call's launch budget
 };
 
 // all of a tracker's storage (defined behind the job structures it holds: "the tracker's storage" below)
 static int sim3_storage_reserve(lsdhip_sim3tracker* t, bool tracking);
-static void sim3_storage_release(lsdhip_sim3tracker* t);
 
 extern "C" int lsdhip_sim3tracker_create(lsdhip_ctx* c, lsdhip_sim3tracker** out) {
   if (!c || !out) return LSDHIP_E_ARG;
   HIPCHK(hipSetDevice(c->device));
-  lsdhip_sim3tracker* t = new lsdhip_sim3tracker();
+  std::unique_ptr<lsdhip_sim3tracker> t(new lsdhip_sim3tracker());
   t->ctx = c;
-  if (int rc = sim3_storage_reserve(t, false)) { sim3_storage_release(t); return rc; }
-  *out = t;
+  if (int rc = sim3_storage_reserve(t.get(), false)) return rc;
+  *out = t.release();
   return LSDHIP_OK;
 }
 extern "C" void lsdhip_sim3tracker_destroy(lsdhip_sim3tracker* t) {
   if (!t) return;
   (void)hipSetDevice(t->ctx->device);
   (void)hipStreamSynchronize(t->ctx->stream);
-  sim3_storage_release(t);
+  delete t;
 }
 extern "C" int lsdhip_sim3tracker_set_max_its(lsdhip_sim3tracker* t, const int its[LSD_LEVELS]) {
   if (!t || !its) return LSDHIP_E_ARG;
@@ -1073,35 +1073,33 @@ static_assert((sizeof(Sim3Set) * S3_MAXB) % alignof(Sim3Track) == 0, "the states
 static size_t sim3_block_bytes(int nstates) { return sizeof(Sim3Set) * S3_MAXB + sizeof(Sim3Track) * (size_t)nstates; }
 static Sim3Track* sim3_block_states(Sim3Set* sets) { return (Sim3Track*)(sets + S3_MAXB); }
 // The evaluation scratch and record of every tracker; with `tracking` also the job storage of trackFrameSim3 (made by the first such call).
-// Every allocation is behind its own pointer, so a call that failed half-way is repeated or released without a leak.
 static int sim3_storage_reserve(lsdhip_sim3tracker* t, bool tracking) {
   if (tracking ? t->d_done != nullptr : t->d_record != nullptr) return LSDHIP_OK;
-  const size_t mb = (size_t)S3_NBMAX * S3_MAXB * 2;
-  if (!t->d_rows) HIPCHK(hipMalloc((void**)&t->d_rows, mb * 64 * 4));
-  if (!t->d_topkey) HIPCHK(hipMalloc((void**)&t->d_topkey, mb * 16));
-  if (!t->h_record) {
-    HIPCHK(hipHostMalloc((void**)&t->h_record, S3_MAXB * 64 * 4, hipHostMallocMapped));
+  if (!t->d_record) {
+    const size_t mb = (size_t)S3_NBMAX * S3_MAXB * 2;
+    float* alias = nullptr;
+    if (int rc = lsd_dev_alloc(t->d_rows, mb * 64)) return rc;
+    if (int rc = lsd_dev_alloc(t->d_topkey, mb)) return rc;
+    if (int rc = lsd_pinned_alloc(t->h_record, (size_t)S3_MAXB * 64, hipHostMallocMapped, &alias)) return rc;
     memset(t->h_record, 0, S3_MAXB * 64 * 4);
+    t->d_record = alias;
   }
-  HIPCHK(hipHostGetDevicePointer((void**)&t->d_record, t->h_record, 0));
   if (!tracking) return LSDHIP_OK;
-  if (!t->d_sets) HIPCHK(hipMalloc((void**)&t->d_sets, sim3_block_bytes(2 * S3_MAXB)));
-  if (!t->h_sets) HIPCHK(hipHostMalloc((void**)&t->h_sets, sim3_block_bytes(S3_MAXB), hipHostMallocDefault));
+  // the job storage: all of it or none, so a call that failed half-way leaves the tracker as it was
+  LsdDev<char> d_jobBlock; LsdPinned<char> h_jobBlock;
+  LsdPinned<lsdhip_sim3_result> h_results; LsdPinned<int> h_done;
+  lsdhip_sim3_result* d_results = nullptr; int* d_done = nullptr;
+  if (int rc = lsd_dev_alloc(d_jobBlock, sim3_block_bytes(2 * S3_MAXB))) return rc;
+  if (int rc = lsd_pinned_alloc(h_jobBlock, sim3_block_bytes(S3_MAXB), hipHostMallocDefault)) return rc;
+  if (int rc = lsd_pinned_alloc(h_results, (size_t)S3_MAXB, hipHostMallocMapped, &d_results)) return rc;
+  if (int rc = lsd_pinned_alloc(h_done, (size_t)S3_MAXB * 2, hipHostMallocMapped, &d_done)) return rc;   // [k]: flag, [S3_MAXB + k]: check word of result k
+  memset(h_done, 0, sizeof(int) * S3_MAXB * 2);
+  t->d_jobBlock = std::move(d_jobBlock); t->h_jobBlock = std::move(h_jobBlock);
+  t->d_sets = (Sim3Set*)t->d_jobBlock.get(); t->h_sets = (Sim3Set*)t->h_jobBlock.get();
   t->d_states = sim3_block_states(t->d_sets); t->h_states = sim3_block_states(t->h_sets);
-  if (!t->h_results) HIPCHK(hipHostMalloc((void**)&t->h_results, sizeof(lsdhip_sim3_result) * S3_MAXB, hipHostMallocMapped));
-  HIPCHK(hipHostGetDevicePointer((void**)&t->d_results, t->h_results, 0));
-  if (!t->h_done) {   // [k]: flag, [S3_MAXB + k]: check word of result k
-    HIPCHK(hipHostMalloc((void**)&t->h_done, sizeof(int) * S3_MAXB * 2, hipHostMallocMapped));
-    memset(t->h_done, 0, sizeof(int) * S3_MAXB * 2);
-  }
-  HIPCHK(hipHostGetDevicePointer((void**)&t->d_done, t->h_done, 0));
+  t->h_results = std::move(h_results); t->d_results = d_results;
+  t->h_done = std::move(h_done); t->d_done = d_done;
   return LSDHIP_OK;
-}
-// ... and the tracker itself (the d_* of pinned blocks are aliases)
-static void sim3_storage_release(lsdhip_sim3tracker* t) {
-  (void)hipFree(t->d_rows); (void)hipFree(t->d_topkey); (void)hipHostFree(t->h_record);
-  (void)hipFree(t->d_sets); (void)hipHostFree(t->h_sets); (void)hipHostFree(t->h_results); (void)hipHostFree(t->h_done);
-  delete t;
 }
 static Sim3LM sim3_lm_params(const lsdhip_sim3tracker* t) {
   Sim3LM P;
@@ -1273,9 +1271,9 @@ extern "C" int lsdhip_devtest_sim3_lm_step(lsdhip_ctx* c, int n, const float* A,
   HIPCHK(hipSetDevice(c->device));
   if (c->pipeline) { if (int rc = lsd_sync_all(c)) return rc; }
   const size_t nd = (size_t)n * (1 + 8 + 8), nf = (size_t)n * (49 + 7 + 1 + 7);
-  LsdDevBuf buf;
-  HIPCHK(hipMalloc(&buf.p, nd * sizeof(double) + nf * sizeof(float)));
-  double* dd = (double*)buf.p;
+  LsdDev<void> buf;      // one device buffer for all inputs and outputs of the call, freed on every return path
+  if (int rc = lsd_dev_alloc(buf, nd * sizeof(double) + nf * sizeof(float))) return rc;
+  double* dd = (double*)buf.get();
   double *dnc = dd, *dT = dnc + n, *dTn = dT + (size_t)n * 8;
   float* df = (float*)(dd + nd);
   float *dA = df, *db = dA + (size_t)n * 49, *dl = db + (size_t)n * 7, *dinc = dl + n;

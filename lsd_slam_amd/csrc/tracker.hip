@@ -1336,7 +1336,8 @@ static TrackScratch scratch_at(const lsdhip_tracker* t, float* base, size_t jobs
 extern "C" int lsdhip_tracker_create(lsdhip_ctx* c, lsdhip_tracker** out) {
   if (!c || !out) return LSDHIP_E_ARG;
   HIPCHK(hipSetDevice(c->device));
-  lsdhip_tracker* t = new lsdhip_tracker();
+  std::unique_ptr<lsdhip_tracker> owner(new lsdhip_tracker());
+  lsdhip_tracker* t = owner.get();
   t->ctx = c;
   const int maxIterations[6] = {5, 20, 50, 100, 100, 100};
   for (int l = 0; l < LSD_LEVELS; l++) {
@@ -1348,7 +1349,7 @@ extern "C" int lsdhip_tracker_create(lsdhip_ctx* c, lsdhip_tracker** out) {
   if (const char* e = getenv("LSDHIP_TRACK_BLOCK")) t->block = atoi(e);
   if (const char* e = getenv("LSDHIP_TRACK_CAP")) t->grid_cap = atoi(e);
   if (const char* e = getenv("LSDHIP_EVAL_BATCH")) t->evalBatch = atoi(e) != 0;
-  if (t->block != 256) { lsd_set_error("LSDHIP_TRACK_BLOCK must be 256"); delete t; return LSDHIP_E_ARG; }
+  if (t->block != 256) { lsd_set_error("LSDHIP_TRACK_BLOCK must be 256"); return LSDHIP_E_ARG; }
   t->grid_cap = lsd_grid_cap(t->grid_cap, t->block, RS_END);
   t->max_blocks = t->grid_cap;
   const size_t partials_bytes = scratch_layout(1, LSD_SPEC_MAX, (size_t)t->max_blocks).end * sizeof(float);
@@ -1367,38 +1368,37 @@ extern "C" int lsdhip_tracker_create(lsdhip_ctx* c, lsdhip_tracker** out) {
     for (int l = 0; l < LSD_LEVELS; l++) t->specLevel[l] = v[l] < 0 ? 0 : (v[l] > LSD_SPEC_MAX ? LSD_SPEC_MAX : v[l]);
   }
   t->maskStride = (((size_t)c->wl[LSD_TRACK_MIN_LEVEL] * c->hl[LSD_TRACK_MIN_LEVEL]) + 255) & ~(size_t)255;
-  HIPCHK(hipMalloc((void**)&t->d_maskSide, 2 * t->maskStride * (LSD_SPEC_MAX - 1)));
+  if (int rc = lsd_dev_alloc(t->d_maskSide, 2 * t->maskStride * (LSD_SPEC_MAX - 1))) return rc;
   HIPCHK(hipMemsetAsync(t->d_maskSide, 0, 2 * t->maskStride * (LSD_SPEC_MAX - 1), c->stream));
-  HIPCHK(hipMalloc((void**)&t->d_partials, partials_bytes));
+  if (int rc = lsd_dev_alloc(t->d_partials, partials_bytes / sizeof(float))) return rc;
   HIPCHK(hipMemsetAsync(t->d_partials, 0, partials_bytes, c->stream));
 #ifdef LSD_ORDER_CHECK
   {
     const size_t nd = 8 + 2 * 8192;
-    HIPCHK(hipMalloc((void**)&t->d_dbg, nd * 8));
+    if (int rc = lsd_dev_alloc(t->d_dbg, nd)) return rc;
     std::vector<unsigned long long> init(nd, 0);
     for (size_t i = 8; i < nd; i += 2) init[i] = ~0ull;     // (min, max) pairs of the per-launch totals hash
     HIPCHK(hipMemcpy(t->d_dbg, init.data(), nd * 8, hipMemcpyHostToDevice));
   }
 #endif
 #ifdef LSD_DEVTOOLS
-  HIPCHK(hipMalloc((void**)&t->d_log, 4096 * 16 * 4));
+  if (int rc = lsd_dev_alloc(t->d_log, 4096 * 16)) return rc;
   HIPCHK(hipMemset(t->d_log, 0, 4096 * 16 * 4));
 #endif
-  HIPCHK(hipMalloc((void**)&t->d_state, 2 * sizeof(TrackState)));
+  if (int rc = lsd_dev_alloc(t->d_state, 2)) return rc;
   HIPCHK(hipMemsetAsync(t->d_state, 0, 2 * sizeof(TrackState), c->stream));
 #ifdef LSD_PHASE_TRACE
-  HIPCHK(hipMalloc((void**)&t->d_trace, (1 + 4096 * LSD_TRACE_WORDS) * 8));
+  if (int rc = lsd_dev_alloc(t->d_trace, 1 + 4096 * LSD_TRACE_WORDS)) return rc;
   HIPCHK(hipMemsetAsync(t->d_trace, 0, (1 + 4096 * LSD_TRACE_WORDS) * 8, c->stream));
 #endif
-  HIPCHK(hipHostMalloc((void**)&t->h_summary, sizeof(TrackSummary), hipHostMallocMapped));
-  HIPCHK(hipHostGetDevicePointer((void**)&t->d_summary, t->h_summary, 0));
+  if (int rc = lsd_pinned_alloc(t->h_summary, 1, hipHostMallocMapped, &t->d_summary)) return rc;
   memset(t->h_summary, 0, sizeof(TrackSummary));
   const char* env = getenv("LSDHIP_HOST_LM");
   t->hostLM = env && env[0] == '1';
   if (const char* e = getenv("LSDHIP_SPIN")) t->spinWait = e[0] != '0';
   if (const char* e = getenv("LSDHIP_BUDGET_EXTRA")) { t->budgetExtra = atoi(e); if (t->budgetExtra < 1) t->budgetExtra = 1; }
   if (const char* e = getenv("LSDHIP_BUDGET_FIXED")) { t->budgetFixed = atoi(e); if (t->budgetFixed < 1) t->budgetFixed = 0; }   // test hook: every job runs out of budget
-  *out = t;
+  *out = owner.release();
   return LSDHIP_OK;
 }
 extern "C" void lsdhip_tracker_destroy(lsdhip_tracker* t) {
@@ -1417,7 +1417,6 @@ extern "C" void lsdhip_tracker_destroy(lsdhip_tracker* t) {
 #endif
   (void)hipSetDevice(t->ctx->device);
   (void)hipStreamSynchronize(t->ctx->stream);
-  if (t->h_overlapSums) (void)hipHostFree(t->h_overlapSums);
 #ifdef LSD_ORDER_CHECK
   {
     std::vector<unsigned long long> h(8 + 2 * 8192, 0);
@@ -1434,7 +1433,6 @@ extern "C" void lsdhip_tracker_destroy(lsdhip_tracker* t) {
                     "%d launch slots hashed, %d in which the workgroups did NOT all see the same totals\n", h[0], t->dbgCum, h[1], h[2], used, split);
   }
 #endif
-  if (t->d_dbg) (void)hipFree(t->d_dbg);
 #ifdef LSD_PHASE_TRACE
   if (const char* path = getenv("LSDHIP_TRACE_FILE")) {
     std::vector<unsigned long long> h(1 + 4096 * LSD_TRACE_WORDS);
@@ -1449,17 +1447,7 @@ extern "C" void lsdhip_tracker_destroy(lsdhip_tracker* t) {
       }
     }
   }
-  (void)hipFree(t->d_trace);
 #endif
-  if (t->d_bjobs) { (void)hipFree(t->d_bjobs); (void)hipFree(t->d_bstate); (void)hipFree(t->d_bscratch); (void)hipHostFree(t->h_bjobs); (void)hipHostFree(t->h_bsummary); }
-  (void)hipFree(t->d_partials);
-  (void)hipFree(t->d_maskSide);
-  (void)hipFree(t->d_state);
-#ifdef LSD_DEVTOOLS
-  (void)hipFree(t->d_log);
-#endif
-  (void)hipHostFree(t->h_summary);
-  if (t->d_pts) (void)hipFree(t->d_pts);
   delete t;
 }
 extern "C" int lsdhip_tracker_set_enqueue_hook(lsdhip_tracker* t, lsdhip_enqueue_hook fn, void* user) {
@@ -2308,15 +2296,19 @@ static int batch_reserve(lsdhip_tracker* t, int n) {
   LSD_CTX_LOCK(c);
   if (n <= t->batch_capacity) return LSDHIP_OK;
   HIPCHK(hipStreamSynchronize(c->stream));
-  if (t->d_bjobs) { (void)hipFree(t->d_bjobs); (void)hipFree(t->d_bstate); (void)hipFree(t->d_bscratch); (void)hipHostFree(t->h_bjobs); (void)hipHostFree(t->h_bsummary); }
-  t->batch_capacity = n < 8 ? 8 : n;
-  const size_t B = (size_t)t->batch_capacity, bytes = scratch_layout(B, LSD_BATCH_SPEC_MAX, (size_t)t->max_blocks).end * sizeof(float);
-  HIPCHK(hipMalloc((void**)&t->d_bjobs, B * sizeof(TrackJob)));
-  HIPCHK(hipMalloc((void**)&t->d_bstate, B * 2 * sizeof(TrackState)));
-  HIPCHK(hipMalloc((void**)&t->d_bscratch, bytes));
-  HIPCHK(hipMemsetAsync(t->d_bscratch, 0, bytes, c->stream));
-  HIPCHK(hipHostMalloc((void**)&t->h_bjobs, B * sizeof(TrackJob), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc((void**)&t->h_bsummary, B * sizeof(TrackSummary), hipHostMallocMapped));
+  // the new set exists before the old one goes: a failed growth leaves the tracker at its old capacity
+  const size_t B = n < 8 ? 8 : (size_t)n, floats = scratch_layout(B, LSD_BATCH_SPEC_MAX, (size_t)t->max_blocks).end;
+  LsdDev<TrackJob> d_bjobs; LsdDev<TrackState> d_bstate; LsdDev<float> d_bscratch;
+  LsdPinned<TrackJob> h_bjobs; LsdPinned<TrackSummary> h_bsummary;
+  if (int rc = lsd_dev_alloc(d_bjobs, B)) return rc;
+  if (int rc = lsd_dev_alloc(d_bstate, B * 2)) return rc;
+  if (int rc = lsd_dev_alloc(d_bscratch, floats)) return rc;
+  HIPCHK(hipMemsetAsync(d_bscratch, 0, floats * sizeof(float), c->stream));
+  if (int rc = lsd_pinned_alloc(h_bjobs, B, hipHostMallocDefault)) return rc;
+  if (int rc = lsd_pinned_alloc(h_bsummary, B, hipHostMallocMapped)) return rc;
+  t->d_bjobs = std::move(d_bjobs); t->d_bstate = std::move(d_bstate); t->d_bscratch = std::move(d_bscratch);
+  t->h_bjobs = std::move(h_bjobs); t->h_bsummary = std::move(h_bsummary);
+  t->batch_capacity = (int)B;
   return LSDHIP_OK;
 }
 // What every launch of a batch takes besides its shape: the scratch (arrays over [job][parity][trial]; cmax = trial slots per parity, 1: no
@@ -2541,13 +2533,9 @@ extern "C" int lsdhip_tracker_eval_throughput(lsdhip_tracker* t, int n, lsdhip_f
   if (o.rc) return o.rc;
   BatchLaunch rec;
   if (int rcl = batch_launch_record(t, 1, &rec)) return rcl;
-  struct EventPair {      // destroyed on every exit path
-    hipEvent_t a = nullptr, b = nullptr;
-    ~EventPair() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  } evp;
-  HIPCHK(hipEventCreate(&evp.a));
-  HIPCHK(hipEventCreate(&evp.b));
-  const hipEvent_t e0 = evp.a, e1 = evp.b;
+  LsdEvent e0, e1;
+  if (int rce = lsd_event_create(e0)) return rce;
+  if (int rce = lsd_event_create(e1)) return rce;
   launch_batch_step<TS_LM>(t, rec, 1, n, 0, 1, TrackSpec{});
   launch_batch_step<TS_EVAL>(t, rec, grid, n, 1, 0, TrackSpec{});     // warm-up
   HIPCHK(hipEventRecord(e0, c->stream));
@@ -2621,9 +2609,9 @@ extern "C" int lsdhip_tracker_evaluate_batch(lsdhip_tracker* t, int n, lsdhip_fr
 
 static int upload_points(lsdhip_tracker* t, const float* pos, const float* colvar, int n) {
   if (n > t->pts_capacity) {
-    if (t->d_pts) HIPCHK(hipFree(t->d_pts));
-    t->pts_capacity = n > 4096 ? n : 4096;
-    HIPCHK(hipMalloc((void**)&t->d_pts, (size_t)t->pts_capacity * 5 * sizeof(float)));
+    const int cap = n > 4096 ? n : 4096;
+    if (int rc = lsd_dev_alloc(t->d_pts, (size_t)cap * 5)) return rc;
+    t->pts_capacity = cap;
   }
   HIPCHK(hipMemcpyAsync(t->d_pts, pos, (size_t)n * 12, hipMemcpyHostToDevice, t->ctx->stream));
   if (colvar) HIPCHK(hipMemcpyAsync(t->d_pts + (size_t)t->pts_capacity * 3, colvar, (size_t)n * 8, hipMemcpyHostToDevice, t->ctx->stream));
@@ -2742,9 +2730,8 @@ static int overlap_bank_run(lsdhip_tracker* t, lsdhip_kfbank* b, int n, const in
   // the sums land in pinned host memory the kernel writes through its device alias (as k_overlap writes the tracker's summary): no copy
   if (n > t->overlapSumsCapacity) {
     HIPCHK(hipStreamSynchronize(c->stream));
-    if (t->h_overlapSums) { (void)hipHostFree(t->h_overlapSums); t->h_overlapSums = nullptr; t->overlapSumsCapacity = 0; }
     const int cap = n < 256 ? 256 : n * 2;
-    HIPCHK(hipHostMalloc((void**)&t->h_overlapSums, sizeof(float) * (size_t)cap, hipHostMallocMapped));
+    if (int rc = lsd_pinned_alloc(t->h_overlapSums, (size_t)cap, hipHostMallocMapped)) return rc;
     t->overlapSumsCapacity = cap;
   }
   float* d_out = nullptr;
@@ -2886,9 +2873,9 @@ extern "C" int lsdhip_devtest_se3f_lm_step(lsdhip_ctx* c, int n, const float* A,
   HIPCHK(hipSetDevice(c->device));
   if (c->pipeline) { if (int rc = lsd_sync_all(c)) return rc; }
   const size_t nin = (size_t)n * (36 + 6 + 1 + 7), nout = (size_t)n * (6 + 7);
-  LsdDevBuf buf;
-  HIPCHK(hipMalloc(&buf.p, (nin + nout) * sizeof(float)));
-  float* d = (float*)buf.p;
+  LsdDev<float> buf;      // one device buffer for all inputs and outputs of the call, freed on every return path
+  if (int rc = lsd_dev_alloc(buf, nin + nout)) return rc;
+  float* d = buf;
   float *dA = d, *db = dA + (size_t)n * 36, *ddamp = db + (size_t)n * 6, *dT = ddamp + n, *dinc = dT + (size_t)n * 7, *dTn = dinc + (size_t)n * 6;
   HIPCHK(hipMemcpyAsync(dA, A, (size_t)n * 36 * sizeof(float), hipMemcpyHostToDevice, c->stream));
   HIPCHK(hipMemcpyAsync(db, b, (size_t)n * 6 * sizeof(float), hipMemcpyHostToDevice, c->stream));
