@@ -335,6 +335,19 @@ int lsdhip_tracker_track_permaref_batch(lsdhip_tracker* t, int n, const float* p
                                         lsdhip_track_result* results);
 int lsdhip_tracker_check_overlap(lsdhip_tracker* t, const float* pos3_host, int n, const double referenceToFrame[7],
                                  float* usage_out);
+/* test hooks for the explicit-point-list evaluation (the arm of the step kernel trackFrameOnPermaref runs): K1+K2+K3 once per list at
+ * QUICK_KF_CHECK_LVL, at a fixed referenceToFrame (float (qw,qx,qy,qz,tx,ty,tz)) and affine pair, records as lsdhip_tracker_evaluate
+ * fills them.  tiles (2 ints per job, may be NULL): the workgroups the list was tiled into, and 1 if every lane had at most one point.
+ * No tracker state that a later track call reads is changed.
+ * _points: one uploaded list, the single job's evaluation (as lsdhip_tracker_evaluate runs a keyframe's).
+ * _points_batch: n lists concatenated (counts[j] points each), job j against frames[j] at referenceToFrame[7 j ..] and
+ *   (affine[2 j], affine[2 j + 1]), laid out and run as lsdhip_tracker_track_permaref_batch lays out and runs its jobs. */
+int lsdhip_tracker_evaluate_points(lsdhip_tracker* t, const float* pos3_host, const float* colorAndVar2_host, int n, lsdhip_frame* frame,
+                                   const float referenceToFrame[7], float affine_a, float affine_b, lsdhip_residual_record* out,
+                                   int* tiles);
+int lsdhip_tracker_evaluate_points_batch(lsdhip_tracker* t, int n, const float* pos3_host, const float* colorAndVar2_host,
+                                         const int* counts, lsdhip_frame** frames, const float* referenceToFrame, const float* affine,
+                                         lsdhip_residual_record* out, int* tiles);
 
 /* ---- keyframe bank: the permanent references of all keyframes on the device ------------------ */
 /* What Frame::setPermaRef (C/DataStructures/Frame.cpp:149-174) keeps per keyframe in host vectors — the level-QUICK_KF_CHECK_LVL
@@ -380,6 +393,11 @@ int lsdhip_tracker_check_overlap_bank(lsdhip_tracker* t, lsdhip_kfbank* bank, in
  * lsdhip_tracker_track_permaref_batch on the downloaded clouds bit for bit. */
 int lsdhip_tracker_track_permaref_bank(lsdhip_tracker* t, lsdhip_kfbank* bank, int n, const int* slots, lsdhip_frame** frames,
                                        const double* refToFrame, lsdhip_track_result* results);
+/* test hook: lsdhip_tracker_evaluate_points_batch over (bank, slots), the jobs reading their points where they lie in the bank; n = 1
+ * takes the single job's evaluation, as lsdhip_tracker_track_permaref_bank takes the single job's chain.  out[j] equals
+ * lsdhip_tracker_evaluate_points_batch (n = 1: lsdhip_tracker_evaluate_points) on the downloaded clouds bit for bit. */
+int lsdhip_tracker_evaluate_points_bank(lsdhip_tracker* t, lsdhip_kfbank* bank, int n, const int* slots, lsdhip_frame** frames,
+                                        const float* referenceToFrame, const float* affine, lsdhip_residual_record* out, int* tiles);
 /* What TrackableKeyFrameSearch::findRePositionCandidate decided (TrackableKeyFrameSearch.cpp:103-172). */
 typedef struct lsdhip_reposition_result {
   int slot, frameId;                        /* bestFrame: its slot and frame id, -1 / -1 if none (:156-171) */

@@ -173,6 +173,9 @@ def _signatures():
         "lsdhip_tracker_track_permaref": (i, [vp, vp, vp, i, vp, vp, C.POINTER(TrackResult)]),
         "lsdhip_tracker_track_permaref_batch": (i, [vp, i, vp, vp, vp, pvp, vp, C.POINTER(TrackResult)]),
         "lsdhip_tracker_check_overlap": (i, [vp, vp, i, vp, C.POINTER(C.c_float)]),
+        "lsdhip_tracker_evaluate_points": (i, [vp, vp, vp, i, vp, vp, f, f, C.POINTER(ResidualRecord), vp]),
+        "lsdhip_tracker_evaluate_points_batch": (i, [vp, i, vp, vp, vp, pvp, vp, vp, C.POINTER(ResidualRecord), vp]),
+        "lsdhip_tracker_evaluate_points_bank": (i, [vp, vp, i, vp, pvp, vp, vp, C.POINTER(ResidualRecord), vp]),
         "lsdhip_kfbank_create": (i, [vp, i, pvp]),
         "lsdhip_kfbank_destroy": (None, [vp]),
         "lsdhip_kfbank_put": (i, [vp, vp, C.POINTER(C.c_int)]),

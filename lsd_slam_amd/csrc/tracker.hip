@@ -2802,6 +2802,119 @@ extern "C" int lsdhip_tracker_track_permaref_bank(lsdhip_tracker* t, lsdhip_kfba
   return permaref_bank_run(t, b, n, slots, frames, refToFrame, results);
 }
 
+// ---- test hooks: one evaluation per explicit point list, in the launches the trackFrameOnPermaref entries run ---------------------------
+// The permaref job of the list (fill_permaref_job: the level's description, its tiling for the batch's shape), evalOnly at the given pose
+// and affine pair.
+static int fill_points_eval_job(lsdhip_tracker* t, TrackJob& job, BatchShape shape, const float* d_pos, const float* d_colvar, int npts,
+                                lsdhip_frame* frame, const float T7[7], float aff_a, float aff_b) {
+  if (int rc = fill_permaref_job(t, job, shape, d_pos, d_colvar, npts, frame, pose_from7(T7))) return rc;
+  job.evalOnly = 1;
+  job.aff_a0 = aff_a; job.aff_b0 = aff_b;
+  return LSDHIP_OK;
+}
+// the tracker's public members an evaluation with a host round trip writes (evaluate_pose): the hooks put them back
+struct EvalMembers {
+  int numEvaluations;
+  float pointUsage, lastGoodCount, lastBadCount, lastMeanRes, aff_a, aff_b, aff_a_lastIt, aff_b_lastIt;
+  explicit EvalMembers(const lsdhip_tracker* t)
+      : numEvaluations(t->numEvaluations), pointUsage(t->pointUsage), lastGoodCount(t->lastGoodCount), lastBadCount(t->lastBadCount),
+        lastMeanRes(t->lastMeanRes), aff_a(t->affineEstimation_a), aff_b(t->affineEstimation_b), aff_a_lastIt(t->affineEstimation_a_lastIt),
+        aff_b_lastIt(t->affineEstimation_b_lastIt) {}
+  void restore(lsdhip_tracker* t) const {
+    t->numEvaluations = numEvaluations;
+    t->pointUsage = pointUsage; t->lastGoodCount = lastGoodCount; t->lastBadCount = lastBadCount; t->lastMeanRes = lastMeanRes;
+    t->affineEstimation_a = aff_a; t->affineEstimation_b = aff_b;
+    t->affineEstimation_a_lastIt = aff_a_lastIt; t->affineEstimation_b_lastIt = aff_b_lastIt;
+  }
+};
+static void tiles_of(const TrackJob& job, int* tiles) {
+  if (!tiles) return;
+  tiles[0] = job.lv[LSD_QUICK_KF_CHECK_LVL].nblocks;
+  tiles[1] = job.lv[LSD_QUICK_KF_CHECK_LVL].singlePass;
+}
+// the single job's evaluation (evaluate_pose) of a list that is already on the device
+static int points_eval_single(lsdhip_tracker* t, const float* d_pos, const float* d_colvar, int n, lsdhip_frame* frame, const float T7[7],
+                              float aff_a, float aff_b, lsdhip_residual_record* out, int* tiles) {
+  const EvalMembers keep(t);
+  t->affineEstimation_a = aff_a; t->affineEstimation_b = aff_b;   // (evaluate_pose evaluates at the tracker's pair)
+  TrackJob job;
+  int rc = fill_points_eval_job(t, job, BatchShape{}, d_pos, d_colvar, n, frame, T7, aff_a, aff_b);
+  EvalOut ev;
+  if (!rc) rc = evaluate_pose(t, job, job.T0, LSD_QUICK_KF_CHECK_LVL, &ev);
+  if (!rc) { record_of(t->h_summary, out); tiles_of(job, tiles); }
+  keep.restore(t);
+  return rc;
+}
+// the records of a finished batch of evalOnly jobs
+static int points_eval_collect(lsdhip_tracker* t, const char* entry, int n, lsdhip_residual_record* out, int* tiles) {
+  for (int j = 0; j < n; j++) {
+    const TrackSummary* S = &t->h_bsummary[j];
+    if (!S->done) { lsd_set_error("%s: job %d did not finish", entry, j); return LSDHIP_E_STATE; }
+    record_of(S, &out[j]);
+    tiles_of(t->h_bjobs[j], tiles ? tiles + 2 * (size_t)j : nullptr);
+  }
+  return LSDHIP_OK;
+}
+
+extern "C" int lsdhip_tracker_evaluate_points(lsdhip_tracker* t, const float* pos, const float* colvar, int n, lsdhip_frame* frame,
+                                              const float T7[7], float aff_a, float aff_b, lsdhip_residual_record* out, int* tiles) {
+  if (!t || !pos || !colvar || n <= 0 || !frame || !T7 || !out) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = t->ctx;
+  LSD_CTX_LOCK(c);
+  LsdTrackJobScope tjob_(c, true);
+  if (tjob_.rc) return tjob_.rc;
+  HIPCHK(hipSetDevice(c->device));
+  if (int rc = upload_points(t, pos, colvar, n)) return rc;
+  return points_eval_single(t, t->d_pts, t->d_pts + (size_t)t->pts_capacity * 3, n, frame, T7, aff_a, aff_b, out, tiles);
+}
+
+extern "C" int lsdhip_tracker_evaluate_points_batch(lsdhip_tracker* t, int n, const float* pos, const float* colvar, const int* counts,
+                                                    lsdhip_frame** frames, const float* refToFrame, const float* affine,
+                                                    lsdhip_residual_record* out, int* tiles) {
+  if (!t || n <= 0 || !pos || !colvar || !counts || !frames || !refToFrame || !affine || !out) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = t->ctx;
+  LSD_CTX_LOCK(c);
+  LsdTrackJobScope tjob_(c, true);
+  if (tjob_.rc) return tjob_.rc;
+  HIPCHK(hipSetDevice(c->device));
+  int total = 0;
+  for (int j = 0; j < n; j++) { if (counts[j] <= 0 || !frames[j]) return LSDHIP_E_ARG; total += counts[j]; }
+  if (int rc = upload_points(t, pos, colvar, total)) return rc;
+  int off = 0;
+  const BatchOpened o = batch_open(t, "lsdhip_tracker_evaluate_points_batch", n, nullptr, frames, false, [&](int j, TrackJob& job, BatchShape shape) {
+    const int at = off;
+    off += counts[j];
+    return fill_points_eval_job(t, job, shape, t->d_pts + (size_t)at * 3, t->d_pts + (size_t)t->pts_capacity * 3 + (size_t)at * 2, counts[j], frames[j],
+                                refToFrame + 7 * (size_t)j, affine[2 * (size_t)j], affine[2 * (size_t)j + 1]);
+  });
+  if (o.rc) return o.rc;
+  if (int rc = batch_run(t, n, false, false)) return rc;
+  return points_eval_collect(t, "lsdhip_tracker_evaluate_points_batch", n, out, tiles);
+}
+
+extern "C" int lsdhip_tracker_evaluate_points_bank(lsdhip_tracker* t, lsdhip_kfbank* b, int n, const int* slots, lsdhip_frame** frames,
+                                                   const float* refToFrame, const float* affine, lsdhip_residual_record* out, int* tiles) {
+  if (!t || !b || n <= 0 || !slots || !frames || !refToFrame || !affine || !out) return LSDHIP_E_ARG;
+  lsdhip_ctx* c = t->ctx;
+  LSD_CTX_LOCK(c);
+  if (int rc = bank_slots_ok("lsdhip_tracker_evaluate_points_bank", t, b, n, slots)) return rc;
+  for (int j = 0; j < n; j++) if (!frames[j] || frames[j]->ctx != c) return LSDHIP_E_ARG;
+  LsdTrackJobScope tjob_(c, true);
+  if (tjob_.rc) return tjob_.rc;
+  HIPCHK(hipSetDevice(c->device));
+  // (one candidate: the single job's chain, as permaref_bank_run)
+  if (n == 1)
+    return points_eval_single(t, b->pos(slots[0]), b->colvar(slots[0]), b->slots[(size_t)slots[0]].numPoints, frames[0], refToFrame, affine[0], affine[1],
+                              out, tiles);
+  const BatchOpened o = batch_open(t, "lsdhip_tracker_evaluate_points_bank", n, nullptr, frames, false, [&](int j, TrackJob& job, BatchShape shape) {
+    return fill_points_eval_job(t, job, shape, b->pos(slots[j]), b->colvar(slots[j]), b->slots[(size_t)slots[j]].numPoints, frames[j],
+                                refToFrame + 7 * (size_t)j, affine[2 * (size_t)j], affine[2 * (size_t)j + 1]);
+  });
+  if (o.rc) return o.rc;
+  if (int rc = batch_run(t, n, false, false)) return rc;
+  return points_eval_collect(t, "lsdhip_tracker_evaluate_points_bank", n, out, tiles);
+}
+
 // TrackableKeyFrameSearch::findRePositionCandidate (TrackableKeyFrameSearch.cpp:103-172): the host stages are reposition_plan.hpp's, the
 // two launches stand between them.  Two host waits per search: the score of stage 3's usages decides which tracking jobs exist.
 extern "C" int lsdhip_tracker_find_reposition_candidate(lsdhip_tracker* t, lsdhip_kfbank* b, lsdhip_frame* frame, const double frameCamToWorld[8],

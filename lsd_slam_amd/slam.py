@@ -603,6 +603,51 @@ class SE3Tracker:
         check(self.L.lsdhip_tracker_evaluate_batch(self.h_, n, kfs, frs, T.ctypes.data, ab.ctypes.data, int(level), res, form.ctypes.data), False)
         return list(res), form
 
+    def evaluatePoints(self, permaRef_pos, permaRef_colVar, frame, referenceToFrame, a=1.0, b=0.0):
+        """test hook: `evaluate` on an explicit level-4 point list, the single job's evaluation (lsdhip_tracker_evaluate_points).
+        Returns (record, [workgroups, single pass])."""
+        pos = np.ascontiguousarray(permaRef_pos, np.float32)
+        cv = np.ascontiguousarray(permaRef_colVar, np.float32)
+        T = np.ascontiguousarray(referenceToFrame, dtype=np.float32)
+        r = capi.ResidualRecord()
+        tiles = np.zeros(2, np.int32)
+        check(self.L.lsdhip_tracker_evaluate_points(self.h_, pos.ctypes.data, cv.ctypes.data, len(pos), frame.h_, T.ctypes.data, a, b, C.byref(r),
+                                                    tiles.ctypes.data), False)
+        return r, tiles
+
+    @staticmethod
+    def _poses_and_affine(n, referenceToFrames, affine):
+        T = np.ascontiguousarray(referenceToFrames, dtype=np.float32).reshape(n, 7)
+        ab = np.ascontiguousarray(np.tile([1.0, 0.0], (n, 1)) if affine is None else affine, dtype=np.float32).reshape(n, 2)
+        return T, ab
+
+    def evaluatePointsBatch(self, clouds, frames, referenceToFrames, affine=None):
+        """test hook: evaluatePoints for n lists in the launches of trackFrameOnPermarefBatch (lsdhip_tracker_evaluate_points_batch);
+        clouds: list of (pos n_j x 3, colVar n_j x 2); affine: n x 2.  Returns (list of n records, tiles n x 2)."""
+        n = len(clouds)
+        pos = np.ascontiguousarray(np.concatenate([c[0] for c in clouds]), np.float32)
+        cv = np.ascontiguousarray(np.concatenate([c[1] for c in clouds]), np.float32)
+        counts = np.array([len(c[0]) for c in clouds], np.int32)
+        frs = (C.c_void_p * n)(*[f.h_ for f in frames])
+        T, ab = self._poses_and_affine(n, referenceToFrames, affine)
+        res = (capi.ResidualRecord * n)()
+        tiles = np.zeros((n, 2), np.int32)
+        check(self.L.lsdhip_tracker_evaluate_points_batch(self.h_, n, pos.ctypes.data, cv.ctypes.data, counts.ctypes.data, frs, T.ctypes.data,
+                                                          ab.ctypes.data, res, tiles.ctypes.data), False)
+        return list(res), tiles
+
+    def evaluatePointsBank(self, bank, slots, frames, referenceToFrames, affine=None):
+        """test hook: evaluatePointsBatch with the lists read where they lie in the bank (lsdhip_tracker_evaluate_points_bank)"""
+        n = len(slots)
+        sl = np.ascontiguousarray(slots, dtype=np.int32)
+        frs = (C.c_void_p * n)(*[f.h_ for f in frames])
+        T, ab = self._poses_and_affine(n, referenceToFrames, affine)
+        res = (capi.ResidualRecord * n)()
+        tiles = np.zeros((n, 2), np.int32)
+        check(self.L.lsdhip_tracker_evaluate_points_bank(self.h_, bank.h_, n, sl.ctypes.data, frs, T.ctypes.data, ab.ctypes.data, res,
+                                                         tiles.ctypes.data), False)
+        return list(res), tiles
+
     def trackFrameOnPermaref(self, permaRef_pos, permaRef_colVar, frame, referenceToFrame):
         pos = np.ascontiguousarray(permaRef_pos, np.float32)
         cv = np.ascontiguousarray(permaRef_colVar, np.float32)

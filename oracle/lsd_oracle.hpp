@@ -194,18 +194,36 @@ struct ResidualRecord {
   double num_constraints;
 };
 
+// one trial of trackFrameOnPermaref's inner loop (SE3Tracker.cpp:196-252), for tests that compare the loop decision by decision
+enum PermarefBranch {
+  PERMAREF_ACCEPTED = 0,            // error < lastErr, the loop goes on
+  PERMAREF_ACCEPTED_CONVERGED = 1,  // ... and error / lastErr > convergenceEpsTestTrack ends it
+  PERMAREF_REJECTED = 2,            // error >= lastErr, lambda grows, next trial
+  PERMAREF_REJECTED_STEP_MIN = 3,   // ... and incdot <= stepSizeMinTestTrack ends the loop
+  PERMAREF_DIVERGED = 4             // fewer warped points than the level's minimum
+};
+struct PermarefTrial {
+  float LM_lambda, error, lastErr, incdot;   // as the trial's comparisons read them (error: 0 on PERMAREF_DIVERGED)
+  int buf_warped_size, branch;
+};
+
 // C/Tracking/SE3Tracker.{h,cpp}
 class SE3Tracker {
  public:
   SE3Tracker(int w, int h, const float K[4], const Params& p);
   SE3d trackFrame(TrackingReference* reference, Frame* frame, const SE3d& frameToReference_initialEstimate);
+  // trace (may be null): one record per inner-loop trial, in order
   SE3d trackFrameOnPermaref(const float* permaRef_pos, const float* permaRef_colVar, int permaRefNumPts, Frame* frame,
-                            const SE3d& referenceToFrame);
+                            const SE3d& referenceToFrame, std::vector<PermarefTrial>* trace = nullptr);
   float checkPermaRefOverlap(const float* permaRef_pos, int permaRefNumPts, Frame* reference,
                              const SE3d& referenceToFrame);
   // one fused evaluation (K1 + K2 + K3) at a fixed pose for kernel-level parity tests
   void evaluate(TrackingReference* reference, Frame* frame, const SE3f& referenceToFrame, int level, float aff_a,
                 float aff_b, ResidualRecord* out);
+  // `evaluate` on an explicit point list (pos: 3 floats per point, colvar: 2), as trackFrameOnPermaref hands one to
+  // calcResidualAndBuffers (idxBuf = 0); the buffers stay readable
+  void evaluatePoints(const float* pos, const float* colvar, int n, Frame* frame, const SE3f& referenceToFrame, int level,
+                      float aff_a, float aff_b, ResidualRecord* out);
 
   DenseDepthTrackerSettings settings;
   TrackerMode mode = TRACKER_SSE;
@@ -230,7 +248,10 @@ class SE3Tracker {
   void calculateWarpUpdateSSE(LGS6& ls, bool exactRcp);
   float callWeights(const SE3f& T);
   void callWarpUpdate(LGS6& ls);
+  void recordAfterResidual(float retval, const SE3f& referenceToFrame, ResidualRecord* out);
+  void reserveBuffers(size_t n);   // a point list may be longer than the w * h the buffers start with
 
+  size_t bufCapacity = 0;
   int width, height;
   Params params;
   float affineEstimation_a_lastIt = 1, affineEstimation_b_lastIt = 0;

@@ -188,6 +188,14 @@ void orc_tracker_evaluate(void* t, void* ref, void* frame, const float refToFram
   T.t = mk3<float>(refToFrame[4], refToFrame[5], refToFrame[6]);
   ((SE3Tracker*)t)->evaluate((TrackingReference*)ref, F(frame), T, level, a, b, out);
 }
+// `orc_tracker_evaluate` on an explicit list of n points (pos 3 floats, colvar 2 floats each) at `level`
+void orc_tracker_evaluate_points(void* t, const float* pos, const float* colvar, int n, void* frame, const float refToFrame[7], int level,
+                                 float a, float b, ResidualRecord* out) {
+  SE3f T;
+  T.q.w = refToFrame[0]; T.q.x = refToFrame[1]; T.q.y = refToFrame[2]; T.q.z = refToFrame[3];
+  T.t = mk3<float>(refToFrame[4], refToFrame[5], refToFrame[6]);
+  ((SE3Tracker*)t)->evaluatePoints(pos, colvar, n, F(frame), T, level, a, b, out);
+}
 // which: 0 x 1 y 2 z 3 dx 4 dy 5 residual 6 d 7 idepthVar 8 weight_p ; returns buf_warped_size
 int orc_tracker_buffer(void* t, int which, float* out) {
   SE3Tracker* tr = (SE3Tracker*)t;
@@ -202,6 +210,23 @@ void orc_tracker_track_permaref(void* t, const float* pos, const float* colvar, 
   tr->numEvaluations = 0; tr->numWarpUpdates = 0;
   SE3d T = tr->trackFrameOnPermaref(pos, colvar, n, F(frame), pose_in(refToFrame));
   fill_result(tr, T, out);
+}
+// as above; trace (may be null, room for trace_cap records): the inner loop's trials in order.  Returns the number of trials, which may
+// exceed trace_cap (the first trace_cap are written).
+int orc_tracker_track_permaref_trace(void* t, const float* pos, const float* colvar, int n, void* frame, const double refToFrame[7],
+                                     orc_track_result* out, PermarefTrial* trace, int trace_cap) {
+  SE3Tracker* tr = (SE3Tracker*)t;
+  tr->numEvaluations = 0; tr->numWarpUpdates = 0;
+  std::vector<PermarefTrial> trials;
+  SE3d T = tr->trackFrameOnPermaref(pos, colvar, n, F(frame), pose_in(refToFrame), &trials);
+  fill_result(tr, T, out);
+  for (int i = 0; trace && i < (int)trials.size() && i < trace_cap; i++) trace[i] = trials[(size_t)i];
+  return (int)trials.size();
+}
+// the settings of trackFrameOnPermaref (DenseDepthTrackerSettings::*TestTrack)
+void orc_tracker_set_testtrack(void* t, float lambdaInitial, float stepSizeMin, float convergenceEps, float maxIts) {
+  DenseDepthTrackerSettings& s = ((SE3Tracker*)t)->settings;
+  s.lambdaInitialTestTrack = lambdaInitial; s.stepSizeMinTestTrack = stepSizeMin; s.convergenceEpsTestTrack = convergenceEps; s.maxItsTestTrack = maxIts;
 }
 float orc_tracker_check_overlap(void* t, const float* pos, int n, void* refFrame, const double refToFrame[7]) {
   return ((SE3Tracker*)t)->checkPermaRefOverlap(pos, n, F(refFrame), pose_in(refToFrame));

@@ -87,9 +87,17 @@ static float* alloc16(size_t n) {
 
 SE3Tracker::SE3Tracker(int w, int h, const float[4], const Params& p) : width(w), height(h), params(p) {
   size_t n = (size_t)w * h;
+  bufCapacity = n;
   buf_warped_residual = alloc16(n); buf_warped_dx = alloc16(n); buf_warped_dy = alloc16(n);
   buf_warped_x = alloc16(n); buf_warped_y = alloc16(n); buf_warped_z = alloc16(n);
   buf_d = alloc16(n); buf_idepthVar = alloc16(n); buf_weight_p = alloc16(n);
+}
+void SE3Tracker::reserveBuffers(size_t n) {
+  if (n <= bufCapacity) return;
+  float** bufs[9] = {&buf_warped_residual, &buf_warped_dx, &buf_warped_dy, &buf_warped_x, &buf_warped_y, &buf_warped_z, &buf_d, &buf_idepthVar, &buf_weight_p};
+  for (float** b : bufs) { free(*b); *b = alloc16(n); }
+  bufCapacity = n;
+  buf_warped_size = 0;
 }
 SE3Tracker::~SE3Tracker() {
   free(buf_warped_residual); free(buf_warped_dx); free(buf_warped_dy); free(buf_warped_x); free(buf_warped_y);
@@ -324,6 +332,20 @@ void SE3Tracker::evaluate(TrackingReference* reference, Frame* frame, const SE3f
   float rv = calcResidualAndBuffers(reference->posData[level].data(), reference->colorAndVarData[level].data(),
                                     ORC_SE3TRACKING_MIN_LEVEL == level ? reference->pointPosInXYGrid[level].data() : 0,
                                     reference->numData[level], frame, referenceToFrame, level);
+  recordAfterResidual(rv, referenceToFrame, out);
+}
+
+void SE3Tracker::evaluatePoints(const float* pos, const float* colvar, int n, Frame* frame, const SE3f& referenceToFrame, int level,
+                                float aff_a, float aff_b, ResidualRecord* out) {
+  reserveBuffers((size_t)n);
+  affineEstimation_a = aff_a;
+  affineEstimation_b = aff_b;
+  float rv = calcResidualAndBuffers(pos, colvar, 0, n, frame, referenceToFrame, level);
+  recordAfterResidual(rv, referenceToFrame, out);
+}
+
+// the record of the evaluation whose calcResidualAndBuffers returned `rv`: weights, then the normal equations
+void SE3Tracker::recordAfterResidual(float rv, const SE3f& referenceToFrame, ResidualRecord* out) {
   out->warped_size = buf_warped_size;
   out->goodCount = lastGoodCount; out->badCount = lastBadCount; out->pointUsage = pointUsage;
   out->meanRes = lastMeanRes; out->retval = rv;
@@ -426,13 +448,21 @@ SE3d SE3Tracker::trackFrame(TrackingReference* reference, Frame* frame, const SE
 
 // SE3Tracker.cpp:162-272 (level QUICK_KF_CHECK_LVL only)
 SE3d SE3Tracker::trackFrameOnPermaref(const float* permaRef_pos, const float* permaRef_colVar, int permaRefNumPts,
-                                      Frame* frame, const SE3d& referenceToFrameOrg) {
+                                      Frame* frame, const SE3d& referenceToFrameOrg, std::vector<PermarefTrial>* trace) {
   SE3f referenceToFrame = referenceToFrameOrg.cast<float>();
+  reserveBuffers((size_t)permaRefNumPts);
   affineEstimation_a = 1; affineEstimation_b = 0;
   LGS6 ls;
   diverged = false;
   trackingWasGood = true;
   const int L = ORC_QUICK_KF_CHECK_LVL;
+  // (tracing only: the dot product the reject branch computes, in its order)
+  auto dot6 = [](const float* inc) {
+    return (inc[0] * inc[0] + (inc[1] * inc[1] + inc[2] * inc[2])) + (inc[3] * inc[3] + (inc[4] * inc[4] + inc[5] * inc[5]));
+  };
+  auto note = [&](float lambda, float error, float lastErr, const float* inc, int branch) {
+    if (trace) trace->push_back(PermarefTrial{lambda, error, lastErr, dot6(inc), buf_warped_size, branch});
+  };
   calcResidualAndBuffers(permaRef_pos, permaRef_colVar, 0, permaRefNumPts, frame, referenceToFrame, L);
   if (buf_warped_size < MIN_GOODPERALL_PIXEL_ABSMIN * (width >> L) * (height >> L)) {
     diverged = true; trackingWasGood = false; return SE3d();
@@ -453,10 +483,12 @@ SE3d SE3Tracker::trackFrameOnPermaref(const float* permaRef_pos, const float* pe
       SE3f new_referenceToFrame = se3_exp<float>(inc) * referenceToFrame;
       calcResidualAndBuffers(permaRef_pos, permaRef_colVar, 0, permaRefNumPts, frame, new_referenceToFrame, L);
       if (buf_warped_size < MIN_GOODPERALL_PIXEL_ABSMIN * (width >> L) * (height >> L)) {
+        note(LM_lambda, 0, lastErr, inc, PERMAREF_DIVERGED);
         diverged = true; trackingWasGood = false; return SE3d();
       }
       float error = callWeights(new_referenceToFrame);
       if (error < lastErr) {
+        note(LM_lambda, error, lastErr, inc, error / lastErr > settings.convergenceEpsTestTrack ? PERMAREF_ACCEPTED_CONVERGED : PERMAREF_ACCEPTED);
         referenceToFrame = new_referenceToFrame;
         if (params.useAffineLightningEstimation) { affineEstimation_a = affineEstimation_a_lastIt; affineEstimation_b = affineEstimation_b_lastIt; }
         if (error / lastErr > settings.convergenceEpsTestTrack) iteration = settings.maxItsTestTrack;
@@ -466,6 +498,7 @@ SE3d SE3Tracker::trackFrameOnPermaref(const float* permaRef_pos, const float* pe
         break;
       } else {
         float incdot = (inc[0] * inc[0] + (inc[1] * inc[1] + inc[2] * inc[2])) + (inc[3] * inc[3] + (inc[4] * inc[4] + inc[5] * inc[5]));
+        note(LM_lambda, error, lastErr, inc, !(incdot > settings.stepSizeMinTestTrack) ? PERMAREF_REJECTED_STEP_MIN : PERMAREF_REJECTED);
         if (!(incdot > settings.stepSizeMinTestTrack)) { iteration = settings.maxItsTestTrack; break; }
         if (LM_lambda == 0) LM_lambda = 0.2;
         else LM_lambda *= std::pow(settings.lambdaFailFac, incTry);

@@ -153,7 +153,10 @@ def lib(fast=False, ref=None, native=False):
         "orc_tracker_set_max_its": (None, [vp, ip]),
         "orc_tracker_track": (None, [vp, vp, vp, dp, C.POINTER(TrackResult)]),
         "orc_tracker_evaluate": (None, [vp, vp, vp, fp, i, f, f, C.POINTER(ResidualRecord)]),
+        "orc_tracker_evaluate_points": (None, [vp, fp, fp, i, vp, fp, i, f, f, C.POINTER(ResidualRecord)]),
         "orc_tracker_buffer": (i, [vp, i, vp]),
+        "orc_tracker_track_permaref_trace": (i, [vp, fp, fp, i, vp, dp, C.POINTER(TrackResult), vp, i]),
+        "orc_tracker_set_testtrack": (None, [vp, f, f, f, f]),
         "orc_tracker_track_permaref": (None, [vp, fp, fp, i, vp, dp, C.POINTER(TrackResult)]),
         "orc_tracker_check_overlap": (f, [vp, fp, i, vp, dp]),
         "orc_se3_exp_f": (None, [fp, fp]),
@@ -207,6 +210,10 @@ def default_params(L=None):
 
 
 SCALAR, SSE, SSE_EXACT_RCP = 0, 1, 2
+# one trial of trackFrameOnPermaref's inner loop (PermarefTrial, oracle/lsd_oracle.hpp) and its branches
+PERMAREF_TRIAL = np.dtype([("LM_lambda", np.float32), ("error", np.float32), ("lastErr", np.float32), ("incdot", np.float32),
+                           ("buf_warped_size", np.int32), ("branch", np.int32)])
+ACCEPTED, ACCEPTED_CONVERGED, REJECTED, REJECTED_STEP_MIN, DIVERGED = range(5)
 
 
 class Frame:
@@ -349,13 +356,31 @@ class SE3Tracker:
         self.L.orc_tracker_buffer(self.h_, k, out.ctypes.data)
         return out
 
-    def track_permaref(self, pos, colvar, frame, refToFrame):
+    def evaluate_points(self, pos, colvar, frame, refToFrame7, level=4, a=1.0, b=0.0):
+        """`evaluate` on an explicit point list (pos n x 3, colvar n x 2); buffer() reads its buffers"""
+        r = ResidualRecord()
+        pos = np.ascontiguousarray(pos, np.float32)
+        colvar = np.ascontiguousarray(colvar, np.float32)
+        self.L.orc_tracker_evaluate_points(self.h_, pos, colvar, len(pos), frame.h_, np.ascontiguousarray(refToFrame7, dtype=np.float32),
+                                           level, a, b, C.byref(r))
+        return r
+
+    def set_testtrack(self, lambdaInitial=0.0, stepSizeMin=1e-3, convergenceEps=0.98, maxIts=5):
+        self.L.orc_tracker_set_testtrack(self.h_, lambdaInitial, stepSizeMin, convergenceEps, maxIts)
+
+    def track_permaref(self, pos, colvar, frame, refToFrame, trace=False):
+        """trace: also return the inner loop's trials (PERMAREF_TRIAL records, in order)"""
         r = TrackResult()
         pos = np.ascontiguousarray(pos, np.float32)
         colvar = np.ascontiguousarray(colvar, np.float32)
-        self.L.orc_tracker_track_permaref(self.h_, pos, colvar, len(pos), frame.h_,
-                                          np.ascontiguousarray(refToFrame, np.float64), C.byref(r))
-        return r
+        T = np.ascontiguousarray(refToFrame, np.float64)
+        if not trace:
+            self.L.orc_tracker_track_permaref(self.h_, pos, colvar, len(pos), frame.h_, T, C.byref(r))
+            return r
+        tr = np.zeros(256, PERMAREF_TRIAL)
+        n = self.L.orc_tracker_track_permaref_trace(self.h_, pos, colvar, len(pos), frame.h_, T, C.byref(r), tr.ctypes.data, len(tr))
+        assert n <= len(tr), n
+        return r, tr[:n].copy()
 
     def check_overlap(self, pos, ref_frame, refToFrame):
         pos = np.ascontiguousarray(pos, np.float32)

@@ -78,6 +78,23 @@ int main() {
     CHECK(P.trials[4] == 6 && P.tiling[4].nblocks == 12 && P.tiling[4].singlePass == 1, "permaref: %d trials, %d workgroups", P.trials[4], P.tiling[4].nblocks);
     CHECK(P.grid == 72 && P.specGrid == 72, "permaref: grid %d", P.grid);
   }
+  {  // point lists under the three policies tests/test_permaref_loop_gpu.py compares (its single_tiles): the default policy caps lists
+     // above LSD_SPEC_CAP_ABOVE_PX points at 80 tiles, lsdhip_tracker_set_speculation(t, 6, 8) caps every list at 8, (t, 1, 0) never caps
+    struct List { int n, dflt, dfltPass, one, onePass, six8, six8Pass; };
+    const List lists[] = {{255, 1, 1, 1, 1, 1, 1},     {2048, 8, 1, 8, 1, 8, 1},      {2049, 9, 1, 9, 1, 8, 0},     {4097, 24, 1, 24, 1, 8, 0},
+                          {4836, 24, 1, 24, 1, 8, 0},  {24576, 96, 1, 96, 1, 8, 0},   {25000, 80, 0, 104, 1, 8, 0}};
+    SpecPolicy six8 = policy(6, false);
+    six8.specCap = 8;
+    for (const List& c : lists) {
+      LevelWork lv[L] = {};
+      lv[4] = {c.n, lsd_level_tiling(c.n, BLOCK, CAP, BatchShape{0, 0}, false, WGS, CAP)};
+      const SinglePlan Pd = lsd_single_plan(lv, policy(LSD_SPEC_MAX, true), 4, 4), P1 = lsd_single_plan(lv, policy(1, false), 4, 4), P6 = lsd_single_plan(lv, six8, 4, 4);
+      CHECK(Pd.tiling[4].nblocks == c.dflt && Pd.tiling[4].singlePass == c.dfltPass, "%d points, default policy: %d tiles, singlePass %d", c.n, Pd.tiling[4].nblocks, Pd.tiling[4].singlePass);
+      CHECK(P1.tiling[4].nblocks == c.one && P1.tiling[4].singlePass == c.onePass && P1.trials[4] == 1, "%d points, (1, 0): %d tiles, singlePass %d", c.n, P1.tiling[4].nblocks, P1.tiling[4].singlePass);
+      CHECK(P6.tiling[4].nblocks == c.six8 && P6.tiling[4].singlePass == c.six8Pass && P6.trials[4] == 6, "%d points, (6, 8): %d tiles, singlePass %d", c.n, P6.tiling[4].nblocks, P6.tiling[4].singlePass);
+      CHECK(Pd.trials[4] == (c.n <= LSD_SPEC_SMALL_PX ? 6 : 5), "%d points, default policy: %d trials", c.n, Pd.trials[4]);
+    }
+  }
 
   // ---- batches
   {
